@@ -2,7 +2,8 @@
 """bench.py — throughput of the rasterizer hot path (forward + backward through the drop-in GaussianRasterizer API) on
 synthetic random-splat scenes, with the roofline of the dominant kernel and the CPU oracle timed beside it.
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload c4|c2|ds|dsc|c1|c4d] [--no-extras] [--no-cpu-baseline]
+    python bench.py [--gpus N --steps K --warmup W] [--workload c4|c2|ds|dsc|c1|c4d] [--dump-outputs DIR]
+                    [--full [--no-extras] [--no-cpu-baseline] [--no-pmc] [--full-line]]
 
 Default workload: c4 = BASELINE.json configs[3] (1 M splats at 1080p), the configuration north_star's roofline target is
 stated on.  A step = one forward + one backward of one scene (inputs resident in HBM).  With N > 1 every rank renders its OWN
@@ -11,7 +12,12 @@ barrier and the max-over-ranks time — hence "scaling": "weak".  `--gpus N` wit
 the N ranks itself (re-executes under `python -m torch.distributed.run --nproc-per-node N`); under torchrun it checks that
 WORLD_SIZE == N.  Prints ONE JSON line on rank 0.
 
-Extra keys beside the contract's: `roofline`, `cpu_baseline`, `kernels` (per-kernel time and algorithmic GB/s), `extras`
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`, `unit`, `ms_per_step`, ...)
+and nothing else.  `--dump-outputs DIR` also writes what the last timed step computed (rank 0) as float32 .npy files: the image
+and radii of the forward, the gradients of every leaf; per-Gaussian arrays as a fixed, seeded sample of DUMP_ROWS rows when
+P is larger.  Everything below is measured with `--full` only.
+
+Extra keys beside the contract's (--full): `roofline`, `cpu_baseline`, `kernels` (per-kernel time and algorithmic GB/s), `extras`
 (N = 1 only, skipped with --no-extras: the other BASELINE shapes c2 / ds / c1, c4 with the densification stress, and
 train-step ms of the DAS3R-shaped optimisation step, fused and unfused), `train_step_ms` + `scenes_per_hour` (every N: the
 farm's unit of work is a 4000-iteration optimisation of one sequence, scripts/testing_psnr_davis.sh:35-59), `jobs_in_flight`
@@ -41,6 +47,9 @@ WORKLOAD_DESC = {
 }
 INIT_STEPS = 30
 ITERS_PER_SCENE = 4000   # BASELINE.json configs[2] / [4]: one sequence = 4000 optimisation iterations
+DUMP_ROWS = 65536        # --dump-outputs: per-Gaussian arrays of a larger P are written as this many seeded rows
+DUMP_SEED = 20240601
+DUMP_MAX_BYTES = 64 * 2 ** 20
 
 
 def parse_args(argv=None):
@@ -49,6 +58,11 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--workload", default=os.environ.get("DAS3R_BENCH_WORKLOAD", "c4"), choices=sorted(WORKLOAD_DESC))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32; per-Gaussian arrays sampled)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-kernel table, forward alone, PMC traffic, other shapes, "
+                         "train step, whole jobs, CPU baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--extras-child", action="store_true", help=argparse.SUPPRESS)
@@ -177,6 +191,8 @@ class RasterJob:
         self.events = []
         self._rs_cls = GaussianRasterizationSettings
         self.steps_done = 0
+        self.keep_outputs = False   # --dump-outputs: step() keeps (color, radii) of its forward in self.last
+        self.last = None
 
     def upload(self):
         import torch
@@ -216,7 +232,25 @@ class RasterJob:
         color.backward(self.dL)
         self.num_rendered = int(color.grad_fn.num_rendered)
         self.steps_done += 1
+        if self.keep_outputs:
+            self.last = (color, radii)
         return color
+
+    def outputs(self):
+        """-> {name: float32 ndarray}: what a caller of step() received from its last call — the forward's image and radii, the
+        gradients of every leaf.  Per-Gaussian arrays of more than DUMP_ROWS rows: the rows of a sample fixed by DUMP_SEED and P."""
+        import numpy as np
+        torch = self._torch
+        color, radii = self.last
+        idx = None
+        if self.P > DUMP_ROWS:
+            pick = np.sort(np.random.default_rng(DUMP_SEED).choice(self.P, DUMP_ROWS, replace=False))
+            idx = torch.from_numpy(pick).to(self.dev)
+        out = {"color": color.detach()}
+        per_gaussian = [("radii", radii)] + [(f"grad_{k}", v.grad) for k, v in self.leaves.items()] + [("grad_means2D", self.means2D.grad)]
+        for name, t in per_gaussian:
+            out[name] = t if idx is None else t.index_select(0, idx)
+        return {k: v.detach().float().cpu().numpy() for k, v in out.items()}
 
     def forward_only(self):
         """The forward render alone (BASELINE.json's metric names "render fwd/bwd Msplats/s": this is the fwd figure): the same call as
@@ -226,6 +260,18 @@ class RasterJob:
         color, radii = self.rast(means3D=L["means3D"], means2D=self.means2D, opacities=L["opacities"], shs=L["shs"], scales=L["scales"],
                                  rotations=L["rotations"])
         return color
+
+
+def write_outputs(directory, arrays):
+    """--dump-outputs: {name: ndarray} -> directory/<name>.npy, float32 (float64 kept), at most DUMP_MAX_BYTES in all."""
+    import numpy as np
+    arrays = {k: (v if v.dtype == np.float64 else v.astype(np.float32)) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_MAX_BYTES})")
+    os.makedirs(directory, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), v)
 
 
 def kernel_times(job, steps):
@@ -682,6 +728,24 @@ def run_extras_child(main_workload):
         return {"error": repr(ex)}
 
 
+def headline(args, rk, job, elapsed, ranks_ok, per_rank_ms, pinned):
+    """The line's contract keys (rank 0), the same in a plain and a --full run: `elapsed` = the K timed steps, max over ranks."""
+    sc = job.sc
+    P_report = job.sc_cpu.P                        # (c4d: P grows; the rate is quoted on the initial P, the growth is in config)
+    msplats = sum(ranks_ok) * P_report / (elapsed / args.steps) / 1e6   # (a rank whose job failed processed nothing)
+    return {"metric": "render fwd+bwd Msplats/s at 1080p" if sc.W == 1920 else f"render fwd+bwd Msplats/s at {sc.W}x{sc.H}",
+            "value": round(msplats, 3), "unit": "Msplats/s", "n_gpus": rk.world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic", "per_rank_ms": per_rank_ms, "ranks_ok": ranks_ok,
+            "config": {"workload": WORKLOAD_DESC[args.workload], "name": args.workload, "splats_per_gpu": P_report,
+                       "splats_per_gpu_final": job.P, "init_steps": INIT_STEPS if args.workload != "c4d" else 1, "image": [sc.W, sc.H],
+                       "sh_degree": sc.sh_degree, "num_rendered": job.num_rendered,
+                       "api": "GaussianRasterizer.forward + autograd backward (drop-in surface)",
+                       "parallelism": f"{rk.world} independent scenes, one per GPU",
+                       "host_cpus": (f"pinned to CPUs {pinned[1][0]}-{pinned[1][-1]} (one core complex per rank)" if pinned
+                                     else "not pinned")}}
+
+
 def main():
     args = parse_args()
     if args.extras_child:
@@ -702,10 +766,12 @@ def main():
             if rk.rank == fail_rank and float(x[0]) > args.warmup + args.steps // 2:
                 raise RuntimeError("stub job failure (DAS3R_BENCH_STUB_FAIL_RANK)")
         elapsed = rk.timed(step, args.steps, args.warmup)
+        if args.dump_outputs and rk.rank == 0:
+            write_outputs(args.dump_outputs, {"stub_state": x.numpy()})
         ranks_ok = [int(round(v)) for v in rk.gather_all(0.0 if rk.failed else 1.0)]
         per_rank_ms = rk.gather_all(rk.last_local_s / args.steps * 1e3)
         jobs = None
-        if rk.world > 1:   # the K-jobs-in-flight leg of an N > 1 run, with stand-in jobs (rank r's take 0.05 (r + 1) s)
+        if rk.world > 1 and args.full:   # the K-jobs-in-flight leg of an N > 1 run, with stand-in jobs (rank r's take 0.05 (r + 1) s)
             jobs = ranked_jobs_in_flight(rk, 2, lambda s_: (time.sleep(0.05 * (rk.rank + 1)), {"ok": 1})[1], "stub jobs")
         if rk.rank == 0:
             out = {"metric": "stub steps/s (launch-logic dry run, no GPU work)", "value": round(sum(ranks_ok) * args.steps / elapsed, 3),
@@ -727,8 +793,25 @@ def main():
     for _ in range(INIT_STEPS if args.workload != "c4d" else 1):
         job.step()
     rk.barrier()
+    job.keep_outputs = bool(args.dump_outputs) and rk.rank == 0
     elapsed = rk.timed(job.step, args.steps, args.warmup)
-    ms_per_step = elapsed / args.steps * 1e3
+    dumped = None
+    if job.keep_outputs:
+        if rk.failed is not None:
+            print(f"bench.py: no --dump-outputs, a step failed: {rk.failed}", file=sys.stderr, flush=True)
+        else:
+            dumped = job.outputs()   # taken now: the --full passes below run more steps
+        job.keep_outputs, job.last = False, None
+    if not args.full:
+        per_rank_ms = rk.gather_all(rk.last_local_s / args.steps * 1e3) if rk.world > 1 else None
+        ranks_ok = [int(round(v)) for v in rk.gather_all(0.0 if rk.failed else 1.0)]
+        unpin(pinned)
+        if rk.rank == 0:
+            if dumped is not None:
+                write_outputs(args.dump_outputs, dumped)
+            print(json.dumps(headline(args, rk, job, elapsed, ranks_ok, per_rank_ms, pinned)), flush=True)
+        rk.close()
+        return
     timed_kernels = kernel_times(job, args.steps) if rk.rank == 0 else None   # right behind the timed region (same clocks)
     per_rank_ms = rk.gather_all(rk.last_local_s / args.steps * 1e3) if rk.world > 1 else None   # a straggler shows here
     ranks_ok = [int(round(v)) for v in rk.gather_all(0.0 if rk.failed else 1.0)]
@@ -736,7 +819,6 @@ def main():
     fwd_elapsed = rk.timed(job.forward_only, args.steps, min(args.warmup, 5)) if args.workload != "c4d" else None
     measured = measure_traffic(args.workload) if (rk.rank == 0 and rk.world == 1 and not args.no_pmc) else None
     P_report = job.sc_cpu.P                        # (c4d: P grows; the rate is quoted on the initial P, the growth is in config)
-    msplats = sum(ranks_ok) * P_report / (elapsed / args.steps) / 1e6   # (a rank whose job failed processed nothing)
 
     kernels, roofline = (None, None)
     if rk.rank == 0:
@@ -802,26 +884,17 @@ def main():
         cpu_baseline = cpu_baseline_of(job.sc_cpu, args.workload if args.workload != "c4d" else "c4")
 
     if rk.rank == 0:
-        sc = job.sc
-        out = {"metric": "render fwd+bwd Msplats/s at 1080p" if sc.W == 1920 else f"render fwd+bwd Msplats/s at {sc.W}x{sc.H}",
-               "value": round(msplats, 3), "unit": "Msplats/s", "n_gpus": rk.world, "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-               "dtype": "f32", "data": "synthetic",
-               "eval_forward": (extras.pop("eval_forward", None) if extras else None),
-               "fwd_only": (None if fwd_elapsed is None else
-                            {"value": round(rk.world * P_report / (fwd_elapsed / args.steps) / 1e6, 3), "unit": "Msplats/s",
-                             "ms_per_step": round(fwd_elapsed / args.steps * 1e3, 4), "what": "forward render alone (training-mode call, no backward), same K / barrier protocol"}),
-               "per_rank_ms": per_rank_ms, "ranks_ok": ranks_ok,
-               "config": {"workload": WORKLOAD_DESC[args.workload], "name": args.workload, "splats_per_gpu": P_report,
-                          "splats_per_gpu_final": job.P, "init_steps": INIT_STEPS if args.workload != "c4d" else 1, "image": [sc.W, sc.H], "sh_degree": sc.sh_degree, "num_rendered": job.num_rendered,
-                          "api": "GaussianRasterizer.forward + autograd backward (drop-in surface)",
-                          "parallelism": f"{rk.world} independent scenes, one per GPU",
-                          "host_cpus": (f"pinned to CPUs {pinned[1][0]}-{pinned[1][-1]} (one core complex per rank)" if pinned
-                                        else "not pinned")},
-               "c4_region_backward_ms": (extras.pop("c4_region_backward_ms", None) if extras else None),
-               "train_step_ms": train, "scenes_per_hour": round(scenes_per_hour, 2),
-               "scenes_per_hour_def": sph_def, "jobs_in_flight": jobs,
-               "roofline": roofline, "cpu_baseline": cpu_baseline, "kernels": kernels, "extras": extras}
+        if dumped is not None:
+            write_outputs(args.dump_outputs, dumped)
+        out = headline(args, rk, job, elapsed, ranks_ok, per_rank_ms, pinned)
+        out.update({"eval_forward": (extras.pop("eval_forward", None) if extras else None),
+                    "fwd_only": (None if fwd_elapsed is None else
+                                 {"value": round(rk.world * P_report / (fwd_elapsed / args.steps) / 1e6, 3), "unit": "Msplats/s",
+                                  "ms_per_step": round(fwd_elapsed / args.steps * 1e3, 4), "what": "forward render alone (training-mode call, no backward), same K / barrier protocol"}),
+                    "c4_region_backward_ms": (extras.pop("c4_region_backward_ms", None) if extras else None),
+                    "train_step_ms": train, "scenes_per_hour": round(scenes_per_hour, 2),
+                    "scenes_per_hour_def": sph_def, "jobs_in_flight": jobs,
+                    "roofline": roofline, "cpu_baseline": cpu_baseline, "kernels": kernels, "extras": extras})
         if extras and not args.full_line:
             # the line stays short enough for any log tail: per-workload detail goes to stderr (and to gpurun_out/ when it exists)
             detail = json.dumps({"bench_extras": extras})

@@ -33,8 +33,9 @@ def test_gpus_flag_spawns_that_many_ranks():
 
 def test_n_ranks_report_jobs_in_flight_over_the_slowest_rank():
     """`bench.py --gpus N` carries `jobs_in_flight` for N > 1 — every rank runs K = 2 whole jobs at once behind one
-    barrier (farm.run_jobs), the rate is N x K jobs over the slowest rank's wall time.  Stub jobs: rank r's take 0.05 (r + 1) s."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--stub"],
+    barrier (farm.run_jobs), the rate is N x K jobs over the slowest rank's wall time.  Stub jobs: rank r's take 0.05 (r + 1) s.
+    The jobs are measured by a --full run only."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--stub", "--full"],
                        capture_output=True, text=True, timeout=300, env=_env(), cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     j = _json_line(p.stdout)["jobs_in_flight"]
@@ -101,3 +102,48 @@ def test_counter_csv_rows_are_grouped_and_converted(tmp_path):
     g = tmp_path / "valu_counter_collection.csv"
     g.write_text(head + row(1, "void das3r::render_backward_blk_kernel<128, 1, 0, 5>(int)", "SQ_INSTS_VALU", 2.5e8))
     assert list(bench.pmc_rows([str(g)], "SQ_INSTS_VALU")) == [("render_backward_kernel", "render_backward_blk_kernel", 2.5e8)]   # a count, not KiB
+
+
+def test_plain_run_measures_the_headline_only():
+    """A plain run times the K steps and prints the line; the whole jobs beside it come with --full only."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "7", "--warmup", "1", "--stub"],
+                       capture_output=True, text=True, timeout=300, env=_env(), cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    out = _json_line(p.stdout)
+    assert out["steps"] == 7 and out["jobs_in_flight"] is None
+    assert abs(out["value"] - 2 * 7 / (out["ms_per_step"] * 7 * 1e-3)) < 1e-3 * out["value"]   # value and ms_per_step: the same K steps
+
+
+def test_dump_outputs_are_float32_and_repeatable(tmp_path):
+    """--dump-outputs DIR: what the last timed step computed, as DIR/<name>.npy in float32, identical for identical arguments."""
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--stub", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=300, env=_env(), cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert _json_line(p.stdout)["steps"] == 5
+    names = sorted(os.listdir(dirs[0]))
+    assert names == ["stub_state.npy"] and sorted(os.listdir(dirs[1])) == names
+    a, b = (np.load(d / names[0]) for d in dirs)
+    assert a.dtype == np.float32 and np.array_equal(a, b) and (a == 7.0).all()   # 2 warm-up + 5 timed steps of x += 1
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_write_outputs_converts_to_float32_and_keeps_the_size_limit(tmp_path):
+    import numpy as np
+    import pytest
+    bench = _bench_module()
+    bench.write_outputs(str(tmp_path / "o"), {"radii": np.arange(5, dtype=np.int32), "x": np.ones(3, np.float64)})
+    r, x = np.load(tmp_path / "o" / "radii.npy"), np.load(tmp_path / "o" / "x.npy")
+    assert r.dtype == np.float32 and r.tolist() == [0, 1, 2, 3, 4] and x.dtype == np.float64
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "big"), {"img": np.zeros(bench.DUMP_MAX_BYTES // 4 + 1, np.float32)})
+    assert not (tmp_path / "big").exists()

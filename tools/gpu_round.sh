@@ -1,6 +1,11 @@
-# One GPU-box session of the round's standing checks: full GPU test suite, smoke, default bench line.   bash tools/gpu_round.sh [tag]
-TAG=${1:-run}; mkdir -p gpurun_out
-(timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -40) > gpurun_out/pytest_$TAG.log
-(timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -5) > gpurun_out/smoke_$TAG.log
-(timeout 900 python bench.py 2>&1 | tail -3) > gpurun_out/bench_$TAG.log
-tail -6 gpurun_out/pytest_$TAG.log; cat gpurun_out/smoke_$TAG.log; cat gpurun_out/bench_$TAG.log
+# The standing checks on a GPU machine: GPU test suite, smoke, the plain bench line and the --full one.
+#   bash tools/gpu_round.sh [tag] [log directory, default logs]
+# Each step has its own time limit and the next one starts only if it passed (a fault ends the sequence).
+TAG=${1:-run}; LOG=${2:-logs}; mkdir -p "$LOG"; rm -f "$LOG"/*_"$TAG".log
+timeout -k 10 1500 python -m pytest tests -m gpu -q > "$LOG/pytest_$TAG.log" 2>&1 &&
+  timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$LOG/smoke_$TAG.log" 2>&1 &&
+  timeout -k 10 300 python bench.py > "$LOG/bench_$TAG.log" 2>&1 &&
+  timeout -k 10 900 python bench.py --full > "$LOG/bench_full_$TAG.log" 2>&1
+rc=$?
+for f in pytest smoke bench bench_full; do [ -f "$LOG/${f}_$TAG.log" ] && tail -6 "$LOG/${f}_$TAG.log"; done
+exit $rc

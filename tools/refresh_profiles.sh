@@ -7,14 +7,14 @@
 # Everything lands in gpurun_out/profiles/ (copied into profiles/ by hand after a look).  Every child is time-bounded.
 R=$PWD; RN=${1:-r05}; OUT=$R/gpurun_out/profiles; mkdir -p $OUT
 export PYTHONPATH=$R
-DAS3R_BENCH_JOBS=full timeout 600 python bench.py --full-line 2>$OUT/${RN}_bench_c4.stderr | tail -1 > $OUT/${RN}_bench_c4.json
+DAS3R_BENCH_JOBS=full timeout 600 python bench.py --full --full-line 2>$OUT/${RN}_bench_c4.stderr | tail -1 > $OUT/${RN}_bench_c4.json
 for w in c2 ds dsc; do
-  timeout 200 python bench.py --workload $w --no-extras 2>/dev/null | tail -1 > $OUT/${RN}_bench_$w.json
+  timeout 200 python bench.py --workload $w --full --no-extras 2>/dev/null | tail -1 > $OUT/${RN}_bench_$w.json
 done
 cd /tmp; export TMPDIR=/tmp
 for w in c4 c2 ds dsc; do
   rm -rf /tmp/kt_$w
-  timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/kt_$w -o kt --output-format csv -- python $R/bench.py --workload $w --no-cpu-baseline --no-pmc > /dev/null 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/kt_$w -o kt --output-format csv -- python $R/bench.py --workload $w --full --no-cpu-baseline --no-pmc > /dev/null 2>&1
   f=$(find /tmp/kt_$w -name '*kernel_stats.csv' | head -1)
   [ -n "$f" ] && cp $f $OUT/${RN}_${w}_kernel_stats.csv
 done

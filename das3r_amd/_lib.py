@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdas3r_hip.so")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
 
@@ -33,7 +33,7 @@ class RasterIn(C.Structure):
 
 
 class RasterOut(C.Structure):
-    _fields_ = [("out_color", C.c_void_p), ("radii", C.c_void_p)]
+    _fields_ = [("out_color", C.c_void_p), ("radii", C.c_void_p), ("out_invdepth", C.c_void_p)]   # ABI 16: + out_invdepth ([H, W] or NULL)
 
 
 class RasterSaved(C.Structure):
@@ -65,7 +65,7 @@ class RasterLayout(C.Structure):
 
 
 # every symbol include/das3r_raster.h declares
-EXPORTS = ("das3r_raster_forward", "das3r_raster_backward", "das3r_raster_check", "das3r_raster_backward_scratch_bytes", "das3r_mark_visible", "das3r_knn3_workspace_bytes",
+EXPORTS = ("das3r_raster_forward", "das3r_raster_backward", "das3r_raster_backward_depth", "das3r_raster_backward_depth_scratch_bytes", "das3r_raster_check", "das3r_raster_backward_scratch_bytes", "das3r_mark_visible", "das3r_knn3_workspace_bytes",
            "das3r_knn3_mean_dist2", "das3r_raster_get_layout", "das3r_abi_version", "das3r_last_error", "das3r_reload_switches", "das3r_get_stats",
            "das3r_raster_forget_shapes", "das3r_raster_learning",
            "das3r_profile_enable", "das3r_profile_report", "das3r_pretransform_forward", "das3r_pretransform_backward", "das3r_pose_matrices", "das3r_pose_chain",
@@ -101,6 +101,11 @@ def load():
     L.das3r_raster_backward.argtypes = [C.POINTER(RasterArgs), C.POINTER(RasterIn), C.POINTER(RasterSaved), C.c_void_p,
                                         C.POINTER(RasterGrads), C.c_void_p]
     L.das3r_raster_backward_scratch_bytes.restype = C.c_size_t
+    L.das3r_raster_backward_depth.restype = C.c_int   # ABI 16
+    L.das3r_raster_backward_depth.argtypes = [C.POINTER(RasterArgs), C.POINTER(RasterIn), C.POINTER(RasterSaved), C.c_void_p, C.c_void_p,
+                                              C.POINTER(RasterGrads), C.c_void_p]
+    L.das3r_raster_backward_depth_scratch_bytes.restype = C.c_size_t
+    L.das3r_raster_backward_depth_scratch_bytes.argtypes = [C.c_int64]
     L.das3r_raster_backward_scratch_bytes.argtypes = [C.c_int64]
     L.das3r_raster_check.restype = C.c_int
     L.das3r_raster_check.argtypes = [C.POINTER(RasterSaved), C.c_void_p]

@@ -233,6 +233,14 @@ void compute_layout(int P, int64_t I, int W, int H, Layout *L) {
     L->b_ctrl_bytes = o - L->b_ghist;
     L->b_ckpt = take(((size_t)In / BUCKET + (size_t)(L->ntiles > 0 ? L->ntiles : 1) + 2) * 256 * 16);
     L->pub.binning_bytes = o;
+    // ABI 16: behind it, what a forward with out_invdepth adds (Layout::d_*: the colour-only layout above is unchanged)
+    const size_t npix_d = (size_t)W * (size_t)H;
+    L->d_ckpt = take(((size_t)In / BUCKET + (size_t)(L->ntiles > 0 ? L->ntiles : 1) + 2) * 256 * 16);
+    L->d_recs = take(16 * SPLAT_REC * Pn);
+    L->d_dpix = take(4 * 3 * (npix_d > 0 ? npix_d : 1));
+    L->d_bg = take(16);
+    L->d_dz = take(4 * Pn);
+    L->d_bytes = o;
     L->pub.point_list = (L->tile_passes & 1) ? L->b_valB : L->b_valA;
     // img
     o = 0;
@@ -468,7 +476,12 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
         set_error("das3r_raster_forward: null output/allocator");
         return DAS3R_ERR_INVALID_ARG;
     }
+    if (out->out_invdepth && switches().render_fwd == 4) {   // ABI 16: every forward kernel the library picks has an inverse-depth form, not the forced slices
+        set_error("das3r_raster_forward: DAS3R_RENDER=slices has no inverse-depth form (das3r_raster_out.out_invdepth)");
+        return DAS3R_ERR_INVALID_ARG;
+    }
     const int P = a->P, W = a->image_width, H = a->image_height;
+    const bool depth = out->out_invdepth != nullptr;   // ABI 16: the binning buffer also holds Layout::d_* (d_bytes instead of binning_bytes)
     Layout L;
     compute_layout(P, 0, W, H, &L);
     saved->geom = alloc_geom(user, L.pub.geom_bytes);
@@ -483,6 +496,7 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
     if (P == 0) {
         // upstream:rasterize_points.cu skips the rasterizer when P == 0: the image stays zero (background NOT applied)
         HIP_TRY(hipMemsetAsync(out->out_color, 0, sizeof(float) * 3 * (size_t)W * H, s));
+        if (out->out_invdepth) HIP_TRY(hipMemsetAsync(out->out_invdepth, 0, sizeof(float) * (size_t)W * H, s));
         HIP_TRY(hipMemsetAsync(saved->img + L.pub.ranges, 0, 8 * (size_t)L.ntiles, s));
         saved->binning = alloc_binning(user, 256);
         return 0;
@@ -661,7 +675,8 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
             lb.keys = dead_keys;
             lb.host_flag = mb->dev + 10;
         }
-        return launch_render_forward(a, in->colors_precomp, out->out_color, saved->geom, saved->binning, saved->img, L, lb, s);
+        return launch_render_forward(a, in->colors_precomp, out->out_color, saved->geom, saved->binning, saved->img, L, lb, s, out->out_invdepth,
+                                     depth ? (float4 *)(saved->binning + L.d_ckpt) : nullptr);
     };
     // prefiltered: the caller's promise that no point fails the near-plane cull (upstream traps when one does: auxiliary.h in_frustum);
     // the preprocess kernel leaves this call's tag in mailbox word 12 when one did
@@ -682,7 +697,7 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
         if (cap > (int64_t)0x7FFFFF00) cap = (int64_t)0x7FFFFF00;
         compute_layout(P, cap, W, H, &L);
         apply_seg();
-        saved->binning = alloc_binning(user, L.pub.binning_bytes);
+        saved->binning = alloc_binning(user, depth ? L.d_bytes : L.pub.binning_bytes);
         if (!saved->binning) { set_error("scratch allocation failed (binning %zu B)", L.pub.binning_bytes); return DAS3R_ERR_ALLOC; }
         // The count is not needed before the end of this call: the preprocess kernel skips its count reduction and the scan
         // delivers it.  When the preprocess grid is resident as a whole (P <= 196 k) the scan and the emission run inside the
@@ -734,7 +749,7 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
         if (I > cap) {
             cap = I;
             compute_layout(P, cap, W, H, &L);
-            saved->binning = alloc_binning(user, L.pub.binning_bytes);
+            saved->binning = alloc_binning(user, depth ? L.d_bytes : L.pub.binning_bytes);
             if (!saved->binning) { set_error("scratch allocation failed (binning %zu B)", L.pub.binning_bytes); return DAS3R_ERR_ALLOC; }
             apply_seg();
             HIP_TRY(hipMemsetAsync(saved->geom + L.g_ghist, 0, L.g_ctrl_bytes, s));          // tickets and look-back words of the scan
@@ -762,7 +777,7 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
         }
         compute_layout(P, cap, W, H, &L);
         apply_seg();
-        saved->binning = alloc_binning(user, L.pub.binning_bytes);
+        saved->binning = alloc_binning(user, depth ? L.d_bytes : L.pub.binning_bytes);
         if (!saved->binning) { set_error("scratch allocation failed (binning %zu B)", L.pub.binning_bytes); return DAS3R_ERR_ALLOC; }
         if (!local && !seg && (rc = launch_depth_sort(P, saved->geom, L, 1, saved->binning + L.b_ghist, L.b_ctrl_bytes, a->debug != 0, s))) return rc;
         if ((rc = bin_and_render(cap, local, !local && !seg))) return rc;
@@ -770,6 +785,7 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
     if (a->debug && late_tag && (rc = check_slot(late_tag % CHECK_SLOTS, true))) return rc;   // debug: report this forward's self-check word right away
     saved->num_rendered = I;
     saved->capacity = cap;
+    if (depth) saved->flags |= DEPTH_SAVED_FLAG;
     return I;
 }
 
@@ -804,6 +820,75 @@ extern "C" int das3r_raster_backward(const das3r_raster_args *a, const das3r_ras
         if ((rc = launch_render_backward(a, dL_dpix, saved->geom, saved->binning, saved->img, L, partial, s, &quad_rows, saved->num_rendered, saved->flags))) return rc;
     }
     return launch_preprocess_backward(a, in, saved->geom, saved->binning, L, g, partial, s, quad_rows);
+}
+
+// ABI 16: the backward of (colour, inverse depth).  The colour pass is das3r_raster_backward's; the depth pass is the same compositing backward
+// (the same kernel: the choice depends on the lists and the flags only) on the colour (1/z, 0, 0) with background 0, upstream gradient
+// (dL/dinvdepth, 0, 0) and the depth checkpoints — preprocess_bwd.hip depth_pass_inputs_kernel / depth_fold_kernel say why that is the
+// backward of the fourth channel.  Its geometry sums are added to the colour pass's rows, its colour sums become dL/dz, which the per-Gaussian
+// kernel adds to dL/dmeans3D (before the chain, with grads->chain).  Everything it writes besides grads and scratch is in the binning
+// buffer's depth part (Layout::d_*), which only a forward with out_invdepth has: das3r_raster_saved.flags bit 1 says so.
+extern "C" int das3r_raster_backward_depth(const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_saved *saved,
+                                           const float *dL_dpix, const float *dL_dinvdepth, const das3r_raster_grads *g, das3r_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    int rc = validate(a, in);
+    if (rc) return rc;
+    const int P = a->P;
+    if (P == 0) return DAS3R_OK;
+    const bool chained = g && g->chain;
+    if (!saved || !saved->geom || !saved->img || !dL_dpix || !dL_dinvdepth || !g || !g->dL_dmeans2D || (!chained && (!g->dL_dopacities || !g->dL_dmeans3D)) ||
+        (saved->num_rendered > 0 && !g->scratch)) {
+        set_error("das3r_raster_backward_depth: null saved state / upstream gradient / gradient buffer");
+        return DAS3R_ERR_INVALID_ARG;
+    }
+    if (!(saved->flags & DEPTH_SAVED_FLAG)) {
+        set_error("das3r_raster_backward_depth: the saved state is not that of a forward with out_invdepth (das3r_raster_saved.flags bit 1 is clear)");
+        return DAS3R_ERR_INVALID_ARG;
+    }
+    const bool has_sh = in->shs != nullptr, has_cov = in->cov3D_precomp != nullptr;
+    if ((has_sh && !g->dL_dshs) || (!has_sh && !g->dL_dcolors_precomp) || (has_cov && !g->dL_dcov3D) ||
+        (!has_cov && !chained && (!g->dL_dscales || !g->dL_drotations))) {
+        set_error("das3r_raster_backward_depth: gradient buffer missing for a provided input");
+        return DAS3R_ERR_INVALID_ARG;
+    }
+    const int kind = switches().render_bwd;
+    if (kind == 2 || kind == 3 || kind == 5) {
+        set_error("das3r_raster_backward_depth: DAS3R_RENDER_BWD=%s has no inverse-depth form", kind == 3 ? "scan" : (kind == 2 ? "mfma" : "stream"));
+        return DAS3R_ERR_INVALID_ARG;
+    }
+    if ((rc = das3r_raster_check(saved, stream))) return rc;
+    Layout L;
+    compute_layout(P, saved->capacity > 0 ? saved->capacity : saved->num_rendered, a->image_width, a->image_height, &L);
+    float *partial = g->scratch;
+    const float *dz = nullptr;
+    bool quad_rows = false;
+    if (saved->num_rendered > 0) {
+        if (!saved->binning) { set_error("das3r_raster_backward_depth: binning buffer missing"); return DAS3R_ERR_INVALID_ARG; }
+        const size_t c = L.capacity > 0 ? (size_t)L.capacity : 1;
+        float *partial_depth = (float *)((char *)g->scratch + align_up(c * 9 * sizeof(float) + 16));
+        if ((rc = launch_render_backward(a, dL_dpix, saved->geom, saved->binning, saved->img, L, partial, s, &quad_rows, saved->num_rendered, saved->flags))) return rc;
+        if ((rc = launch_depth_pass_inputs(P, a->image_width * a->image_height, saved->geom, L, saved->binning, dL_dinvdepth, s, a->debug != 0))) return rc;
+        Layout Ld = L;   // the depth pass reads its splat records and checkpoints from the binning buffer's depth part
+        Ld.pub.xy = L.d_recs;
+        Ld.pub.conic_opacity = L.d_recs + 16;
+        Ld.pub.rgbd = L.d_recs + 32;
+        Ld.b_ckpt = L.d_ckpt;
+        das3r_raster_args ad = *a;
+        ad.bg = (const float *)(saved->binning + L.d_bg);
+        bool quad_rows_d = false;
+        if ((rc = launch_render_backward(&ad, (const float *)(saved->binning + L.d_dpix), saved->binning, saved->binning, saved->img, Ld, partial_depth, s,
+                                         &quad_rows_d, saved->num_rendered, saved->flags))) return rc;
+        float *dzw = (float *)(saved->binning + L.d_dz);
+        if ((rc = launch_depth_fold(P, saved->geom, L, partial, partial_depth, dzw, s, a->debug != 0))) return rc;
+        dz = dzw;
+    }
+    return launch_preprocess_backward(a, in, saved->geom, saved->binning, L, g, partial, s, quad_rows, dz);
+}
+
+// das3r_raster_backward_scratch_bytes' rows twice: the colour pass's and the depth pass's (whose first column is the per-instance depth sum)
+extern "C" size_t das3r_raster_backward_depth_scratch_bytes(int64_t capacity) {
+    const size_t c = capacity > 0 ? (size_t)capacity : 1;
+    return align_up(c * 9 * sizeof(float) + 16) + c * 9 * sizeof(float) + 16;
 }
 
 // One 36-byte row of partial sums per instance + 16 bytes (the per-Gaussian backward reads the rows of a workgroup as 16-byte

@@ -193,6 +193,8 @@ static inline int tile_bits(int ntiles) {
 constexpr int BUCKET = 1024;
 constexpr int SPLAT_REC = 4;   // float4s per Gaussian record (xyh, conic+opacity, rgb+depth, pad): 64 bytes, one cache-line gather
 
+// das3r_raster_saved.flags bit 1 (ABI 16): the forward was given out_invdepth, its binning buffer holds Layout::d_* (bits 0 and 8 - 15: api.hip)
+constexpr uint32_t DEPTH_SAVED_FLAG = 2u;
 struct Layout {
     das3r_raster_layout pub;
     // private scratch offsets
@@ -200,6 +202,10 @@ struct Layout {
     size_t b_keyA, b_keyB, b_valA, b_valB, b_hist, b_totals, b_gid_of, b_slot;
     size_t b_e2;     // u32[capacity]: ping-pong partner of b_slot for the emission slots travelling through the partition passes
     size_t b_ckpt;   // float4[(capacity / BUCKET + ntiles + 2) * 256]: per-pixel (T, C) at the bucket boundaries of long tile lists
+    // ABI 16: what a forward with out_invdepth appends to the binning buffer (pub.binning_bytes .. d_bytes; a colour-only forward's layout is
+    // unchanged).  d_ckpt: per-pixel (T, D, 0, 0) at the same bucket boundaries as b_ckpt (D = inverse depth so far) — the depth as the first
+    // colour of a checkpoint; d_recs / d_dpix / d_bg / d_dz: written by das3r_raster_backward_depth (api.hip) for its depth pass.
+    size_t d_ckpt, d_recs, d_dpix, d_bg, d_dz, d_bytes;
     // single-pass radix control words (sort_onesweep.hip): [global digit histograms][tickets][status granules], contiguous
     // so that one store loop / one memset zeroes them: geom side by preprocess_kernel, binning side by a memset before emit
     size_t g_ghist, g_ticket, g_status, g_scan_status, g_ctrl_bytes;
@@ -290,16 +296,16 @@ inline PreXform pre_xform(const das3r_raster_in *in) {
     return x;
 }
 int launch_render_forward_regions(const das3r_raster_args *a, float *out_color, char *geom, char *binning, char *img, const Layout &L, const LocalBin &lb,
-                                  hipStream_t s);   // the same shapes: sixteen lanes per pixel, a wave per 2x2 region, four workgroups per tile (render_regions.hip)
+                                  hipStream_t s, float *out_invdepth, float4 *dckpt);   // the same shapes: sixteen lanes per pixel, a wave per 2x2 region, four workgroups per tile (render_regions.hip)
 int launch_tile_lpt(char *img, const Layout &L, uint32_t cap, bool debug, hipStream_t s);   // render_regions.hip
 int launch_list_skew(const char *img, const char *binning, const char *geom, const Layout &L, uint32_t cap, uint32_t last_g, uint32_t *mailbox_words, uint32_t tag,
                      bool debug, hipStream_t s);
 int launch_render_forward_slices(const das3r_raster_args *a, float *out_color, char *geom, char *binning, char *img, const Layout &L, const LocalBin &lb,
                                  hipStream_t s);   // the same shapes, a block's list cut into chunks any wave takes (render_slices.hip)
 int launch_render_forward_lanes(const das3r_raster_args *a, float *out_color, char *geom, char *binning, char *img, const Layout &L,
-                                const LocalBin &lb, hipStream_t s);
+                                const LocalBin &lb, hipStream_t s, float *out_invdepth, float4 *dckpt);
 int launch_render_forward_rows(const das3r_raster_args *a, float *out_color, char *geom, char *binning, char *img, const Layout &L,
-                               const LocalBin &lb, hipStream_t s);
+                               const LocalBin &lb, hipStream_t s, float *out_invdepth, float4 *dckpt);
 int launch_render_backward_mfma(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
                                 float *partial, hipStream_t s);
 // independent waves (render_bwd_stream.hip): scratch = rows[capacity][4][12] + one byte per row that exists
@@ -331,7 +337,12 @@ int launch_segment_sort(int64_t cap, const uint32_t *n_ptr, const uint32_t *keys
                         hipStream_t s, int dbits, uint2 *ranges, const uint32_t *err, uint32_t *host_late, uint32_t tag, uint32_t inject);
 // lb.point_list != null: the tile lists are in index order and the kernel sorts them by depth first
 int launch_render_forward(const das3r_raster_args *a, const float *colors_precomp, float *out_color, char *geom, char *binning,
-                          char *img, const Layout &L, const LocalBin &lb, hipStream_t s);
+                          char *img, const Layout &L, const LocalBin &lb, hipStream_t s, float *out_invdepth /*ABI 16: NULL = colour only*/,
+                          float4 *dckpt /*with out_invdepth: Layout::d_ckpt*/);
+// ABI 16, das3r_raster_backward_depth (api.hip): the depth pass's splat records (xy, conic, (1/z, 0, 0, z)), upstream gradient planes
+// (dL/dinvdepth, 0, 0) and zero background; then the fold of its per-instance sums into the colour pass's and the per-Gaussian dL/dz.
+int launch_depth_pass_inputs(int P, int npix, const char *geom, const Layout &L, char *binning, const float *dL_dinvdepth, hipStream_t s, bool debug);
+int launch_depth_fold(int P, const char *geom, const Layout &L, float *partial, const float *partial_depth, float *dz, hipStream_t s, bool debug);
 // partial: [num_rendered, 9] per-instance sums written by the render backward, gathered by the preprocess backward
 // *quad_rows (out): false = partial[I][9], one row per instance; true = the stream kernel's rows[I][4][12] + existence bytes
 int launch_render_backward(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
@@ -339,7 +350,7 @@ int launch_render_backward(const das3r_raster_args *a, const float *dL_dpix, cha
 // pair_count.hip (measurement aid): out[0] += live pairs, out[1] += (pixel, list position) pairs below the pixel's n_contrib
 int launch_count_live_pairs(const das3r_raster_args *a, char *geom, char *binning, char *img, const Layout &L, unsigned long long *out, hipStream_t s);
 int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in *in, char *geom, char *binning, const Layout &L,
-                               const das3r_raster_grads *g, const float *partial, hipStream_t s, bool quad_rows);
+                               const das3r_raster_grads *g, const float *partial, hipStream_t s, bool quad_rows, const float *dz = nullptr /*ABI 16: [P] dL/dz of the depth pass, or null*/);
 
 // ---- device helpers ----
 #ifdef __HIPCC__

@@ -109,7 +109,9 @@ struct ChainArgs {
     float *g_conf_flat, *g_small, *det_partials;
     uint32_t *arrived;
 };
-template <bool HAS_SH, bool HAS_COV, bool STAGE_IN, bool STAGE_OUT, bool DEG0 = false, bool CHAIN = false>
+// DEPTH (ABI 16, das3r_raster_backward_depth): dz_g[i] = dL/dz of splat i from the inverse-depth image (launch_depth_fold) goes into
+// dL/dmeans3D along dz/dmeans3D = column 2 of the view matrix — before CHAIN carries dL/dmeans3D on to xyz and the pose.
+template <bool HAS_SH, bool HAS_COV, bool STAGE_IN, bool STAGE_OUT, bool DEG0 = false, bool CHAIN = false, bool DEPTH = false>
 __global__ void __launch_bounds__(256, DEG0 ? (CHAIN ? 4 : 6) : 3) preprocess_backward_kernel(
     int P, int D_in, int M, const float *__restrict__ means3D, const float *__restrict__ scales, float scale_modifier,
     const float *__restrict__ rotations, const float *__restrict__ shs, const float *__restrict__ cov3D_precomp,
@@ -121,7 +123,7 @@ __global__ void __launch_bounds__(256, DEG0 ? (CHAIN ? 4 : 6) : 3) preprocess_ba
     float *__restrict__ dL_dcolors_precomp /*[P,3] out, precomp mode*/, float *__restrict__ dL_dmeans3D,
     float *__restrict__ dL_dscales, float *__restrict__ dL_drot, float *__restrict__ dL_dsh, float *__restrict__ dL_dcov3D,
     const PreXform pre /*xyz != null (das3r_raster_in.pre): the raw parameters + the pose, as in preprocess.hip*/,
-    const ChainArgs ch /*CHAIN only*/
+    const ChainArgs ch /*CHAIN only*/, const float *__restrict__ dz_g /*DEPTH only*/
 #ifdef DAS3R_EXPERIMENTS
     , unsigned long long *__restrict__ trace /*common.h BLK_STAMP (tools/wg_trace.py), region 6*/
 #endif
@@ -520,6 +522,14 @@ __global__ void __launch_bounds__(256, DEG0 ? (CHAIN ? 4 : 6) : 3) preprocess_ba
             }
         }
 
+        if constexpr (DEPTH) {
+            if (visible) {
+                const float dz = dz_g[idx];
+                dmean[0] += dz * viewmatrix[2];
+                dmean[1] += dz * viewmatrix[6];
+                dmean[2] += dz * viewmatrix[10];
+            }
+        }
         if (XPOSE) {
 #pragma unroll
             for (int k = 0; k < 3; k++) o_m3d[k] = dmean[k], o_sc[k] = dscale[k];
@@ -653,7 +663,7 @@ static float *chain_scratch(hipStream_t s, size_t blocks, uint32_t **arrived) {
 }
 
 int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in *in, char *geom, char *binning, const Layout &L,
-                               const das3r_raster_grads *g, const float *partial, hipStream_t s, bool quad_rows) {
+                               const das3r_raster_grads *g, const float *partial, hipStream_t s, bool quad_rows, const float *dz) {
     const int P = a->P;
     if (P == 0) return DAS3R_OK;
     dim3 grid(div_up(P, 256)), block(256);
@@ -674,7 +684,7 @@ int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in
         a->viewmatrix, a->projmatrix, a->campos, a->image_width, a->image_height, a->tanfovx, a->tanfovy,                    \
         (const uint32_t *)(geom + L.pub.tiles_touched), (const uint8_t *)(geom + L.pub.clamped), partial, exists,        \
         (const uint32_t *)(geom + L.g_off_by_gid), g->dL_dmeans2D, g->dL_dopacities, g->dL_dcolors_precomp, g->dL_dmeans3D,  \
-        g->dL_dscales, g->dL_drotations, g->dL_dshs, g->dL_dcov3D, pre, ch PB_TRACE_ARG
+        g->dL_dscales, g->dL_drotations, g->dL_dshs, g->dL_dcov3D, pre, ch, dz PB_TRACE_ARG
     // ---- the chained form (das3r_raster_grads.chain): unstaged SH rows, raw parameters ----
     ChainArgs ch;
     memset(&ch, 0, sizeof(ch));
@@ -701,12 +711,18 @@ int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in
         ch.g_conf_flat = c->g_conf_flat; ch.g_small = c->g_small;
         ch.det_partials = chain_scratch(s, (size_t)grid.x, &ch.arrived);   // (null: float atomics, said once)
     }
-#define LAUNCH(SH, COV, SI, SO) DAS3R_LAUNCH((preprocess_backward_kernel<SH, COV, SI, SO>), grid, block, 0, s, ARGS)
-#define LAUNCH0(SH, COV) DAS3R_LAUNCH((preprocess_backward_kernel<SH, COV, false, false, true>), grid, block, 0, s, ARGS)
+    // (dz: the DEPTH instantiation of the same form)
+#define LAUNCH6(SH, COV, SI, SO, D0, CH)                                                                             \
+    do {                                                                                                             \
+        if (dz) DAS3R_LAUNCH((preprocess_backward_kernel<SH, COV, SI, SO, D0, CH, true>), grid, block, 0, s, ARGS); \
+        else DAS3R_LAUNCH((preprocess_backward_kernel<SH, COV, SI, SO, D0, CH>), grid, block, 0, s, ARGS);          \
+    } while (0)
+#define LAUNCH(SH, COV, SI, SO) LAUNCH6(SH, COV, SI, SO, false, false)
+#define LAUNCH0(SH, COV) LAUNCH6(SH, COV, false, false, true, false)
     const bool deg0 = a->sh_degree == 0 && !stage_out;
     if (g->chain) {
-        if (deg0) DAS3R_LAUNCH((preprocess_backward_kernel<true, false, false, false, true, true>), grid, block, 0, s, ARGS);
-        else DAS3R_LAUNCH((preprocess_backward_kernel<true, false, false, false, false, true>), grid, block, 0, s, ARGS);
+        if (deg0) LAUNCH6(true, false, false, false, true, true);
+        else LAUNCH6(true, false, false, false, false, true);
     } else if (has_sh && !has_cov) {
         if (stage_in) LAUNCH(true, false, true, true);
         else if (stage_out) LAUNCH(true, false, false, true);
@@ -724,8 +740,68 @@ int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in
     }
 #undef LAUNCH
 #undef LAUNCH0
+#undef LAUNCH6
 #undef ARGS
     KERNEL_CHECK(s, a->debug, "preprocess_backward");
+    return DAS3R_OK;
+}
+
+// ---- ABI 16: the depth pass of das3r_raster_backward_depth (api.hip) --------------------------------------------------------------------------
+// The inverse depth sum_i (1/z_i) alpha_i T_i is a fourth colour channel, and every gradient is linear in the upstream gradient: the backward of
+// (colour, inverse depth) is the colour backward plus the SAME compositing backward run once more on the colour (1/z, 0, 0), background 0 and
+// upstream gradient (dL/dinvdepth, 0, 0).  That second pass's dL/dalpha carries the term (1/z) dL/dinvdepth adds to c . dL/dpix, its bucket
+// starts take (D_final - D_far) dL/dinvdepth from the depth checkpoints (Layout::d_ckpt, written by the DEPTH forwards), and its colour sum of
+// channel 0 is the per-instance sum over pixels of alpha T dL/dinvdepth.  These two kernels make its inputs and fold its results in.
+__global__ void __launch_bounds__(256) depth_pass_inputs_kernel(int P, int npix, const float4 *__restrict__ rec_in /*geom records*/, float4 *__restrict__ rec_out,
+                                                                const float *__restrict__ dL_dinvdepth, float *__restrict__ dpix, float *__restrict__ bg) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < P) {
+        const float4 *r = rec_in + (size_t)i * SPLAT_REC;
+        float4 *o = rec_out + (size_t)i * SPLAT_REC;
+        const float4 c = r[2];
+        o[0] = r[0];
+        o[1] = r[1];
+        o[2] = make_float4(c.w > 0.f ? 1.0f / c.w : 0.f, 0.f, 0.f, c.w);   // (the forward's staged_invz; a culled splat is never read)
+    }
+    if (i < npix) {
+        dpix[i] = dL_dinvdepth[i];
+        dpix[(size_t)npix + i] = 0.f;
+        dpix[2 * (size_t)npix + i] = 0.f;
+    }
+    if (i < 4) bg[i] = 0.f;
+}
+// per splat: the geometry sums of the depth pass are added to the colour pass's rows (partial[3 .. 8]); the depth pass's channel-0 sums over the
+// splat's instances give dL/d(1/z), and dz[i] = -dL/d(1/z) / z^2.  Rows e0 .. e0 + tiles_touched - 1 belong to splat i alone: no atomics.
+__global__ void __launch_bounds__(256) depth_fold_kernel(int P, const uint32_t *__restrict__ tiles_touched, const uint32_t *__restrict__ off_by_gid,
+                                                         const float4 *__restrict__ rgbd, float *__restrict__ partial, const float *__restrict__ partial_depth,
+                                                         float *__restrict__ dz) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P) return;
+    const uint32_t n = tiles_touched[i];
+    float s = 0.f;
+    if (n > 0u) {
+        const uint32_t e0 = off_by_gid[i];
+        for (uint32_t k = 0; k < n; k++) {
+            const size_t row = (size_t)(e0 + k) * 9;
+            s += partial_depth[row];
+#pragma unroll
+            for (int q = 3; q < 9; q++) partial[row + q] += partial_depth[row + q];
+        }
+    }
+    const float z = rgbd[(size_t)i * SPLAT_REC].w;
+    dz[i] = n > 0u ? -s / (z * z) : 0.f;
+}
+int launch_depth_pass_inputs(int P, int npix, const char *geom, const Layout &L, char *binning, const float *dL_dinvdepth, hipStream_t s, bool debug) {
+    const int n = std::max(std::max(P, npix), 4);
+    DAS3R_LAUNCH(depth_pass_inputs_kernel, dim3(div_up(n, 256)), dim3(256), 0, s, P, npix, (const float4 *)(geom + L.pub.xy), (float4 *)(binning + L.d_recs),
+                 dL_dinvdepth, (float *)(binning + L.d_dpix), (float *)(binning + L.d_bg));
+    KERNEL_CHECK(s, debug, "depth_pass_inputs");
+    return DAS3R_OK;
+}
+int launch_depth_fold(int P, const char *geom, const Layout &L, float *partial, const float *partial_depth, float *dz, hipStream_t s, bool debug) {
+    DAS3R_LAUNCH(depth_fold_kernel, dim3(div_up(P, 256)), dim3(256), 0, s, P, (const uint32_t *)(geom + L.pub.tiles_touched),
+                 (const uint32_t *)(geom + L.g_off_by_gid), (const float4 *)(geom + L.pub.rgbd), partial, partial_depth, dz);
+    KERNEL_CHECK(s, debug, "depth_fold");
     return DAS3R_OK;
 }
 

@@ -155,7 +155,16 @@ __device__ __forceinline__ float alpha_if_visible(const float a1, const float po
 // lastf: staged index of the pixel's last contributor in the CURRENT batch, -1 = none yet (batch_begin / batch_end).
 struct PixelBlend {
     float T, C0, C1, C2, live, lastf;
+    float D;   // ABI 16, DEPTH instantiations only: the inverse depth sum(1/z alpha T)
 };
+// ABI 16 (das3r_raster_out.out_invdepth): the DEPTH instantiations of the forward kernels stage 1/z in the w component of a splat's
+// colour record — where the other kernels keep the view-space depth the walk never reads — so that the reciprocal is taken once per
+// staged entry, not once per pair; the colour arithmetic is untouched.  A record past the list (null_splat) keeps its 0.
+// (Called from the DEPTH branch of an `if constexpr` only: the colour-only statement stays as it was — even an identity wrapper around
+// the record load changed the register allocation of render_forward_rows_kernel.)
+__device__ __forceinline__ float4 staged_invz(const float4 r) {
+    return make_float4(r.x, r.y, r.z, 1.0f / r.w);   // (z > the near plane of preprocess: finite)
+}
 // Blend staged entry j (jf = (float)j, colour c, alpha `a` from alpha_if_visible) into the pixel.  The reference's loop:
 //     test_T = T (1 - alpha);  if (test_T < 1e-4) { done; } else { C += c alpha T; T = test_T; last = position; }
 //   * s = 1 where test_T >= 1e-4f, else 0: clamp(test_T 2^100 - c' 2^100) with c' the float below 1e-4f — the product and the
@@ -165,6 +174,8 @@ struct PixelBlend {
 //     w > 0 (w >= 1/255 there) and last where w = 0 (last >= -1).  (NOT med3(last, j, 1e30 w - 1): render_rows.hip reads a stale
 //     list byte past the end of a row's list — an inert pair, but its j may be below `last`, and the median would take it.)
 // T never drops below 1e-4 while a lane is live, and a stopped lane has alpha = 0: s = 1 there, nothing changes.
+// DEPTH: c.w is the staged 1/z (staged_invz) and D gathers it like a fourth colour channel.
+template <bool DEPTH = false>
 __device__ __forceinline__ void blend_pair(PixelBlend &px, const float alpha, const float4 c, const float jf) {
     const float a = alpha * px.live;
     const float test_T = px.T * (1.0f - a);
@@ -174,6 +185,7 @@ __device__ __forceinline__ void blend_pair(PixelBlend &px, const float alpha, co
     px.C0 = __fmaf_rn(c.x, wT, px.C0);
     px.C1 = __fmaf_rn(c.y, wT, px.C1);
     px.C2 = __fmaf_rn(c.z, wT, px.C2);
+    if constexpr (DEPTH) px.D = __fmaf_rn(c.w, wT, px.D);
     px.T = px.T * (1.0f - w);
     px.live *= s;
     px.lastf = fmaxf(px.lastf, fminf(jf, __fmaf_rn(w, 1e30f, -1.0f)));
@@ -365,7 +377,7 @@ struct NoMark {
     __device__ __forceinline__ void operator()(int) const {}
 };
 // mark(k): phase clocks of the experiments build (common.h PHASE_MARK; tools/phase_clocks.py), a no-op otherwise
-template <class Mark = NoMark>
+template <bool DEPTH = false, class Mark = NoMark>
 __device__ __forceinline__ bool local_order_tile(const LocalBin &lb, const uint2 range, const float4 *__restrict__ xyh,
                                                  const float4 *__restrict__ conic_opacity, const float4 *__restrict__ rgbd,
                                                  StagedSplat *stage /*[TILE_PIX]*/, uint32_t *s_gid /*[LOCAL_MAX]*/, const int tid,
@@ -398,7 +410,8 @@ __device__ __forceinline__ bool local_order_tile(const LocalBin &lb, const uint2
             }
             stage[rank].xyh = r0;
             stage[rank].co = r1;
-            stage[rank].rgbd = r2;
+            if constexpr (DEPTH) stage[rank].rgbd = staged_invz(r2);
+            else stage[rank].rgbd = r2;
             pl[rank] = g;
             sl[rank] = slot;
         } else {

@@ -5,12 +5,15 @@
 
 namespace das3r {
 
+// DEPTH (ABI 16): also blends 1/z (render_common.h staged_invz) and writes the inverse-depth image out_invdepth; off: today's kernel.
+template <bool DEPTH>
 __global__ void __launch_bounds__(256) render_forward_kernel(const uint2 *__restrict__ ranges, const uint32_t *__restrict__ point_list,
                                                              int W, int H, int tiles_x, int ntiles_strip /*render_common.h pack_tiles*/, const float4 *__restrict__ xyh,
                                                              const float4 *__restrict__ conic_opacity, const float4 *__restrict__ rgbd,
                                                              const float *__restrict__ bg, float *__restrict__ final_T,
                                                              uint32_t *__restrict__ n_contrib, float *__restrict__ out_color, const LocalBin lb,
-                                                             unsigned long long *__restrict__ pairs /*common.h pair_counters()*/) {
+                                                             unsigned long long *__restrict__ pairs /*common.h pair_counters()*/,
+                                                             float *__restrict__ out_invdepth, float4 *__restrict__ dckpt) {
     __shared__ StagedSplat stage[TILE_PIX];
     __shared__ uint32_t s_gid[LOCAL_MAX];   // local depth order: the tile's sorted list
     const int ntiles = packed_ntiles(ntiles_strip);
@@ -26,7 +29,7 @@ __global__ void __launch_bounds__(256) render_forward_kernel(const uint2 *__rest
     const uint2 range = safe_range(ranges[tile], lb.cap);
     const bool sorted_here = lb.point_list != nullptr && (int)(range.y - range.x) <= LOCAL_MAX;   // (uniform)
     // local depth order: sort this tile's list first (a list of one batch is staged by the sort itself)
-    const bool prestaged = lb.point_list != nullptr && local_order_tile(lb, range, xyh, conic_opacity, rgbd, stage, s_gid, threadIdx.x);
+    const bool prestaged = lb.point_list != nullptr && local_order_tile<DEPTH>(lb, range, xyh, conic_opacity, rgbd, stage, s_gid, threadIdx.x);
     int toDo = (int)(range.y - range.x);
     const int rounds = (toDo + TILE_PIX - 1) / TILE_PIX;
 
@@ -47,13 +50,17 @@ __global__ void __launch_bounds__(256) render_forward_kernel(const uint2 *__rest
     int visits = 0;   // (wave-uniform) (splat, quadrant) visits = 64 pairs each
     for (int i = 0; i < rounds; i++, toDo -= TILE_PIX) {
         if (__syncthreads_count(live == 0.f) == TILE_PIX) break;
-        if (nb > 1 && i > 0 && (i * TILE_PIX) % BUCKET == 0) ckpt_slot(lb.ckpt, range, tile, next_slot++)[cpix] = make_float4(T, C0, C1, C2);
+        if (nb > 1 && i > 0 && (i * TILE_PIX) % BUCKET == 0) {
+            if constexpr (DEPTH) ckpt_slot(dckpt, range, tile, next_slot)[cpix] = make_float4(T, pb.D, 0.f, 0.f);
+            ckpt_slot(lb.ckpt, range, tile, next_slot++)[cpix] = make_float4(T, C0, C1, C2);
+        }
         const uint32_t progress = range.x + i * TILE_PIX + tid;
         if (progress < range.y && !prestaged) {
             const uint32_t g = min(sorted_here ? s_gid[i * TILE_PIX + tid] : (lb.point_list ? lb.point_list[progress] : point_list[progress]), lb.last_g);
             stage[tid].xyh = xyh[(size_t)g * SPLAT_REC];           // one 64-byte record: a single cache line per splat
             stage[tid].co = conic_opacity[(size_t)g * SPLAT_REC];
-            stage[tid].rgbd = rgbd[(size_t)g * SPLAT_REC];
+            if constexpr (DEPTH) stage[tid].rgbd = staged_invz(rgbd[(size_t)g * SPLAT_REC]);
+            else stage[tid].rgbd = rgbd[(size_t)g * SPLAT_REC];
         }
         __syncthreads();
         const int n = toDo < TILE_PIX ? toDo : TILE_PIX;
@@ -80,12 +87,15 @@ __global__ void __launch_bounds__(256) render_forward_kernel(const uint2 *__rest
                 const float q = __fmaf_rn(__fmul_rn(co.x, dx), dx, __fmul_rn(__fmul_rn(co.z, dy), dy));
                 const float power = __fmaf_rn(-0.5f, q, -__fmul_rn(__fmul_rn(co.y, dx), dy));   // (pair_alpha's arithmetic, its
                 const float a1 = fminf(0.99f, __fmul_rn(co.w, __expf(power)));                    // two tests by arithmetic)
-                blend_pair(pb, alpha_if_visible(a1, power), c, (float)j);
+                blend_pair<DEPTH>(pb, alpha_if_visible(a1, power), c, (float)j);
             }
         }
         last_contributor = blend_batch_end(pb, last_contributor, (uint32_t)(i * TILE_PIX));
     }
-    for (; nb > 1 && next_slot < nb; next_slot++) ckpt_slot(lb.ckpt, range, tile, next_slot)[cpix] = make_float4(T, C0, C1, C2);   // (early exit: nothing changes any more)
+    for (; nb > 1 && next_slot < nb; next_slot++) {   // (early exit: nothing changes any more)
+        if constexpr (DEPTH) ckpt_slot(dckpt, range, tile, next_slot)[cpix] = make_float4(T, pb.D, 0.f, 0.f);
+        ckpt_slot(lb.ckpt, range, tile, next_slot)[cpix] = make_float4(T, C0, C1, C2);
+    }
     if (inside) {
         const size_t pix = (size_t)py * W + px, plane = (size_t)H * W;
         final_T[pix] = T;
@@ -93,6 +103,7 @@ __global__ void __launch_bounds__(256) render_forward_kernel(const uint2 *__rest
         out_color[pix] = C0 + T * bg[0];
         out_color[plane + pix] = C1 + T * bg[1];
         out_color[2 * plane + pix] = C2 + T * bg[2];
+        if constexpr (DEPTH) out_invdepth[pix] = pb.D;
     }
     if (pairs != nullptr && lane == 0 && visits > 0) {
         atomicAdd(pairs, (unsigned long long)visits * 64ull);
@@ -101,22 +112,31 @@ __global__ void __launch_bounds__(256) render_forward_kernel(const uint2 *__rest
 }
 
 int launch_render_forward(const das3r_raster_args *a, const float *colors_precomp, float *out_color, char *geom, char *binning,
-                          char *img, const Layout &L, const LocalBin &lb, hipStream_t s) {
+                          char *img, const Layout &L, const LocalBin &lb, hipStream_t s, float *out_invdepth, float4 *dckpt) {
     (void)colors_precomp;  // precomputed colours were copied into rgbd by the preprocess kernel
     if (use_quad_lanes(L, lb))
     {   // one workgroup per tile (lanes), or four (regions) where the tile lists are skewed: the host has been told by the forwards before this one
         const int f = switches().render_fwd;
-        if (f == 4) return launch_render_forward_slices(a, out_color, geom, binning, img, L, lb, s);
-        if (f == 5 || (f == 0 && lb.prefer_regions)) return launch_render_forward_regions(a, out_color, geom, binning, img, L, lb, s);
-        return launch_render_forward_lanes(a, out_color, geom, binning, img, L, lb, s);
+        if (f == 4) {
+            if (out_invdepth) {   // (das3r_raster_forward refuses this combination before it launches anything; kept as a guard)
+                set_error("DAS3R_RENDER=slices has no inverse-depth form (das3r_raster_out.out_invdepth)");
+                return DAS3R_ERR_INVALID_ARG;
+            }
+            return launch_render_forward_slices(a, out_color, geom, binning, img, L, lb, s);
+        }
+        if (f == 5 || (f == 0 && lb.prefer_regions)) return launch_render_forward_regions(a, out_color, geom, binning, img, L, lb, s, out_invdepth, dckpt);
+        return launch_render_forward_lanes(a, out_color, geom, binning, img, L, lb, s, out_invdepth, dckpt);
     }
-    if (use_row_private(L.capacity, L.ntiles)) return launch_render_forward_rows(a, out_color, geom, binning, img, L, lb, s);
+    if (use_row_private(L.capacity, L.ntiles)) return launch_render_forward_rows(a, out_color, geom, binning, img, L, lb, s, out_invdepth, dckpt);
     const int pad_lds = switches().fwd_pad_lds;   // occupancy experiments
-    DAS3R_LAUNCH(render_forward_kernel, dim3(xcd_grid(L)), dim3(TILE_PIX), pad_lds, s, (const uint2 *)(img + L.pub.ranges),
-                 (const uint32_t *)(binning + L.pub.point_list), a->image_width, a->image_height, L.tiles_x, pack_tiles(L),
-                 (const float4 *)(geom + L.pub.xy), (const float4 *)(geom + L.pub.conic_opacity),
-                 (const float4 *)(geom + L.pub.rgbd), a->bg, (float *)(img + L.pub.final_T), (uint32_t *)(img + L.pub.n_contrib),
-                 out_color, lb, pair_counters());
+#define ARGS                                                                                                                    \
+    (const uint2 *)(img + L.pub.ranges), (const uint32_t *)(binning + L.pub.point_list), a->image_width, a->image_height, L.tiles_x, \
+        pack_tiles(L), (const float4 *)(geom + L.pub.xy), (const float4 *)(geom + L.pub.conic_opacity),                              \
+        (const float4 *)(geom + L.pub.rgbd), a->bg, (float *)(img + L.pub.final_T), (uint32_t *)(img + L.pub.n_contrib), out_color, \
+        lb, pair_counters(), out_invdepth, dckpt
+    if (out_invdepth) DAS3R_LAUNCH((render_forward_kernel<true>), dim3(xcd_grid(L)), dim3(TILE_PIX), pad_lds, s, ARGS);
+    else DAS3R_LAUNCH((render_forward_kernel<false>), dim3(xcd_grid(L)), dim3(TILE_PIX), pad_lds, s, ARGS);
+#undef ARGS
     KERNEL_CHECK(s, a->debug, "render_forward");
     return DAS3R_OK;
 }

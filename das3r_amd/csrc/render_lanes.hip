@@ -23,13 +23,16 @@
 
 namespace das3r {
 
+// DEPTH (ABI 16): also blends the staged 1/z (render_common.h staged_invz) into out_invdepth.
+template <bool DEPTH>
 __global__ void __launch_bounds__(LN_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) render_forward_lanes_kernel(const uint2 *__restrict__ ranges, const uint32_t *__restrict__ point_list, int W, int H,
                                                                           int tiles_x, int ntiles_strip /*render_common.h pack_tiles*/,
                                                                           const float4 *__restrict__ xyh, const float4 *__restrict__ conic_opacity,
                                                                           const float4 *__restrict__ rgbd, const float *__restrict__ bg,
                                                                           float *__restrict__ final_T, uint32_t *__restrict__ n_contrib,
                                                                           float *__restrict__ out_color, const LocalBin lb,
-                                                                          unsigned long long *__restrict__ pairs /*common.h pair_counters()*/) {
+                                                                          unsigned long long *__restrict__ pairs /*common.h pair_counters()*/,
+                                                                          float *__restrict__ out_invdepth, float4 *__restrict__ dckpt) {
     __shared__ StagedSplat stage_all[2 * LN_BATCH];
     __shared__ uint16_t lists[16][LN_LIST];     // [wave][position]: staged index
     __shared__ uint32_t s_done[2][16];
@@ -45,6 +48,7 @@ __global__ void __launch_bounds__(LN_THREADS) __attribute__((amdgpu_waves_per_eu
     const int rounds = (int)((n + LN_BATCH - 1) / LN_BATCH);
     QuadLane q;
     q.T = 1.0f; q.live = inside ? 1.f : 0.f; q.C0 = q.C1 = q.C2 = 0.f;
+    if constexpr (DEPTH) q.D = 0.f;
     q.pxf = (float)px; q.pyf = (float)py; q.k = k; q.kf = (float)k;
     q.mk0 = k > 0 ? 0.f : 1.f; q.mk1 = k > 1 ? 0.f : 1.f; q.mk2 = k > 2 ? 0.f : 1.f;
     uint32_t last_contributor = 0;                                              // (this lane's entries; the quad's maximum is the pixel's)
@@ -66,7 +70,8 @@ __global__ void __launch_bounds__(LN_THREADS) __attribute__((amdgpu_waves_per_eu
             const uint32_t g = min(point_list[range.x + tid], lb.last_g);
             rec.xyh = xyh[(size_t)g * SPLAT_REC];
             rec.co = conic_opacity[(size_t)g * SPLAT_REC];
-            rec.rgbd = rgbd[(size_t)g * SPLAT_REC];
+            if constexpr (DEPTH) rec.rgbd = staged_invz(rgbd[(size_t)g * SPLAT_REC]);
+            else rec.rgbd = rgbd[(size_t)g * SPLAT_REC];
         }
         if ((uint32_t)(LN_BATCH + tid) < n) g_ahead = point_list[range.x + LN_BATCH + tid];
         stage_all[tid] = rec;
@@ -84,6 +89,10 @@ __global__ void __launch_bounds__(LN_THREADS) __attribute__((amdgpu_waves_per_eu
         if (nb > 1 && i > 0 && first % BUCKET == 0) {   // the state in front of list position `first`
             const float q0 = quad_sum(q.C0), q1 = quad_sum(q.C1), q2 = quad_sum(q.C2);
             if (k == 0) ckpt_slot(lb.ckpt, range, tile, next_slot)[cpix] = make_float4(q.T, q0, q1, q2);
+            if constexpr (DEPTH) {
+                const float qd = quad_sum(q.D);
+                if (k == 0) ckpt_slot(dckpt, range, tile, next_slot)[cpix] = make_float4(q.T, qd, 0.f, 0.f);
+            }
             next_slot++;
         }
         StagedSplat rec = null_splat();
@@ -93,7 +102,8 @@ __global__ void __launch_bounds__(LN_THREADS) __attribute__((amdgpu_waves_per_eu
                 const uint32_t g = min(g_ahead, lb.last_g);
                 rec.xyh = xyh[(size_t)g * SPLAT_REC];
                 rec.co = conic_opacity[(size_t)g * SPLAT_REC];
-                rec.rgbd = rgbd[(size_t)g * SPLAT_REC];
+                if constexpr (DEPTH) rec.rgbd = staged_invz(rgbd[(size_t)g * SPLAT_REC]);
+                else rec.rgbd = rgbd[(size_t)g * SPLAT_REC];
             }
             if (progress + LN_BATCH < range.y) g_ahead = point_list[progress + LN_BATCH];
         }
@@ -116,13 +126,18 @@ __global__ void __launch_bounds__(LN_THREADS) __attribute__((amdgpu_waves_per_eu
         if (loader && i + 1 < rounds) stage_all[((i + 1) & 1) * LN_BATCH + tid] = rec;
         if (wave_done) continue;   // (uniform; the wave has staged its share and meets the barriers)
         // ---- the walk: four entries per step, one per lane of a quad -----------------------------------------------------------
-        const float lastf = lanes_walk(stage, mine, len, q, steps);
+        const float lastf = lanes_walk<DEPTH>(stage, mine, len, q, steps);
         if (lastf >= 0.0f) last_contributor = first + (uint32_t)lastf + 1u;
     }
     const float q0 = quad_sum(q.C0), q1 = quad_sum(q.C1), q2 = quad_sum(q.C2);
     const uint32_t last = quad_max(last_contributor);
+    float qd = 0.f;
+    if constexpr (DEPTH) qd = quad_sum(q.D);
     if (k == 0)
-        for (; nb > 1 && next_slot < nb; next_slot++) ckpt_slot(lb.ckpt, range, tile, next_slot)[cpix] = make_float4(q.T, q0, q1, q2);   // (final values)
+        for (; nb > 1 && next_slot < nb; next_slot++) {   // (final values)
+            ckpt_slot(lb.ckpt, range, tile, next_slot)[cpix] = make_float4(q.T, q0, q1, q2);
+            if constexpr (DEPTH) ckpt_slot(dckpt, range, tile, next_slot)[cpix] = make_float4(q.T, qd, 0.f, 0.f);
+        }
     if (inside && k == 0) {
         const size_t at = (size_t)py * W + px, plane = (size_t)H * W;
         final_T[at] = q.T;
@@ -130,6 +145,7 @@ __global__ void __launch_bounds__(LN_THREADS) __attribute__((amdgpu_waves_per_eu
         out_color[at] = q0 + q.T * bg[0];
         out_color[plane + at] = q1 + q.T * bg[1];
         out_color[2 * plane + at] = q2 + q.T * bg[2];
+        if constexpr (DEPTH) out_invdepth[at] = qd;
     }
     if (pairs != nullptr && lane == 0 && steps > 0) {
         atomicAdd(pairs, (unsigned long long)steps * 64ull);
@@ -146,12 +162,13 @@ bool use_quad_lanes(const Layout &L, const LocalBin &lb) {
 }
 
 int launch_render_forward_lanes(const das3r_raster_args *a, float *out_color, char *geom, char *binning, char *img, const Layout &L, const LocalBin &lb,
-                                hipStream_t s) {
+                                hipStream_t s, float *out_invdepth, float4 *dckpt) {
 #define ARGS                                                                                                                                   \
     (const uint2 *)(img + L.pub.ranges), (const uint32_t *)(binning + L.pub.point_list), a->image_width, a->image_height, L.tiles_x, pack_tiles(L), \
         (const float4 *)(geom + L.pub.xy), (const float4 *)(geom + L.pub.conic_opacity), (const float4 *)(geom + L.pub.rgbd), a->bg,                \
-        (float *)(img + L.pub.final_T), (uint32_t *)(img + L.pub.n_contrib), out_color, lb, pair_counters()
-    DAS3R_LAUNCH(render_forward_lanes_kernel, dim3(xcd_grid(L)), dim3(LN_THREADS), 0, s, ARGS);
+        (float *)(img + L.pub.final_T), (uint32_t *)(img + L.pub.n_contrib), out_color, lb, pair_counters(), out_invdepth, dckpt
+    if (out_invdepth) DAS3R_LAUNCH((render_forward_lanes_kernel<true>), dim3(xcd_grid(L)), dim3(LN_THREADS), 0, s, ARGS);
+    else DAS3R_LAUNCH((render_forward_lanes_kernel<false>), dim3(xcd_grid(L)), dim3(LN_THREADS), 0, s, ARGS);
 #undef ARGS
     KERNEL_CHECK(s, a->debug, "render_forward_lanes");
     return DAS3R_OK;

@@ -58,12 +58,15 @@ __device__ __forceinline__ uint32_t quad_max(const uint32_t v) {
 // Per-pixel state of a quad's lanes and the lane's constants.  T and live are the same in the four lanes of a quad; C: this lane's entries.
 struct QuadLane {
     float T, live, C0, C1, C2;
+    float D;                             // ABI 16, DEPTH walks only: this lane's entries' sum(1/z alpha T)
     float pxf, pyf, kf, mk0, mk1, mk2;   // pixel centre; lane of the quad; max(1 - alpha_j, mk[j]): the factor of the quad's lane j in front of MY entry — 1 - alpha_j for j < k, 1 for j >= k
     int k;
 };
 
 // The walk of one block's list `mine[0 .. len)` (staged indices) of a staged batch: four entries per step, one per lane of a quad.
 // -> staged index of this lane's last contributing entry as a float, -1 = none.
+// DEPTH: c.w of a staged entry is 1/z (render_common.h staged_invz), gathered into q.D like a fourth colour channel.
+template <bool DEPTH = false>
 __device__ __forceinline__ float lanes_walk(const StagedSplat *__restrict__ stage, const uint16_t *__restrict__ mine, const int len, QuadLane &q, int &steps) {
     float lastf = -1.0f;
     const float lenf = (float)len - q.kf;   // (my position of step t exists where lenf - t >= 1)
@@ -100,6 +103,7 @@ __device__ __forceinline__ float lanes_walk(const StagedSplat *__restrict__ stag
         q.C0 = __fmaf_rn(c.x, wT, q.C0);
         q.C1 = __fmaf_rn(c.y, wT, q.C1);
         q.C2 = __fmaf_rn(c.z, wT, q.C2);
+        if constexpr (DEPTH) q.D = __fmaf_rn(c.w, wT, q.D);
         lastf = max_raw(lastf, min_raw(jf, __fmaf_rn(w, 1e30f, -1.0f)));
         q.T = t_next;
         q.live = l_next;

@@ -94,10 +94,13 @@ __device__ __forceinline__ uint32_t row_max_u32(uint32_t v) {
 // state of a row's pixel: T and live are the same in its sixteen lanes; C and the last contributor are per-lane partial results
 struct RowLane {
     float T, live, C0, C1, C2, pxf, pyf, ef;   // ef: my slot in a step, 0 .. 15
+    float D;                                   // ABI 16, DEPTH walks only: this lane's entries' sum(1/z alpha T)
 };
 
 // The walk of the region's list `mine[0 .. len)` (staged indices) of a staged batch: sixteen entries per step, one per lane of a row.
 // -> staged index of this lane's last contributing entry as a float, -1 = none.
+// DEPTH: c.w of a staged entry is 1/z (render_common.h staged_invz), gathered into q.D like a fourth colour channel.
+template <bool DEPTH = false>
 __device__ __forceinline__ float regions_walk(const StagedSplat *__restrict__ stage, const uint16_t *__restrict__ mine, const int len, const int e,
                                               RowLane &q, int &steps) {
     float lastf = -1.0f;
@@ -144,6 +147,7 @@ __device__ __forceinline__ float regions_walk(const StagedSplat *__restrict__ st
             q.C0 = __fmaf_rn(c[U].x, wT, q.C0);                                                                                     \
             q.C1 = __fmaf_rn(c[U].y, wT, q.C1);                                                                                     \
             q.C2 = __fmaf_rn(c[U].z, wT, q.C2);                                                                                     \
+            if constexpr (DEPTH) q.D = __fmaf_rn(c[U].w, wT, q.D);                                                                  \
             lastf = max_raw(lastf, min_raw((float)j[U], __fmaf_rn(w, 1e30f, -1.0f)));                                               \
             q.T = t_next;                                                                                                           \
             q.live = l_next;                                                                                                        \
@@ -160,11 +164,13 @@ __device__ __forceinline__ float regions_walk(const StagedSplat *__restrict__ st
     return lastf;
 }
 
+// DEPTH (ABI 16): also blends the staged 1/z (render_common.h staged_invz) into out_invdepth.
+template <bool DEPTH>
 __global__ void __launch_bounds__(RG_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) render_forward_regions_kernel(
     const uint2 *__restrict__ ranges, const uint32_t *__restrict__ point_list, int W, int H, int tiles_x, int ntiles_strip /*render_common.h pack_tiles*/,
     const float4 *__restrict__ xyh, const float4 *__restrict__ conic_opacity, const float4 *__restrict__ rgbd, const float *__restrict__ bg,
     float *__restrict__ final_T, uint32_t *__restrict__ n_contrib, float *__restrict__ out_color, const LocalBin lb,
-    unsigned long long *__restrict__ pairs /*common.h pair_counters()*/) {
+    unsigned long long *__restrict__ pairs /*common.h pair_counters()*/, float *__restrict__ out_invdepth, float4 *__restrict__ dckpt) {
     __shared__ StagedSplat stage_all[2 * RG_BATCH];
     __shared__ uint16_t lists[16][RG_LIST];     // [wave][position]: staged index
     __shared__ uint32_t s_done[2][16];
@@ -192,6 +198,7 @@ __global__ void __launch_bounds__(RG_THREADS) __attribute__((amdgpu_waves_per_eu
     const int rounds = (int)((n + RG_BATCH - 1) / RG_BATCH);
     RowLane q;
     q.T = 1.0f; q.live = inside ? 1.f : 0.f; q.C0 = q.C1 = q.C2 = 0.f;
+    if constexpr (DEPTH) q.D = 0.f;
     q.pxf = (float)px; q.pyf = (float)py; q.ef = (float)e;
     uint32_t last_contributor = 0;                                              // (this lane's entries; the row's maximum is the pixel's)
     const int nb = ckpt_buckets(range);
@@ -209,7 +216,8 @@ __global__ void __launch_bounds__(RG_THREADS) __attribute__((amdgpu_waves_per_eu
             const uint32_t g = min(point_list[range.x + tid], lb.last_g);
             rec.xyh = xyh[(size_t)g * SPLAT_REC];
             rec.co = conic_opacity[(size_t)g * SPLAT_REC];
-            rec.rgbd = rgbd[(size_t)g * SPLAT_REC];
+            if constexpr (DEPTH) rec.rgbd = staged_invz(rgbd[(size_t)g * SPLAT_REC]);
+            else rec.rgbd = rgbd[(size_t)g * SPLAT_REC];
         }
         if ((uint32_t)(RG_BATCH + tid) < n) g_ahead = point_list[range.x + RG_BATCH + tid];
         stage_all[tid] = rec;
@@ -228,6 +236,10 @@ __global__ void __launch_bounds__(RG_THREADS) __attribute__((amdgpu_waves_per_eu
         if (nb > 1 && i > 0 && first % BUCKET == 0) {   // the state in front of list position `first`
             const float q0 = row_sum(q.C0), q1 = row_sum(q.C1), q2 = row_sum(q.C2);
             if (e == 0) ckpt_slot(lb.ckpt, range, tile, next_slot)[cpix] = make_float4(q.T, q0, q1, q2);
+            if constexpr (DEPTH) {
+                const float qd = row_sum(q.D);
+                if (e == 0) ckpt_slot(dckpt, range, tile, next_slot)[cpix] = make_float4(q.T, qd, 0.f, 0.f);
+            }
             next_slot++;
         }
         StagedSplat rec = null_splat();
@@ -237,7 +249,8 @@ __global__ void __launch_bounds__(RG_THREADS) __attribute__((amdgpu_waves_per_eu
                 const uint32_t g = min(g_ahead, lb.last_g);
                 rec.xyh = xyh[(size_t)g * SPLAT_REC];
                 rec.co = conic_opacity[(size_t)g * SPLAT_REC];
-                rec.rgbd = rgbd[(size_t)g * SPLAT_REC];
+                if constexpr (DEPTH) rec.rgbd = staged_invz(rgbd[(size_t)g * SPLAT_REC]);
+                else rec.rgbd = rgbd[(size_t)g * SPLAT_REC];
             }
             if (progress + RG_BATCH < range.y) g_ahead = point_list[progress + RG_BATCH];
         }
@@ -261,13 +274,18 @@ __global__ void __launch_bounds__(RG_THREADS) __attribute__((amdgpu_waves_per_eu
             s_mask[(i + 1) & 1][tid] = (uint16_t)region_mask(rec.xyh, qcx0, qcy0);
         }
         if (wave_done) continue;   // (uniform; the wave has staged its share and meets the barriers)
-        const float lastf = regions_walk(stage, mine, len, e, q, steps);
+        const float lastf = regions_walk<DEPTH>(stage, mine, len, e, q, steps);
         if (lastf >= 0.0f) last_contributor = first + (uint32_t)lastf + 1u;
     }
     const float q0 = row_sum(q.C0), q1 = row_sum(q.C1), q2 = row_sum(q.C2);
     const uint32_t last = row_max_u32(last_contributor);
+    float qd = 0.f;
+    if constexpr (DEPTH) qd = row_sum(q.D);
     if (e == 0)
-        for (; nb > 1 && next_slot < nb; next_slot++) ckpt_slot(lb.ckpt, range, tile, next_slot)[cpix] = make_float4(q.T, q0, q1, q2);   // (final values)
+        for (; nb > 1 && next_slot < nb; next_slot++) {   // (final values)
+            ckpt_slot(lb.ckpt, range, tile, next_slot)[cpix] = make_float4(q.T, q0, q1, q2);
+            if constexpr (DEPTH) ckpt_slot(dckpt, range, tile, next_slot)[cpix] = make_float4(q.T, qd, 0.f, 0.f);
+        }
     if (inside && e == 0) {
         const size_t at = (size_t)py * W + px, plane = (size_t)H * W;
         final_T[at] = q.T;
@@ -275,6 +293,7 @@ __global__ void __launch_bounds__(RG_THREADS) __attribute__((amdgpu_waves_per_eu
         out_color[at] = q0 + q.T * bg[0];
         out_color[plane + at] = q1 + q.T * bg[1];
         out_color[2 * plane + at] = q2 + q.T * bg[2];
+        if constexpr (DEPTH) out_invdepth[at] = qd;
     }
     if (pairs != nullptr && lane == 0 && steps > 0) {
         atomicAdd(pairs, (unsigned long long)steps * 64ull);
@@ -366,12 +385,14 @@ int launch_list_skew(const char *img, const char *binning, const char *geom, con
 }
 
 int launch_render_forward_regions(const das3r_raster_args *a, float *out_color, char *geom, char *binning, char *img, const Layout &L, const LocalBin &lb,
-                                  hipStream_t s) {
+                                  hipStream_t s, float *out_invdepth, float4 *dckpt) {
 #define ARGS                                                                                                                                   \
     (const uint2 *)(img + L.pub.ranges), (const uint32_t *)(binning + L.pub.point_list), a->image_width, a->image_height, L.tiles_x, pack_tiles(L), \
         (const float4 *)(geom + L.pub.xy), (const float4 *)(geom + L.pub.conic_opacity), (const float4 *)(geom + L.pub.rgbd), a->bg,                \
-        (float *)(img + L.pub.final_T), (uint32_t *)(img + L.pub.n_contrib), out_color, lb, pair_counters()
-    DAS3R_LAUNCH(render_forward_regions_kernel, dim3(lb.tile_order ? 32 * div_up(L.ntiles, 8) : 4 * xcd_grid(L)), dim3(RG_THREADS), 0, s, ARGS);
+        (float *)(img + L.pub.final_T), (uint32_t *)(img + L.pub.n_contrib), out_color, lb, pair_counters(), out_invdepth, dckpt
+    const dim3 grid(lb.tile_order ? 32 * div_up(L.ntiles, 8) : 4 * xcd_grid(L));
+    if (out_invdepth) DAS3R_LAUNCH((render_forward_regions_kernel<true>), grid, dim3(RG_THREADS), 0, s, ARGS);
+    else DAS3R_LAUNCH((render_forward_regions_kernel<false>), grid, dim3(RG_THREADS), 0, s, ARGS);
 #undef ARGS
     KERNEL_CHECK(s, a->debug, "render_forward_regions");
     return DAS3R_OK;

@@ -82,15 +82,18 @@ __device__ __forceinline__ void build_row_lists(const StagedSplat *stage, const 
 // "320 bytes of LDS and 3 registers away") — 64 VGPRs (waves-per-EU attribute; two spills outside the walk) and exactly 20 480 B of
 // LDS: the done flags of the early exit live in the tail of s_gid instead of __syncthreads_count's 256-byte scratch, the list rows
 // lose their 4 bytes of bank padding.  1 M splats at 1080p: 0.2298 -> 0.2242 ms (same box, A-B-B-B).
+// DEPTH (ABI 16): also blends the staged 1/z (render_common.h staged_invz) into out_invdepth; the eight-workgroup register bound is not
+// asked of it (one more accumulator in the walk).
 #define FWD_WAVES(PREFETCH) __attribute__((amdgpu_waves_per_eu((PREFETCH) ? 1 : 8, 8)))
-template <bool PREFETCH>
-__global__ void __launch_bounds__(256) FWD_WAVES(PREFETCH) render_forward_rows_kernel(const uint2 *__restrict__ ranges, const uint32_t *__restrict__ point_list,
+template <bool PREFETCH, bool DEPTH = false>
+__global__ void __launch_bounds__(256) FWD_WAVES(PREFETCH || DEPTH) render_forward_rows_kernel(const uint2 *__restrict__ ranges, const uint32_t *__restrict__ point_list,
                                                                   int W, int H, int tiles_x, int ntiles_strip /*render_common.h pack_tiles*/, const float4 *__restrict__ xyh,
                                                                   const float4 *__restrict__ conic_opacity,
                                                                   const float4 *__restrict__ rgbd, const float *__restrict__ bg,
                                                                   float *__restrict__ final_T, uint32_t *__restrict__ n_contrib,
                                                                   float *__restrict__ out_color, const LocalBin lb,
-                                                                  unsigned long long *__restrict__ pairs_arg /*common.h pair_counters()*/) {
+                                                                  unsigned long long *__restrict__ pairs_arg /*common.h pair_counters()*/,
+                                                                  float *__restrict__ out_invdepth, float4 *__restrict__ dckpt) {
 #ifdef DAS3R_EXPERIMENTS
     DECODE_PAIRS_OR_TRACE(pairs_arg)   // (tools/wg_trace.py)
 #else
@@ -122,7 +125,7 @@ __global__ void __launch_bounds__(256) FWD_WAVES(PREFETCH) render_forward_rows_k
     const uint2 range = safe_range(ranges[tile], lb.cap);
     const bool sorted_here = lb.point_list != nullptr && (int)(range.y - range.x) <= LOCAL_MAX;   // (uniform)
     // local depth order: sort this tile's list first (a list of one batch is staged by the sort itself)
-    const bool prestaged = lb.point_list != nullptr && local_order_tile(lb, range, xyh, conic_opacity, rgbd, stage, s_gid, threadIdx.x, [&](const int k) { (void)k; PHASE_MARK(k) });
+    const bool prestaged = lb.point_list != nullptr && local_order_tile<DEPTH>(lb, range, xyh, conic_opacity, rgbd, stage, s_gid, threadIdx.x, [&](const int k) { (void)k; PHASE_MARK(k) });
     int toDo = (int)(range.y - range.x);
     const int rounds = (toDo + TILE_PIX - 1) / TILE_PIX;
     PHASE_MARK(0)   // prologue + local sort
@@ -165,13 +168,17 @@ __global__ void __launch_bounds__(256) FWD_WAVES(PREFETCH) render_forward_rows_k
             if (flags_free && (s_done[0] & s_done[1] & s_done[2] & s_done[3])) break;
         }
         PHASE_MARK(1)   // waiting for the workgroup's slowest wave
-        if (nb > 1 && i > 0 && (i * TILE_PIX) % BUCKET == 0) ckpt_slot(lb.ckpt, range, tile, next_slot++)[cpix] = make_float4(T, C0, C1, C2);
+        if (nb > 1 && i > 0 && (i * TILE_PIX) % BUCKET == 0) {
+            if constexpr (DEPTH) ckpt_slot(dckpt, range, tile, next_slot)[cpix] = make_float4(T, pb.D, 0.f, 0.f);
+            ckpt_slot(lb.ckpt, range, tile, next_slot++)[cpix] = make_float4(T, C0, C1, C2);
+        }
         const uint32_t progress = range.x + i * TILE_PIX + tid;
         if (PREFETCH) {
             if (progress < range.y) {
                 stage[tid].xyh = pf0;
                 stage[tid].co = pf1;
-                stage[tid].rgbd = pf2;
+                if constexpr (DEPTH) stage[tid].rgbd = staged_invz(pf2);
+                else stage[tid].rgbd = pf2;
             } else {
                 stage[tid] = null_splat();
             }
@@ -186,7 +193,8 @@ __global__ void __launch_bounds__(256) FWD_WAVES(PREFETCH) render_forward_rows_k
             const uint32_t g = min(sorted_here ? s_gid[i * TILE_PIX + tid] : (lb.point_list ? lb.point_list[progress] : point_list[progress]), lb.last_g);
             stage[tid].xyh = xyh[(size_t)g * SPLAT_REC];           // one 64-byte record: a single cache line per splat
             stage[tid].co = conic_opacity[(size_t)g * SPLAT_REC];
-            stage[tid].rgbd = rgbd[(size_t)g * SPLAT_REC];
+            if constexpr (DEPTH) stage[tid].rgbd = staged_invz(rgbd[(size_t)g * SPLAT_REC]);
+            else stage[tid].rgbd = rgbd[(size_t)g * SPLAT_REC];
         } else if (!prestaged) {
             stage[tid] = null_splat();   // (every staged entry is initialised: see null_splat)
         }
@@ -242,13 +250,16 @@ __global__ void __launch_bounds__(256) FWD_WAVES(PREFETCH) render_forward_rows_k
                 //  VALU -> SALU -> branch round trip)
                 const int j = jj[u];
                 const float4 c = lds_read4(&stage[j].rgbd);   // (b128, not b96: half the LDS cycles)
-                blend_pair(pb, aa[u], c, (float)((packed >> (8 * u)) & 0xFFu));   // (v_cvt_f32_ubyte<u>: straight from the list word)
+                blend_pair<DEPTH>(pb, aa[u], c, (float)((packed >> (8 * u)) & 0xFFu));   // (v_cvt_f32_ubyte<u>: straight from the list word)
             }
         }
         last_contributor = blend_batch_end(pb, last_contributor, (uint32_t)(i * TILE_PIX));
         PHASE_MARK(4)   // the walk
     }
-    for (; nb > 1 && next_slot < nb; next_slot++) ckpt_slot(lb.ckpt, range, tile, next_slot)[cpix] = make_float4(T, C0, C1, C2);   // (early exit: nothing changes any more)
+    for (; nb > 1 && next_slot < nb; next_slot++) {   // (early exit: nothing changes any more)
+        if constexpr (DEPTH) ckpt_slot(dckpt, range, tile, next_slot)[cpix] = make_float4(T, pb.D, 0.f, 0.f);
+        ckpt_slot(lb.ckpt, range, tile, next_slot)[cpix] = make_float4(T, C0, C1, C2);
+    }
     if (inside) {
         const size_t pix = (size_t)py * W + px, plane = (size_t)H * W;
         final_T[pix] = T;
@@ -256,6 +267,7 @@ __global__ void __launch_bounds__(256) FWD_WAVES(PREFETCH) render_forward_rows_k
         out_color[pix] = C0 + T * bg[0];
         out_color[plane + pix] = C1 + T * bg[1];
         out_color[2 * plane + pix] = C2 + T * bg[2];
+        if constexpr (DEPTH) out_invdepth[pix] = pb.D;
     }
     PHASE_MARK(5)   // output
     PHASE_END(0)
@@ -282,15 +294,18 @@ bool use_row_private(int64_t instances, int ntiles) {
 }
 
 int launch_render_forward_rows(const das3r_raster_args *a, float *out_color, char *geom, char *binning, char *img, const Layout &L,
-                               const LocalBin &lb, hipStream_t s) {
+                               const LocalBin &lb, hipStream_t s, float *out_invdepth, float4 *dckpt) {
 #define ARGS                                                                                                              \
     (const uint2 *)(img + L.pub.ranges), (const uint32_t *)(binning + L.pub.point_list), a->image_width, a->image_height,  \
         L.tiles_x, pack_tiles(L), (const float4 *)(geom + L.pub.xy), (const float4 *)(geom + L.pub.conic_opacity),         \
         (const float4 *)(geom + L.pub.rgbd), a->bg, (float *)(img + L.pub.final_T), (uint32_t *)(img + L.pub.n_contrib),   \
-        out_color, lb, PAIRS_ARG
+        out_color, lb, PAIRS_ARG, out_invdepth, dckpt
     // globally sorted lists and fewer tiles than the chip has workgroup slots (4 per CU and more): see PREFETCH
     const bool prefetch = lb.point_list == nullptr && L.ntiles <= 1024 && !switches().fwd_no_prefetch;
-    if (prefetch) DAS3R_LAUNCH((render_forward_rows_kernel<true>), dim3(xcd_grid(L)), dim3(TILE_PIX), 0, s, ARGS);
+    if (out_invdepth) {
+        if (prefetch) DAS3R_LAUNCH((render_forward_rows_kernel<true, true>), dim3(xcd_grid(L)), dim3(TILE_PIX), 0, s, ARGS);
+        else DAS3R_LAUNCH((render_forward_rows_kernel<false, true>), dim3(xcd_grid(L)), dim3(TILE_PIX), 0, s, ARGS);
+    } else if (prefetch) DAS3R_LAUNCH((render_forward_rows_kernel<true>), dim3(xcd_grid(L)), dim3(TILE_PIX), 0, s, ARGS);
     else DAS3R_LAUNCH((render_forward_rows_kernel<false>), dim3(xcd_grid(L)), dim3(TILE_PIX), 0, s, ARGS);
 #undef ARGS
     KERNEL_CHECK(s, a->debug, "render_forward_rows");

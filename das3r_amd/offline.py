@@ -115,12 +115,13 @@ class _EvalState:
 
 
 @torch.no_grad()
-def render_view_fused(model, view, pose7, background, pipe=PIPE):
+def render_view_fused(model, view, pose7, background, pipe=PIPE, invdepth=False):
     """render_test of one view (gaussian_renderer/__init__.py:152-277) with the pose pre-transform INSIDE the rasterizer's per-Gaussian
     kernel (include/das3r_raster.h das3r_raster_in.pre, as the direct training iteration uses it): R xyz + t, quaternion product, exp,
     sigmoid x the per-Gaussian conf_static column — the dozen PyTorch kernels of the reference's glue (a boolean-mask gather of every
     tensor among them: 190 bytes of SH per Gaussian copied per view) are not launched and the camera-frame tensors never exist.
-    Same arithmetic up to the rounding of the pre-transform (tests: within the parity bars of the glue form).  -> (image, radii)"""
+    Same arithmetic up to the rounding of the pre-transform (tests: within the parity bars of the glue form).  -> (image, radii), or with
+    invdepth (image, radii, inverse-depth image [1, H, W]: include/das3r_raster.h das3r_raster_out.out_invdepth)"""
     import ctypes as C
     from . import _lib
     from .rasterizer import _forward_full, _on_device, _stream, check_forward
@@ -142,37 +143,63 @@ def render_view_fused(model, view, pose7, background, pipe=PIPE):
     pre.conf_flat, pre.mask_index = conf.data_ptr(), None
     pre.R, pre.t, pre.Lq = st.mats.data_ptr(), st.mats.data_ptr() + 36, st.mats.data_ptr() + 48
     rs = _settings(view, model, pipe, background, 1.0, dev)
-    I, image, radii, geom, binning, img, cap = _forward_full(rs, xyz, st.packed_sh(model), st.e, op, sc, rot, st.e, pre=pre)
-    check_forward(cap, dev)   # (no backward pass will examine this forward's binning self-check)
-    return image, radii
+    res = _forward_full(rs, xyz, st.packed_sh(model), st.e, op, sc, rot, st.e, pre=pre, invdepth=invdepth)
+    check_forward(res[6], dev)   # (no backward pass will examine this forward's binning self-check)
+    return (res[1], res[2], res[7]) if invdepth else (res[1], res[2])
+
+
+def invdepth_median_rel_error(invdepth, depth):
+    """Diagnostic of --depth: median over the pixels with invdepth > 0 of |1/invdepth - depth| / depth, the rendered inverse depth against
+    a sequence's depth map (depth_maps/frame_%04d.npy, [H, W]).  NaN when no pixel is covered."""
+    inv = torch.as_tensor(invdepth).detach().reshape(-1).float().cpu()
+    d = torch.as_tensor(depth).detach().reshape(-1).float().cpu()
+    sel = (inv > 0) & (d > 0)
+    if not bool(sel.any()):
+        return float("nan")
+    return float(((1.0 / inv[sel] - d[sel]).abs() / d[sel]).median())
 
 
 @torch.no_grad()
-def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=None, poses=None, write=True, fused=False):
+def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=None, poses=None, write=True, fused=False, invdepth=None):
     """render.py:72-86.  views: cameras carrying .pose7 (qw, qx, qy, qz, tx, ty, tz world-to-camera); poses: optional [N, 4, 4]
     world-to-camera matrices that override them.  fused: render_view_fused instead of the reference's PyTorch glue in front of the
-    rasterizer (opt-in, like every fused form).  -> list of the rendered [3, H, W] tensors (on the device)."""
+    rasterizer (opt-in, like every fused form).  invdepth: a list that receives every view's inverse-depth image [1, H, W] (written as
+    invdepth/%05d.npy next to renders/ when `write`); None: colour only.  -> list of the rendered [3, H, W] tensors (on the device)."""
     dev = model.get_xyz.device
     background = background if background is not None else torch.zeros(3, device=dev)
     render_path = os.path.join(model_path, name, f"ours_{iteration}", "renders")
+    depth_path = os.path.join(model_path, name, f"ours_{iteration}", "invdepth")
+    want = invdepth is not None
     out = []
     for idx, view in enumerate(views):
         pose = view.pose7 if poses is None else tensor_from_camera(poses[idx], dev)
-        img = (render_view_fused(model, view, pose, background, pipe)[0] if fused
-               else das3r_render(view, model, pipe, background, camera_pose=pose, variant="test")["render"])
+        if fused:
+            res = render_view_fused(model, view, pose, background, pipe, invdepth=want)
+            img, inv = res[0], (res[2] if want else None)
+        else:
+            pkg = das3r_render(view, model, pipe, background, camera_pose=pose, variant="test", return_invdepth=want)
+            img, inv = pkg["render"], pkg.get("invdepth")
         out.append(img)
+        if want:
+            invdepth.append(inv)
         if write:
             save_image(img, os.path.join(render_path, f"{idx:05d}.png"))
+            if want:
+                os.makedirs(depth_path, exist_ok=True)
+                np.save(os.path.join(depth_path, f"{idx:05d}.npy"), inv[0].detach().cpu().numpy())
     return out
 
 
-def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=False, optimised_poses=False, device="cuda", write=True, fused=False):
+def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=False, optimised_poses=False, device="cuda", write=True, fused=False,
+                depth=False):
     """render.py:89-123: load the trained model, write pose_interpolated.npy, render the "interp" set.  seq: the sequence the model was
-    trained on (its cameras).  -> (iteration, list of rendered images)"""
+    trained on (its cameras).  depth: also the inverse-depth images (invdepth/%05d.npy) and, per view, the median relative error of
+    1 / invdepth against the sequence's depth map (printed: a diagnostic).  -> (iteration, list of rendered images)"""
     model, iteration = load_trained_model(model_path, iteration, sh_degree, device)
     inter = save_interpolate_pose(model_path, iteration)
     bg = torch.tensor([1.0, 1.0, 1.0] if white_background else [0.0, 0.0, 0.0], dtype=torch.float32, device=device)
     views = sequence_cameras(seq, device)
+    frames = list(range(len(views)))   # (the sequence frame of each view: its depth map)
     poses = None
     if optimised_poses:
         if inter is None:
@@ -183,8 +210,14 @@ def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=Fal
             if len(inter) != len(tr):
                 raise ValueError(f"pose_{iteration}.npy holds {len(inter)} poses, the sequence {len(views)} frames ({len(tr)} training frames)")
             views = [views[i] for i in tr]
+            frames = list(tr)
         poses = inter
-    return iteration, render_set(model_path, "interp", iteration, views, model, PIPE, bg, poses=poses, write=write, fused=fused)
+    inv = [] if depth else None
+    imgs = render_set(model_path, "interp", iteration, views, model, PIPE, bg, poses=poses, write=write, fused=fused, invdepth=inv)
+    if depth and seq.get("depths") is not None:
+        for idx, (f, d) in enumerate(zip(frames, inv)):
+            print(f"view {idx:05d} (frame {f}): median |1/invdepth - depth| / depth = {invdepth_median_rel_error(d, seq['depths'][f]):.4f}")
+    return iteration, imgs
 
 
 @torch.no_grad()
@@ -216,11 +249,14 @@ def main(argv=None):
     ap.add_argument("--optimised-poses", action="store_true", help="render from pose/pose_N.npy instead of the poses the cameras were loaded with")
     ap.add_argument("--dataset", default="sintel", choices=("sintel", "davis"))
     ap.add_argument("--fused", action="store_true", help="the pose pre-transform inside the rasterizer's kernels instead of the reference's PyTorch glue (render_view_fused)")
+    ap.add_argument("--depth", action="store_true", help="also write the inverse-depth images (invdepth/%%05d.npy next to renders/) and print each view's "
+                                                         "median relative error of 1/invdepth against the sequence's depth_maps")
     args = ap.parse_args(argv)
     from .io_formats import load_sequence
     print("Rendering " + args.model_path)
     seq = load_sequence(args.source_path, device="cuda", dataset=args.dataset)
-    it, imgs = render_sets(args.model_path, seq, args.iteration, args.sh_degree, args.white_background, args.optimised_poses, fused=args.fused)
+    it, imgs = render_sets(args.model_path, seq, args.iteration, args.sh_degree, args.white_background, args.optimised_poses, fused=args.fused,
+                           depth=args.depth)
     print(f"wrote {len(imgs)} images to {os.path.join(args.model_path, 'interp', f'ours_{it}', 'renders')}")
 
 

@@ -189,9 +189,10 @@ def _forward_impl(rs, means3D, sh, colors_precomp, opacities, scales, rotations,
     return _forward_full(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, exact=True)[:6]
 
 
-def _forward_full(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, exact=False, pre=None):
+def _forward_full(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, exact=False, pre=None, invdepth=False):
     """-> (num_rendered, color, radii, geom, binning, img, capacity); capacity >= num_rendered is what the binning buffer
-    was laid out for (`_lib.layout(P, capacity, W, H)`), == num_rendered when `exact`."""
+    was laid out for (`_lib.layout(P, capacity, W, H)`), == num_rendered when `exact`.  invdepth: the inverse-depth image [1, H, W]
+    (ABI 16, das3r_raster_out.out_invdepth) is appended to the tuple."""
     lib = _lib.load()
     device = means3D.device
     if device.type != "cuda":
@@ -208,8 +209,9 @@ def _forward_full(rs, means3D, sh, colors_precomp, opacities, scales, rotations,
         M = sh.shape[1]
     if P == 0:   # upstream: zero image, background not applied, empty radii
         e = torch.empty(0, dtype=torch.uint8, device=device)
-        return (0, torch.zeros(3, H, W, dtype=torch.float32, device=device), torch.zeros(0, dtype=torch.int32, device=device),
-                e, e, e, 0)
+        out = (0, torch.zeros(3, H, W, dtype=torch.float32, device=device), torch.zeros(0, dtype=torch.int32, device=device),
+               e, e, e, 0)
+        return out + (torch.zeros(1, H, W, dtype=torch.float32, device=device),) if invdepth else out
     # every pixel and every radii entry is written by the kernels: no memset needed
     color = torch.empty(3, H, W, dtype=torch.float32, device=device)
     radii = torch.empty(P, dtype=torch.int32, device=device)
@@ -220,6 +222,8 @@ def _forward_full(rs, means3D, sh, colors_precomp, opacities, scales, rotations,
     i = _fill_in(means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp, pre)
     o = _lib.RasterOut()
     o.out_color, o.radii = color.data_ptr(), radii.data_ptr()
+    inv = torch.empty(1, H, W, dtype=torch.float32, device=device) if invdepth else None
+    o.out_invdepth = _ptr(inv)
     saved = _lib.RasterSaved()
     with _on_device(device):
         rc = lib.das3r_raster_forward(C.byref(a), C.byref(i), C.byref(o), alloc.fns["geom"], alloc.fns["binning"],
@@ -229,11 +233,14 @@ def _forward_full(rs, means3D, sh, colors_precomp, opacities, scales, rotations,
     bufs = alloc.take()
     cap = _Capacity(saved.capacity)
     cap.check_word, cap.check_tag, cap.flags = saved.check_word, int(saved.check_tag), int(saved.flags)
-    return (int(rc), color, radii, bufs.get("geom", empty), bufs.get("binning", empty), bufs.get("img", empty), cap)
+    out = (int(rc), color, radii, bufs.get("geom", empty), bufs.get("binning", empty), bufs.get("img", empty), cap)
+    return out + (inv,) if invdepth else out
 
 
 def _backward_impl(rs, num_rendered, grad_out_color, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                   geom, binning, img, capacity=None, _scratch_misalign=0, pre=None, chain=None):
+                   geom, binning, img, capacity=None, _scratch_misalign=0, pre=None, chain=None, grad_invdepth=None):
+    """grad_invdepth ([1, H, W] or None): also the backward of the forward's inverse-depth image (ABI 16, das3r_raster_backward_depth; the
+    forward must have been made with invdepth=True).  grad_out_color may then be None (zero)."""
     ticket = capacity
     capacity = int(num_rendered) if capacity is None else int(capacity)
     lib = _lib.load()
@@ -255,7 +262,9 @@ def _backward_impl(rs, num_rendered, grad_out_color, means3D, sh, colors_precomp
         return g_means2D, g_colors, g_opac, g_means3D, g_cov, g_sh, g_scales, g_rot
     # per-instance partial sums, written by the render backward and added per Gaussian (no atomics, no memset by the caller)
     # (_scratch_misalign: tests hand the library a scratch buffer that is only 4-byte aligned — a C caller may)
-    scratch = torch.empty(int(lib.das3r_raster_backward_scratch_bytes(max(capacity, 1))) + int(_scratch_misalign), dtype=torch.uint8, device=device)
+    depth = grad_invdepth is not None
+    nbytes = (lib.das3r_raster_backward_depth_scratch_bytes if depth else lib.das3r_raster_backward_scratch_bytes)(max(capacity, 1))
+    scratch = torch.empty(int(nbytes) + int(_scratch_misalign), dtype=torch.uint8, device=device)
     keep = []
     a = _fill_args(rs, P, M, device, keep)
     i = _fill_in(means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp, pre)
@@ -275,9 +284,19 @@ def _backward_impl(rs, num_rendered, grad_out_color, means3D, sh, colors_precomp
     g.dL_dscales, g.dL_drotations = _ptr(g_scales), _ptr(g_rot)
     g.dL_dcov3D = _ptr(g_cov)
     g.scratch = scratch.data_ptr() + int(_scratch_misalign)
-    dL = grad_out_color.contiguous()
+    H, W = int(rs.image_height), int(rs.image_width)
+    dL = grad_out_color.contiguous() if grad_out_color is not None else torch.zeros(3, H, W, dtype=torch.float32, device=device)
     if dL.dtype != torch.float32:
         dL = dL.float()
+    if depth:
+        dD = grad_invdepth.contiguous()
+        if dD.dtype != torch.float32:
+            dD = dD.float()
+        with _on_device(device):
+            rc = lib.das3r_raster_backward_depth(C.byref(a), C.byref(i), C.byref(saved), C.c_void_p(dL.data_ptr()), C.c_void_p(dD.data_ptr()),
+                                                 C.byref(g), _stream(device))
+        _lib.check(rc, "das3r_raster_backward_depth")
+        return g_means2D, g_colors, g_opac, g_means3D, g_cov, g_sh, g_scales, g_rot
     with _on_device(device):
         rc = lib.das3r_raster_backward(C.byref(a), C.byref(i), C.byref(saved), C.c_void_p(dL.data_ptr()), C.byref(g),
                                        _stream(device))
@@ -315,6 +334,10 @@ _last = threading.local()
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
+        return _RasterizeGaussians._forward(ctx, False, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
+
+    @staticmethod
+    def _forward(ctx, invdepth, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
         device = means3D.device
         means3D = _prep(means3D, device, "means3D")
         sh = _prep(sh, device, "shs")
@@ -327,13 +350,14 @@ class _RasterizeGaussians(torch.autograd.Function):
         if raster_settings.debug:
             cpu_args = cpu_deep_copy_tuple(args)  # copy them before they can be corrupted
             try:
-                num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer, capacity = _forward_full(*args)
+                res = _forward_full(*args, invdepth=invdepth)
             except Exception as ex:
                 torch.save(cpu_args, "snapshot_fw.dump")
                 print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
                 raise ex
         else:
-            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer, capacity = _forward_full(*args)
+            res = _forward_full(*args, invdepth=invdepth)
+        num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer, capacity = res[:7]
         ctx.raster_settings = raster_settings
         ctx.num_rendered = num_rendered
         ctx.capacity = capacity
@@ -342,31 +366,48 @@ class _RasterizeGaussians(torch.autograd.Function):
                               binningBuffer, imgBuffer)
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)   # no zero-filled 'gradient' for radii on every backward (a fill kernel per step)
-        return color, radii
+        return (color, radii, res[7]) if invdepth else (color, radii)
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii):
+        return _RasterizeGaussians._backward(ctx, grad_out_color, None)
+
+    @staticmethod
+    def _backward(ctx, grad_out_color, grad_invdepth):
         rs = ctx.raster_settings
-        if grad_out_color is None:   # (grads are not materialised) nothing flows back
+        if grad_out_color is None and grad_invdepth is None:   # (grads are not materialised) nothing flows back
             return (None,) * 9
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, opacities, geomBuffer, binningBuffer,
          imgBuffer) = ctx.saved_tensors
         args = (rs, ctx.num_rendered, grad_out_color, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 geomBuffer, binningBuffer, imgBuffer, ctx.capacity)
+        kw = {} if grad_invdepth is None else {"grad_invdepth": grad_invdepth}   # (None: today's das3r_raster_backward call)
         if rs.debug:
             cpu_args = cpu_deep_copy_tuple(args)
             try:
-                out = _backward_impl(*args)
+                out = _backward_impl(*args, **kw)
             except Exception as ex:
                 torch.save(cpu_args, "snapshot_bw.dump")
                 print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
                 raise ex
         else:
-            out = _backward_impl(*args)
+            out = _backward_impl(*args, **kw)
         g_means2D, g_colors, g_opac, g_means3D, g_cov, g_sh, g_scales, g_rot = out
         return (g_means3D, g_means2D, g_sh if sh.numel() else None, g_colors if colors_precomp.numel() else None, g_opac,
                 g_scales if scales.numel() else None, g_rot if rotations.numel() else None,
                 g_cov if cov3Ds_precomp.numel() else None, None)
+
+
+class _RasterizeGaussiansInvDepth(torch.autograd.Function):
+    """_RasterizeGaussians with the inverse-depth image as a third output (ABI 16), differentiable: a backward that receives no gradient for
+    it is today's das3r_raster_backward call; otherwise das3r_raster_backward_depth takes both."""
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
+        return _RasterizeGaussians._forward(ctx, True, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _grad_radii, grad_invdepth):
+        return _RasterizeGaussians._backward(ctx, grad_out_color, grad_invdepth)
 
 
 class GaussianRasterizer(nn.Module):
@@ -392,7 +433,11 @@ class GaussianRasterizer(nn.Module):
             return present.bool()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None):
+                cov3D_precomp=None, return_invdepth=False):
+        """-> (color [3, H, W], radii [P]); with return_invdepth, (color, radii, invdepth [1, H, W]) as upstream's newer rasterizer returns:
+        per pixel sum_i (1/z_i) alpha_i T_i over the splats the colour is blended from, 0 where nothing is (no background term).  The
+        colour and radii are the same bit for bit either way.  The inverse depth is differentiable (back to means3D, scales, rotations,
+        opacities and means2D through alpha, and to means3D through 1/z)."""
         raster_settings = self.raster_settings
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
@@ -411,11 +456,15 @@ class GaussianRasterizer(nn.Module):
         if cov3D_precomp is None:
             cov3D_precomp = e
         _last.capacity = None
-        color, radii = rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                           raster_settings)
+        if return_invdepth:
+            color, radii, invdepth = _RasterizeGaussiansInvDepth.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                                                       cov3D_precomp, raster_settings)
+        else:
+            color, radii = rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                                               raster_settings)
         if not color.requires_grad and getattr(_last, "capacity", None) is not None:
             # evaluation (torch.no_grad, or no input that takes a gradient): no backward pass will examine this forward's binning
             # self-check, so it is examined here, before the image is used (include/das3r_raster.h: das3r_raster_check)
             check_forward(_last.capacity, means3D.device)
         _last.capacity = None
-        return color, radii
+        return (color, radii, invdepth) if return_invdepth else (color, radii)

@@ -172,16 +172,21 @@ def rasterizer_inputs(cam, pc, pipe, bg_color, scaling_modifier=1.0, override_co
 
 
 def das3r_render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, camera_pose=None,
-                 filtering=None, use_conf=True, fused=False, variant="render"):
+                 filtering=None, use_conf=True, fused=False, variant="render", return_invdepth=False):
     """viewpoint_camera: .FoVx .FoVy .image_height .image_width .projection_matrix (4x4, already transposed) [.camera_center for
     pipe.convert_SHs_python]; pc: splat model (das3r_amd.model.SplatModel or anything with the same attributes); pipe: .debug
-    .compute_cov3D_python .convert_SHs_python; camera_pose: (7,) tensor (qw,qx,qy,qz,tx,ty,tz), may require grad."""
+    .compute_cov3D_python .convert_SHs_python; camera_pose: (7,) tensor (qw,qx,qy,qz,tx,ty,tz), may require grad.
+    return_invdepth: render_pkg["invdepth"] = the [1, H, W] inverse-depth image (GaussianRasterizer.forward; differentiable)."""
     settings, kw = rasterizer_inputs(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, camera_pose, filtering,
                                      use_conf, fused, variant)
-    image, radii = GaussianRasterizer(raster_settings=settings)(**kw)
+    out = GaussianRasterizer(raster_settings=settings)(**kw, **({"return_invdepth": True} if return_invdepth else {}))   # (upstream's call when off)
+    image, radii = out[0], out[1]
     if variant == "confidence":
         return image   # (render_confidence returns the image alone: gaussian_renderer/__init__.py:510)
-    return {"render": image, "viewspace_points": kw["means2D"], "visibility_filter": radii > 0, "radii": radii}
+    pkg = {"render": image, "viewspace_points": kw["means2D"], "visibility_filter": radii > 0, "radii": radii}
+    if return_invdepth:
+        pkg["invdepth"] = out[2]
+    return pkg
 
 
 def das3r_render_3dgs(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None):

@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define DAS3R_ABI_VERSION 15
+#define DAS3R_ABI_VERSION 16
 
 typedef enum {
     DAS3R_OK = 0,
@@ -123,6 +123,13 @@ typedef struct {
 typedef struct {
     float *out_color; /* [3,H,W] planar */
     int32_t *radii;   /* [P] */
+    float *out_invdepth; /* ABI 16: [H,W] or NULL.  The inverse-depth image of upstream's newer rasterizer: per pixel sum_i (1/z_i) alpha_i T_i
+                          * over the splats the colour is blended from (same order, same alpha / T cut-offs; z_i = view-space depth), no
+                          * background term — an empty pixel is 0.  The colour, radii and everything saved for the backward pass are the
+                          * same bit for bit as without it; das3r_raster_saved.flags bit 1 marks such a forward (its binning buffer is
+                          * larger: it also holds the inverse depth at the bucket boundaries of long lists), and das3r_raster_backward_depth
+                          * differentiates it.  DAS3R_RENDER=slices has no form of it: the forward then fails with DAS3R_ERR_INVALID_ARG
+                          * before it launches anything.  NULL: as ABI 15 (a caller that zero-fills the struct keeps working). */
 } das3r_raster_out;
 
 /* What forward leaves behind for backward (upstream: geomBuffer, binningBuffer, imgBuffer, num_rendered). */
@@ -137,7 +144,8 @@ typedef struct {
     uint32_t flags;          /* ABI 14 (in what was the struct's tail padding: size and offsets unchanged).  Bit 0: this forward's tile lists are
                               * long and spatially coherent or skewed (a real sequence's depth maps) — it was composited by the 2x2-region kernel
                               * and its backward pass takes the 2x2-region kernel too (render_regions.hip / render_bwd_rgn.hip).  A caller that
-                              * rebuilds this struct for the backward call hands the forward's value back; 0 is always valid (block walk). */
+                              * rebuilds this struct for the backward call hands the forward's value back; 0 is always valid (block walk) for
+                              * das3r_raster_backward.  Bit 1 (ABI 16): the forward was given out_invdepth (das3r_raster_backward_depth needs it). */
 } das3r_raster_saved;
 
 /* Gradient outputs of backward.  Every buffer is fully written by the call (no pre-zeroing needed). */
@@ -167,6 +175,18 @@ int das3r_raster_backward(const das3r_raster_args *args, const das3r_raster_in *
  * 36 bytes (nine partial sums) per instance + 16 (the rows are read back as 16-byte words).  16-byte alignment of the buffer
  * lets the per-Gaussian backward do that; any other alignment falls back to 4-byte loads. */
 size_t das3r_raster_backward_scratch_bytes(int64_t capacity);
+
+/* ABI 16: the backward of a forward that was given out_invdepth — das3r_raster_backward for the colour gradient dL_dpix [3,H,W] plus
+ * that of dL_dinvdepth [H,W] (either may be all zero), into the same gradient outputs (grads->chain included: the depth term reaches
+ * dL/dmeans3D before the chain carries it on).  grads->scratch: das3r_raster_backward_depth_scratch_bytes(saved->capacity) bytes.
+ * A saved state without flags bit 1 (a colour-only forward, or a caller that handed back flags = 0) is refused with
+ * DAS3R_ERR_INVALID_ARG before anything is launched, as are DAS3R_RENDER_BWD=scan* (and the experiments build's mfma / stream). */
+int das3r_raster_backward_depth(const das3r_raster_args *args, const das3r_raster_in *in, const das3r_raster_saved *saved,
+                                const float *dL_dpix /* [3,H,W] */, const float *dL_dinvdepth /* [H,W] */, const das3r_raster_grads *grads,
+                                das3r_stream_t stream);
+/* das3r_raster_backward_scratch_bytes' nine-float rows twice (256-byte aligned between): the colour pass's and the depth pass's, whose
+ * first column is the per-instance sum over pixels of alpha T dL/dinvdepth. */
+size_t das3r_raster_backward_depth_scratch_bytes(int64_t capacity);
 
 /* das3r_raster_forward returns as soon as its kernels are enqueued.  Its binning kernels check themselves (a bounded wait on
  * another workgroup that timed out, an index out of range, counts that do not add up) and leave one word for the host; this call

@@ -172,7 +172,7 @@ bool use_onesweep() { return true; }   // the three-kernel radix passes are buil
 #endif
 bool use_tight_rect() { return !switches().rect_upstream; }
 
-void compute_layout(int P, int64_t I, int W, int H, Layout *L) {
+void compute_layout(int P, int64_t I, int W, int H, Layout *L, bool shjac) {
     memset(L, 0, sizeof(*L));
     const size_t Pn = P > 0 ? (size_t)P : 1, In = I > 0 ? (size_t)I : 1;
     L->capacity = I;
@@ -215,6 +215,7 @@ void compute_layout(int P, int64_t I, int W, int H, Layout *L) {
     L->g_status = take(onesweep_status_bytes((int64_t)Pn, 4));
     L->g_scan_status = take(scan_status_bytes((int)Pn));
     L->g_ctrl_bytes = o - L->g_ghist;
+    if (shjac) L->g_shjac = take(4 * 9 * Pn);   // (last: every other offset is the same with and without it)
     L->pub.geom_bytes = o;
     // binning
     o = 0;
@@ -482,8 +483,11 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
     }
     const int P = a->P, W = a->image_width, H = a->image_height;
     const bool depth = out->out_invdepth != nullptr;   // ABI 16: the binning buffer also holds Layout::d_* (d_bytes instead of binning_bytes)
+    // the geometry buffer also holds Layout::g_shjac (flags bit 2) — unless the caller said that no backward will read it (flags bit 3 on the
+    // way in, read before the struct is cleared below)
+    const bool shjac = in->shs != nullptr && a->sh_degree >= 2 && !(saved->flags & NO_BACKWARD_IN_FLAG);
     Layout L;
-    compute_layout(P, 0, W, H, &L);
+    compute_layout(P, 0, W, H, &L, shjac);
     saved->geom = alloc_geom(user, L.pub.geom_bytes);
     saved->img = alloc_img(user, L.pub.img_bytes);
     saved->binning = nullptr;
@@ -695,7 +699,7 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
         // of different density overflows rarely
         cap = std::max(verdict.last_I + verdict.last_I / 4, verdict.peak_I + verdict.peak_I / 20) + 4096;
         if (cap > (int64_t)0x7FFFFF00) cap = (int64_t)0x7FFFFF00;
-        compute_layout(P, cap, W, H, &L);
+        compute_layout(P, cap, W, H, &L, shjac);
         apply_seg();
         saved->binning = alloc_binning(user, depth ? L.d_bytes : L.pub.binning_bytes);
         if (!saved->binning) { set_error("scratch allocation failed (binning %zu B)", L.pub.binning_bytes); return DAS3R_ERR_ALLOC; }
@@ -748,7 +752,7 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
         verdict.peak_I = std::max(I, verdict.peak_I - verdict.peak_I / 1024);
         if (I > cap) {
             cap = I;
-            compute_layout(P, cap, W, H, &L);
+            compute_layout(P, cap, W, H, &L, shjac);
             saved->binning = alloc_binning(user, depth ? L.d_bytes : L.pub.binning_bytes);
             if (!saved->binning) { set_error("scratch allocation failed (binning %zu B)", L.pub.binning_bytes); return DAS3R_ERR_ALLOC; }
             apply_seg();
@@ -775,7 +779,7 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
             local = false;
             if ((rc = launch_depth_sort(P, saved->geom, L, 0, nullptr, 0, a->debug != 0, s))) return rc;
         }
-        compute_layout(P, cap, W, H, &L);
+        compute_layout(P, cap, W, H, &L, shjac);
         apply_seg();
         saved->binning = alloc_binning(user, depth ? L.d_bytes : L.pub.binning_bytes);
         if (!saved->binning) { set_error("scratch allocation failed (binning %zu B)", L.pub.binning_bytes); return DAS3R_ERR_ALLOC; }
@@ -786,7 +790,14 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
     saved->num_rendered = I;
     saved->capacity = cap;
     if (depth) saved->flags |= DEPTH_SAVED_FLAG;
+    if (shjac) saved->flags |= SHJAC_SAVED_FLAG;
     return I;
+}
+
+// flags bit 2: the forward left the SH colour's Jacobian for the per-Gaussian backward (Layout::g_shjac), which then reads it instead of
+// the SH rows.  Without it (a caller that handed back flags = 0) the backward reads the rows as before.
+static bool shjac_saved(const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_saved *saved) {
+    return (saved->flags & SHJAC_SAVED_FLAG) != 0 && in->shs != nullptr && a->sh_degree >= 2;
 }
 
 extern "C" int das3r_raster_backward(const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_saved *saved,
@@ -811,7 +822,7 @@ extern "C" int das3r_raster_backward(const das3r_raster_args *a, const das3r_ras
     // the forward's binning self-check first: nothing is launched on the strength of an invalid image / list
     if ((rc = das3r_raster_check(saved, stream))) return rc;
     Layout L;
-    compute_layout(P, saved->capacity > 0 ? saved->capacity : saved->num_rendered, a->image_width, a->image_height, &L);
+    compute_layout(P, saved->capacity > 0 ? saved->capacity : saved->num_rendered, a->image_width, a->image_height, &L, shjac_saved(a, in, saved));
     // scratch = per-instance partial sums [num_rendered, 9]; no accumulator needs zeroing (no atomics anywhere)
     float *partial = g->scratch;
     bool quad_rows = false;
@@ -858,7 +869,7 @@ extern "C" int das3r_raster_backward_depth(const das3r_raster_args *a, const das
     }
     if ((rc = das3r_raster_check(saved, stream))) return rc;
     Layout L;
-    compute_layout(P, saved->capacity > 0 ? saved->capacity : saved->num_rendered, a->image_width, a->image_height, &L);
+    compute_layout(P, saved->capacity > 0 ? saved->capacity : saved->num_rendered, a->image_width, a->image_height, &L, shjac_saved(a, in, saved));
     float *partial = g->scratch;
     const float *dz = nullptr;
     bool quad_rows = false;

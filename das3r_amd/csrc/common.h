@@ -195,6 +195,12 @@ constexpr int SPLAT_REC = 4;   // float4s per Gaussian record (xyh, conic+opacit
 
 // das3r_raster_saved.flags bit 1 (ABI 16): the forward was given out_invdepth, its binning buffer holds Layout::d_* (bits 0 and 8 - 15: api.hip)
 constexpr uint32_t DEPTH_SAVED_FLAG = 2u;
+// das3r_raster_saved.flags bit 2: the forward wrote the SH colour's Jacobian w.r.t. the view direction into the geometry buffer
+// (Layout::g_shjac; SH given and the active degree >= 2, where its 36 bytes are fewer than the coefficients the backward would re-read)
+constexpr uint32_t SHJAC_SAVED_FLAG = 4u;
+// das3r_raster_saved.flags bit 3, on the way IN to das3r_raster_forward: no backward pass will follow this forward (evaluation), so it leaves
+// out what only the backward reads (the Jacobian planes: bit 2 stays clear)
+constexpr uint32_t NO_BACKWARD_IN_FLAG = 8u;
 struct Layout {
     das3r_raster_layout pub;
     // private scratch offsets
@@ -220,6 +226,7 @@ struct Layout {
                                 // partition's digits start above them
     int part_passes;            // passes of the instance partition: tile_passes, or one more when the segmented path wants more bucket bits
     size_t g_dhist;
+    size_t g_shjac;   // f32[9][P] behind everything else of the geometry buffer: plane 3c + k = d(rgb_c)/d(dir_k) (preprocess.hip); 0 = none
     const uint32_t *dhist_ptr;  // round 6: where this forward's depth histogram really is (a library-owned slot: api.hip dhist_slots); null = geom + g_dhist
     size_t i_order;   // img buffer, u32[ntiles]: the tiles longest list first (render_regions.hip tile_lpt_kernel; round 6)
 };
@@ -241,7 +248,7 @@ struct LocalBin {
     bool prefer_regions;
     const uint32_t *tile_order;         // with prefer_regions: the tiles, longest list first (tile_lpt_kernel); null: the locality order
 };
-void compute_layout(int P, int64_t I, int W, int H, Layout *L);
+void compute_layout(int P, int64_t I, int W, int H, Layout *L, bool shjac = false);
 
 // Emission fused into the preprocess kernel (speculative local-order path, grid resident: api.hip).  status == null: off.
 // The control words live in a library-owned ring slot that is zero at rest (ghist, err: re-armed by tile_ranges_kernel) or

@@ -2,7 +2,8 @@
 // rect, SH -> RGB.  Replaces upstream:cuda_rasterizer/forward.cu preprocessCUDA for the call
 // at /root/reference/gaussian_renderer/__init__.py:131-140.
 //
-// Pure streaming map, HBM-bound: 44 + 12(D+1)^2 input bytes and 53 output bytes per Gaussian.  One lane per
+// Pure streaming map, HBM-bound: 44 + 12(D+1)^2 input bytes and 53 output bytes per Gaussian (+ 36 with SH at degree >= 2: the
+// colour's Jacobian w.r.t. the view direction, which the backward then reads instead of the 12(D+1)^2-byte row).  One lane per
 // Gaussian, 256-lane blocks; the (P,M,3) SH rows are 16-byte aligned (M = 16 -> 192 B) and are read as float4;
 // outputs are SoA so every store instruction of a wave writes one contiguous run.
 // Compiled with -ffp-contract=off: all arithmetic is plain IEEE fp32 (+,-,*,/,sqrt correctly rounded), which
@@ -29,7 +30,8 @@ __global__ void __launch_bounds__(256) preprocess_kernel(
     uint32_t *__restrict__ dhist /*segmented binning path: 256-bin depth histogram of this forward, zeroed by the caller (segkey.h); else null*/,
     uint32_t dhist_mask /*a pseudo-random 1 / (mask + 1) of the workgroups contribute (`sampled` below): a sample is all the bucket map needs*/,
     uint32_t *__restrict__ dhist_next /*round 6: the library's OTHER histogram slot, zeroed here for the next forward of this stream (api.hip dhist_slots); else null*/,
-    const PreXform pre /*xyz != null (round 6, das3r_raster_in.pre): the raw parameters + the pose; means3D / scales / rotations / opacities are not read*/) {
+    const PreXform pre /*xyz != null (round 6, das3r_raster_in.pre): the raw parameters + the pose; means3D / scales / rotations / opacities are not read*/,
+    float *__restrict__ shjac /*[9][P] or null: the colour's Jacobian w.r.t. the view direction, plane 3c + k = d(rgb_c)/d(dir_k) (Layout::g_shjac)*/) {
     const int gidx = blockIdx.x * blockDim.x + threadIdx.x;
     // Which workgroups sample the depth histogram: a full-avalanche hash of the index (round 5).  "Every (mask + 1)-th workgroup" is a
     // biased sample of a DAS3R model — its Gaussians are the pixels of its frames in row-major order, 256 of them are half an image row, and
@@ -120,6 +122,7 @@ __global__ void __launch_bounds__(256) preprocess_kernel(
     float4 xy_out = make_float4(0.f, 0.f, -1e30f, -1e30f);
     float4 co_out = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 rgbd_out = make_float4(0.f, 0.f, 0.f, 0.f);
+    float jac_out[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     int bx0 = 0, by0 = 0, bx1 = 0, by1 = 0;   // binned tile rectangle (fused emission)
 
     const float3 p_view = xform43(p, V);
@@ -168,8 +171,13 @@ __global__ void __launch_bounds__(256) preprocess_kernel(
                         }
                     }
                     col = sh_regs_to_rgb(D, sh, p, campos, clamp_out);
+                    if (shjac != nullptr) sh_ddir_regs(D, sh, p, campos, jac_out);
                 } else if (HAS_SH) {
-                    col = sh_to_rgb(D, M, shs + (size_t)idx * M * 3, p, campos, clamp_out);
+                    float sh[48];
+                    const float *row = shs + (size_t)idx * M * 3;
+                    load_sh_row(row, D, sh_vec_ok(row, D, M), sh);
+                    col = sh_regs_to_rgb(D, sh, p, campos, clamp_out);
+                    if (shjac != nullptr) sh_ddir_regs(D, sh, p, campos, jac_out);
                 } else {
                     col = make_float3(colors_precomp[3 * idx], colors_precomp[3 * idx + 1], colors_precomp[3 * idx + 2]);
                 }
@@ -205,6 +213,10 @@ __global__ void __launch_bounds__(256) preprocess_kernel(
     // the binned rectangle, packed (tile counts <= 255 per axis: 4080 pixels; above that the scan reads the records instead)
     rect32[idx] = tiles_out ? ((uint32_t)bx0 | ((uint32_t)bx1 << 8) | ((uint32_t)by0 << 16) | ((uint32_t)by1 << 24)) : 0u;
     clamped[idx] = clamp_out;
+    if (HAS_SH && shjac != nullptr) {   // (uniform) nine planes: every store of a wave is one contiguous 256-byte run
+#pragma unroll
+        for (int j = 0; j < 9; j++) shjac[(size_t)j * P + idx] = jac_out[j];
+    }
     }
     // The 64-byte records (xyh | conic + opacity | rgb + depth | radius, tiles_touched) leave through LDS: written per lane they
     // are four 16-byte stores at a 64-byte stride (256 separate write requests per wave); the workgroup's 256 records are one
@@ -387,13 +399,14 @@ int launch_preprocess(const das3r_raster_args *a, const das3r_raster_in *in, int
     while ((grid.x >> __builtin_popcount(dhist_mask)) > 512u) dhist_mask = (dhist_mask << 1) | 1u;
     const bool has_sh = in->shs != nullptr, has_cov = in->cov3D_precomp != nullptr;
     const PreXform pre = pre_xform(in);
+    float *const shjac = has_sh && L.g_shjac ? (float *)(geom + L.g_shjac) : nullptr;   // (the layout has the planes when the forward wants them)
 #define ARGS                                                                                                              \
     P, a->sh_degree, a->M, in->means3D, in->scales, a->scale_modifier, in->rotations, in->opacities, in->shs,             \
         in->cov3D_precomp, in->colors_precomp, a->viewmatrix, a->projmatrix, a->campos, a->image_width, a->image_height,  \
         a->tanfovx, a->tanfovy, L.tiles_x, L.tiles_y, radii, (uint32_t *)(geom + L.g_keyA), (float4 *)(geom + L.pub.xy),  \
         (float4 *)(geom + L.pub.conic_opacity), (float4 *)(geom + L.pub.rgbd), (uint8_t *)(geom + L.pub.clamped),         \
         (uint32_t *)(geom + L.pub.tiles_touched), (uint32_t *)(geom + L.g_rect), (use_tight_rect() ? 1 : 0) | (a->prefiltered ? 2 : 0), (uint32_t *)(geom + L.g_ghist), (uint32_t)(L.g_ctrl_bytes / 4),                 \
-        (uint32_t *)(img + L.pub.ranges), (uint32_t)(2 * L.ntiles), (uint32_t *)binning_ctrl, (uint32_t)(binning_ctrl_bytes / 4), arrive, host_out, tag, em, dhist, dhist_mask, dhist_next, pre
+        (uint32_t *)(img + L.pub.ranges), (uint32_t)(2 * L.ntiles), (uint32_t *)binning_ctrl, (uint32_t)(binning_ctrl_bytes / 4), arrive, host_out, tag, em, dhist, dhist_mask, dhist_next, pre, shjac
     const bool stage = has_sh && a->M == 16 && a->sh_degree >= 2 && ((uintptr_t)in->shs & 15) == 0 && !switches().no_sh_stage;
     if (has_sh && !has_cov && stage) DAS3R_LAUNCH((preprocess_kernel<true, false, true>), grid, block, 0, s, ARGS);
     else if (has_sh && has_cov && stage) DAS3R_LAUNCH((preprocess_kernel<true, true, true>), grid, block, 0, s, ARGS);

@@ -50,33 +50,6 @@ __device__ __forceinline__ void sh_basis(const int D, const float x, const float
     }
 }
 
-// d(rgb_c)/d(dir) for one channel; sh = that channel's coefficients accessed as SHC(k)
-#define SH_DDIR(SHC, dRdx, dRdy, dRdz)                                                                                          \
-    do {                                                                                                                        \
-        dRdx = 0.f; dRdy = 0.f; dRdz = 0.f;                                                                                     \
-        if (D > 0) {                                                                                                            \
-            dRdx = -SH_C1 * SHC(3);                                                                                             \
-            dRdy = -SH_C1 * SHC(1);                                                                                             \
-            dRdz = SH_C1 * SHC(2);                                                                                              \
-            if (D > 1) {                                                                                                        \
-                dRdx += SH_C2_0 * y * SHC(4) + SH_C2_2 * 2.f * -x * SHC(6) + SH_C2_3 * z * SHC(7) + SH_C2_4 * 2.f * x * SHC(8); \
-                dRdy += SH_C2_0 * x * SHC(4) + SH_C2_1 * z * SHC(5) + SH_C2_2 * 2.f * -y * SHC(6) + SH_C2_4 * 2.f * -y * SHC(8); \
-                dRdz += SH_C2_1 * y * SHC(5) + SH_C2_2 * 2.f * 2.f * z * SHC(6) + SH_C2_3 * x * SHC(7);                       \
-                if (D > 2) {                                                                                                    \
-                    dRdx += SH_C3_0 * SHC(9) * 3.f * 2.f * xy + SH_C3_1 * SHC(10) * yz + SH_C3_2 * SHC(11) * -2.f * xy +       \
-                            SH_C3_3 * SHC(12) * -3.f * 2.f * xz + SH_C3_4 * SHC(13) * (-3.f * xx + 4.f * zz - yy) +            \
-                            SH_C3_5 * SHC(14) * 2.f * xz + SH_C3_6 * SHC(15) * 3.f * (xx - yy);                                \
-                    dRdy += SH_C3_0 * SHC(9) * 3.f * (xx - yy) + SH_C3_1 * SHC(10) * xz +                                      \
-                            SH_C3_2 * SHC(11) * (-3.f * yy + 4.f * zz - xx) + SH_C3_3 * SHC(12) * -3.f * 2.f * yz +            \
-                            SH_C3_4 * SHC(13) * -2.f * xy + SH_C3_5 * SHC(14) * -2.f * yz + SH_C3_6 * SHC(15) * -3.f * 2.f * xy; \
-                    dRdz += SH_C3_1 * SHC(10) * xy + SH_C3_2 * SHC(11) * 4.f * 2.f * yz +                                      \
-                            SH_C3_3 * SHC(12) * 3.f * (2.f * zz - xx - yy) + SH_C3_4 * SHC(13) * 4.f * 2.f * xz +              \
-                            SH_C3_5 * SHC(14) * (xx - yy);                                                                      \
-                }                                                                                                               \
-            }                                                                                                                   \
-        }                                                                                                                       \
-    } while (0)
-
 // A wave's 64 rows of K floats (12- or 24-byte AoS gradient rows), stored with unit-stride dword stores: every lane parks its
 // row in the wave's private LDS scratch and the wave writes the 64 K floats back out in order.  Written lane by lane these rows
 // are K stores of 4 bytes at a K-word stride; on the 5 M-splat DAS3R-shaped scene the per-Gaussian backward wrote 1.24 GB for
@@ -104,6 +77,9 @@ __device__ __forceinline__ void wave_store_rows(float *__restrict__ dst /*row 0 
 // parameters, their Adam step, dL/d(confidence), the camera's 28 sums in a fixed order.  The four gradient tensors are neither written nor
 // read back (88 B per Gaussian) and the raw parameters are read once for the forward's inputs and the chain rule (40 B): the pair
 // preprocess_backward + pretransform_backward<1> 0.221 -> see docs/ledger.md (bi).  Needs the raw parameters (`pre`) and an unstaged SH layout.
+// waves per SIMD the unchained JAC forms are built for: the staged one's 26 KB of LDS would leave room for six workgroups per CU, its
+// registers for five (87 VGPRs; at six it spills)
+constexpr int JAC_WAVES = 5;
 struct ChainArgs {
     GeometryAdam A;
     float *g_conf_flat, *g_small, *det_partials;
@@ -111,8 +87,12 @@ struct ChainArgs {
 };
 // DEPTH (ABI 16, das3r_raster_backward_depth): dz_g[i] = dL/dz of splat i from the inverse-depth image (launch_depth_fold) goes into
 // dL/dmeans3D along dz/dmeans3D = column 2 of the view matrix — before CHAIN carries dL/dmeans3D on to xyz and the pose.
-template <bool HAS_SH, bool HAS_COV, bool STAGE_IN, bool STAGE_OUT, bool DEG0 = false, bool CHAIN = false, bool DEPTH = false>
-__global__ void __launch_bounds__(256, DEG0 ? (CHAIN ? 4 : 6) : 3) preprocess_backward_kernel(
+// JAC (das3r_raster_saved.flags bit 2): the forward left d(rgb)/d(view direction) in the geometry buffer (Layout::g_shjac, nine planes) and
+// the colour's view-direction term is taken from it instead of the SH row (36 instead of 192 bytes per splat at degree 3, bit for bit the same:
+// SH_DDIR's values in the same order).  No SH input is staged, so the staged form assembles its dL_dsh rows in two halves of 128 rows: 26 KB
+// of LDS instead of 53 (five workgroups per CU instead of three).
+template <bool HAS_SH, bool HAS_COV, bool STAGE_IN, bool STAGE_OUT, bool DEG0 = false, bool CHAIN = false, bool DEPTH = false, bool JAC = false>
+__global__ void __launch_bounds__(256, DEG0 ? (CHAIN ? 4 : 6) : JAC && !CHAIN ? JAC_WAVES : 3) preprocess_backward_kernel(
     int P, int D_in, int M, const float *__restrict__ means3D, const float *__restrict__ scales, float scale_modifier,
     const float *__restrict__ rotations, const float *__restrict__ shs, const float *__restrict__ cov3D_precomp,
     const float *__restrict__ viewmatrix, const float *__restrict__ projmatrix, const float *__restrict__ campos, int W, int H,
@@ -123,7 +103,7 @@ __global__ void __launch_bounds__(256, DEG0 ? (CHAIN ? 4 : 6) : 3) preprocess_ba
     float *__restrict__ dL_dcolors_precomp /*[P,3] out, precomp mode*/, float *__restrict__ dL_dmeans3D,
     float *__restrict__ dL_dscales, float *__restrict__ dL_drot, float *__restrict__ dL_dsh, float *__restrict__ dL_dcov3D,
     const PreXform pre /*xyz != null (das3r_raster_in.pre): the raw parameters + the pose, as in preprocess.hip*/,
-    const ChainArgs ch /*CHAIN only*/, const float *__restrict__ dz_g /*DEPTH only*/
+    const ChainArgs ch /*CHAIN only*/, const float *__restrict__ dz_g /*DEPTH only*/, const float *__restrict__ shjac /*JAC only: [9][P]*/
 #ifdef DAS3R_EXPERIMENTS
     , unsigned long long *__restrict__ trace /*common.h BLK_STAMP (tools/wg_trace.py), region 6*/
 #endif
@@ -132,8 +112,10 @@ __global__ void __launch_bounds__(256, DEG0 ? (CHAIN ? 4 : 6) : 3) preprocess_ba
     constexpr unsigned long long *trace = nullptr;
 #endif
     BLK_STAMP(trace, 6, 0)
-    // one 208-byte (13 x float4) LDS row per lane: SH coefficients in (STAGE_IN), dL_dsh out (STAGE_OUT)
-    __shared__ float4 sh_lds[(STAGE_IN || STAGE_OUT) ? 256 * 13 : 1];
+    // one 208-byte (13 x float4) LDS row per lane: SH coefficients in (STAGE_IN), dL_dsh out (STAGE_OUT; JAC: per half of the workgroup)
+    static_assert(!(JAC && (STAGE_IN || DEG0)), "JAC replaces the SH row at degree >= 2");
+    constexpr int LDS_ROWS = JAC ? 128 : 256;
+    __shared__ float4 sh_lds[(STAGE_IN || STAGE_OUT) ? LDS_ROWS * 13 : 1];
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     const int D = DEG0 ? 0 : D_in;
     // Everything a lane needs that does not depend on another load is requested FIRST, ahead of the SH staging loads and their
@@ -144,6 +126,9 @@ __global__ void __launch_bounds__(256, DEG0 ? (CHAIN ? 4 : 6) : 3) preprocess_ba
     float3 mean_in, sc_in = make_float3(0.f, 0.f, 0.f);
     float4 q_in = make_float4(0.f, 0.f, 0.f, 0.f);
     float c3_in[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float jac[JAC ? 9 : 1];   // (requested here with the rest: ledger (bj), a late request is one more trip to memory)
+#pragma unroll
+    for (int j = 0; j < (JAC ? 9 : 0); j++) jac[j] = shjac[(size_t)j * P + ic];
     float raw_x = 0.f, raw_y = 0.f, raw_z = 0.f, raw_s0 = 0.f, raw_s1 = 0.f, raw_s2 = 0.f, raw_o = 0.f, raw_c = 0.f;   // CHAIN: kept for the chain rule at the end
     float4 raw_q = make_float4(0.f, 0.f, 0.f, 0.f);
     long long raw_ci = 0;
@@ -181,7 +166,9 @@ __global__ void __launch_bounds__(256, DEG0 ? (CHAIN ? 4 : 6) : 3) preprocess_ba
     // with coalesced loads, 1024 rows at a time, and each lane then adds its own rows out of LDS in the same order as before
     // (bit-identical sums).  A lane used to walk its rows with one trip to L2 per row: the longest walk of 64 lanes set the pace.
     constexpr bool LDS_GATHER = STAGE_OUT;
-    constexpr int CHUNK_ROWS = 1020;                                      // 36 KB of the 52 KB region: 2304 float4 = 9 per thread with the 3 + 3 floats of alignment slack
+    // 36 KB of the 52 KB region: 2304 float4 = 9 per thread with the 3 + 3 floats of alignment slack; JAC: 26 KB, 1664 float4 in 7 per thread
+    constexpr int CHUNK_ROWS = JAC ? 738 : 1020;
+    constexpr int CHUNK_LOADS = JAC ? 7 : 9;
     float acc[9];
 #pragma unroll
     for (int q = 0; q < 9; q++) acc[q] = 0.f;
@@ -245,16 +232,16 @@ __global__ void __launch_bounds__(256, DEG0 ? (CHAIN ? 4 : 6) : 3) preprocess_ba
             if (aligned_base) {
                 head = (int)((reinterpret_cast<uintptr_t>(src) & 15u) >> 2);
                 const float4 *src4 = reinterpret_cast<const float4 *>(src - head);
-                const int n4 = (head + n9 + 3) >> 2;   // <= 2304 = 9 x 256 (CHUNK_ROWS)
-                float4 w[9];
+                const int n4 = (head + n9 + 3) >> 2;   // <= 2304 = 9 x 256 (CHUNK_ROWS); JAC: <= 1662, inside the 1664 of the region
+                float4 w[CHUNK_LOADS];
 #pragma unroll
-                for (int i = 0; i < 9; i++) {
+                for (int i = 0; i < CHUNK_LOADS; i++) {
                     const int f = i * 256 + (int)threadIdx.x;
                     w[i] = src4[f < n4 ? f : n4 - 1];
                 }
                 if (!sh_requested) request_sh();
 #pragma unroll
-                for (int i = 0; i < 9; i++) {
+                for (int i = 0; i < CHUNK_LOADS; i++) {
                     const int f = i * 256 + (int)threadIdx.x;
                     if (f < n4) buf4[f] = w[i];
                 }
@@ -301,6 +288,9 @@ __global__ void __launch_bounds__(256, DEG0 ? (CHAIN ? 4 : 6) : 3) preprocess_ba
     float o_col[3] = {0.f, 0.f, 0.f}, o_sh0[3] = {0.f, 0.f, 0.f};
     static_assert(!CHAIN || (XPOSE && HAS_SH && !HAS_COV), "the chained backward: unstaged SH layouts, scales + rotations");
     float o_rot[4] = {0.f, 0.f, 0.f, 0.f}, o_op = 0.f;   // CHAIN: dL/d(camera-frame rotation, opacity) stay in registers like o_m3d / o_sc
+    constexpr bool HALVES = JAC && STAGE_OUT;   // the dL_dsh row waits in registers for its half's turn in LDS
+    float h_dir[3] = {0.f, 0.f, 0.f}, h_g[3] = {0.f, 0.f, 0.f};   // (the basis is evaluated again there: 6 registers instead of 19)
+    int h_nk = 0;
 
     if (idx < P) {
         const bool visible = ntiles_g > 0;
@@ -447,9 +437,17 @@ __global__ void __launch_bounds__(256, DEG0 ? (CHAIN ? 4 : 6) : 3) preprocess_ba
 #pragma unroll
                 for (int c = 0; c < 3; c++) g[c] = ((cl >> c) & 1) ? 0.f : acc[c];
                 sh_basis(D, x, y, z, basis);
+                if (HALVES) h_dir[0] = x, h_dir[1] = y, h_dir[2] = z;
                 float ddir[3] = {0.f, 0.f, 0.f};
                 if (D > 0) {
-                    if (STAGE_IN) {
+                    if (JAC) {
+#pragma unroll
+                        for (int c = 0; c < 3; c++) {
+                            ddir[0] += jac[3 * c] * g[c];
+                            ddir[1] += jac[3 * c + 1] * g[c];
+                            ddir[2] += jac[3 * c + 2] * g[c];
+                        }
+                    } else if (STAGE_IN) {
                         // the lane's 48 coefficients come out of LDS as twelve 16-byte reads (rows are 13 quad-words apart: no
                         // bank conflict); single-word reads of the same rows collide four ways (52-word stride; r02 PMC:
                         // 6.8e6 conflict cycles per launch at 1 M splats)
@@ -554,7 +552,11 @@ __global__ void __launch_bounds__(256, DEG0 ? (CHAIN ? 4 : 6) : 3) preprocess_ba
         // ---- dL_dsh row: basis[k] * g[c] for the active coefficients, zero above; zero row for culled splats
         if (HAS_SH) {
             const int nk = visible ? (D + 1) * (D + 1) : 0;
-            if (STAGE_OUT) {   // own LDS row (the SH inputs staged there are dead by now): 12 x ds_write_b128
+            if (HALVES) {
+#pragma unroll
+                for (int c = 0; c < 3; c++) h_g[c] = g[c];
+                h_nk = nk;
+            } else if (STAGE_OUT) {   // own LDS row (the SH inputs staged there are dead by now): 12 x ds_write_b128
 #pragma unroll
                 for (int i = 0; i < 12; i++) {
                     float o[4];
@@ -590,7 +592,34 @@ __global__ void __launch_bounds__(256, DEG0 ? (CHAIN ? 4 : 6) : 3) preprocess_ba
         else if (M == 1) wave_store_rows<3>(dL_dsh + 3 * (size_t)wave_first, rows_valid, o_sh0, xp, lane);
     }
     BLK_STAMP(trace, 6, 5)   // per-Gaussian arithmetic done, small rows stored
-    if (STAGE_OUT) {
+    if (HALVES) {   // lanes 0-127 then 128-255: 24 KB of contiguous rows each time (the gather is done with the region: its last barrier)
+        float4 *dst = reinterpret_cast<float4 *>(dL_dsh) + blk4;
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            if (h) __syncthreads();   // the first half's rows are out of LDS
+            if ((int)(threadIdx.x >> 7) == h && idx < P) {
+                float h_basis[16];
+                sh_basis(D, h_dir[0], h_dir[1], h_dir[2], h_basis);
+#pragma unroll
+                for (int i = 0; i < 12; i++) {
+                    float o[4];
+#pragma unroll
+                    for (int e = 0; e < 4; e++) {
+                        const int f = 4 * i + e, k = f / 3, c = f - 3 * k;
+                        o[e] = k < h_nk ? h_basis[k] * h_g[c] : 0.f;
+                    }
+                    sh_lds[(threadIdx.x & 127) * 13 + i] = make_float4(o[0], o[1], o[2], o[3]);
+                }
+            }
+            __syncthreads();
+            const size_t base = (size_t)h * 128 * 12;
+#pragma unroll
+            for (int i = 0; i < 6; i++) {
+                const int f = i * 256 + threadIdx.x;
+                if (base + f < limit4) dst[base + f] = sh_lds[(f / 12) * 13 + (f % 12)];
+            }
+        }
+    } else if (STAGE_OUT) {
         __syncthreads();
         float4 *dst = reinterpret_cast<float4 *>(dL_dsh) + blk4;
 #pragma unroll
@@ -672,7 +701,8 @@ int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in
     const size_t cap_rows = L.capacity > 0 ? (size_t)L.capacity : 1;
     const uint8_t *exists = quad_rows ? reinterpret_cast<const uint8_t *>(partial) + align_up(cap_rows * 4 * 12 * sizeof(float)) : nullptr;
     const bool stage_out = has_sh && a->M == 16 && ((uintptr_t)g->dL_dshs & 15) == 0 && !nostage;
-    const bool stage_in = stage_out && a->sh_degree >= 2 && ((uintptr_t)in->shs & 15) == 0;
+    const bool jac = has_sh && L.g_shjac != 0;   // (api.hip shjac_saved: flags bit 2, degree >= 2)
+    const bool stage_in = stage_out && a->sh_degree >= 2 && ((uintptr_t)in->shs & 15) == 0 && !jac;
 #ifdef DAS3R_EXPERIMENTS
 #define PB_TRACE_ARG , wg_trace()
 #else
@@ -684,7 +714,7 @@ int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in
         a->viewmatrix, a->projmatrix, a->campos, a->image_width, a->image_height, a->tanfovx, a->tanfovy,                    \
         (const uint32_t *)(geom + L.pub.tiles_touched), (const uint8_t *)(geom + L.pub.clamped), partial, exists,        \
         (const uint32_t *)(geom + L.g_off_by_gid), g->dL_dmeans2D, g->dL_dopacities, g->dL_dcolors_precomp, g->dL_dmeans3D,  \
-        g->dL_dscales, g->dL_drotations, g->dL_dshs, g->dL_dcov3D, pre, ch, dz PB_TRACE_ARG
+        g->dL_dscales, g->dL_drotations, g->dL_dshs, g->dL_dcov3D, pre, ch, dz, jac ? (const float *)(geom + L.g_shjac) : nullptr PB_TRACE_ARG
     // ---- the chained form (das3r_raster_grads.chain): unstaged SH rows, raw parameters ----
     ChainArgs ch;
     memset(&ch, 0, sizeof(ch));
@@ -712,17 +742,27 @@ int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in
         ch.det_partials = chain_scratch(s, (size_t)grid.x, &ch.arrived);   // (null: float atomics, said once)
     }
     // (dz: the DEPTH instantiation of the same form)
-#define LAUNCH6(SH, COV, SI, SO, D0, CH)                                                                             \
-    do {                                                                                                             \
-        if (dz) DAS3R_LAUNCH((preprocess_backward_kernel<SH, COV, SI, SO, D0, CH, true>), grid, block, 0, s, ARGS); \
-        else DAS3R_LAUNCH((preprocess_backward_kernel<SH, COV, SI, SO, D0, CH>), grid, block, 0, s, ARGS);          \
+#define LAUNCH7(SH, COV, SI, SO, D0, CH, J)                                                                                \
+    do {                                                                                                                   \
+        if (dz) DAS3R_LAUNCH((preprocess_backward_kernel<SH, COV, SI, SO, D0, CH, true, J>), grid, block, 0, s, ARGS);    \
+        else DAS3R_LAUNCH((preprocess_backward_kernel<SH, COV, SI, SO, D0, CH, false, J>), grid, block, 0, s, ARGS);      \
     } while (0)
+#define LAUNCH6(SH, COV, SI, SO, D0, CH) LAUNCH7(SH, COV, SI, SO, D0, CH, false)
 #define LAUNCH(SH, COV, SI, SO) LAUNCH6(SH, COV, SI, SO, false, false)
 #define LAUNCH0(SH, COV) LAUNCH6(SH, COV, false, false, true, false)
     const bool deg0 = a->sh_degree == 0 && !stage_out;
     if (g->chain) {
         if (deg0) LAUNCH6(true, false, false, false, true, true);
+        else if (jac) LAUNCH7(true, false, false, false, false, true, true);
         else LAUNCH6(true, false, false, false, false, true);
+    } else if (jac) {
+        if (has_cov) {
+            if (stage_out) LAUNCH7(true, true, false, true, false, false, true);
+            else LAUNCH7(true, true, false, false, false, false, true);
+        } else {
+            if (stage_out) LAUNCH7(true, false, false, true, false, false, true);
+            else LAUNCH7(true, false, false, false, false, false, true);
+        }
     } else if (has_sh && !has_cov) {
         if (stage_in) LAUNCH(true, false, true, true);
         else if (stage_out) LAUNCH(true, false, false, true);
@@ -741,6 +781,7 @@ int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in
 #undef LAUNCH
 #undef LAUNCH0
 #undef LAUNCH6
+#undef LAUNCH7
 #undef ARGS
     KERNEL_CHECK(s, a->debug, "preprocess_backward");
     return DAS3R_OK;

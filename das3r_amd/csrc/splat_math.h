@@ -166,6 +166,35 @@ __device__ __forceinline__ float3 sh_eval(const int deg, const float sh[48], con
     return make_float3(out[0], out[1], out[2]);
 }
 
+// d(rgb_c)/d(dir) for one channel; sh = that channel's coefficients accessed as SHC(k).  Needs D and the unit direction x, y, z with
+// xx, yy, zz, xy, yz, xz in scope.  The forward evaluates it once per splat into the geometry buffer's Jacobian planes (sh_ddir_planes);
+// the backward evaluates it itself when the forward did not (preprocess_bwd.hip): the same expressions in the same order, the same bits.
+#define SH_DDIR(SHC, dRdx, dRdy, dRdz)                                                                                          \
+    do {                                                                                                                        \
+        dRdx = 0.f; dRdy = 0.f; dRdz = 0.f;                                                                                     \
+        if (D > 0) {                                                                                                            \
+            dRdx = -SH_C1 * SHC(3);                                                                                             \
+            dRdy = -SH_C1 * SHC(1);                                                                                             \
+            dRdz = SH_C1 * SHC(2);                                                                                              \
+            if (D > 1) {                                                                                                        \
+                dRdx += SH_C2_0 * y * SHC(4) + SH_C2_2 * 2.f * -x * SHC(6) + SH_C2_3 * z * SHC(7) + SH_C2_4 * 2.f * x * SHC(8); \
+                dRdy += SH_C2_0 * x * SHC(4) + SH_C2_1 * z * SHC(5) + SH_C2_2 * 2.f * -y * SHC(6) + SH_C2_4 * 2.f * -y * SHC(8); \
+                dRdz += SH_C2_1 * y * SHC(5) + SH_C2_2 * 2.f * 2.f * z * SHC(6) + SH_C2_3 * x * SHC(7);                       \
+                if (D > 2) {                                                                                                    \
+                    dRdx += SH_C3_0 * SHC(9) * 3.f * 2.f * xy + SH_C3_1 * SHC(10) * yz + SH_C3_2 * SHC(11) * -2.f * xy +       \
+                            SH_C3_3 * SHC(12) * -3.f * 2.f * xz + SH_C3_4 * SHC(13) * (-3.f * xx + 4.f * zz - yy) +            \
+                            SH_C3_5 * SHC(14) * 2.f * xz + SH_C3_6 * SHC(15) * 3.f * (xx - yy);                                \
+                    dRdy += SH_C3_0 * SHC(9) * 3.f * (xx - yy) + SH_C3_1 * SHC(10) * xz +                                      \
+                            SH_C3_2 * SHC(11) * (-3.f * yy + 4.f * zz - xx) + SH_C3_3 * SHC(12) * -3.f * 2.f * yz +            \
+                            SH_C3_4 * SHC(13) * -2.f * xy + SH_C3_5 * SHC(14) * -2.f * yz + SH_C3_6 * SHC(15) * -3.f * 2.f * xy; \
+                    dRdz += SH_C3_1 * SHC(10) * xy + SH_C3_2 * SHC(11) * 4.f * 2.f * yz +                                      \
+                            SH_C3_3 * SHC(12) * 3.f * (2.f * zz - xx - yy) + SH_C3_4 * SHC(13) * 4.f * 2.f * xz +              \
+                            SH_C3_5 * SHC(14) * (xx - yy);                                                                      \
+                }                                                                                                               \
+            }                                                                                                                   \
+        }                                                                                                                       \
+    } while (0)
+
 // float4 reads are legal when the row is 16-byte aligned and the padded read stays inside the row
 __device__ __forceinline__ bool sh_vec_ok(const float *row, const int D, const int M) {
     const int n3 = 3 * (D + 1) * (D + 1);
@@ -181,15 +210,19 @@ __device__ __forceinline__ float3 sh_regs_to_rgb(const int D, const float sh[48]
     return make_float3(fmaxf(r.x, 0.f), fmaxf(r.y, 0.f), fmaxf(r.z, 0.f));
 }
 
-__device__ __forceinline__ float3 sh_to_rgb(const int D, const int M, const float *__restrict__ row, const float3 p,
-                                            const float *campos, uint8_t &clamp_bits) {
-    float sh[48];
-    load_sh_row(row, D, sh_vec_ok(row, D, M), sh);
+// J[3c + k] = d(rgb_c)/d(dir_k), the colour before its clamp, at the direction sh_regs_to_rgb evaluates it at (SH_DDIR: the backward's
+// expressions, bit for bit — preprocess_bwd.hip reads these nine floats instead of the SH row when the forward wrote them).
+__device__ __forceinline__ void sh_ddir_regs(const int D, const float sh[48], const float3 p, const float *campos, float J[9]) {
     const float dx = p.x - campos[0], dy = p.y - campos[1], dz = p.z - campos[2];
     const float inv = 1.f / sqrtf(dx * dx + dy * dy + dz * dz);
-    const float3 r = sh_eval(D, sh, dx * inv, dy * inv, dz * inv);
-    clamp_bits = (uint8_t)((r.x < 0.f ? 1 : 0) | (r.y < 0.f ? 2 : 0) | (r.z < 0.f ? 4 : 0));
-    return make_float3(fmaxf(r.x, 0.f), fmaxf(r.y, 0.f), fmaxf(r.z, 0.f));
+    const float x = dx * inv, y = dy * inv, z = dz * inv;
+    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+#define SHC_REG(k) sh[(k) * 3 + c]
+        SH_DDIR(SHC_REG, J[3 * c], J[3 * c + 1], J[3 * c + 2]);
+#undef SHC_REG
+    }
 }
 
 }  // namespace das3r

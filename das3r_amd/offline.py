@@ -143,7 +143,7 @@ def render_view_fused(model, view, pose7, background, pipe=PIPE, invdepth=False)
     pre.conf_flat, pre.mask_index = conf.data_ptr(), None
     pre.R, pre.t, pre.Lq = st.mats.data_ptr(), st.mats.data_ptr() + 36, st.mats.data_ptr() + 48
     rs = _settings(view, model, pipe, background, 1.0, dev)
-    res = _forward_full(rs, xyz, st.packed_sh(model), st.e, op, sc, rot, st.e, pre=pre, invdepth=invdepth)
+    res = _forward_full(rs, xyz, st.packed_sh(model), st.e, op, sc, rot, st.e, pre=pre, invdepth=invdepth, no_backward=True)
     check_forward(res[6], dev)   # (no backward pass will examine this forward's binning self-check)
     return (res[1], res[2], res[7]) if invdepth else (res[1], res[2])
 

@@ -189,10 +189,12 @@ def _forward_impl(rs, means3D, sh, colors_precomp, opacities, scales, rotations,
     return _forward_full(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, exact=True)[:6]
 
 
-def _forward_full(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, exact=False, pre=None, invdepth=False):
+def _forward_full(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, exact=False, pre=None, invdepth=False,
+                  no_backward=False):
     """-> (num_rendered, color, radii, geom, binning, img, capacity); capacity >= num_rendered is what the binning buffer
     was laid out for (`_lib.layout(P, capacity, W, H)`), == num_rendered when `exact`.  invdepth: the inverse-depth image [1, H, W]
-    (ABI 16, das3r_raster_out.out_invdepth) is appended to the tuple."""
+    (ABI 16, das3r_raster_out.out_invdepth) is appended to the tuple.  no_backward: no backward pass will follow (evaluation) — the
+    library leaves out what only the backward reads (das3r_raster_saved.flags bit 3 on the way in)."""
     lib = _lib.load()
     device = means3D.device
     if device.type != "cuda":
@@ -225,6 +227,7 @@ def _forward_full(rs, means3D, sh, colors_precomp, opacities, scales, rotations,
     inv = torch.empty(1, H, W, dtype=torch.float32, device=device) if invdepth else None
     o.out_invdepth = _ptr(inv)
     saved = _lib.RasterSaved()
+    saved.flags = _lib.NO_BACKWARD_IN_FLAG if no_backward else 0
     with _on_device(device):
         rc = lib.das3r_raster_forward(C.byref(a), C.byref(i), C.byref(o), alloc.fns["geom"], alloc.fns["binning"],
                                       alloc.fns["img"], None, C.byref(saved), _stream(device))
@@ -324,11 +327,20 @@ def count_live_pairs(rs, P, M, num_rendered, geom, binning, img, capacity):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
-    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                     raster_settings)
+    return _apply(_RasterizeGaussians, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
 
 
 _last = threading.local()
+
+
+def _apply(fn, *args):
+    """fn.apply(*args), telling its forward whether a backward pass can follow: not under torch.no_grad, nor when no input takes a
+    gradient (inside the autograd function's forward grad mode is always off, and needs_input_grad ignores it)."""
+    _last.no_backward = not (torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in args))
+    try:
+        return fn.apply(*args)
+    finally:
+        _last.no_backward = False
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -347,16 +359,17 @@ class _RasterizeGaussians(torch.autograd.Function):
         rotations = _prep(rotations, device, "rotations")
         cov3Ds_precomp = _prep(cov3Ds_precomp, device, "cov3D_precomp")
         args = (raster_settings, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
+        no_backward = getattr(_last, "no_backward", False)
         if raster_settings.debug:
             cpu_args = cpu_deep_copy_tuple(args)  # copy them before they can be corrupted
             try:
-                res = _forward_full(*args, invdepth=invdepth)
+                res = _forward_full(*args, invdepth=invdepth, no_backward=no_backward)
             except Exception as ex:
                 torch.save(cpu_args, "snapshot_fw.dump")
                 print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
                 raise ex
         else:
-            res = _forward_full(*args, invdepth=invdepth)
+            res = _forward_full(*args, invdepth=invdepth, no_backward=no_backward)
         num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer, capacity = res[:7]
         ctx.raster_settings = raster_settings
         ctx.num_rendered = num_rendered
@@ -457,8 +470,8 @@ class GaussianRasterizer(nn.Module):
             cov3D_precomp = e
         _last.capacity = None
         if return_invdepth:
-            color, radii, invdepth = _RasterizeGaussiansInvDepth.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                                                       cov3D_precomp, raster_settings)
+            color, radii, invdepth = _apply(_RasterizeGaussiansInvDepth, means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                            cov3D_precomp, raster_settings)
         else:
             color, radii = rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                                raster_settings)

@@ -145,7 +145,13 @@ typedef struct {
                               * long and spatially coherent or skewed (a real sequence's depth maps) — it was composited by the 2x2-region kernel
                               * and its backward pass takes the 2x2-region kernel too (render_regions.hip / render_bwd_rgn.hip).  A caller that
                               * rebuilds this struct for the backward call hands the forward's value back; 0 is always valid (block walk) for
-                              * das3r_raster_backward.  Bit 1 (ABI 16): the forward was given out_invdepth (das3r_raster_backward_depth needs it). */
+                              * das3r_raster_backward.  Bit 1 (ABI 16): the forward was given out_invdepth (das3r_raster_backward_depth needs it).
+                              * Bit 2: the forward had SH coefficients at an active degree >= 2 and left the colour's Jacobian w.r.t. the view
+                              * direction in geom (36 bytes per Gaussian more); the backward then reads it instead of the SH rows.  Without it
+                              * (flags = 0) the backward reads the rows: the gradients are the same bit for bit either way.
+                              * On the way IN, das3r_raster_forward reads bit 3 before it clears the struct: set, it is the caller's word that no
+                              * backward pass will follow (an evaluation render), and the forward does not write the Jacobian (bit 2 stays clear;
+                              * a backward would still be correct, reading the rows).  A zero-filled struct: the Jacobian is written as above. */
 } das3r_raster_saved;
 
 /* Gradient outputs of backward.  Every buffer is fully written by the call (no pre-zeroing needed). */

@@ -486,6 +486,7 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
     // the geometry buffer also holds Layout::g_shjac (flags bit 2) — unless the caller said that no backward will read it (flags bit 3 on the
     // way in, read before the struct is cleared below)
     const bool shjac = in->shs != nullptr && a->sh_degree >= 2 && !(saved->flags & NO_BACKWARD_IN_FLAG);
+    const bool aa = (saved->flags & ANTIALIAS_FLAG) != 0;   // (bit 4 on the way in: an antialiased forward; set again on the way out)
     Layout L;
     compute_layout(P, 0, W, H, &L, shjac);
     saved->geom = alloc_geom(user, L.pub.geom_bytes);
@@ -495,7 +496,7 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
     saved->capacity = 0;
     saved->check_word = nullptr;
     saved->check_tag = 0;
-    saved->flags = 0;
+    saved->flags = aa ? ANTIALIAS_FLAG : 0u;
     if (!saved->geom || !saved->img) { set_error("scratch allocation failed (geom %zu B, img %zu B)", L.pub.geom_bytes, L.pub.img_bytes); return DAS3R_ERR_ALLOC; }
     if (P == 0) {
         // upstream:rasterize_points.cu skips the rasterizer when P == 0: the image stays zero (background NOT applied)
@@ -729,7 +730,7 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
                                  (uint32_t *)(saved->geom + L.g_off_by_gid), (uint32_t)cap, L.tbits, (uint32_t *)(saved->geom + L.g_count), mb->dev};
             emit_ring_dirty = true;   // until the last binning kernel of this forward is enqueued (it re-arms the slot)
             if ((rc = launch_preprocess(a, in, out->radii, saved->geom, saved->img, saved->binning + L.b_ghist, L.b_ctrl_bytes, L, nullptr, mb->dev,
-                                        count_tag, s, &em))) return rc;
+                                        count_tag, s, &em, nullptr, nullptr, aa))) return rc;
             if ((rc = bin_and_render(cap, true, true, nullptr, 0, emit_slot))) return rc;
             emit_ring_dirty = false;
         } else {
@@ -741,7 +742,7 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
             seg_dhist = dhist;
             apply_seg();
             if ((rc = launch_preprocess(a, in, out->radii, saved->geom, saved->img, saved->binning + L.b_ghist, L.b_ctrl_bytes, L, nullptr, mb->dev,
-                                        count_tag, s, nullptr, dhist, dhist_next))) return rc;
+                                        count_tag, s, nullptr, dhist, dhist_next, aa))) return rc;
             if ((rc = bin_and_render(cap, local, true, mb->dev, count_tag))) return rc;
         }
         if ((rc = mailbox_wait(mb, 2, count_tag, s))) return rc;
@@ -767,7 +768,7 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
             HIP_TRY(hipMemsetAsync(dhist, 0, 4 * 256, s));
         }
         seg_dhist = dhist;
-        if ((rc = launch_preprocess(a, in, out->radii, saved->geom, saved->img, nullptr, 0, L, arrive, mb->dev, count_tag, s, nullptr, dhist, dhist_next))) return rc;
+        if ((rc = launch_preprocess(a, in, out->radii, saved->geom, saved->img, nullptr, 0, L, arrive, mb->dev, count_tag, s, nullptr, dhist, dhist_next, aa))) return rc;
         if (!local && !seg && (rc = launch_depth_sort(P, saved->geom, L, 0, nullptr, 0, a->debug != 0, s))) return rc;
         if ((rc = mailbox_wait(mb, 2, count_tag, s))) return rc;    // usually there already: preprocess finished long ago
         if ((rc = prefiltered_ok())) return rc;
@@ -830,7 +831,7 @@ extern "C" int das3r_raster_backward(const das3r_raster_args *a, const das3r_ras
         if (!saved->binning) { set_error("das3r_raster_backward: binning buffer missing"); return DAS3R_ERR_INVALID_ARG; }
         if ((rc = launch_render_backward(a, dL_dpix, saved->geom, saved->binning, saved->img, L, partial, s, &quad_rows, saved->num_rendered, saved->flags))) return rc;
     }
-    return launch_preprocess_backward(a, in, saved->geom, saved->binning, L, g, partial, s, quad_rows);
+    return launch_preprocess_backward(a, in, saved->geom, saved->binning, L, g, partial, s, quad_rows, nullptr, (saved->flags & ANTIALIAS_FLAG) != 0);
 }
 
 // ABI 16: the backward of (colour, inverse depth).  The colour pass is das3r_raster_backward's; the depth pass is the same compositing backward
@@ -893,7 +894,8 @@ extern "C" int das3r_raster_backward_depth(const das3r_raster_args *a, const das
         if ((rc = launch_depth_fold(P, saved->geom, L, partial, partial_depth, dzw, s, a->debug != 0))) return rc;
         dz = dzw;
     }
-    return launch_preprocess_backward(a, in, saved->geom, saved->binning, L, g, partial, s, quad_rows, dz);
+    // (the depth pass's opacity sums were folded into `partial` above: the antialiasing factor's derivative is applied once, to the total)
+    return launch_preprocess_backward(a, in, saved->geom, saved->binning, L, g, partial, s, quad_rows, dz, (saved->flags & ANTIALIAS_FLAG) != 0);
 }
 
 // das3r_raster_backward_scratch_bytes' rows twice: the colour pass's and the depth pass's (whose first column is the per-instance depth sum)

@@ -201,6 +201,9 @@ constexpr uint32_t SHJAC_SAVED_FLAG = 4u;
 // das3r_raster_saved.flags bit 3, on the way IN to das3r_raster_forward: no backward pass will follow this forward (evaluation), so it leaves
 // out what only the backward reads (the Jacobian planes: bit 2 stays clear)
 constexpr uint32_t NO_BACKWARD_IN_FLAG = 8u;
+// das3r_raster_saved.flags bit 4, read on the way IN to das3r_raster_forward and set again on the way out: the antialiased forward
+// (splat_math.h aa_factor scales every splat's opacity); das3r_raster_backward / _depth differentiate the factor iff it is set
+constexpr uint32_t ANTIALIAS_FLAG = 16u;
 struct Layout {
     das3r_raster_layout pub;
     // private scratch offsets
@@ -272,7 +275,7 @@ constexpr int EMIT_STATUS_GRANULES = 1024;             // >= resident grid + its
 // arrive: a zeroed 64-bit device word (self re-arming); host_out / tag: pinned mailbox that receives num_rendered
 int launch_preprocess(const das3r_raster_args *a, const das3r_raster_in *in, int32_t *radii, char *geom, char *img, char *binning_ctrl,
                       size_t binning_ctrl_bytes, const Layout &L, unsigned long long *arrive, uint32_t *host_out, uint32_t tag,
-                      hipStream_t s, const EmitArgs *emit = nullptr, uint32_t *dhist = nullptr, uint32_t *dhist_next = nullptr);
+                      hipStream_t s, const EmitArgs *emit, uint32_t *dhist, uint32_t *dhist_next, bool aa /*ANTIALIAS_FLAG*/);
 int launch_mark_visible(int P, const float *means3D, const float *viewmatrix, uint8_t *present, hipStream_t s);
 // part 0: everything that can be enqueued before num_rendered is known; part 1: the rest, which also zeroes the binning buffer's
 // control words (binning_ctrl may be null)
@@ -357,7 +360,8 @@ int launch_render_backward(const das3r_raster_args *a, const float *dL_dpix, cha
 // pair_count.hip (measurement aid): out[0] += live pairs, out[1] += (pixel, list position) pairs below the pixel's n_contrib
 int launch_count_live_pairs(const das3r_raster_args *a, char *geom, char *binning, char *img, const Layout &L, unsigned long long *out, hipStream_t s);
 int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in *in, char *geom, char *binning, const Layout &L,
-                               const das3r_raster_grads *g, const float *partial, hipStream_t s, bool quad_rows, const float *dz = nullptr /*ABI 16: [P] dL/dz of the depth pass, or null*/);
+                               const das3r_raster_grads *g, const float *partial, hipStream_t s, bool quad_rows, const float *dz /*ABI 16: [P] dL/dz of the depth pass, or null*/,
+                               bool aa /*ANTIALIAS_FLAG: the forward was antialiased*/);
 
 // ---- device helpers ----
 #ifdef __HIPCC__

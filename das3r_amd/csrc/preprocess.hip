@@ -16,7 +16,9 @@
 
 namespace das3r {
 
-template <bool HAS_SH, bool HAS_COV, bool STAGE>
+// AA (das3r_raster_saved.flags bit 4): the splat is blended with its opacity times splat_math.h aa_factor — the record's opacity, the
+// 1/255 cut-off and the opacity-aware tile box all see the product; conic, radius, tile rectangle, depth key and colour are unchanged.
+template <bool HAS_SH, bool HAS_COV, bool STAGE, bool AA = false>
 __global__ void __launch_bounds__(256) preprocess_kernel(
     int P, int D, int M, const float *__restrict__ means3D, const float *__restrict__ scales, float scale_modifier,
     const float *__restrict__ rotations, const float *__restrict__ opacities, const float *__restrict__ shs,
@@ -142,8 +144,14 @@ __global__ void __launch_bounds__(256) preprocess_kernel(
         float3 t;
         bool cx, cy;
         ewa_T(p_view, V, focal_x, focal_y, tanfovx, tanfovy, T, t, cx, cy);
-        float a, b, c;
-        cov2d_from_T(T, c3, a, b, c);
+        float a, b, c, a0 = 0.f, c0 = 0.f;
+        if constexpr (AA) {
+            cov2d_undilated(T, c3, a0, b, c0);
+            a = a0 + 0.3f;
+            c = c0 + 0.3f;
+        } else {
+            cov2d_from_T(T, c3, a, b, c);
+        }
         const float det = a * c - b * b;
         if (det != 0.0f) {
             const float det_inv = 1.f / det;
@@ -183,6 +191,7 @@ __global__ void __launch_bounds__(256) preprocess_kernel(
                 }
                 radius_out = r;
                 key_out = __float_as_uint(p_view.z);
+                if constexpr (AA) op = op * aa_factor(aa_rho(a0, b, c0, det));
                 // half extents of the axis-aligned box outside which alpha = opacity * exp(power) cannot reach 1/255
                 // (ellipse d^T Sigma'^-1 d <= 2 ln(255 o)); generous safety margin, used only for wave-level culling
                 float hx = -1e30f, hy = -1e30f;
@@ -390,7 +399,7 @@ __global__ void __launch_bounds__(256) mark_visible_kernel(int P, const float *_
 
 int launch_preprocess(const das3r_raster_args *a, const das3r_raster_in *in, int32_t *radii, char *geom, char *img, char *binning_ctrl,
                       size_t binning_ctrl_bytes, const Layout &L, unsigned long long *arrive, uint32_t *host_out, uint32_t tag,
-                      hipStream_t s, const EmitArgs *emit, uint32_t *dhist, uint32_t *dhist_next) {
+                      hipStream_t s, const EmitArgs *emit, uint32_t *dhist, uint32_t *dhist_next, bool aa) {
     const int P = a->P;
     if (P == 0) return DAS3R_OK;
     const EmitArgs em = emit ? *emit : EmitArgs{nullptr, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0, nullptr, nullptr};
@@ -408,12 +417,18 @@ int launch_preprocess(const das3r_raster_args *a, const das3r_raster_in *in, int
         (uint32_t *)(geom + L.pub.tiles_touched), (uint32_t *)(geom + L.g_rect), (use_tight_rect() ? 1 : 0) | (a->prefiltered ? 2 : 0), (uint32_t *)(geom + L.g_ghist), (uint32_t)(L.g_ctrl_bytes / 4),                 \
         (uint32_t *)(img + L.pub.ranges), (uint32_t)(2 * L.ntiles), (uint32_t *)binning_ctrl, (uint32_t)(binning_ctrl_bytes / 4), arrive, host_out, tag, em, dhist, dhist_mask, dhist_next, pre, shjac
     const bool stage = has_sh && a->M == 16 && a->sh_degree >= 2 && ((uintptr_t)in->shs & 15) == 0 && !switches().no_sh_stage;
-    if (has_sh && !has_cov && stage) DAS3R_LAUNCH((preprocess_kernel<true, false, true>), grid, block, 0, s, ARGS);
-    else if (has_sh && has_cov && stage) DAS3R_LAUNCH((preprocess_kernel<true, true, true>), grid, block, 0, s, ARGS);
-    else if (has_sh && !has_cov) DAS3R_LAUNCH((preprocess_kernel<true, false, false>), grid, block, 0, s, ARGS);
-    else if (has_sh && has_cov) DAS3R_LAUNCH((preprocess_kernel<true, true, false>), grid, block, 0, s, ARGS);
-    else if (!has_sh && !has_cov) DAS3R_LAUNCH((preprocess_kernel<false, false, false>), grid, block, 0, s, ARGS);
-    else DAS3R_LAUNCH((preprocess_kernel<false, true, false>), grid, block, 0, s, ARGS);
+#define LAUNCH_PRE(SH, COV, ST)                                                                                   \
+    do {                                                                                                          \
+        if (aa) DAS3R_LAUNCH((preprocess_kernel<SH, COV, ST, true>), grid, block, 0, s, ARGS);                   \
+        else DAS3R_LAUNCH((preprocess_kernel<SH, COV, ST>), grid, block, 0, s, ARGS);                            \
+    } while (0)
+    if (has_sh && !has_cov && stage) LAUNCH_PRE(true, false, true);
+    else if (has_sh && has_cov && stage) LAUNCH_PRE(true, true, true);
+    else if (has_sh && !has_cov) LAUNCH_PRE(true, false, false);
+    else if (has_sh && has_cov) LAUNCH_PRE(true, true, false);
+    else if (!has_sh && !has_cov) LAUNCH_PRE(false, false, false);
+    else LAUNCH_PRE(false, true, false);
+#undef LAUNCH_PRE
 #undef ARGS
     KERNEL_CHECK(s, a->debug, "preprocess");
     return DAS3R_OK;

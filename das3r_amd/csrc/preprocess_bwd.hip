@@ -91,8 +91,16 @@ struct ChainArgs {
 // the colour's view-direction term is taken from it instead of the SH row (36 instead of 192 bytes per splat at degree 3, bit for bit the same:
 // SH_DDIR's values in the same order).  No SH input is staged, so the staged form assembles its dL_dsh rows in two halves of 128 rows: 26 KB
 // of LDS instead of 53 (five workgroups per CU instead of three).
-template <bool HAS_SH, bool HAS_COV, bool STAGE_IN, bool STAGE_OUT, bool DEG0 = false, bool CHAIN = false, bool DEPTH = false, bool JAC = false>
-__global__ void __launch_bounds__(256, DEG0 ? (CHAIN ? 4 : 6) : JAC && !CHAIN ? JAC_WAVES : 3) preprocess_backward_kernel(
+// AA (das3r_raster_saved.flags bit 4): the forward blended opacity o' = o f (splat_math.h aa_factor).  acc[8] is dL/do' summed over every
+// compositing pass; dL/do = dL/do' f, and dL/df = dL/do' o reaches the 2D covariance through rho (unless f sat at its clamp).
+// The AA forms that cannot hold their target without spilling take their own: DEG0 5 waves instead of 6, the unchained JAC forms 4 instead
+// of 5, and the chained form with SH rows 2 (its non-AA form, which the same bound of 3 would leave as it is, spills already).
+constexpr int pb_waves(const bool DEG0, const bool CHAIN, const bool JAC, const bool AA) {
+    return DEG0 ? (CHAIN ? 4 : (AA ? 5 : 6)) : JAC && !CHAIN ? (AA ? JAC_WAVES - 1 : JAC_WAVES) : (AA && CHAIN && !JAC ? 2 : 3);
+}
+template <bool HAS_SH, bool HAS_COV, bool STAGE_IN, bool STAGE_OUT, bool DEG0 = false, bool CHAIN = false, bool DEPTH = false, bool JAC = false,
+          bool AA = false>
+__global__ void __launch_bounds__(256, pb_waves(DEG0, CHAIN, JAC, AA)) preprocess_backward_kernel(
     int P, int D_in, int M, const float *__restrict__ means3D, const float *__restrict__ scales, float scale_modifier,
     const float *__restrict__ rotations, const float *__restrict__ shs, const float *__restrict__ cov3D_precomp,
     const float *__restrict__ viewmatrix, const float *__restrict__ projmatrix, const float *__restrict__ campos, int W, int H,
@@ -103,7 +111,8 @@ __global__ void __launch_bounds__(256, DEG0 ? (CHAIN ? 4 : 6) : JAC && !CHAIN ? 
     float *__restrict__ dL_dcolors_precomp /*[P,3] out, precomp mode*/, float *__restrict__ dL_dmeans3D,
     float *__restrict__ dL_dscales, float *__restrict__ dL_drot, float *__restrict__ dL_dsh, float *__restrict__ dL_dcov3D,
     const PreXform pre /*xyz != null (das3r_raster_in.pre): the raw parameters + the pose, as in preprocess.hip*/,
-    const ChainArgs ch /*CHAIN only*/, const float *__restrict__ dz_g /*DEPTH only*/, const float *__restrict__ shjac /*JAC only: [9][P]*/
+    const ChainArgs ch /*CHAIN only*/, const float *__restrict__ dz_g /*DEPTH only*/, const float *__restrict__ shjac /*JAC only: [9][P]*/,
+    const float *__restrict__ opacities /*AA only, without `pre`*/
 #ifdef DAS3R_EXPERIMENTS
     , unsigned long long *__restrict__ trace /*common.h BLK_STAMP (tools/wg_trace.py), region 6*/
 #endif
@@ -325,7 +334,7 @@ __global__ void __launch_bounds__(256, DEG0 ? (CHAIN ? 4 : 6) : JAC && !CHAIN ? 
             }
         }
         if constexpr (CHAIN) o_op = acc[8];
-        else dL_dopacity[idx] = acc[8];
+        else if constexpr (!AA) dL_dopacity[idx] = acc[8];
         if (XPOSE) {
             o_m2d[0] = acc[3]; o_m2d[1] = acc[4];
             o_col[0] = acc[0]; o_col[1] = acc[1]; o_col[2] = acc[2];
@@ -380,17 +389,38 @@ __global__ void __launch_bounds__(256, DEG0 ? (CHAIN ? 4 : 6) : JAC && !CHAIN ? 
                     TS0[j] = T[0][0] * S[j][0] + T[0][1] * S[j][1] + T[0][2] * S[j][2];
                     TS1[j] = T[1][0] * S[j][0] + T[1][1] * S[j][1] + T[1][2] * S[j][2];
                 }
-                const float ca = TS0[0] * T[0][0] + TS0[1] * T[0][1] + TS0[2] * T[0][2] + 0.3f;
+                const float ca0 = TS0[0] * T[0][0] + TS0[1] * T[0][1] + TS0[2] * T[0][2];
                 const float cb = TS0[0] * T[1][0] + TS0[1] * T[1][1] + TS0[2] * T[1][2];
-                const float cc = TS1[0] * T[1][0] + TS1[1] * T[1][1] + TS1[2] * T[1][2] + 0.3f;
+                const float cc0 = TS1[0] * T[1][0] + TS1[1] * T[1][1] + TS1[2] * T[1][2];
+                const float ca = ca0 + 0.3f, cc = cc0 + 0.3f;   // (the forward's cov2d_from_T, bit for bit)
                 const float gA = acc[5], gB = acc[6], gC = acc[7];
                 const float denom = ca * cc - cb * cb;
+                float aa_r = 0.f, aa_drho = 0.f;
+                if constexpr (AA) {   // rho and f of the forward (the same bits); acc[8] becomes dL/do
+                    // the forward's opacity before the factor, read here rather than with the other inputs: a register held through the
+                    // gather made the 6-wave DEG0, 5-wave JAC and staged forms spill
+                    float op_in;
+                    if constexpr (CHAIN) op_in = pre_opacity(raw_o, raw_c);
+                    else if (!HAS_COV && pre.xyz != nullptr) op_in = pre_opacity(pre.opacity_raw[idx], pre.conf_flat[pre.mask_index ? pre.mask_index[idx] : (int64_t)idx]);
+                    else op_in = opacities[idx];
+                    aa_r = aa_rho(ca0, cb, cc0, denom);
+                    const float f = aa_factor(aa_r);
+                    const float g_op = acc[8];
+                    acc[8] = g_op * f;
+                    if (aa_r > AA_RHO_MIN) aa_drho = g_op * op_in / (2.f * f);
+                }
                 float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
                 const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
                 if (denom2inv != 0.f) {
                     dL_da = denom2inv * (-cc * cc * gA + 2 * cb * cc * gB + (denom - ca * cc) * gC);
                     dL_dc = denom2inv * (-ca * ca * gC + 2 * ca * cb * gB + (denom - ca * cc) * gA);
                     dL_db = denom2inv * 2 * (cb * cc * gA - (denom + 2 * cb * cb) * gB + ca * cb * gC);
+                    if constexpr (AA) {   // + dL/drho drho/d(a, b, c); drho/da = (c0 det - det0 c) / det^2 = (c0 - rho c) / det, and so on
+                        const float k = aa_drho / denom;
+                        dL_da += k * (cc0 - aa_r * cc);
+                        dL_dc += k * (ca0 - aa_r * ca);
+                        dL_db += k * (-2.f * cb * (1.f - aa_r));
+                    }
                     dcov[0] = (T[0][0] * T[0][0] * dL_da + T[0][0] * T[1][0] * dL_db + T[1][0] * T[1][0] * dL_dc);
                     dcov[3] = (T[0][1] * T[0][1] * dL_da + T[0][1] * T[1][1] * dL_db + T[1][1] * T[1][1] * dL_dc);
                     dcov[5] = (T[0][2] * T[0][2] * dL_da + T[0][2] * T[1][2] * dL_db + T[1][2] * T[1][2] * dL_dc);
@@ -520,6 +550,10 @@ __global__ void __launch_bounds__(256, DEG0 ? (CHAIN ? 4 : 6) : JAC && !CHAIN ? 
             }
         }
 
+        if constexpr (AA) {   // (acc[8] = dL/do' f for a visible splat, 0 otherwise)
+            if constexpr (CHAIN) o_op = acc[8];
+            else dL_dopacity[idx] = acc[8];
+        }
         if constexpr (DEPTH) {
             if (visible) {
                 const float dz = dz_g[idx];
@@ -692,7 +726,7 @@ static float *chain_scratch(hipStream_t s, size_t blocks, uint32_t **arrived) {
 }
 
 int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in *in, char *geom, char *binning, const Layout &L,
-                               const das3r_raster_grads *g, const float *partial, hipStream_t s, bool quad_rows, const float *dz) {
+                               const das3r_raster_grads *g, const float *partial, hipStream_t s, bool quad_rows, const float *dz, bool aa) {
     const int P = a->P;
     if (P == 0) return DAS3R_OK;
     dim3 grid(div_up(P, 256)), block(256);
@@ -714,7 +748,7 @@ int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in
         a->viewmatrix, a->projmatrix, a->campos, a->image_width, a->image_height, a->tanfovx, a->tanfovy,                    \
         (const uint32_t *)(geom + L.pub.tiles_touched), (const uint8_t *)(geom + L.pub.clamped), partial, exists,        \
         (const uint32_t *)(geom + L.g_off_by_gid), g->dL_dmeans2D, g->dL_dopacities, g->dL_dcolors_precomp, g->dL_dmeans3D,  \
-        g->dL_dscales, g->dL_drotations, g->dL_dshs, g->dL_dcov3D, pre, ch, dz, jac ? (const float *)(geom + L.g_shjac) : nullptr PB_TRACE_ARG
+        g->dL_dscales, g->dL_drotations, g->dL_dshs, g->dL_dcov3D, pre, ch, dz, jac ? (const float *)(geom + L.g_shjac) : nullptr, in->opacities PB_TRACE_ARG
     // ---- the chained form (das3r_raster_grads.chain): unstaged SH rows, raw parameters ----
     ChainArgs ch;
     memset(&ch, 0, sizeof(ch));
@@ -742,10 +776,15 @@ int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in
         ch.det_partials = chain_scratch(s, (size_t)grid.x, &ch.arrived);   // (null: float atomics, said once)
     }
     // (dz: the DEPTH instantiation of the same form)
-#define LAUNCH7(SH, COV, SI, SO, D0, CH, J)                                                                                \
-    do {                                                                                                                   \
-        if (dz) DAS3R_LAUNCH((preprocess_backward_kernel<SH, COV, SI, SO, D0, CH, true, J>), grid, block, 0, s, ARGS);    \
-        else DAS3R_LAUNCH((preprocess_backward_kernel<SH, COV, SI, SO, D0, CH, false, J>), grid, block, 0, s, ARGS);      \
+#define LAUNCH8(SH, COV, SI, SO, D0, CH, J, AA)                                                                                \
+    do {                                                                                                                       \
+        if (dz) DAS3R_LAUNCH((preprocess_backward_kernel<SH, COV, SI, SO, D0, CH, true, J, AA>), grid, block, 0, s, ARGS);    \
+        else DAS3R_LAUNCH((preprocess_backward_kernel<SH, COV, SI, SO, D0, CH, false, J, AA>), grid, block, 0, s, ARGS);      \
+    } while (0)
+#define LAUNCH7(SH, COV, SI, SO, D0, CH, J)                                                                                    \
+    do {                                                                                                                       \
+        if (aa) LAUNCH8(SH, COV, SI, SO, D0, CH, J, true);                                                                     \
+        else LAUNCH8(SH, COV, SI, SO, D0, CH, J, false);                                                                       \
     } while (0)
 #define LAUNCH6(SH, COV, SI, SO, D0, CH) LAUNCH7(SH, COV, SI, SO, D0, CH, false)
 #define LAUNCH(SH, COV, SI, SO) LAUNCH6(SH, COV, SI, SO, false, false)
@@ -782,6 +821,7 @@ int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in
 #undef LAUNCH0
 #undef LAUNCH6
 #undef LAUNCH7
+#undef LAUNCH8
 #undef ARGS
     KERNEL_CHECK(s, a->debug, "preprocess_backward");
     return DAS3R_OK;

@@ -68,18 +68,33 @@ __device__ __forceinline__ void ewa_T(const float3 p_view, const float *V, const
     }
 }
 
-// cov2D = T Sigma T^T + 0.3 I  ->  (a, b, c)
-__device__ __forceinline__ void cov2d_from_T(const float T[2][3], const float *c3, float &a, float &b, float &c) {
+// T Sigma T^T before the 0.3 px^2 dilation  ->  (a0, b, c0)
+__device__ __forceinline__ void cov2d_undilated(const float T[2][3], const float *c3, float &a0, float &b, float &c0) {
     const float S[3][3] = {{c3[0], c3[1], c3[2]}, {c3[1], c3[3], c3[4]}, {c3[2], c3[4], c3[5]}};
     float TS[2][3];
 #pragma unroll
     for (int i = 0; i < 2; i++)
 #pragma unroll
         for (int j = 0; j < 3; j++) TS[i][j] = T[i][0] * S[0][j] + T[i][1] * S[1][j] + T[i][2] * S[2][j];
-    a = TS[0][0] * T[0][0] + TS[0][1] * T[0][1] + TS[0][2] * T[0][2] + 0.3f;
+    a0 = TS[0][0] * T[0][0] + TS[0][1] * T[0][1] + TS[0][2] * T[0][2];
     b = TS[0][0] * T[1][0] + TS[0][1] * T[1][1] + TS[0][2] * T[1][2];
-    c = TS[1][0] * T[1][0] + TS[1][1] * T[1][1] + TS[1][2] * T[1][2] + 0.3f;
+    c0 = TS[1][0] * T[1][0] + TS[1][1] * T[1][1] + TS[1][2] * T[1][2];
 }
+
+// cov2D = T Sigma T^T + 0.3 I  ->  (a, b, c)   (sums are left to right: the same bits as adding 0.3 to cov2d_undilated's)
+__device__ __forceinline__ void cov2d_from_T(const float T[2][3], const float *c3, float &a, float &b, float &c) {
+    float a0, c0;
+    cov2d_undilated(T, c3, a0, b, c0);
+    a = a0 + 0.3f;
+    c = c0 + 0.3f;
+}
+
+// Antialiasing (das3r_raster_saved.flags bit 4, upstream's 2D mip filter): a splat is blended with its opacity times
+// f = sqrt(max(rho, 2.5e-5)), rho = det0 / det, by how much the 0.3 px^2 dilation spreads it out.  det0 = a0 c0 - b^2 of the
+// un-dilated entries, det = a c - b^2 of the dilated ones (a = a0 + 0.3, c = c0 + 0.3).
+constexpr float AA_RHO_MIN = 2.5e-5f;
+__device__ __forceinline__ float aa_rho(const float a0, const float b, const float c0, const float det) { return (a0 * c0 - b * b) / det; }
+__device__ __forceinline__ float aa_factor(const float rho) { return sqrtf(fmaxf(rho, AA_RHO_MIN)); }
 
 // tile rectangle touched by a 2D splat of integer radius r (C truncation toward zero, clamped to the grid)
 __device__ __forceinline__ void tile_rect(const float px, const float py, const int r, const int tiles_x, const int tiles_y,

@@ -143,7 +143,7 @@ def _settings(st, cam, model, bg):
     return rs
 
 
-def forward_backward(model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda_dssim, bg, geometry="grads", rearm_rows=None):
+def forward_backward(model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda_dssim, bg, geometry="grads", rearm_rows=None, antialiasing=False):
     """Render `cam` with the pose (q_row, t_row: views of one row of Q / T), masked photometric loss against cam.original_image
     under `static_hw` [H, W], and the complete backward.  Gradients: model parameters' .grad (f_rest: compact or none, as in
     das3r_amd.render), the pose gradient into gq_row / gt_row, d loss / d static_hw returned.
@@ -151,13 +151,14 @@ def forward_backward(model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda
     returns — "grads": chain rule through the pre-transform, left on the parameters' .grad; "adam": the same chain rule with the Adam
     step of the four tensors taken in that very pass (das3r_pretransform_backward_adam: they never reach memory; model.optimizer.step()
     then finds the four without gradient and passes them by); "pose": the camera's sums alone, every per-Gaussian gradient dropped.
+    antialiasing: the rasterizer's antialiasing mode (pipe.antialiasing), forward and backward, in every geometry mode.
     -> (out8 = {loss, mse x 3, psnr_frame, ...} device tensor, d_static [H, W], package)"""
     st = _state(model)
     with _on_device(st.dev):   # (the library's per-device state and the raw stream belong to the model's GPU, current or not)
-        return _forward_backward(st, model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda_dssim, bg, geometry, rearm_rows)
+        return _forward_backward(st, model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda_dssim, bg, geometry, rearm_rows, antialiasing)
 
 
-def _forward_backward(st, model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda_dssim, bg, geometry, rearm_rows=None):
+def _forward_backward(st, model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda_dssim, bg, geometry, rearm_rows=None, antialiasing=False):
     lib = _lib.load()
     dev, P = st.dev, st.P
     H, W = int(cam.image_height), int(cam.image_width)
@@ -193,7 +194,7 @@ def _forward_backward(st, model, cam, q_row, t_row, gq_row, gt_row, static_hw, l
         shs = _packed_sh(st, model, 1 + model._features_rest.shape[1])
     rs = _settings(st, cam, model, bg)
     e = st.e
-    I, image, radii, geom, binning, img, cap = _forward_full(rs, means3D, shs, e, opac, scales, rotations, e, pre=pre)
+    I, image, radii, geom, binning, img, cap = _forward_full(rs, means3D, shs, e, opac, scales, rotations, e, pre=pre, antialiasing=antialiasing)
     # ---- loss
     gt = _dense_f32(cam, "original_image")
     static_hw = static_hw if (static_hw.is_contiguous() and static_hw.dtype == torch.float32) else static_hw.contiguous().float()
@@ -282,7 +283,8 @@ def train_step(model, cam, opt, iteration, pipe, background):
         prev = getattr(st, "dirty_uid", None)
         out8, d_static, pkg = forward_backward(model, cam, model.Q[uid], model.T[uid], st.Qg[uid], st.Tg[uid], model._conf_static[uid],
                                                opt.lambda_dssim, background, geometry="adam" if getattr(model, "fuse_geometry_adam", True) else "grads",
-                                               rearm_rows=None if prev is None else (st.Qg[prev], st.Tg[prev]))
+                                               rearm_rows=None if prev is None else (st.Qg[prev], st.Tg[prev]),
+                                               antialiasing=bool(getattr(pipe, "antialiasing", False)))
         st.dirty_uid = uid
         model._conf_static.grad[uid] += d_static             # the loss sees conf_static twice: as opacity factor and as the frame's mask
         model.optimizer.step()
@@ -293,7 +295,7 @@ def train_step(model, cam, opt, iteration, pipe, background):
     return out8[0], out8[4], pkg
 
 
-def test_pose_step(model, cam, static_hw, opt, background):
+def test_pose_step(model, cam, static_hw, opt, background, pipe=None):
     """One view of train_test_psnr.py's pass over the held-out views (das3r_amd.train.test_pose_pass): render with the test pose,
     loss, backward — and every gradient dropped: the Gaussian optimizer is zeroed without a step and optimizer_cam owns no
     gradient here.  Reproduced for its cost; nothing changes."""
@@ -303,7 +305,8 @@ def test_pose_step(model, cam, static_hw, opt, background):
         st.tQg, st.tTg = torch.zeros_like(model.test_Q), torch.zeros_like(model.test_T)
     with torch.no_grad(), _on_device(st.dev):
         out8, _d_static, _pkg = forward_backward(model, cam, model.test_Q[uid], model.test_T[uid], st.tQg[uid], st.tTg[uid], static_hw,
-                                                 opt.lambda_dssim, background, geometry="pose")
+                                                 opt.lambda_dssim, background, geometry="pose",
+                                                 antialiasing=bool(getattr(pipe, "antialiasing", False)))
         model.optimizer.zero_grad(set_to_none=True)
         model.optimizer_cam.zero_grad(set_to_none=True)
     return out8

@@ -143,7 +143,8 @@ def render_view_fused(model, view, pose7, background, pipe=PIPE, invdepth=False)
     pre.conf_flat, pre.mask_index = conf.data_ptr(), None
     pre.R, pre.t, pre.Lq = st.mats.data_ptr(), st.mats.data_ptr() + 36, st.mats.data_ptr() + 48
     rs = _settings(view, model, pipe, background, 1.0, dev)
-    res = _forward_full(rs, xyz, st.packed_sh(model), st.e, op, sc, rot, st.e, pre=pre, invdepth=invdepth, no_backward=True)
+    res = _forward_full(rs, xyz, st.packed_sh(model), st.e, op, sc, rot, st.e, pre=pre, invdepth=invdepth, no_backward=True,
+                        antialiasing=bool(getattr(pipe, "antialiasing", False)))
     check_forward(res[6], dev)   # (no backward pass will examine this forward's binning self-check)
     return (res[1], res[2], res[7]) if invdepth else (res[1], res[2])
 
@@ -191,10 +192,11 @@ def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=
 
 
 def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=False, optimised_poses=False, device="cuda", write=True, fused=False,
-                depth=False):
+                depth=False, pipe=PIPE):
     """render.py:89-123: load the trained model, write pose_interpolated.npy, render the "interp" set.  seq: the sequence the model was
     trained on (its cameras).  depth: also the inverse-depth images (invdepth/%05d.npy) and, per view, the median relative error of
-    1 / invdepth against the sequence's depth map (printed: a diagnostic).  -> (iteration, list of rendered images)"""
+    1 / invdepth against the sequence's depth map (printed: a diagnostic).  pipe: PIPE, or pipe_from_args' (pipe.antialiasing: a model
+    trained with antialiasing is rendered with it).  -> (iteration, list of rendered images)"""
     model, iteration = load_trained_model(model_path, iteration, sh_degree, device)
     inter = save_interpolate_pose(model_path, iteration)
     bg = torch.tensor([1.0, 1.0, 1.0] if white_background else [0.0, 0.0, 0.0], dtype=torch.float32, device=device)
@@ -213,7 +215,7 @@ def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=Fal
             frames = list(tr)
         poses = inter
     inv = [] if depth else None
-    imgs = render_set(model_path, "interp", iteration, views, model, PIPE, bg, poses=poses, write=write, fused=fused, invdepth=inv)
+    imgs = render_set(model_path, "interp", iteration, views, model, pipe, bg, poses=poses, write=write, fused=fused, invdepth=inv)
     if depth and seq.get("depths") is not None:
         for idx, (f, d) in enumerate(zip(frames, inv)):
             print(f"view {idx:05d} (frame {f}): median |1/invdepth - depth| / depth = {invdepth_median_rel_error(d, seq['depths'][f]):.4f}")
@@ -239,7 +241,12 @@ def forward_throughput(model, views, repeats=3, background=None, fused=False):
     return dict(ms_per_view=dt * 1e3, views_per_s=1.0 / dt, views=len(views), splats=int(model.get_xyz.shape[0]))
 
 
-def main(argv=None):
+def pipe_from_args(args):
+    """The `pipe` a command line renders with: PIPE, and pipe.antialiasing from --antialiasing."""
+    return SimpleNamespace(**vars(PIPE), antialiasing=bool(getattr(args, "antialiasing", False)))
+
+
+def parser():
     ap = argparse.ArgumentParser(description="Testing script parameters (render.py)")
     ap.add_argument("--model-path", "-m", "--model_path", dest="model_path", required=True)
     ap.add_argument("--source-path", "-s", "--source_path", dest="source_path", required=True, help="the preprocessed sequence directory the model was trained on")
@@ -251,12 +258,18 @@ def main(argv=None):
     ap.add_argument("--fused", action="store_true", help="the pose pre-transform inside the rasterizer's kernels instead of the reference's PyTorch glue (render_view_fused)")
     ap.add_argument("--depth", action="store_true", help="also write the inverse-depth images (invdepth/%%05d.npy next to renders/) and print each view's "
                                                          "median relative error of 1/invdepth against the sequence's depth_maps")
-    args = ap.parse_args(argv)
+    ap.add_argument("--antialiasing", action="store_true", help="the rasterizer's antialiasing mode (upstream's 2D mip filter), fused or not: "
+                                                                "render a model trained with it (farm --antialiasing) this way")
+    return ap
+
+
+def main(argv=None):
+    args = parser().parse_args(argv)
     from .io_formats import load_sequence
     print("Rendering " + args.model_path)
     seq = load_sequence(args.source_path, device="cuda", dataset=args.dataset)
     it, imgs = render_sets(args.model_path, seq, args.iteration, args.sh_degree, args.white_background, args.optimised_poses, fused=args.fused,
-                           depth=args.depth)
+                           depth=args.depth, pipe=pipe_from_args(args))
     print(f"wrote {len(imgs)} images to {os.path.join(args.model_path, 'interp', f'ours_{it}', 'renders')}")
 
 

@@ -190,11 +190,12 @@ def _forward_impl(rs, means3D, sh, colors_precomp, opacities, scales, rotations,
 
 
 def _forward_full(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, exact=False, pre=None, invdepth=False,
-                  no_backward=False):
+                  no_backward=False, antialiasing=False):
     """-> (num_rendered, color, radii, geom, binning, img, capacity); capacity >= num_rendered is what the binning buffer
     was laid out for (`_lib.layout(P, capacity, W, H)`), == num_rendered when `exact`.  invdepth: the inverse-depth image [1, H, W]
     (ABI 16, das3r_raster_out.out_invdepth) is appended to the tuple.  no_backward: no backward pass will follow (evaluation) — the
-    library leaves out what only the backward reads (das3r_raster_saved.flags bit 3 on the way in)."""
+    library leaves out what only the backward reads (das3r_raster_saved.flags bit 3 on the way in).  antialiasing: upstream's 2D mip filter
+    (flags bit 4 on the way in; the capacity's `flags` carry it back to `_backward_impl`, which then differentiates it)."""
     lib = _lib.load()
     device = means3D.device
     if device.type != "cuda":
@@ -227,7 +228,7 @@ def _forward_full(rs, means3D, sh, colors_precomp, opacities, scales, rotations,
     inv = torch.empty(1, H, W, dtype=torch.float32, device=device) if invdepth else None
     o.out_invdepth = _ptr(inv)
     saved = _lib.RasterSaved()
-    saved.flags = _lib.NO_BACKWARD_IN_FLAG if no_backward else 0
+    saved.flags = (_lib.NO_BACKWARD_IN_FLAG if no_backward else 0) | (_lib.ANTIALIAS_FLAG if antialiasing else 0)
     with _on_device(device):
         rc = lib.das3r_raster_forward(C.byref(a), C.byref(i), C.byref(o), alloc.fns["geom"], alloc.fns["binning"],
                                       alloc.fns["img"], None, C.byref(saved), _stream(device))
@@ -326,21 +327,25 @@ def count_live_pairs(rs, P, M, num_rendered, geom, binning, img, capacity):
     return int(out[0]), int(out[1])
 
 
-def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
-    return _apply(_RasterizeGaussians, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
+def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, antialiasing=False):
+    return _apply(_RasterizeGaussians, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
+                  antialiasing=antialiasing)
 
 
 _last = threading.local()
 
 
-def _apply(fn, *args):
+def _apply(fn, *args, antialiasing=False):
     """fn.apply(*args), telling its forward whether a backward pass can follow: not under torch.no_grad, nor when no input takes a
-    gradient (inside the autograd function's forward grad mode is always off, and needs_input_grad ignores it)."""
+    gradient (inside the autograd function's forward grad mode is always off, and needs_input_grad ignores it) — and whether it is an
+    antialiased forward (the settings tuple keeps upstream's twelve fields)."""
     _last.no_backward = not (torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in args))
+    _last.antialiasing = bool(antialiasing)
     try:
         return fn.apply(*args)
     finally:
         _last.no_backward = False
+        _last.antialiasing = False
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -360,16 +365,17 @@ class _RasterizeGaussians(torch.autograd.Function):
         cov3Ds_precomp = _prep(cov3Ds_precomp, device, "cov3D_precomp")
         args = (raster_settings, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
         no_backward = getattr(_last, "no_backward", False)
+        aa = getattr(_last, "antialiasing", False)   # (the backward learns it from the forward's flags: ctx.capacity)
         if raster_settings.debug:
             cpu_args = cpu_deep_copy_tuple(args)  # copy them before they can be corrupted
             try:
-                res = _forward_full(*args, invdepth=invdepth, no_backward=no_backward)
+                res = _forward_full(*args, invdepth=invdepth, no_backward=no_backward, antialiasing=aa)
             except Exception as ex:
                 torch.save(cpu_args, "snapshot_fw.dump")
                 print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
                 raise ex
         else:
-            res = _forward_full(*args, invdepth=invdepth, no_backward=no_backward)
+            res = _forward_full(*args, invdepth=invdepth, no_backward=no_backward, antialiasing=aa)
         num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer, capacity = res[:7]
         ctx.raster_settings = raster_settings
         ctx.num_rendered = num_rendered
@@ -446,11 +452,13 @@ class GaussianRasterizer(nn.Module):
             return present.bool()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, return_invdepth=False):
+                cov3D_precomp=None, return_invdepth=False, antialiasing=False):
         """-> (color [3, H, W], radii [P]); with return_invdepth, (color, radii, invdepth [1, H, W]) as upstream's newer rasterizer returns:
         per pixel sum_i (1/z_i) alpha_i T_i over the splats the colour is blended from, 0 where nothing is (no background term).  The
         colour and radii are the same bit for bit either way.  The inverse depth is differentiable (back to means3D, scales, rotations,
-        opacities and means2D through alpha, and to means3D through 1/z)."""
+        opacities and means2D through alpha, and to means3D through 1/z).
+        antialiasing: upstream's antialiasing mode (its 2D mip filter) — every splat is blended with its opacity times
+        sqrt(max(det(Sigma2D) / det(Sigma2D + 0.3 I), 2.5e-5)), and the backward differentiates that factor too.  Radii are unchanged."""
         raster_settings = self.raster_settings
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
@@ -471,10 +479,10 @@ class GaussianRasterizer(nn.Module):
         _last.capacity = None
         if return_invdepth:
             color, radii, invdepth = _apply(_RasterizeGaussiansInvDepth, means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                            cov3D_precomp, raster_settings)
+                                            cov3D_precomp, raster_settings, antialiasing=antialiasing)
         else:
             color, radii = rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                               raster_settings)
+                                               raster_settings, antialiasing=antialiasing)
         if not color.requires_grad and getattr(_last, "capacity", None) is not None:
             # evaluation (torch.no_grad, or no input that takes a gradient): no backward pass will examine this forward's binning
             # self-check, so it is examined here, before the image is used (include/das3r_raster.h: das3r_raster_check)

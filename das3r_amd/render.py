@@ -171,15 +171,24 @@ def rasterizer_inputs(cam, pc, pipe, bg_color, scaling_modifier=1.0, override_co
     return settings, kw
 
 
+def _mode_kw(pipe, return_invdepth):
+    """GaussianRasterizer.forward's keywords beyond upstream's eight tensors: only those that are on."""
+    kw = {"return_invdepth": True} if return_invdepth else {}
+    if bool(getattr(pipe, "antialiasing", False)):
+        kw["antialiasing"] = True
+    return kw
+
+
 def das3r_render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, camera_pose=None,
                  filtering=None, use_conf=True, fused=False, variant="render", return_invdepth=False):
     """viewpoint_camera: .FoVx .FoVy .image_height .image_width .projection_matrix (4x4, already transposed) [.camera_center for
     pipe.convert_SHs_python]; pc: splat model (das3r_amd.model.SplatModel or anything with the same attributes); pipe: .debug
     .compute_cov3D_python .convert_SHs_python; camera_pose: (7,) tensor (qw,qx,qy,qz,tx,ty,tz), may require grad.
-    return_invdepth: render_pkg["invdepth"] = the [1, H, W] inverse-depth image (GaussianRasterizer.forward; differentiable)."""
+    return_invdepth: render_pkg["invdepth"] = the [1, H, W] inverse-depth image (GaussianRasterizer.forward; differentiable).
+    pipe.antialiasing (where upstream's newer renderer reads it; absent = False): the rasterizer's antialiasing mode."""
     settings, kw = rasterizer_inputs(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, camera_pose, filtering,
                                      use_conf, fused, variant)
-    out = GaussianRasterizer(raster_settings=settings)(**kw, **({"return_invdepth": True} if return_invdepth else {}))   # (upstream's call when off)
+    out = GaussianRasterizer(raster_settings=settings)(**kw, **_mode_kw(pipe, return_invdepth))   # (upstream's call when both are off)
     image, radii = out[0], out[1]
     if variant == "confidence":
         return image   # (render_confidence returns the image alone: gaussian_renderer/__init__.py:510)
@@ -219,7 +228,7 @@ def das3r_render_3dgs(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0
         kw["colors_precomp"] = torch.clamp_min(sh_to_rgb(pc.active_sh_degree, per_channel, away / away.norm(dim=1, keepdim=True)) + 0.5, 0.0)
     else:
         kw["shs"] = pc.get_features
-    image, radii = GaussianRasterizer(raster_settings=settings)(**kw)
+    image, radii = GaussianRasterizer(raster_settings=settings)(**kw, **_mode_kw(pipe, False))
     return {"render": image, "viewspace_points": means2D, "visibility_filter": radii > 0, "radii": radii}
 
 

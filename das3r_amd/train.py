@@ -204,7 +204,7 @@ def test_pose_pass(model, test_cams, gt_dynamic_masks, opt: OptimParams, pipe, b
             m = gt_dynamic_masks.get(cam.uid) if gt_dynamic_masks else None
             H, W = cam.image_height, cam.image_width
             static_hw = (1 - resize_mask_nearest(m, H, W)[0]).contiguous() if m is not None else _ones_hw(model, H, W)
-            fast_step.test_pose_step(model, cam, static_hw, opt, background)
+            fast_step.test_pose_step(model, cam, static_hw, opt, background, pipe)
             continue
         pkg = das3r_render(cam, model, pipe, background, camera_pose=model.get_RT_test(cam.uid), fused=fused)
         m = gt_dynamic_masks.get(cam.uid) if gt_dynamic_masks else None

@@ -151,7 +151,12 @@ typedef struct {
                               * (flags = 0) the backward reads the rows: the gradients are the same bit for bit either way.
                               * On the way IN, das3r_raster_forward reads bit 3 before it clears the struct: set, it is the caller's word that no
                               * backward pass will follow (an evaluation render), and the forward does not write the Jacobian (bit 2 stays clear;
-                              * a backward would still be correct, reading the rows).  A zero-filled struct: the Jacobian is written as above. */
+                              * a backward would still be correct, reading the rows).  A zero-filled struct: the Jacobian is written as above.
+                              * Bit 4, read on the way IN as bit 3 is and set again on the way out: an antialiased forward (upstream's 2D mip
+                              * filter): every splat is blended with opacity o * sqrt(max(rho, 2.5e-5)), rho = det(cov2D) / det(cov2D + 0.3 I);
+                              * radii, conics and colours are unchanged.  das3r_raster_backward / _depth differentiate the factor iff bit 4 is
+                              * set in the flags handed back: a caller that asked for antialiasing hands the forward's flags back.  flags = 0
+                              * stays valid for every forward that was not antialiased. */
 } das3r_raster_saved;
 
 /* Gradient outputs of backward.  Every buffer is fully written by the call (no pre-zeroing needed). */

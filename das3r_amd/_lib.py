@@ -74,7 +74,8 @@ EXPORTS = ("das3r_raster_forward", "das3r_raster_backward", "das3r_raster_backwa
            "das3r_adam_step", "das3r_adam_step_gated", "das3r_photometric_blocks", "das3r_photometric_forward", "das3r_photometric_backward",
            "das3r_has_experiments", "das3r_pair_counters", "das3r_debug_poison_lds", "das3r_debug_inject_fault", "das3r_debug_mutate",
            "das3r_pose_matrices_qt", "das3r_pose_chain_qt", "das3r_photometric_finish", "das3r_pretransform_backward_adam", "das3r_pretransform_pose_sums",
-           "das3r_raster_count_live_pairs", "das3r_photometric_backward_finish", "das3r_pose_chain_qt_rearm", "das3r_ssim_map_forward", "das3r_ssim_map_backward")
+           "das3r_raster_count_live_pairs", "das3r_photometric_backward_finish", "das3r_pose_chain_qt_rearm", "das3r_ssim_map_forward", "das3r_ssim_map_backward",
+           "das3r_split_colour_rule", "das3r_split_colour_switch")
 
 _lib = None
 
@@ -167,6 +168,28 @@ def reload_switches():
     L.das3r_reload_switches.restype = None
     L.das3r_reload_switches.argtypes = []
     L.das3r_reload_switches()
+
+
+def split_colour_rule(has_sh, sh_degree, P, binning_path, forced=None, no_backward=False):
+    """include/das3r_raster.h das3r_split_colour_rule: does a forward of this shape take the split preprocess?  binning_path: 0 global
+    depth sort, 1 local order / segmented, 2 fused emission; forced=None: what DAS3R_SPLIT_COLOUR says (as last read); no_backward: an
+    evaluation forward (das3r_raster_saved.flags bit 3 on the way in)."""
+    L = load()
+    L.das3r_split_colour_rule.restype = C.c_int
+    L.das3r_split_colour_rule.argtypes = [C.c_int32] * 6
+    L.das3r_split_colour_switch.restype = C.c_int
+    L.das3r_split_colour_switch.argtypes = []
+    if forced is None:
+        forced = L.das3r_split_colour_switch()
+    return bool(L.das3r_split_colour_rule(int(bool(has_sh)), int(sh_degree), int(P), int(binning_path), int(bool(no_backward)), int(forced)))
+
+
+def split_colour_switch():
+    """-1 / 0 / 1: DAS3R_SPLIT_COLOUR = "0" / unset / "1", as the library last read it (reload_switches)."""
+    L = load()
+    L.das3r_split_colour_switch.restype = C.c_int
+    L.das3r_split_colour_switch.argtypes = []
+    return int(L.das3r_split_colour_switch())
 
 
 def has_experiments():

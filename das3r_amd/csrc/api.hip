@@ -75,6 +75,7 @@ static void load_switches() {
     if ((e = env("DAS3R_BINNING"))) w.binning = e[0] == 'l' ? 1 : (e[0] == 'r' ? -1 : (e[0] == 's' ? (strchr(e, '3') ? 3 : 2) : 0));
     w.capacity_exact = (e = env("DAS3R_CAPACITY")) && e[0] == 'e';
     w.fused_emit_off = (e = env("DAS3R_FUSED_EMIT")) && e[0] == '0';
+    if ((e = env("DAS3R_SPLIT_COLOUR"))) w.split_colour = e[0] == '0' ? -1 : (e[0] == '1' ? 1 : 0);   // (A-B runs, tests: the split preprocess off / on)
     w.tile_lpt_off = (e = env("DAS3R_TILE_LPT")) && e[0] == '0';   // (A-B runs: the region forward in the locality order of the other kernels)
     if ((e = env("DAS3R_RENDER"))) w.render_fwd = e[0] == 'q' ? 1 : (e[0] == 'r' ? 2 : (e[0] == 'l' ? 3 : (e[0] == 's' ? 4 : (e[0] == 'f' ? 5 : 0))));
     if ((e = env("DAS3R_RENDER_BWD"))) {   // dpp | mfma | scan[a][64|128|256|512]
@@ -162,6 +163,57 @@ bool grid_is_resident(int nblocks) {
         cached_limit = cus * 2;   // the heaviest chained kernels get 3 workgroups per CU
     }
     return nblocks <= cached_limit;
+}
+
+// The split preprocess (preprocess.hip: geometry kernel on the caller's stream, SH colour kernel on a side stream beside the binning chain):
+// taken or not from the call's SHAPE alone, never from a timing, so that a job computes with the same kernels however it was scheduled (both
+// forms store the same bits; the rule keeps the launch sequence reproducible too).
+//   binning_path   0 the global depth sort (it scatters the depth keys the colour kernel reads: fused kernel)
+//                  1 index-order emission with a binning chain of its own (local order, segmented): the window the colour kernel fills
+//                  2 emission fused into the preprocess kernel (P <= 196 k, the whole grid resident: no chain to run beside)
+//   forced         Switches::split_colour: -1 never, 1 wherever it can run (SH given, active degree >= 1, path 1), 0 by shape:
+// active degree >= 2 (rows of 108 / 192 bytes and the nine Jacobian planes: at degree 0 / 1 the colour is 12 / 48 bytes of input, nothing to
+// hide), P >= SPLIT_MIN_P (below that the colour kernel is a few microseconds, of the order of the fork and the join themselves), and a
+// forward a backward may follow (flags bit 3 clear on the way in).  An evaluation forward keeps the fused kernel: its callers wait for every
+// view, and where the stream has run dry before the call — the no-grad glue render, bench.py's eval_forward — the six host calls of the fork
+// and the join are on the critical path themselves: 3.11 -> 3.18 ms per view measured, against 0.657 -> 0.648 on the fused evaluation path.
+constexpr int SPLIT_MIN_P = 1 << 18;
+bool split_colour_rule(bool has_sh, int sh_degree, int P, int binning_path, bool no_backward, int forced) {
+    if (!has_sh || sh_degree < 1 || binning_path != 1 || forced < 0 || P <= 0) return false;
+    if (forced > 0) return true;
+    return sh_degree >= 2 && P >= SPLIT_MIN_P && !no_backward;
+}
+
+// One side stream and its two events per (host thread, device, caller stream), created at the first split forward of the stream and destroyed
+// with the thread.  K jobs in flight (farm.run_jobs: K host threads, each on its own stream) get one each; the hardware queue count is the
+// runtime's business.  (A side stream of the lowest priority the device offers measured the same as this one: ledger.)
+struct SideStreams {
+    struct Entry { int dev; hipStream_t caller; SideStream ss; };
+    std::vector<Entry> all;
+    ~SideStreams() {
+        for (auto &e : all) {
+            (void)hipEventDestroy(e.ss.fork);
+            (void)hipEventDestroy(e.ss.join);
+            (void)hipStreamDestroy(e.ss.stream);
+        }
+    }
+};
+static int side_stream_for(hipStream_t s, SideStream *out) {
+    static thread_local SideStreams streams;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    for (auto &e : streams.all)
+        if (e.dev == dev && e.caller == s) { *out = e.ss; return DAS3R_OK; }
+    SideStream ss = {nullptr, nullptr, nullptr, 0};
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    ss.colour_blocks = COLOUR_WGS_PER_CU * (cus > 0 ? cus : 1);
+    HIP_TRY(hipStreamCreateWithFlags(&ss.stream, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&ss.fork, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&ss.join, hipEventDisableTiming));
+    streams.all.push_back(SideStreams::Entry{dev, s, ss});
+    *out = ss;
+    return DAS3R_OK;
 }
 
 int sort_ipl_override() { return switches().sort_ipl; }
@@ -323,6 +375,10 @@ extern "C" void das3r_debug_mutate(uint32_t what) {
     load_switches();
 }
 extern "C" const char *das3r_last_error(void) { return g_err; }
+extern "C" int das3r_split_colour_switch(void) { return switches().split_colour; }
+extern "C" int das3r_split_colour_rule(int32_t has_sh, int32_t sh_degree, int32_t P, int32_t binning_path, int32_t no_backward, int32_t forced) {
+    return split_colour_rule(has_sh != 0, sh_degree, P, binning_path, no_backward != 0, forced) ? 1 : 0;
+}
 
 extern "C" int das3r_raster_get_layout(int32_t P, int64_t num_rendered, int32_t W, int32_t H, das3r_raster_layout *out) {
     if (!out || P < 0 || num_rendered < 0 || W <= 0 || H <= 0) { set_error("das3r_raster_get_layout: invalid argument"); return DAS3R_ERR_INVALID_ARG; }
@@ -486,6 +542,7 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
     // the geometry buffer also holds Layout::g_shjac (flags bit 2) — unless the caller said that no backward will read it (flags bit 3 on the
     // way in, read before the struct is cleared below)
     const bool shjac = in->shs != nullptr && a->sh_degree >= 2 && !(saved->flags & NO_BACKWARD_IN_FLAG);
+    const bool no_backward = (saved->flags & NO_BACKWARD_IN_FLAG) != 0;
     const bool aa = (saved->flags & ANTIALIAS_FLAG) != 0;   // (bit 4 on the way in: an antialiased forward; set again on the way out)
     Layout L;
     compute_layout(P, 0, W, H, &L, shjac);
@@ -620,6 +677,45 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
     if (forced == 0 && verdict.radix_left > 0) verdict.radix_left--;
     const uint32_t count_tag = ++mb->seq ? mb->seq : ++mb->seq;
     unsigned long long *arrive = arrive_ring + (size_t)(count_tag % ARRIVE_SLOTS) * ARRIVE_WORDS;
+    // The split preprocess: the fork event is recorded behind the geometry kernel (launch_preprocess); the colour kernel goes to the side
+    // stream once the binning kernels are enqueued on s (join.launch()), and s waits for it (join.now()) in front of the first kernel that
+    // reads a colour, `clamped` or a Jacobian plane — the compositing forward.  Whatever is pending on the side stream when this function
+    // returns, on EVERY way out, s waits for: once the call's work on s is complete the side stream touches neither the caller's tensors
+    // nor the geometry buffer.  (A way out between the fork and the launch leaves nothing on the side stream.)
+    struct Join {
+        hipStream_t s;
+        const das3r_raster_args *a;
+        const das3r_raster_in *in;
+        char *const *geom;
+        const Layout *L;
+        SideStream side;
+        bool forked, pending;
+        int launch() {
+            if (!forked) return DAS3R_OK;
+            forked = false;
+            pending = true;   // (from the first call that touches the side stream on)
+            return launch_sh_colour(a, in, *geom, *L, &side);
+        }
+        int now() {
+            const int r = launch();
+            if (r) return r;
+            if (!pending) return DAS3R_OK;
+            pending = false;
+            HIP_TRY(hipStreamWaitEvent(s, side.join, 0));
+            return DAS3R_OK;
+        }
+        ~Join() {
+            if (pending) (void)hipStreamWaitEvent(s, side.join, 0);
+        }
+    } join = {s, a, in, &saved->geom, &L, {nullptr, nullptr, nullptr, 0}, false, false};
+    auto split_side = [&](int binning_path, const SideStream **side) -> int {   // *side: null = the fused kernel
+        *side = nullptr;
+        if (!split_colour_rule(in->shs != nullptr, a->sh_degree, P, binning_path, no_backward, switches().split_colour)) return DAS3R_OK;
+        const int r = side_stream_for(s, &join.side);
+        if (r) return r;
+        *side = &join.side;
+        return DAS3R_OK;
+    };
     // everything behind the count: scan + emission, partition, tile ranges, compositing (L laid out for `cap`, buffer allocated)
     auto bin_and_render = [&](int64_t cap, bool local_order, bool ctrl_zeroed, uint32_t *count_out = nullptr, uint32_t count_out_tag = 0,
                               uint32_t *emit_slot = nullptr /*the preprocess kernel has emitted the instances already*/) -> int {
@@ -645,6 +741,7 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
         uint32_t *dead_keys = nullptr;
         if ((r = launch_binning(P, cap, W, H, out->radii, saved->geom, saved->binning, saved->img, L, fused_scan, host_late, late_tag,
                                 a->debug != 0, s, &dead_keys, emit_slot, mb->dev + 10, verdict.gen))) return r;
+        if ((r = join.launch())) return r;   // the split preprocess: the colour kernel, beside the binning kernels enqueued above
         LocalBin lb = {(float4 *)(saved->binning + L.b_ckpt), nullptr, nullptr, nullptr, nullptr, verdict.gen, (uint32_t)(P - 1), (uint32_t)cap};
         if (decide_fine && cap > 0 && use_quad_lanes(L, lb)) {   // (shapes the one-workgroup-per-tile kernel would take: few tiles, long lists)
             const uint32_t tag = ++mb->seq ? mb->seq : ++mb->seq;
@@ -680,6 +777,7 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
             lb.keys = dead_keys;
             lb.host_flag = mb->dev + 10;
         }
+        if ((r = join.now())) return r;   // (a redo finds the colours there already: nothing is pending the second time)
         return launch_render_forward(a, in->colors_precomp, out->out_color, saved->geom, saved->binning, saved->img, L, lb, s, out->out_invdepth,
                                      depth ? (float4 *)(saved->binning + L.d_ckpt) : nullptr);
     };
@@ -741,8 +839,11 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
             }
             seg_dhist = dhist;
             apply_seg();
+            const SideStream *side = nullptr;
+            if ((rc = split_side(1, &side))) return rc;
             if ((rc = launch_preprocess(a, in, out->radii, saved->geom, saved->img, saved->binning + L.b_ghist, L.b_ctrl_bytes, L, nullptr, mb->dev,
-                                        count_tag, s, nullptr, dhist, dhist_next, aa))) return rc;
+                                        count_tag, s, nullptr, dhist, dhist_next, aa, side))) return rc;
+            join.forked = side != nullptr;
             if ((rc = bin_and_render(cap, local, true, mb->dev, count_tag))) return rc;
         }
         if ((rc = mailbox_wait(mb, 2, count_tag, s))) return rc;
@@ -768,7 +869,10 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
             HIP_TRY(hipMemsetAsync(dhist, 0, 4 * 256, s));
         }
         seg_dhist = dhist;
-        if ((rc = launch_preprocess(a, in, out->radii, saved->geom, saved->img, nullptr, 0, L, arrive, mb->dev, count_tag, s, nullptr, dhist, dhist_next, aa))) return rc;
+        const SideStream *side = nullptr;
+        if ((rc = split_side((local || seg) ? 1 : 0, &side))) return rc;
+        if ((rc = launch_preprocess(a, in, out->radii, saved->geom, saved->img, nullptr, 0, L, arrive, mb->dev, count_tag, s, nullptr, dhist, dhist_next, aa, side))) return rc;
+        join.forked = side != nullptr;
         if (!local && !seg && (rc = launch_depth_sort(P, saved->geom, L, 0, nullptr, 0, a->debug != 0, s))) return rc;
         if ((rc = mailbox_wait(mb, 2, count_tag, s))) return rc;    // usually there already: preprocess finished long ago
         if ((rc = prefiltered_ok())) return rc;
@@ -778,6 +882,7 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
         verdict.peak_I = std::max(I, verdict.peak_I - verdict.peak_I / 1024);
         if (local && forced == 0 && I > LOCAL_AVG * L.ntiles) {   // the scene grew: global sort after all
             local = false;
+            if ((rc = join.now())) return rc;   // (the sort scatters the depth keys the colour kernel reads)
             if ((rc = launch_depth_sort(P, saved->geom, L, 0, nullptr, 0, a->debug != 0, s))) return rc;
         }
         compute_layout(P, cap, W, H, &L, shjac);

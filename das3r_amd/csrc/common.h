@@ -47,6 +47,7 @@ struct Switches {
     int inject_fault;
     int mutate;            // das3r_debug_mutate (tests): 1 = the block-walk backward evaluates exp(power) (1 + 1e-4) — a biased kernel the parity tests must catch
     bool fwd_no_prefetch;   // DAS3R_FWD_PREFETCH=0: the rows forward kernel without its software prefetch (A-B runs)
+    int split_colour;      // DAS3R_SPLIT_COLOUR=0 | 1: the split preprocess (preprocess.hip) forced off (-1) / on (1) where it can run; unset (0): by shape (api.hip split_colour_rule)
     int tile_strip;   // DAS3R_TILE_STRIP: rows per strip of the compositing kernels' tile order (0 = row-major)      // DAS3R_INJECT_FAULT: bits OR-ed into the binning self-check word of every forward (fault-injection tests)
 };
 const Switches &switches();
@@ -273,9 +274,23 @@ constexpr int EMIT_STATUS_GRANULES = 1024;             // >= resident grid + its
 // ---- launchers implemented in the individual .hip files ----
 // binning_ctrl (may be null): the binning buffer's control words, zeroed by the same kernel when the buffer already exists
 // arrive: a zeroed 64-bit device word (self re-arming); host_out / tag: pinned mailbox that receives num_rendered
+// The split preprocess (preprocess.hip): a library-owned non-blocking stream beside the caller's, and the two events of the fork (recorded on
+// the caller's stream behind the geometry kernel; the side stream waits for it) and of the join (recorded on the side stream behind the colour
+// kernel; the caller's stream waits for it in front of the compositing kernel).  One per (host thread, device, caller stream): api.hip.
+constexpr int COLOUR_WGS_PER_CU = 4;   // persistent grid of sh_colour_kernel (preprocess.hip says why four)
+struct SideStream {
+    hipStream_t stream;
+    hipEvent_t fork, join;
+    int colour_blocks;   // COLOUR_WGS_PER_CU x the device's CUs
+};
+// side != null: the split form — the geometry kernel on s and the fork event recorded behind it; the caller then enqueues the colour kernel
+// (launch_sh_colour: side->stream waits for the fork, the join event is recorded behind the kernel) and makes s wait for side->join before
+// anything reads a colour, `clamped` or the Jacobian planes
 int launch_preprocess(const das3r_raster_args *a, const das3r_raster_in *in, int32_t *radii, char *geom, char *img, char *binning_ctrl,
                       size_t binning_ctrl_bytes, const Layout &L, unsigned long long *arrive, uint32_t *host_out, uint32_t tag,
-                      hipStream_t s, const EmitArgs *emit, uint32_t *dhist, uint32_t *dhist_next, bool aa /*ANTIALIAS_FLAG*/);
+                      hipStream_t s, const EmitArgs *emit, uint32_t *dhist, uint32_t *dhist_next, bool aa /*ANTIALIAS_FLAG*/,
+                      const SideStream *side = nullptr);
+int launch_sh_colour(const das3r_raster_args *a, const das3r_raster_in *in, char *geom, const Layout &L, const SideStream *side);
 int launch_mark_visible(int P, const float *means3D, const float *viewmatrix, uint8_t *present, hipStream_t s);
 // part 0: everything that can be enqueued before num_rendered is known; part 1: the rest, which also zeroes the binning buffer's
 // control words (binning_ctrl may be null)

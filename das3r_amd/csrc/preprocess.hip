@@ -18,22 +18,28 @@ namespace das3r {
 
 // AA (das3r_raster_saved.flags bit 4): the splat is blended with its opacity times splat_math.h aa_factor — the record's opacity, the
 // 1/255 cut-off and the opacity-aware tile box all see the product; conic, radius, tile rectangle, depth key and colour are unchanged.
-template <bool HAS_SH, bool HAS_COV, bool STAGE, bool AA = false>
-__global__ void __launch_bounds__(256) preprocess_kernel(
-    int P, int D, int M, const float *__restrict__ means3D, const float *__restrict__ scales, float scale_modifier,
-    const float *__restrict__ rotations, const float *__restrict__ opacities, const float *__restrict__ shs,
-    const float *__restrict__ cov3D_precomp, const float *__restrict__ colors_precomp, const float *__restrict__ viewmatrix,
-    const float *__restrict__ projmatrix, const float *__restrict__ campos, int W, int H, float tanfovx, float tanfovy,
-    int tiles_x, int tiles_y, int32_t *__restrict__ radii, uint32_t *__restrict__ depth_key, float4 *__restrict__ xyh,
-    float4 *__restrict__ conic_opacity, float4 *__restrict__ rgbd, uint8_t *__restrict__ clamped,
-    uint32_t *__restrict__ tiles_touched, uint32_t *__restrict__ rect32, int tight_rect /*bit 0: opacity-aware clipped rectangle; bit 1: prefiltered*/, uint32_t *__restrict__ zero_a, uint32_t zero_a_words, uint32_t *__restrict__ zero_b,
-    uint32_t zero_b_words, uint32_t *__restrict__ zero_c, uint32_t zero_c_words, unsigned long long *__restrict__ arrive,
-    uint32_t *__restrict__ host_out, uint32_t tag, const EmitArgs em,
-    uint32_t *__restrict__ dhist /*segmented binning path: 256-bin depth histogram of this forward, zeroed by the caller (segkey.h); else null*/,
-    uint32_t dhist_mask /*a pseudo-random 1 / (mask + 1) of the workgroups contribute (`sampled` below): a sample is all the bucket map needs*/,
-    uint32_t *__restrict__ dhist_next /*round 6: the library's OTHER histogram slot, zeroed here for the next forward of this stream (api.hip dhist_slots); else null*/,
-    const PreXform pre /*xyz != null (round 6, das3r_raster_in.pre): the raw parameters + the pose; means3D / scales / rotations / opacities are not read*/,
-    float *__restrict__ shjac /*[9][P] or null: the colour's Jacobian w.r.t. the view direction, plane 3c + k = d(rgb_c)/d(dir_k) (Layout::g_shjac)*/) {
+#define PRE_PARAMS \
+ \
+    int P, int D, int M, const float *__restrict__ means3D, const float *__restrict__ scales, float scale_modifier, \
+    const float *__restrict__ rotations, const float *__restrict__ opacities, const float *__restrict__ shs, \
+    const float *__restrict__ cov3D_precomp, const float *__restrict__ colors_precomp, const float *__restrict__ viewmatrix, \
+    const float *__restrict__ projmatrix, const float *__restrict__ campos, int W, int H, float tanfovx, float tanfovy, \
+    int tiles_x, int tiles_y, int32_t *__restrict__ radii, uint32_t *__restrict__ depth_key, float4 *__restrict__ xyh, \
+    float4 *__restrict__ conic_opacity, float4 *__restrict__ rgbd, uint8_t *__restrict__ clamped, \
+    uint32_t *__restrict__ tiles_touched, uint32_t *__restrict__ rect32, int tight_rect /*bit 0: opacity-aware clipped rectangle; bit 1: prefiltered*/, uint32_t *__restrict__ zero_a, uint32_t zero_a_words, uint32_t *__restrict__ zero_b, \
+    uint32_t zero_b_words, uint32_t *__restrict__ zero_c, uint32_t zero_c_words, unsigned long long *__restrict__ arrive, \
+    uint32_t *__restrict__ host_out, uint32_t tag, const EmitArgs em, \
+    uint32_t *__restrict__ dhist /*segmented binning path: 256-bin depth histogram of this forward, zeroed by the caller (segkey.h); else null*/, \
+    uint32_t dhist_mask /*a pseudo-random 1 / (mask + 1) of the workgroups contribute (`sampled` below): a sample is all the bucket map needs*/, \
+    uint32_t *__restrict__ dhist_next /*round 6: the library's OTHER histogram slot, zeroed here for the next forward of this stream (api.hip dhist_slots); else null*/, \
+    const PreXform pre /*xyz != null (round 6, das3r_raster_in.pre): the raw parameters + the pose; means3D / scales / rotations / opacities are not read*/, \
+    float *__restrict__ shjac /*[9][P] or null: the colour's Jacobian w.r.t. the view direction, plane 3c + k = d(rgb_c)/d(dir_k) (Layout::g_shjac)*/
+// GEOM: the geometry half of the split form (below, preprocess_geometry_kernel): no colour is read or evaluated, `clamped` and the Jacobian
+// planes are not stored — they belong to sh_colour_kernel — and the record's third float4 leaves as (0, 0, 0, depth), to be overwritten.
+// GEOM = false is the fused form: geometry and colour of a splat in one lane, one launch — the only form for precomputed colours, SH degree
+// 0, the emission fused in (em.status != null), the global depth sort and evaluation forwards (api.hip split_colour_rule).
+template <bool HAS_SH, bool HAS_COV, bool STAGE, bool AA = false, bool GEOM = false>
+__global__ void __launch_bounds__(256) preprocess_kernel(PRE_PARAMS) {
     const int gidx = blockIdx.x * blockDim.x + threadIdx.x;
     // Which workgroups sample the depth histogram: a full-avalanche hash of the index (round 5).  "Every (mask + 1)-th workgroup" is a
     // biased sample of a DAS3R model — its Gaussians are the pixels of its frames in row-major order, 256 of them are half an image row, and
@@ -186,6 +192,8 @@ __global__ void __launch_bounds__(256) preprocess_kernel(
                     load_sh_row(row, D, sh_vec_ok(row, D, M), sh);
                     col = sh_regs_to_rgb(D, sh, p, campos, clamp_out);
                     if (shjac != nullptr) sh_ddir_regs(D, sh, p, campos, jac_out);
+                } else if (GEOM) {
+                    col = make_float3(0.f, 0.f, 0.f);   // (a placeholder: sh_colour_kernel stores rgb + depth once this kernel has ended)
                 } else {
                     col = make_float3(colors_precomp[3 * idx], colors_precomp[3 * idx + 1], colors_precomp[3 * idx + 2]);
                 }
@@ -221,7 +229,7 @@ __global__ void __launch_bounds__(256) preprocess_kernel(
     tiles_touched[idx] = tiles_out;
     // the binned rectangle, packed (tile counts <= 255 per axis: 4080 pixels; above that the scan reads the records instead)
     rect32[idx] = tiles_out ? ((uint32_t)bx0 | ((uint32_t)bx1 << 8) | ((uint32_t)by0 << 16) | ((uint32_t)by1 << 24)) : 0u;
-    clamped[idx] = clamp_out;
+    if (!GEOM) clamped[idx] = clamp_out;
     if (HAS_SH && shjac != nullptr) {   // (uniform) nine planes: every store of a wave is one contiguous 256-byte run
 #pragma unroll
         for (int j = 0; j < 9; j++) shjac[(size_t)j * P + idx] = jac_out[j];
@@ -386,6 +394,112 @@ __global__ void __launch_bounds__(256) preprocess_kernel(
     }
 }
 
+// The split form (api.hip SideStream): the forward's critical path needs the geometry only — the binning reads rectangles, counts and depth
+// keys, never a colour — so this kernel does everything preprocess_kernel does except the colour, on the caller's stream, and
+// sh_colour_kernel evaluates the SH rows on a side stream BESIDE the latency-bound binning chain, joined in front of the compositing kernel.
+// Who writes which bytes of the 64-byte record, and when:
+//   preprocess_geometry_kernel   the whole record — bytes 0 - 31 (xyh, conic + opacity) and 48 - 63 (radius, tiles_touched, pad) for good,
+//                                bytes 32 - 47 as the placeholder (0, 0, 0, depth): whole 64-byte lines leave in unit-stride sweeps (with the
+//                                third float4 left out the kernel took 38 us instead of 29 at 1 M splats); besides the records: radii,
+//                                depth_key, tiles_touched, g_rect, the count hand-off, the depth histogram, every control word it zeroes
+//   sh_colour_kernel             bytes 32 - 47 (rgb + depth, one whole float4) and nothing else of a record; `clamped`, the nine Jacobian planes
+// The two never store at the same time: the side stream waits for an event recorded BEHIND the geometry kernel.  Nothing between the fork and
+// the join reads bytes 32 - 47, `clamped` or a plane (the binning reads rectangles, counts and depth keys).
+// Same code, same translation unit, same contraction flags: every byte the geometry kernel stores for good is the fused kernel's.  (An
+// instantiation of preprocess_kernel under a name of its own — the launch record, das3r_profile_report, says preprocess_geometry_kernel; a
+// kernel trace shows preprocess_kernel<false, ., false, ., true>.  The fused instantiations are the code they were before the split existed.)
+template <bool HAS_COV, bool AA>
+constexpr auto preprocess_geometry_kernel = preprocess_kernel<false, HAS_COV, false, AA, true>;
+
+// The colour half: lane per splat, launched behind the geometry kernel (the side stream waits for an event recorded behind it), so what that
+// kernel left is there: depth_key[idx] is 0xFFFFFFFF for a culled splat (near plane, singular covariance, empty rectangle: the fused
+// kernel stores zeros for those and so does this one, without redoing the test) and the bits of the view-space depth otherwise — the
+// record's rgbd.w, stored from here so that the store is one whole float4.  Only binning paths that leave the depth keys alone take the
+// split (the global depth sort scatters them).  The view direction comes from the camera-frame mean by the fused kernel's expressions
+// (sh_regs_to_rgb / sh_ddir_regs; the mean itself through pretransform_math.h with das3r_raster_in.pre), the SH rows through LDS by its
+// unit-stride float4 sweeps with clamped indices.  64 lanes and 13 KB of LDS per workgroup: small enough to become resident on a CU
+// beside two 52 KB workgroups of a partition pass.
+// Two things keep it from slowing the binning chain it runs beside more than it must (1 M splats, ms per step, parent 0.867 - 0.870;
+// docs/ledger.md (ca) has every run):
+//   * a persistent grid of COLOUR_WGS_PER_CU workgroups per CU, each taking slices of 64 splats in turn (api.hip SideStream::colour_blocks):
+//     one workgroup per slice (15 625 of them) 0.855, eight per CU 0.854 - 0.858, four 0.851 - 0.853, two 0.857 — the bytes in flight stay
+//     bounded and the chain's workgroups are not dispatched in between thousands of these;
+//   * the SH rows are read and the planes stored with the non-temporal hint — each byte is touched once, and without the hint the 250 MB
+//     stream evicts what the partition passes keep in cache: same box, 0.859 - 0.866 without, 0.842 - 0.845 with.
+constexpr int COLOUR_T = 64;
+template <bool STAGE>
+__global__ void __launch_bounds__(COLOUR_T) sh_colour_kernel(int P, int D, int M, const float *__restrict__ means3D, const PreXform pre,
+                                                             const float *__restrict__ shs, const float *__restrict__ campos,
+                                                             const uint32_t *__restrict__ depth_key, float4 *__restrict__ rgbd,
+                                                             uint8_t *__restrict__ clamped, float *__restrict__ shjac) {
+    __shared__ float4 sh_lds[STAGE ? COLOUR_T * 13 : 1];   // rows padded to 13 float4, as in the fused kernel
+    const int nblk = (P + COLOUR_T - 1) / COLOUR_T;
+    for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+        const int gidx = blk * COLOUR_T + threadIdx.x;
+        const bool live = gidx < P;
+        const int idx = live ? gidx : P - 1;
+        float3 p;
+        if (pre.xyz != nullptr) {   // (uniform)
+            PoseRegs pose;
+            load_pose(pre.Rm, pre.tv, pre.Lq, pose);
+            p = pre_mean(pose, pre.xyz[3 * idx], pre.xyz[3 * idx + 1], pre.xyz[3 * idx + 2]);
+        } else {
+            p = make_float3(means3D[3 * idx], means3D[3 * idx + 1], means3D[3 * idx + 2]);
+        }
+        const uint32_t key = depth_key[idx];
+        if (STAGE) {
+            const float4 *src = reinterpret_cast<const float4 *>(shs) + (size_t)blk * COLOUR_T * 12;
+            const size_t limit = (size_t)P * 12 - (size_t)blk * COLOUR_T * 12;   // (>= 12: the workgroup has a splat)
+            float4 v[12];
+#pragma unroll
+            for (int i = 0; i < 12; i++) {
+                const size_t f = (size_t)(i * COLOUR_T + threadIdx.x);
+                const float4 *q = src + (f < limit ? f : limit - 1);
+                const float *qf = reinterpret_cast<const float *>(q);   // (one global_load_dwordx4 ... nt)
+                v[i] = make_float4(__builtin_nontemporal_load(qf), __builtin_nontemporal_load(qf + 1), __builtin_nontemporal_load(qf + 2),
+                                   __builtin_nontemporal_load(qf + 3));
+            }
+#pragma unroll
+            for (int i = 0; i < 12; i++) {
+                const int f = i * COLOUR_T + threadIdx.x;
+                sh_lds[(f / 12) * 13 + (f % 12)] = v[i];
+            }
+            __syncthreads();
+        }
+        uint8_t clamp_out = 0;
+        float4 rgbd_out = make_float4(0.f, 0.f, 0.f, 0.f);
+        float jac_out[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (key != 0xFFFFFFFFu) {
+            float sh[48];
+            if (STAGE) {
+                const int n4 = (3 * (D + 1) * (D + 1) + 3) >> 2;
+#pragma unroll
+                for (int i = 0; i < 12; i++) {
+                    if (i < n4) {
+                        const float4 v = sh_lds[threadIdx.x * 13 + i];
+                        sh[4 * i] = v.x; sh[4 * i + 1] = v.y; sh[4 * i + 2] = v.z; sh[4 * i + 3] = v.w;
+                    }
+                }
+            } else {
+                const float *row = shs + (size_t)idx * M * 3;
+                load_sh_row(row, D, sh_vec_ok(row, D, M), sh);
+            }
+            const float3 col = sh_regs_to_rgb(D, sh, p, campos, clamp_out);
+            if (shjac != nullptr) sh_ddir_regs(D, sh, p, campos, jac_out);
+            rgbd_out = make_float4(col.x, col.y, col.z, __uint_as_float(key));
+        }
+        if (live) {
+            rgbd[(size_t)idx * SPLAT_REC] = rgbd_out;
+            clamped[idx] = clamp_out;
+            if (shjac != nullptr) {   // (uniform)
+#pragma unroll
+                for (int j = 0; j < 9; j++) __builtin_nontemporal_store(jac_out[j], &shjac[(size_t)j * P + idx]);   // (read next by the backward)
+            }
+        }
+        if (STAGE) __syncthreads();   // (the next slice's rows overwrite the staging area)
+    }
+}
+
 __global__ void __launch_bounds__(256) mark_visible_kernel(int P, const float *__restrict__ means3D,
                                                            const float *__restrict__ viewmatrix, uint8_t *__restrict__ present) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -399,7 +513,7 @@ __global__ void __launch_bounds__(256) mark_visible_kernel(int P, const float *_
 
 int launch_preprocess(const das3r_raster_args *a, const das3r_raster_in *in, int32_t *radii, char *geom, char *img, char *binning_ctrl,
                       size_t binning_ctrl_bytes, const Layout &L, unsigned long long *arrive, uint32_t *host_out, uint32_t tag,
-                      hipStream_t s, const EmitArgs *emit, uint32_t *dhist, uint32_t *dhist_next, bool aa) {
+                      hipStream_t s, const EmitArgs *emit, uint32_t *dhist, uint32_t *dhist_next, bool aa, const SideStream *side) {
     const int P = a->P;
     if (P == 0) return DAS3R_OK;
     const EmitArgs em = emit ? *emit : EmitArgs{nullptr, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0, nullptr, nullptr};
@@ -417,6 +531,24 @@ int launch_preprocess(const das3r_raster_args *a, const das3r_raster_in *in, int
         (uint32_t *)(geom + L.pub.tiles_touched), (uint32_t *)(geom + L.g_rect), (use_tight_rect() ? 1 : 0) | (a->prefiltered ? 2 : 0), (uint32_t *)(geom + L.g_ghist), (uint32_t)(L.g_ctrl_bytes / 4),                 \
         (uint32_t *)(img + L.pub.ranges), (uint32_t)(2 * L.ntiles), (uint32_t *)binning_ctrl, (uint32_t)(binning_ctrl_bytes / 4), arrive, host_out, tag, em, dhist, dhist_mask, dhist_next, pre, shjac
     const bool stage = has_sh && a->M == 16 && a->sh_degree >= 2 && ((uintptr_t)in->shs & 15) == 0 && !switches().no_sh_stage;
+    if (side != nullptr) {   // the split form (api.hip split_colour_rule: SH given, no fused emission, a binning path that keeps the depth keys)
+        if (!has_sh || emit != nullptr) { set_error("launch_preprocess: the split form needs SH rows and a binning chain of its own"); return DAS3R_ERR_INVALID_ARG; }
+        if (has_cov) {
+            if (aa) DAS3R_LAUNCH((preprocess_geometry_kernel<true, true>), grid, block, 0, s, ARGS);
+            else DAS3R_LAUNCH((preprocess_geometry_kernel<true, false>), grid, block, 0, s, ARGS);
+        } else {
+            if (aa) DAS3R_LAUNCH((preprocess_geometry_kernel<false, true>), grid, block, 0, s, ARGS);
+            else DAS3R_LAUNCH((preprocess_geometry_kernel<false, false>), grid, block, 0, s, ARGS);
+        }
+        KERNEL_CHECK(s, a->debug, "preprocess_geometry");
+        // fork BEHIND the geometry kernel: the colour kernel reads the depth keys it left, and two bandwidth-bound kernels side by side
+        // would only share the HBM rate — the window that is worth filling is the binning chain's.  Only the event is recorded here: the
+        // side stream's own calls (launch_sh_colour) are made once the binning kernels are enqueued on s, so that a caller whose stream
+        // had run dry (an evaluation loop that waits for every view) does not find the device idle behind the short geometry kernel
+        // while the host is busy with the side stream.
+        HIP_TRY(hipEventRecord(side->fork, s));
+        return DAS3R_OK;
+    }
 #define LAUNCH_PRE(SH, COV, ST)                                                                                   \
     do {                                                                                                          \
         if (aa) DAS3R_LAUNCH((preprocess_kernel<SH, COV, ST, true>), grid, block, 0, s, ARGS);                   \
@@ -431,6 +563,27 @@ int launch_preprocess(const das3r_raster_args *a, const das3r_raster_in *in, int
 #undef LAUNCH_PRE
 #undef ARGS
     KERNEL_CHECK(s, a->debug, "preprocess");
+    return DAS3R_OK;
+}
+
+// The colour half of the split form, on the side stream: waits for the fork event launch_preprocess recorded behind the geometry kernel,
+// leaves the join event behind the colour kernel.
+int launch_sh_colour(const das3r_raster_args *a, const das3r_raster_in *in, char *geom, const Layout &L, const SideStream *side) {
+    const int P = a->P;
+    const PreXform pre = pre_xform(in);
+    float *const shjac = L.g_shjac ? (float *)(geom + L.g_shjac) : nullptr;
+    const bool stage = a->M == 16 && a->sh_degree >= 2 && ((uintptr_t)in->shs & 15) == 0 && !switches().no_sh_stage;
+    HIP_TRY(hipStreamWaitEvent(side->stream, side->fork, 0));
+    const int slices = div_up(P, COLOUR_T);
+    const dim3 cgrid(slices < side->colour_blocks ? slices : side->colour_blocks), cblock(COLOUR_T);
+#define COLOUR_ARGS                                                                                                                 \
+    P, a->sh_degree, a->M, in->means3D, pre, in->shs, a->campos, (const uint32_t *)(geom + L.g_keyA), (float4 *)(geom + L.pub.rgbd), \
+        (uint8_t *)(geom + L.pub.clamped), shjac
+    if (stage) DAS3R_LAUNCH((sh_colour_kernel<true>), cgrid, cblock, 0, side->stream, COLOUR_ARGS);
+    else DAS3R_LAUNCH((sh_colour_kernel<false>), cgrid, cblock, 0, side->stream, COLOUR_ARGS);
+#undef COLOUR_ARGS
+    HIP_TRY(hipEventRecord(side->join, side->stream));   // (the caller's stream waits for it in front of the compositing kernel: api.hip)
+    KERNEL_CHECK(side->stream, a->debug, "sh_colour");
     return DAS3R_OK;
 }
 

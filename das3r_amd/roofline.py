@@ -37,7 +37,9 @@ def algorithmic_bytes(P, D, M, I, W, H):
     return per_kernel, b_fwd, b_bwd
 
 
-ALIASES = {"render_forward_rows_kernel": "render_forward_kernel",     # several implementations of each compositing stage
+ALIASES = {"preprocess_geometry_kernel": "preprocess_kernel",         # the split preprocess (preprocess.hip): two launches, the same
+           "sh_colour_kernel": "preprocess_kernel",                   # algorithmic bytes as the fused kernel
+           "render_forward_rows_kernel": "render_forward_kernel",     # several implementations of each compositing stage
            "render_forward_lanes_kernel": "render_forward_kernel",
            "render_backward_mfma_kernel": "render_backward_kernel",    # (render_rows.hip, render_bwd_mfma.hip,
            "render_backward_scan_kernel": "render_backward_kernel",    #  render_bwd_scan.hip, render_bwd_blk.hip)

@@ -33,7 +33,9 @@
  *     self-check ticket) instead of upstream's tuple; `capacity_hint` lets a caller forbid the speculative buffer layout;
  *     the k-NN entry point takes a caller-owned workspace.
  *
- * State between calls: the library owns no tensor, scratch or stream.  Per host thread and per device it keeps a pinned
+ * State between calls: the library owns no tensor and no scratch.  Per host thread, device and caller stream it keeps one non-blocking side
+ * stream and two events: a training forward of SH degree >= 2 on a large scene evaluates its colours there, beside the binning kernels, and has the
+ * caller's stream wait for them before it returns control of that stream (das3r_split_colour_rule).  Per host thread and per device it keeps a pinned
  * host mailbox (instance count, error word, a ring of 16 self-check tickets), the arrival counters of the count reduction,
  * the control ring of the fused scan and the last shape's instance counts (speculative capacity).  Calls of one thread on
  * one device must be issued in stream order; different threads / devices are independent.  Experiment switches (DAS3R_*
@@ -434,6 +436,15 @@ int das3r_raster_learning(int32_t set, uint32_t state[2]);
 /* 1 when the library was built with the superseded experiment kernels (make EXPERIMENTS=1: DAS3R_RENDER_BWD=mfma | stream,
  * DAS3R_SORT=classic), 0 for the shipped build; the parity tests of those kernels skip themselves on 0. */
 int das3r_has_experiments(void);
+
+/* The split preprocess (geometry kernel on the caller's stream, SH colour kernel on the library's side stream).  Which form a forward takes
+ * depends on its shape alone: has_sh (SH rows given), the active degree, P, the binning path the forward is on — 0 the global depth
+ * sort, 1 index-order emission with binning kernels of its own (local order, segmented), 2 emission fused into the preprocess kernel —
+ * and no_backward (das3r_raster_saved.flags bit 3 on the way in: an evaluation forward keeps the fused kernel).
+ * forced: what DAS3R_SPLIT_COLOUR says (das3r_split_colour_switch: -1 = "0", never; 1 = "1", wherever the split form can run; 0 = unset).
+ * Both forms store the same bits.  Host-only, no device needed. */
+int das3r_split_colour_rule(int32_t has_sh, int32_t sh_degree, int32_t P, int32_t binning_path, int32_t no_backward, int32_t forced);
+int das3r_split_colour_switch(void);
 
 int das3r_abi_version(void);
 const char *das3r_last_error(void);

@@ -244,7 +244,7 @@ def sequence_cost(seq_dir):
 
 
 def run_sequence_job(scene_id, iterations, device, frames=6, seq_dir=None, out_dir=None, fused=False, gt_mask_dir=None, dataset="sintel",
-                     progress=None, seq=None, keep=None, checkpoint_every=0, resume=False, pipe=None):
+                     progress=None, seq=None, keep=None, checkpoint_every=0, resume=False, pipe=None, depth_l1_init=0.0, depth_l1_final=0.0):
     """One independent 'sequence': load a preprocessed DAS3R sequence directory (das3r_amd.io_formats.load_sequence) — or,
     without one, build a synthetic multi-frame scene —, optimise it with the train-step harness, report the held-out PSNR and,
     with out_dir, write what the reference writes (point_cloud/iteration_N/point_cloud.ply, pose/pose_N.npy:
@@ -254,6 +254,9 @@ def run_sequence_job(scene_id, iterations, device, frames=6, seq_dir=None, out_d
     checkpoint_every (with out_dir): write <out_dir>/chkpnt<iteration>.pth every so many iterations (train_gui.py:626-628); resume: a job
     whose out_dir holds such a checkpoint continues from the newest one instead of starting at iteration 1 (a job killed at iteration
     3900 of 4000 used to start over — VERDICT r5 missing #5) and ends with the parameters the uninterrupted job ends with.
+    depth_l1_init / depth_l1_final (default 0: off): train with the sequence's depth maps as supervision — OptimParams.depth_l1_weight_init /
+    _final, and the training cameras then carry their frame's depth map (train.make_camera(depth=...)).  Both are kept in the checkpoints;
+    resuming with other values raises train.ResumeMismatch (the one failure that is NOT turned into a failed record: it is a wrong command).
     progress: called at the job's stages and every few hundred iterations (Rendezvous.tick).  pipe: the `pipe` of training and of the held-out
     report (job_pipe; None: the default one)."""
     progress = progress or (lambda: None)
@@ -263,7 +266,7 @@ def run_sequence_job(scene_id, iterations, device, frames=6, seq_dir=None, out_d
         with torch.cuda.device(device):
             _lib.forget_shapes()
     from .model import OptimParams
-    from .train import build_from_sequence, psnr_report, synthetic_sequence, train
+    from .train import ResumeMismatch, build_from_sequence, psnr_report, synthetic_sequence, train
     try:
         if seq is not None:
             pass
@@ -275,8 +278,8 @@ def run_sequence_job(scene_id, iterations, device, frames=6, seq_dir=None, out_d
         masks = seq.get("gt_dynamic_masks")   # ground-truth masks only: the report skips views without one
         # Gaussians, training poses and conf_static from the TRAINING frames only; the held-out frames ((idx + 5) % 10 == 0) give
         # their poses and their images as ground truth (scene/__init__.py:88-93, dataset_readers.py:342-347)
-        model, train_cams, test = build_from_sequence(seq, heldout=True)
-        opt = OptimParams(iterations=iterations)
+        model, train_cams, test = build_from_sequence(seq, heldout=True, depth_targets=depth_l1_init > 0 or depth_l1_final > 0)
+        opt = OptimParams(iterations=iterations, depth_l1_weight_init=float(depth_l1_init), depth_l1_weight_final=float(depth_l1_final))
         start, loop_state = 1, None
         if resume and out_dir is not None:
             from .train import latest_checkpoint, load_checkpoint
@@ -307,6 +310,8 @@ def run_sequence_job(scene_id, iterations, device, frames=6, seq_dir=None, out_d
         import math
         return dict(scene_id=scene_id, psnr=rep["psnr"], l1=rep["l1"], iters_per_s=stats["iters_per_s"],
                     n_splats=model.get_xyz.shape[0], ok=int(rep["views"] > 0 and math.isfinite(rep["psnr"])))
+    except ResumeMismatch:
+        raise
     except Exception as ex:  # noqa: BLE001 - keep the farm alive, report the failure in the table
         import traceback
         print(f"[farm] sequence {scene_id} failed: {ex!r}\n{traceback.format_exc()}", file=sys.stderr, flush=True)
@@ -421,6 +426,9 @@ def parser():
     ap.add_argument("--rendezvous", default=None, help="directory of the ranks' heartbeat / record files (default: <out>/.farm or /tmp/das3r_farm_<port>)")
     ap.add_argument("--antialiasing", action="store_true", help="train and report with the rasterizer's antialiasing mode (upstream's 2D mip filter); "
                     "render such a model with `das3r_amd.offline --antialiasing`")
+    ap.add_argument("--depth-l1-init", type=float, default=0.0, help="depth supervision: weight of the inverse-depth L1 term mean |(D - D*) m s| against "
+                    "the sequence's depth maps at iteration 1 (0 with --depth-l1-final 0, the default: off; upstream 3DGS uses 1.0)")
+    ap.add_argument("--depth-l1-final", type=float, default=0.0, help="its weight at the last iteration, log-linear in between (upstream 3DGS uses 0.01)")
     return ap
 
 
@@ -455,11 +463,13 @@ def main(argv=None):
         job = lambda s: run_sequence_job(s, args.iterations, device, seq_dir=os.path.join(args.data, dirs[s]),
                                          out_dir=os.path.join(args.out, dirs[s]) if args.out else None, fused=args.fused,
                                          gt_mask_dir=os.path.join(args.gt_dynamic_mask, dirs[s]) if args.gt_dynamic_mask else None,
-                                         dataset=args.dataset, progress=tick, checkpoint_every=args.checkpoint_every, resume=args.resume, pipe=pipe)
+                                         dataset=args.dataset, progress=tick, checkpoint_every=args.checkpoint_every, resume=args.resume, pipe=pipe,
+                                         depth_l1_init=args.depth_l1_init, depth_l1_final=args.depth_l1_final)
     else:
         mine = assign(args.sequences, rank, world)
         job = lambda s: run_sequence_job(s, args.iterations, device, fused=args.fused, progress=tick, checkpoint_every=args.checkpoint_every,
-                                         resume=args.resume, out_dir=os.path.join(args.out, f"seq_{s}") if args.out else None, pipe=pipe)
+                                         resume=args.resume, out_dir=os.path.join(args.out, f"seq_{s}") if args.out else None, pipe=pipe,
+                                         depth_l1_init=args.depth_l1_init, depth_l1_final=args.depth_l1_final)
     # (default: two in flight with the fused kernels — the measured configuration; the reference's PyTorch glue runs its backward passes in
     #  autograd's one device thread, where two jobs would queue behind each other: one at a time unless asked for)
     records = run_jobs(mine, job, args.jobs_per_gpu if args.jobs_per_gpu else (2 if (use_gpu and args.fused) else 1), device)

@@ -118,6 +118,23 @@ def _dense_f32(obj, name):
     return cache[1]
 
 
+def _dense_hw(cam, name, H, W):
+    """cam.<name> ([H, W]; a camera without depth_mask counts every pixel) as a dense fp32 device tensor, copied once if it is not one."""
+    if getattr(cam, name, None) is None and name == "depth_mask":
+        cam.depth_mask = torch.ones_like(cam.invdepthmap)
+    t = getattr(cam, name)
+    if tuple(t.shape) != (H, W):
+        raise ValueError(f"camera.{name} must be [H, W] = [{H}, {W}], got {tuple(t.shape)}")
+    if t.is_contiguous() and t.dtype == torch.float32:
+        return t
+    cache = getattr(cam, "_das3r_dense_" + name, None)
+    key = (t.data_ptr(), tuple(t.stride()), t.dtype, t._version)
+    if cache is None or cache[0] != key:
+        cache = (key, t.detach().contiguous().float())
+        setattr(cam, "_das3r_dense_" + name, cache)
+    return cache[1]
+
+
 def _settings(st, cam, model, bg):
     """GaussianRasterizationSettings of render() for this camera (gaussian_renderer/__init__.py:53-78): identity view matrix,
     projmatrix = I @ P^T, campos = 0.  Built once per (image size, FoV, projection-matrix tensor, SH degree, background tensor) —
@@ -143,7 +160,8 @@ def _settings(st, cam, model, bg):
     return rs
 
 
-def forward_backward(model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda_dssim, bg, geometry="grads", rearm_rows=None, antialiasing=False):
+def forward_backward(model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda_dssim, bg, geometry="grads", rearm_rows=None, antialiasing=False,
+                     depth_weight=0.0):
     """Render `cam` with the pose (q_row, t_row: views of one row of Q / T), masked photometric loss against cam.original_image
     under `static_hw` [H, W], and the complete backward.  Gradients: model parameters' .grad (f_rest: compact or none, as in
     das3r_amd.render), the pose gradient into gq_row / gt_row, d loss / d static_hw returned.
@@ -152,13 +170,19 @@ def forward_backward(model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda
     step of the four tensors taken in that very pass (das3r_pretransform_backward_adam: they never reach memory; model.optimizer.step()
     then finds the four without gradient and passes them by); "pose": the camera's sums alone, every per-Gaussian gradient dropped.
     antialiasing: the rasterizer's antialiasing mode (pipe.antialiasing), forward and backward, in every geometry mode.
+    depth_weight (host float; > 0 needs cam.invdepthmap and a geometry other than "pose"): the inverse-depth L1 term w * mean |(D - D*) m s|
+    with s = static_hw as a constant — the forward also renders the inverse-depth image, das3r_depth_l1 adds the term to out8 behind the
+    photometric loss (out8[0] the total, out8[5] the pure term, out8[6] the weighted one), and the rasterizer's backward is
+    das3r_raster_backward_depth.  0.0: none of that — the calls of a photometric step, one for one.
     -> (out8 = {loss, mse x 3, psnr_frame, ...} device tensor, d_static [H, W], package)"""
     st = _state(model)
     with _on_device(st.dev):   # (the library's per-device state and the raw stream belong to the model's GPU, current or not)
-        return _forward_backward(st, model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda_dssim, bg, geometry, rearm_rows, antialiasing)
+        return _forward_backward(st, model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda_dssim, bg, geometry, rearm_rows, antialiasing,
+                                 float(depth_weight))
 
 
-def _forward_backward(st, model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda_dssim, bg, geometry, rearm_rows=None, antialiasing=False):
+def _forward_backward(st, model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda_dssim, bg, geometry, rearm_rows=None, antialiasing=False,
+                      depth_weight=0.0):
     lib = _lib.load()
     dev, P = st.dev, st.P
     H, W = int(cam.image_height), int(cam.image_width)
@@ -194,7 +218,14 @@ def _forward_backward(st, model, cam, q_row, t_row, gq_row, gt_row, static_hw, l
         shs = _packed_sh(st, model, 1 + model._features_rest.shape[1])
     rs = _settings(st, cam, model, bg)
     e = st.e
-    I, image, radii, geom, binning, img, cap = _forward_full(rs, means3D, shs, e, opac, scales, rotations, e, pre=pre, antialiasing=antialiasing)
+    depth = depth_weight > 0.0
+    if depth and geometry == "pose":
+        raise ValueError("fast_step.forward_backward: the held-out pose pass never takes the depth term")
+    if depth:
+        I, image, radii, geom, binning, img, cap, invdepth = _forward_full(rs, means3D, shs, e, opac, scales, rotations, e, pre=pre,
+                                                                           antialiasing=antialiasing, invdepth=True)
+    else:
+        I, image, radii, geom, binning, img, cap = _forward_full(rs, means3D, shs, e, opac, scales, rotations, e, pre=pre, antialiasing=antialiasing)
     # ---- loss
     gt = _dense_f32(cam, "original_image")
     static_hw = static_hw if (static_hw.is_contiguous() and static_hw.dtype == torch.float32) else static_hw.contiguous().float()
@@ -208,6 +239,13 @@ def _forward_backward(st, model, cam, q_row, t_row, gq_row, gt_row, static_hw, l
     # (ABI 15: the loss / PSNR reduction of das3r_photometric_finish is the backward kernel's first workgroup's side duty — one launch less)
     _lib.check(lib.das3r_photometric_backward_finish(H, W, _p(image), _p(gt), _p(static_hw), C.c_float(lam), _p(dmaps), _p(st.one), _p(d_render),
                                                      _p(d_static), _p(partials), _p(out8), s), "das3r_photometric_backward_finish")
+    d_invdepth = None
+    if depth:   # ---- the inverse-depth L1 term: value into out8 (behind the kernel above, which wrote it), gradient for the rasterizer's backward
+        target, dmask = _dense_hw(cam, "invdepthmap", H, W), _dense_hw(cam, "depth_mask", H, W)
+        d_invdepth = torch.empty_like(invdepth)
+        dpart = torch.empty(int(lib.das3r_depth_l1_blocks(H, W)), 8, device=dev)
+        _lib.check(lib.das3r_depth_l1(H, W, _p(invdepth), _p(target), _p(dmask), _p(static_hw), C.c_float(depth_weight), None, _p(d_invdepth),
+                                      _p(dpart), _p(out8), s), "das3r_depth_l1")
     # ---- rasterizer backward (examines the forward's binning self-check first: include/das3r_raster.h)
     # round 6 (include/das3r_raster.h das3r_chain): with geometry == "adam" the rasterizer's backward goes on through the pre-transform — chain
     # rule, the Adam step of xyz / rotation / scaling / opacity, dL/d(confidence), the pose sums — and the four camera-frame gradient tensors
@@ -222,7 +260,8 @@ def _forward_backward(st, model, cam, q_row, t_row, gq_row, gt_row, static_hw, l
         chain.beta1, chain.beta2, chain.eps = opt_.betas[0], opt_.betas[1], opt_.eps
         conf_grad = g_conf
     g_means2D, _g_colors, g_opac, g_means3D, _g_cov, g_sh, g_scales, g_rot = _backward_impl(
-        rs, I, d_render, means3D, shs, e, opac, scales, rotations, e, geom, binning, img, cap, pre=pre, chain=chain)
+        rs, I, d_render, means3D, shs, e, opac, scales, rotations, e, geom, binning, img, cap, pre=pre, chain=chain,
+        **({"grad_invdepth": d_invdepth} if depth else {}))
     # ---- pre-transform backward, pose chain rule
     if chain is not None:
         del keep
@@ -268,23 +307,28 @@ def _forward_backward(st, model, cam, q_row, t_row, gq_row, gt_row, static_hw, l
         model._conf_static.grad = conf_grad.view(model._conf_static.shape)
     st.means2D.grad = g_means2D
     pkg = _Pkg(render=image, viewspace_points=st.means2D, radii=radii)
+    if depth:
+        pkg["invdepth"] = invdepth
     return out8, d_static, pkg
 
 
 def train_step(model, cam, opt, iteration, pipe, background):
-    """das3r_amd.train.train_step(fused=True) without autograd.  -> (loss, psnr_frame, package): 0-dim device tensors."""
+    """das3r_amd.train.train_step(fused=True) without autograd.  -> (loss, psnr_frame, package): 0-dim device tensors; the loss is the
+    total (photometric + the weighted inverse-depth L1 term when that is active for this view and iteration: train.depth_term_weight)."""
     model.update_learning_rate(iteration)
     if iteration % 3000 == 0:
         model.oneupSHdegree()
     st = _state(model)
     uid = cam.uid
+    from .train import depth_term_weight
+    w_depth = depth_term_weight(cam, opt, iteration)   # (a host float; 0.0 = today's step)
     with torch.no_grad(), _on_device(st.dev):   # (FusedAdam's launches too)
         # the dense pose gradients are zero outside the row of the view that stepped last; that row is zeroed by this step's pose chain launch
         prev = getattr(st, "dirty_uid", None)
         out8, d_static, pkg = forward_backward(model, cam, model.Q[uid], model.T[uid], st.Qg[uid], st.Tg[uid], model._conf_static[uid],
                                                opt.lambda_dssim, background, geometry="adam" if getattr(model, "fuse_geometry_adam", True) else "grads",
                                                rearm_rows=None if prev is None else (st.Qg[prev], st.Tg[prev]),
-                                               antialiasing=bool(getattr(pipe, "antialiasing", False)))
+                                               antialiasing=bool(getattr(pipe, "antialiasing", False)), depth_weight=w_depth)
         st.dirty_uid = uid
         model._conf_static.grad[uid] += d_static             # the loss sees conf_static twice: as opacity factor and as the frame's mask
         model.optimizer.step()

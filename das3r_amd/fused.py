@@ -437,6 +437,45 @@ class _Photometric(torch.autograd.Function):
         return d_render, None, d_static, None
 
 
+class _DepthL1(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, invdepth, target, mask, static, weight):
+        lib = _lib.load()
+        dev = invdepth.device
+        if dev.type != "cuda":
+            raise RuntimeError("das3r_amd.fused.depth_l1_loss: tensors must live on a HIP device; there is no CPU path")
+        H, W = int(invdepth.shape[-2]), int(invdepth.shape[-1])
+        if invdepth.numel() != H * W or any(t is not None and tuple(t.shape) != (H, W) for t in (target, mask, static)):
+            raise ValueError("invdepth must be [H, W] or [1, H, W]; target, mask and static [H, W]")
+        dense = lambda t: t.detach().contiguous().float()
+        D, target, mask = dense(invdepth), dense(target), dense(mask)
+        static = None if static is None else dense(static)
+        # value and gradient come out of the same sweep: the gradient for an upstream gradient of 1 is kept and scaled in backward.  The weight
+        # goes into the sweep, as in the direct iteration: behind `loss = photometric + term` the upstream gradient is exactly 1, and the
+        # gradient the rasterizer gets is then the direct iteration's bit for bit (a `w * term` outside would round once more)
+        d_invdepth = torch.empty_like(D)
+        partials = torch.empty(int(lib.das3r_depth_l1_blocks(H, W)), 8, device=dev)
+        out8 = torch.zeros(8, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.das3r_depth_l1(H, W, _p(D), _p(target), _p(mask), _p(static) if static is not None else None, C.c_float(weight), None,
+                                    _p(d_invdepth), _p(partials), _p(out8), _stream(dev))
+        _lib.check(rc, "das3r_depth_l1")
+        ctx.save_for_backward(d_invdepth)
+        return out8[6]
+
+    @staticmethod
+    def backward(ctx, g):
+        (d_invdepth,) = ctx.saved_tensors
+        return d_invdepth * g, None, None, None, None
+
+
+def depth_l1_loss(invdepth, target, mask, static=None, weight=1.0):
+    """-> weight * mean over all pixels of |(invdepth - target) * mask * static| (das3r_amd.losses.depth_l1) from one fused HIP sweep that
+    also leaves the gradient; differentiable in `invdepth` ([H, W] or [1, H, W]) only — `static` (the frame's conf_static, or None) is a
+    constant, `weight` a host float (the schedule's w)."""
+    return _DepthL1.apply(invdepth, target, mask, static, float(weight))
+
+
 class _SsimMap(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img1, img2):

@@ -17,6 +17,28 @@ def l1_loss(pred, gt, reduce=True):
     return d.mean() if reduce else d
 
 
+def depth_l1(invdepth, target, mask, static=None):
+    """The inverse-depth L1 term of a depth-supervised step (upstream 3DGS: torch.abs((invDepth - mono_invdepth) * depth_mask).mean()):
+    mean over ALL pixels of |(invdepth - target) * mask * static|, `static` (the frame's conf_static; None = 1) taken as a constant.  A pixel
+    whose mask * static is 0 contributes exactly 0 to value and gradient whatever `target` holds there (NaN included).  Any dtype; the
+    plain statement of what das3r_amd/csrc/depth_loss.hip computes."""
+    w = mask if static is None else mask * static.detach()
+    w = w.to(invdepth.dtype)
+    target = torch.where(w != 0, target.to(invdepth.dtype), torch.zeros((), dtype=invdepth.dtype, device=invdepth.device))
+    return ((invdepth - target) * w).abs().mean()
+
+
+def depth_l1_weight(opt, iteration):
+    """w(iteration) of the depth term: expon_lr_func(depth_l1_weight_init, depth_l1_weight_final, max_steps = opt.iterations) as a host float.
+    0.0 (the term is off) when both ends are 0, the default; upstream's values are 1.0 -> 0.01."""
+    w0, w1 = float(getattr(opt, "depth_l1_weight_init", 0.0)), float(getattr(opt, "depth_l1_weight_final", 0.0))
+    if w0 == 0.0 and w1 == 0.0:
+        return 0.0
+    if w0 <= 0.0 or w1 <= 0.0:
+        raise ValueError(f"depth_l1_weight_init / depth_l1_weight_final must both be positive (a log-linear schedule) or both 0 (off); got {w0}, {w1}")
+    return float(expon_lr_func(w0, w1, max_steps=opt.iterations)(iteration))
+
+
 _WINDOWS = {}
 
 

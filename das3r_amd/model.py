@@ -35,6 +35,10 @@ class OptimParams:   # /root/reference/arguments/__init__.py:73-90 (densificatio
     rotation_lr: float = 0.001
     lambda_dssim: float = 0.2
     psnr_threshold: float = 26.0   # train_gui.py:584 camera-optimizer gate
+    # depth supervision (upstream 3DGS's depth regularisation; not in the reference): loss += w(iteration) * mean |(D - D*) m s| for cameras that
+    # carry `invdepthmap`, w log-linear from _init to _final over `iterations` (losses.depth_l1_weight).  Both 0: off.  Upstream: 1.0 -> 0.01.
+    depth_l1_weight_init: float = 0.0
+    depth_l1_weight_final: float = 0.0
 
 
 def depth_to_points(K, cam2world, depth):

@@ -14,16 +14,39 @@ from types import SimpleNamespace
 import torch
 
 from .camera import focal2fov, projection_matrix
-from .losses import l1_loss, psnr, ssim
+from .losses import depth_l1, depth_l1_weight, l1_loss, psnr, ssim
 from .model import OptimParams, SplatModel
 from .render import das3r_render
 
 
-def make_camera(uid, image, focal, W, H, device, focal_y=None, camera_center=None):
+def make_camera(uid, image, focal, W, H, device, focal_y=None, camera_center=None, depth=None):
+    """depth ([H, W] metric depth of the frame, optional): the camera then carries the depth target as upstream 3DGS names it —
+    invdepthmap = 1 / depth where depth is finite and > 0, else 0, and depth_mask = 1 at those pixels, else 0 (both [H, W] fp32).  Without it
+    the two attributes are absent and the depth term never applies to the camera."""
     fovx, fovy = focal2fov(focal, W), focal2fov(focal if focal_y is None else focal_y, H)
     center = torch.zeros(3, device=device) if camera_center is None else camera_center.to(device)   # (only render()'s convert_SHs_python mode reads it)
-    return SimpleNamespace(uid=uid, FoVx=fovx, FoVy=fovy, image_width=W, image_height=H, original_image=image, camera_center=center,
-                           projection_matrix=projection_matrix(0.01, 100.0, fovx, fovy).transpose(0, 1).to(device))
+    cam = SimpleNamespace(uid=uid, FoVx=fovx, FoVy=fovy, image_width=W, image_height=H, original_image=image, camera_center=center,
+                          projection_matrix=projection_matrix(0.01, 100.0, fovx, fovy).transpose(0, 1).to(device))
+    if depth is not None:
+        d = torch.as_tensor(depth).to(device=device, dtype=torch.float32)
+        if tuple(d.shape) != (H, W):
+            raise ValueError(f"make_camera: depth must be [H, W] = [{H}, {W}], got {tuple(d.shape)}")
+        valid = torch.isfinite(d) & (d > 0)
+        cam.invdepthmap = torch.where(valid, 1.0 / torch.where(valid, d, torch.ones_like(d)), torch.zeros_like(d)).contiguous()
+        cam.depth_mask = valid.to(torch.float32).contiguous()
+    return cam
+
+
+def depth_term_weight(cam, opt, iteration):
+    """w(iteration) of the inverse-depth L1 term for this view, a host float: 0.0 unless the schedule's weight is positive AND the camera
+    carries `invdepthmap` (make_camera(depth=...)).  Nothing on the device is read."""
+    w = depth_l1_weight(opt, iteration)
+    return w if (w > 0.0 and getattr(cam, "invdepthmap", None) is not None) else 0.0
+
+
+def depth_mask_of(cam):
+    m = getattr(cam, "depth_mask", None)
+    return m if m is not None else torch.ones_like(cam.invdepthmap)
 
 
 def train_step(model: SplatModel, cam, opt: OptimParams, iteration, pipe, background, fused=False, fused_loss=None):
@@ -47,7 +70,8 @@ def train_step(model: SplatModel, cam, opt: OptimParams, iteration, pipe, backgr
     if iteration % 3000 == 0:
         model.oneupSHdegree()
     pose = model.get_RT(cam.uid)
-    pkg = das3r_render(cam, model, pipe, background, camera_pose=pose, fused=fused)
+    w_depth = depth_term_weight(cam, opt, iteration)   # (0.0: the step below is the photometric one, call for call)
+    pkg = das3r_render(cam, model, pipe, background, camera_pose=pose, fused=fused, **({"return_invdepth": True} if w_depth > 0.0 else {}))
     image = pkg["render"]
     gt = cam.original_image
     static = model._conf_static[cam.uid]
@@ -55,6 +79,9 @@ def train_step(model: SplatModel, cam, opt: OptimParams, iteration, pipe, backgr
         from .fused import masked_photometric_loss
         loss, mse = masked_photometric_loss(image, gt, static, opt.lambda_dssim)
         psnr_frame = (20 * torch.log10(1.0 / torch.sqrt(mse))).mean()
+        if w_depth > 0.0:
+            from .fused import depth_l1_loss
+            loss = loss + depth_l1_loss(pkg["invdepth"], cam.invdepthmap, depth_mask_of(cam), static, weight=w_depth)
         loss.backward(retain_graph=True)
         with torch.no_grad():
             model.optimizer.step()
@@ -71,6 +98,8 @@ def train_step(model: SplatModel, cam, opt: OptimParams, iteration, pipe, backgr
     Lssim = ssim_fn(image, gt, size_average=False)
     psnr_frame = psnr(image, gt).mean()
     loss = ((1.0 - opt.lambda_dssim) * Ll1 + opt.lambda_dssim * (1.0 - Lssim)).mean()
+    if w_depth > 0.0:
+        loss = loss + w_depth * depth_l1(pkg["invdepth"][0], cam.invdepthmap, depth_mask_of(cam), static)
     loss.backward(retain_graph=True)
     with torch.no_grad():
         model.optimizer.step()
@@ -79,6 +108,10 @@ def train_step(model: SplatModel, cam, opt: OptimParams, iteration, pipe, backgr
             model.optimizer_cam.step()
         model.optimizer_cam.zero_grad(set_to_none=True)
     return loss.detach(), psnr_frame.detach(), pkg
+
+
+class ResumeMismatch(ValueError):
+    """A checkpoint is resumed with settings that would silently change the job's schedule."""
 
 
 def save_checkpoint(path, model, iteration, loop_state=None):
@@ -125,6 +158,8 @@ def train(model, cameras, opt: OptimParams, iterations, pipe=None, background=No
     """Random camera without replacement per epoch (train_gui.py:546-555).  With test_cameras: train_test_psnr.py's loop, which
     walks the held-out views whenever the training stack has run empty (test_pose_pass).  Returns dict(loss, psnr, iters_per_s).
     checkpoint_every / checkpoint_dir: write chkpnt<iteration>.pth every so many iterations (train_gui.py:626-628 --checkpoint_iterations);
+    The weights of the depth term (opt.depth_l1_weight_init / _final) go into the checkpoint's loop state; resuming with other values raises
+    ResumeMismatch.
     start_iteration / loop_state: continue a job from load_checkpoint's result — the iterations that follow are the ones the
     uninterrupted job would have run (same cameras in the same order, same schedules, same optimizer moments)."""
     pipe = pipe or SimpleNamespace(debug=False, compute_cov3D_python=False, convert_SHs_python=False)
@@ -132,7 +167,13 @@ def train(model, cameras, opt: OptimParams, iterations, pipe=None, background=No
     background = background if background is not None else torch.zeros(3, device=dev)
     rng = random.Random(seed)
     stack, ema, last_psnr = [], torch.zeros((), device=dev), torch.zeros((), device=dev)
+    depth_l1 = (float(getattr(opt, "depth_l1_weight_init", 0.0)), float(getattr(opt, "depth_l1_weight_final", 0.0)))
     if loop_state is not None:
+        was = tuple(float(v) for v in (loop_state.get("depth_l1") or (0.0, 0.0)))   # (a checkpoint from before the depth term: off)
+        if was != depth_l1:
+            raise ResumeMismatch(f"this checkpoint was written by a job with depth-L1 weights {was[0]:g} -> {was[1]:g}; it is being resumed with "
+                                 f"{depth_l1[0]:g} -> {depth_l1[1]:g}, which would change the loss schedule mid-run: resume with the same "
+                                 "--depth-l1-init / --depth-l1-final (OptimParams.depth_l1_weight_init / _final)")
         rng.setstate(loop_state["rng"])
         by_uid = {c.uid: c for c in cameras}
         stack = [by_uid[u] for u in loop_state["stack"]]
@@ -166,7 +207,7 @@ def train(model, cameras, opt: OptimParams, iterations, pipe=None, background=No
                     library = _lib.learning()
             save_checkpoint(os.path.join(checkpoint_dir, f"chkpnt{it}.pth"), model, it,
                             dict(rng=rng.getstate(), stack=[c.uid for c in stack], ema=ema.detach().clone(), last_psnr=last_psnr.detach().clone(),
-                                 library=library))
+                                 library=library, depth_l1=depth_l1))
     if dev.type == "cuda":
         torch.cuda.current_stream(dev).synchronize()
     done = max(iterations - start_iteration + 1, 1)
@@ -430,8 +471,10 @@ def split_sequence(seq):
     return [i for i in range(F) if not is_test_index(i)], test
 
 
-def build_from_sequence(seq, sh_degree=3, heldout=False):
-    """-> (model, cameras) from every frame, or with heldout=True -> (model, train cameras, test cameras): Gaussians, training
+def build_from_sequence(seq, sh_degree=3, heldout=False, depth_targets=False):
+    """depth_targets: the TRAINING cameras carry their frame's depth map as the depth term's target (make_camera(depth=...)); held-out
+    cameras never do.
+    -> (model, cameras) from every frame, or with heldout=True -> (model, train cameras, test cameras): Gaussians, training
     poses and conf_static come from the TRAINING frames only (the reference builds them from scene.train_cameras:
     scene/__init__.py:88-93), the held-out frames only contribute their poses (init_test_RT_seq) and their images as ground
     truth.  Camera uids index the model's per-frame tensors: 0..n_train-1 / 0..n_test-1."""
@@ -444,9 +487,9 @@ def build_from_sequence(seq, sh_degree=3, heldout=False):
     model = SplatModel(sh_degree).create_from_frames(seq["images"][sel], seq["depths"][sel], seq["confs"][sel], seq["dyna_avg"][sel],
                                                      seq["K"][sel], seq["cam2world"][sel], seq["w2c_pose7"][sel])
     K = seq["K"]   # per-frame focals (cameras.txt: scene/dataset_readers.py:139-147); principal point at the image centre
-    mk = lambda uid, i: make_camera(uid, seq["images"][i], float(K[i, 0, 0]), seq["W"], seq["H"], dev, focal_y=float(K[i, 1, 1]),
-                                    camera_center=seq["cam2world"][i][:3, 3])
-    cams = [mk(u, i) for u, i in enumerate(tr)]
+    mk = lambda uid, i, depth=None: make_camera(uid, seq["images"][i], float(K[i, 0, 0]), seq["W"], seq["H"], dev, focal_y=float(K[i, 1, 1]),
+                                                camera_center=seq["cam2world"][i][:3, 3], depth=depth)
+    cams = [mk(u, i, seq["depths"][i] if depth_targets else None) for u, i in enumerate(tr)]
     model.init_fov(cams[0].FoVx, cams[0].FoVy)
     if not heldout:
         return model, cams

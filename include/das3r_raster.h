@@ -352,6 +352,22 @@ int das3r_photometric_backward_finish(int32_t H, int32_t W, const float *render,
                                       const float *dmaps, const float *grad_loss, float *d_render, float *d_static, const float *partials,
                                       float *out8, das3r_stream_t stream);
 
+/* ---- inverse-depth L1 term (depth-supervised training; opt-in) ------------------------------------------------------------
+ * Additive symbols under ABI 16 (no struct and no existing entry point changes, as antialiasing and the split-colour rule were added).
+ * With D = the rasterizer's inverse-depth image (das3r_raster_out.out_invdepth), D* = target, m = mask, s = static_mask (NULL = 1; taken as
+ * a constant: no gradient to it), all [H,W] fp32 device pointers:
+ *     L_pure     = mean over all H*W pixels of |(D - D*) m s|
+ *     d_invdepth = grad_loss * weight * m s sgn((D - D*) m s) / (H W)      [H,W]; grad_loss: device scalar, NULL = 1; sgn(0) = 0
+ * A pixel with m s == 0 gives exactly 0 to both, whatever D* holds there (NaN included).  Values go into the caller's out8 in stream
+ * order: out8[5] = L_pure, out8[6] = weight * L_pure, out8[0] += weight * L_pure — behind das3r_photometric_backward_finish that makes
+ * out8[0] the step's total loss; a stand-alone caller hands in a zeroed out8.  partials: scratch of das3r_depth_l1_blocks(H, W) rows of 8
+ * floats (one partial sum per workgroup; need not be zeroed).  Two launches: the sweep, then one workgroup that adds the rows in index order
+ * — no floating-point atomics, bit-identical from run to run.  H <= 0, W <= 0, H * W > 2^30 or a NULL pointer other than static_mask /
+ * grad_loss: DAS3R_ERR_INVALID_ARG with a das3r_last_error() message, nothing launched. */
+int64_t das3r_depth_l1_blocks(int32_t H, int32_t W);
+int das3r_depth_l1(int32_t H, int32_t W, const float *invdepth, const float *target, const float *mask, const float *static_mask, float weight,
+                   const float *grad_loss, float *d_invdepth, float *partials, float *out8, das3r_stream_t stream);
+
 /* ---- introspection (used by the parity tests and the roofline accounting) ---- */
 
 /* Byte offsets of the saved intermediates inside geom / binning / img for given extents. */

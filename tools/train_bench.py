@@ -27,13 +27,16 @@ def main():
     ap.add_argument("--fused-pre", action="store_true")
     ap.add_argument("--breakdown", action="store_true")
     ap.add_argument("--depth", default="noise", choices=("noise", "smooth"), help="depth maps of the synthetic sequence (das3r_amd.train.synthetic_sequence)")
+    ap.add_argument("--depth-l1", nargs=2, type=float, default=(0.0, 0.0), metavar=("INIT", "FINAL"), help="time the depth-supervised step: weights of the "
+                    "inverse-depth L1 term (OptimParams.depth_l1_weight_init / _final; upstream 3DGS: 1.0 0.01); the cameras then carry the sequence's depth maps")
     args = ap.parse_args()
     from types import SimpleNamespace
     from das3r_amd.model import OptimParams
     from das3r_amd.train import build_from_sequence, synthetic_sequence, train_step
     seq = synthetic_sequence(frames=args.frames, W=args.W, H=args.H, focal=600.0, n_splats=20000, seed=0, depth=args.depth)
-    model, cams = build_from_sequence(seq)
-    opt = OptimParams(iterations=4000)
+    w0, w1 = args.depth_l1
+    model, cams = build_from_sequence(seq, depth_targets=w0 > 0 or w1 > 0)
+    opt = OptimParams(iterations=4000, depth_l1_weight_init=w0, depth_l1_weight_final=w1)
     model.training_setup(opt, fused=args.fused_adam) if args.fused_adam else model.training_setup(opt)
     pipe = SimpleNamespace(debug=False, compute_cov3D_python=False, convert_SHs_python=False)
     bg = torch.zeros(3, device="cuda")
@@ -47,7 +50,8 @@ def main():
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / args.iters * 1e3
     out = {"train_step_ms": round(ms, 3), "splats": int(model.get_xyz.shape[0]), "frames": args.frames, "image": [args.W, args.H],
-           "iters_per_s": round(1e3 / ms, 2), "fused_adam": bool(args.fused_adam), "fused_pre": bool(args.fused_pre)}
+           "iters_per_s": round(1e3 / ms, 2), "fused_adam": bool(args.fused_adam), "fused_pre": bool(args.fused_pre),
+           "depth_l1": [w0, w1]}
     if args.breakdown:
         from torch.profiler import ProfilerActivity, profile
         with profile(activities=[ProfilerActivity.CUDA]) as prof:

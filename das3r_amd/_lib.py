@@ -60,6 +60,19 @@ class RasterGrads(C.Structure):
                 ("dL_drotations", C.c_void_p), ("dL_dcov3D", C.c_void_p), ("scratch", C.c_void_p), ("chain", C.POINTER(Chain))]
 
 
+class PruneTensor(C.Structure):
+    """include/das3r_raster.h das3r_prune_tensor: one row-major tensor of das3r_prune_compact."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int64)]
+
+
+PRUNE_GROUP_ROWS = 1024   # DAS3R_PRUNE_GROUP_ROWS
+
+
+def prune_count_words(P):
+    """DAS3R_PRUNE_COUNT_WORDS(P): int32 words of das3r_prune_select's `count` (word 0 = kept rows, the rest scratch)."""
+    return 1 + (int(P) + PRUNE_GROUP_ROWS - 1) // PRUNE_GROUP_ROWS
+
+
 class RasterLayout(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in
                 ("geom_bytes", "binning_bytes", "img_bytes", "depth_key", "xy", "conic_opacity", "rgbd", "splat_stride", "clamped",
@@ -75,7 +88,7 @@ EXPORTS = ("das3r_raster_forward", "das3r_raster_backward", "das3r_raster_backwa
            "das3r_has_experiments", "das3r_pair_counters", "das3r_debug_poison_lds", "das3r_debug_inject_fault", "das3r_debug_mutate",
            "das3r_pose_matrices_qt", "das3r_pose_chain_qt", "das3r_photometric_finish", "das3r_pretransform_backward_adam", "das3r_pretransform_pose_sums",
            "das3r_raster_count_live_pairs", "das3r_photometric_backward_finish", "das3r_pose_chain_qt_rearm", "das3r_ssim_map_forward", "das3r_ssim_map_backward",
-           "das3r_split_colour_rule", "das3r_split_colour_switch", "das3r_depth_l1_blocks", "das3r_depth_l1")
+           "das3r_split_colour_rule", "das3r_split_colour_switch", "das3r_depth_l1_blocks", "das3r_depth_l1", "das3r_prune_select", "das3r_prune_compact")
 
 _lib = None
 
@@ -155,6 +168,11 @@ def load():
     L.das3r_depth_l1.restype = C.c_int
     L.das3r_depth_l1.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p]
+    L.das3r_prune_select.restype = C.c_int
+    L.das3r_prune_select.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]
+    L.das3r_prune_compact.restype = C.c_int
+    L.das3r_prune_compact.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(PruneTensor), C.c_void_p]
     L.das3r_photometric_finish.restype = C.c_int
     L.das3r_photometric_finish.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
     L.das3r_adam_step_gated.restype = C.c_int

@@ -244,7 +244,8 @@ def sequence_cost(seq_dir):
 
 
 def run_sequence_job(scene_id, iterations, device, frames=6, seq_dir=None, out_dir=None, fused=False, gt_mask_dir=None, dataset="sintel",
-                     progress=None, seq=None, keep=None, checkpoint_every=0, resume=False, pipe=None, depth_l1_init=0.0, depth_l1_final=0.0):
+                     progress=None, seq=None, keep=None, checkpoint_every=0, resume=False, pipe=None, depth_l1_init=0.0, depth_l1_final=0.0,
+                     prune_from=0, prune_interval=0, prune_until=0, prune_min_opacity=0.005, prune_max_world_scale=0.0):
     """One independent 'sequence': load a preprocessed DAS3R sequence directory (das3r_amd.io_formats.load_sequence) — or,
     without one, build a synthetic multi-frame scene —, optimise it with the train-step harness, report the held-out PSNR and,
     with out_dir, write what the reference writes (point_cloud/iteration_N/point_cloud.ply, pose/pose_N.npy:
@@ -257,6 +258,8 @@ def run_sequence_job(scene_id, iterations, device, frames=6, seq_dir=None, out_d
     depth_l1_init / depth_l1_final (default 0: off): train with the sequence's depth maps as supervision — OptimParams.depth_l1_weight_init /
     _final, and the training cameras then carry their frame's depth map (train.make_camera(depth=...)).  Both are kept in the checkpoints;
     resuming with other values raises train.ResumeMismatch (the one failure that is NOT turned into a failed record: it is a wrong command).
+    prune_* (default: off): the pruning schedule — OptimParams.prune_from_iter / prune_interval / prune_until_iter / prune_min_opacity /
+    prune_max_world_scale (das3r_amd.prune); kept in the checkpoints like the depth weights.  The record's n_splats is the final count.
     progress: called at the job's stages and every few hundred iterations (Rendezvous.tick).  pipe: the `pipe` of training and of the held-out
     report (job_pipe; None: the default one)."""
     progress = progress or (lambda: None)
@@ -279,7 +282,9 @@ def run_sequence_job(scene_id, iterations, device, frames=6, seq_dir=None, out_d
         # Gaussians, training poses and conf_static from the TRAINING frames only; the held-out frames ((idx + 5) % 10 == 0) give
         # their poses and their images as ground truth (scene/__init__.py:88-93, dataset_readers.py:342-347)
         model, train_cams, test = build_from_sequence(seq, heldout=True, depth_targets=depth_l1_init > 0 or depth_l1_final > 0)
-        opt = OptimParams(iterations=iterations, depth_l1_weight_init=float(depth_l1_init), depth_l1_weight_final=float(depth_l1_final))
+        opt = OptimParams(iterations=iterations, depth_l1_weight_init=float(depth_l1_init), depth_l1_weight_final=float(depth_l1_final),
+                          prune_from_iter=int(prune_from), prune_interval=int(prune_interval), prune_until_iter=int(prune_until),
+                          prune_min_opacity=float(prune_min_opacity), prune_max_world_scale=float(prune_max_world_scale))
         start, loop_state = 1, None
         if resume and out_dir is not None:
             from .train import latest_checkpoint, load_checkpoint
@@ -404,6 +409,12 @@ def job_pipe(args):
     return SimpleNamespace(debug=False, compute_cov3D_python=False, convert_SHs_python=False, antialiasing=bool(getattr(args, "antialiasing", False)))
 
 
+def prune_kwargs(args):
+    """run_sequence_job's pruning keywords from a parsed command line."""
+    return dict(prune_from=args.prune_from, prune_interval=args.prune_interval, prune_until=args.prune_until,
+                prune_min_opacity=args.prune_min_opacity, prune_max_world_scale=args.prune_max_world_scale)
+
+
 def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sequences", type=int, default=8)
@@ -429,6 +440,13 @@ def parser():
     ap.add_argument("--depth-l1-init", type=float, default=0.0, help="depth supervision: weight of the inverse-depth L1 term mean |(D - D*) m s| against "
                     "the sequence's depth maps at iteration 1 (0 with --depth-l1-final 0, the default: off; upstream 3DGS uses 1.0)")
     ap.add_argument("--depth-l1-final", type=float, default=0.0, help="its weight at the last iteration, log-linear in between (upstream 3DGS uses 0.01)")
+    ap.add_argument("--prune-from", type=int, default=0, help="pruning (off by default): first iteration whose optimizer steps may be followed by a prune event")
+    ap.add_argument("--prune-interval", type=int, default=0, help="an event after every iteration that is a multiple of this, between --prune-from and "
+                    "--prune-until (0, the default: never)")
+    ap.add_argument("--prune-until", type=int, default=0, help="last iteration that may be followed by a prune event")
+    ap.add_argument("--prune-min-opacity", type=float, default=0.005, help="an event drops the Gaussians rendered with sigmoid(opacity) * conf_static below "
+                    "this (0.005: the reference's commented-out call; at or below 1/255 nothing that is left changes)")
+    ap.add_argument("--prune-max-world-scale", type=float, default=0.0, help="and, when positive, those whose largest scale exceeds this in world units")
     return ap
 
 
@@ -464,12 +482,12 @@ def main(argv=None):
                                          out_dir=os.path.join(args.out, dirs[s]) if args.out else None, fused=args.fused,
                                          gt_mask_dir=os.path.join(args.gt_dynamic_mask, dirs[s]) if args.gt_dynamic_mask else None,
                                          dataset=args.dataset, progress=tick, checkpoint_every=args.checkpoint_every, resume=args.resume, pipe=pipe,
-                                         depth_l1_init=args.depth_l1_init, depth_l1_final=args.depth_l1_final)
+                                         depth_l1_init=args.depth_l1_init, depth_l1_final=args.depth_l1_final, **prune_kwargs(args))
     else:
         mine = assign(args.sequences, rank, world)
         job = lambda s: run_sequence_job(s, args.iterations, device, fused=args.fused, progress=tick, checkpoint_every=args.checkpoint_every,
                                          resume=args.resume, out_dir=os.path.join(args.out, f"seq_{s}") if args.out else None, pipe=pipe,
-                                         depth_l1_init=args.depth_l1_init, depth_l1_final=args.depth_l1_final)
+                                         depth_l1_init=args.depth_l1_init, depth_l1_final=args.depth_l1_final, **prune_kwargs(args))
     # (default: two in flight with the fused kernels — the measured configuration; the reference's PyTorch glue runs its backward passes in
     #  autograd's one device thread, where two jobs would queue behind each other: one at a time unless asked for)
     records = run_jobs(mine, job, args.jobs_per_gpu if args.jobs_per_gpu else (2 if (use_gpu and args.fused) else 1), device)

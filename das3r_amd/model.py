@@ -39,6 +39,15 @@ class OptimParams:   # /root/reference/arguments/__init__.py:73-90 (densificatio
     # carry `invdepthmap`, w log-linear from _init to _final over `iterations` (losses.depth_l1_weight).  Both 0: off.  Upstream: 1.0 -> 0.01.
     depth_l1_weight_init: float = 0.0
     depth_l1_weight_final: float = 0.0
+    # pruning (das3r_amd.prune; the reference carries prune_points and never calls it): after the optimizer steps of iteration `it` when
+    # prune_interval > 0 and prune_from_iter <= it <= prune_until_iter and it % prune_interval == 0, drop the Gaussians rendered with
+    # sigmoid(opacity) * conf_static below prune_min_opacity (0.005: the value in the reference's commented call) or, with
+    # prune_max_world_scale > 0, larger than that in world units.  The three schedule fields at 0: off.
+    prune_from_iter: int = 0
+    prune_interval: int = 0
+    prune_until_iter: int = 0
+    prune_min_opacity: float = 0.005
+    prune_max_world_scale: float = 0.0
 
 
 def depth_to_points(K, cam2world, depth):
@@ -203,6 +212,8 @@ class SplatModel:
         optimizer state is torch.optim.Adam's, which FusedAdam reads).  extras: capture_extras() of the same moment, when there is one."""
         (self.active_sh_degree, xyz, f_dc, f_rest, scaling, rotation, opacity, _mr, _acc, _den, opt_dict, self.spatial_lr_scale, Q, T) = model_args
         dev = torch.device(device) if device is not None else xyz.device
+        for stale in ("_mask_index", "_fast_state", "_das3r_eval"):   # caches of the tensors being replaced (the checkpoint may hold another P: a pruned job)
+            self.__dict__.pop(stale, None)
         par = lambda t: nn.Parameter(t.detach().to(dev, torch.float32).clone().contiguous())
         self._xyz, self._features_dc, self._features_rest = par(xyz), par(f_dc), par(f_rest)
         self._scaling, self._rotation, self._opacity = par(scaling), par(rotation), par(opacity)

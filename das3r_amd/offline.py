@@ -192,12 +192,20 @@ def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=
 
 
 def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=False, optimised_poses=False, device="cuda", write=True, fused=False,
-                depth=False, pipe=PIPE):
+                depth=False, pipe=PIPE, prune_min_opacity=0.0, write_pruned_ply=False):
     """render.py:89-123: load the trained model, write pose_interpolated.npy, render the "interp" set.  seq: the sequence the model was
     trained on (its cameras).  depth: also the inverse-depth images (invdepth/%05d.npy) and, per view, the median relative error of
     1 / invdepth against the sequence's depth map (printed: a diagnostic).  pipe: PIPE, or pipe_from_args' (pipe.antialiasing: a model
-    trained with antialiasing is rendered with it).  -> (iteration, list of rendered images)"""
+    trained with antialiasing is rendered with it).  prune_min_opacity > 0: the loaded model is compacted first (das3r_amd.prune.prune_points:
+    the Gaussians with sigmoid(opacity) * conf_static below it go; at or below 1/255 the renders do not change); write_pruned_ply: the
+    compacted model is saved as point_cloud/iteration_N/point_cloud_pruned.ply.  -> (iteration, list of rendered images)"""
     model, iteration = load_trained_model(model_path, iteration, sh_degree, device)
+    if prune_min_opacity > 0:
+        from .prune import prune_points, write_pruned_ply as save_pruned
+        info = prune_points(model, min_opacity=prune_min_opacity)
+        print(f"pruned {info['dropped']} of {info['before']} Gaussians below opacity {prune_min_opacity:g}")
+        if write_pruned_ply:
+            save_pruned(os.path.join(model_path, "point_cloud", f"iteration_{iteration}", "point_cloud_pruned.ply"), model)
     inter = save_interpolate_pose(model_path, iteration)
     bg = torch.tensor([1.0, 1.0, 1.0] if white_background else [0.0, 0.0, 0.0], dtype=torch.float32, device=device)
     views = sequence_cameras(seq, device)
@@ -260,6 +268,10 @@ def parser():
                                                          "median relative error of 1/invdepth against the sequence's depth_maps")
     ap.add_argument("--antialiasing", action="store_true", help="the rasterizer's antialiasing mode (upstream's 2D mip filter), fused or not: "
                                                                 "render a model trained with it (farm --antialiasing) this way")
+    ap.add_argument("--prune-min-opacity", type=float, default=0.0, help="compact the loaded model before rendering: drop the Gaussians with "
+                    "sigmoid(opacity) * conf_static below this (0: off; at or below 1/255 = 0.0039 the renders do not change)")
+    ap.add_argument("--write-pruned-ply", action="store_true", help="with --prune-min-opacity: save the compacted model as "
+                    "point_cloud/iteration_N/point_cloud_pruned.ply")
     return ap
 
 
@@ -269,7 +281,7 @@ def main(argv=None):
     print("Rendering " + args.model_path)
     seq = load_sequence(args.source_path, device="cuda", dataset=args.dataset)
     it, imgs = render_sets(args.model_path, seq, args.iteration, args.sh_degree, args.white_background, args.optimised_poses, fused=args.fused,
-                           depth=args.depth, pipe=pipe_from_args(args))
+                           depth=args.depth, pipe=pipe_from_args(args), prune_min_opacity=args.prune_min_opacity, write_pruned_ply=args.write_pruned_ply)
     print(f"wrote {len(imgs)} images to {os.path.join(args.model_path, 'interp', f'ours_{it}', 'renders')}")
 
 

@@ -110,6 +110,21 @@ def train_step(model: SplatModel, cam, opt: OptimParams, iteration, pipe, backgr
     return loss.detach(), psnr_frame.detach(), pkg
 
 
+def prune_schedule(opt):
+    """The pruning schedule of `opt` as the tuple the checkpoints keep — (from, interval, until, min_opacity, max_world_scale) — or None
+    when it is off (prune_interval <= 0: OptimParams' default)."""
+    interval = int(getattr(opt, "prune_interval", 0) or 0)
+    if interval <= 0:
+        return None
+    return (int(getattr(opt, "prune_from_iter", 0)), interval, int(getattr(opt, "prune_until_iter", 0)),
+            float(getattr(opt, "prune_min_opacity", 0.005)), float(getattr(opt, "prune_max_world_scale", 0.0)))
+
+
+def prune_due(schedule, iteration):
+    """Does a prune event follow the optimizer steps of `iteration`?"""
+    return schedule is not None and schedule[0] <= iteration <= schedule[2] and iteration % schedule[1] == 0
+
+
 class ResumeMismatch(ValueError):
     """A checkpoint is resumed with settings that would silently change the job's schedule."""
 
@@ -159,7 +174,8 @@ def train(model, cameras, opt: OptimParams, iterations, pipe=None, background=No
     walks the held-out views whenever the training stack has run empty (test_pose_pass).  Returns dict(loss, psnr, iters_per_s).
     checkpoint_every / checkpoint_dir: write chkpnt<iteration>.pth every so many iterations (train_gui.py:626-628 --checkpoint_iterations);
     The weights of the depth term (opt.depth_l1_weight_init / _final) go into the checkpoint's loop state; resuming with other values raises
-    ResumeMismatch.
+    ResumeMismatch.  The same holds for the pruning schedule (opt.prune_*: prune_schedule above) — an event (das3r_amd.prune.prune_points)
+    follows the optimizer steps of every iteration the schedule names, in all three step forms.
     start_iteration / loop_state: continue a job from load_checkpoint's result — the iterations that follow are the ones the
     uninterrupted job would have run (same cameras in the same order, same schedules, same optimizer moments)."""
     pipe = pipe or SimpleNamespace(debug=False, compute_cov3D_python=False, convert_SHs_python=False)
@@ -168,7 +184,14 @@ def train(model, cameras, opt: OptimParams, iterations, pipe=None, background=No
     rng = random.Random(seed)
     stack, ema, last_psnr = [], torch.zeros((), device=dev), torch.zeros((), device=dev)
     depth_l1 = (float(getattr(opt, "depth_l1_weight_init", 0.0)), float(getattr(opt, "depth_l1_weight_final", 0.0)))
+    pruning = prune_schedule(opt)
     if loop_state is not None:
+        was_pruning = loop_state.get("prune")   # (a checkpoint from before pruning: off)
+        was_pruning = None if was_pruning is None else tuple(was_pruning)
+        if was_pruning != pruning:
+            raise ResumeMismatch(f"this checkpoint was written by a job with the pruning schedule {was_pruning} (from, interval, until, min opacity, max "
+                                 f"world scale; None: off); it is being resumed with {pruning}, which would change the model mid-run: resume with "
+                                 "the same --prune-* settings (OptimParams.prune_*)")
         was = tuple(float(v) for v in (loop_state.get("depth_l1") or (0.0, 0.0)))   # (a checkpoint from before the depth term: off)
         if was != depth_l1:
             raise ResumeMismatch(f"this checkpoint was written by a job with depth-L1 weights {was[0]:g} -> {was[1]:g}; it is being resumed with "
@@ -190,6 +213,9 @@ def train(model, cameras, opt: OptimParams, iterations, pipe=None, background=No
             stack = list(cameras)
         cam = stack.pop(rng.randint(0, len(stack) - 1))
         loss, p, _ = train_step(model, cam, opt, it, pipe, background, fused=fused)
+        if prune_due(pruning, it):
+            from .prune import prune_points
+            prune_points(model, min_opacity=pruning[3], max_world_scale=pruning[4])
         if not stack and test_cameras and model.enable_test:
             test_pose_pass(model, test_cameras, gt_dynamic_masks, opt, pipe, background, rng, fused=fused)
         ema = torch.lerp(ema, loss, 0.4)      # 0.4 loss + 0.6 ema, one kernel; stays on the device: a float() here would stall the host every iteration
@@ -207,7 +233,7 @@ def train(model, cameras, opt: OptimParams, iterations, pipe=None, background=No
                     library = _lib.learning()
             save_checkpoint(os.path.join(checkpoint_dir, f"chkpnt{it}.pth"), model, it,
                             dict(rng=rng.getstate(), stack=[c.uid for c in stack], ema=ema.detach().clone(), last_psnr=last_psnr.detach().clone(),
-                                 library=library, depth_l1=depth_l1))
+                                 library=library, depth_l1=depth_l1, prune=pruning))
     if dev.type == "cuda":
         torch.cuda.current_stream(dev).synchronize()
     done = max(iterations - start_iteration + 1, 1)

@@ -368,6 +368,39 @@ int64_t das3r_depth_l1_blocks(int32_t H, int32_t W);
 int das3r_depth_l1(int32_t H, int32_t W, const float *invdepth, const float *target, const float *mask, const float *static_mask, float weight,
                    const float *grad_loss, float *d_invdepth, float *partials, float *out8, das3r_stream_t stream);
 
+/* ---- pruning: selection and stable compaction (opt-in) ---------------------------------------------------------------------
+ * Additive symbols under ABI 16.  The reference carries the operation and never calls it (scene/gaussian_model.py:436-468 prune_points /
+ * _prune_optimizer, 552-566 densify_and_prune; call sites commented out, train_gui.py:612-623).
+ *
+ * das3r_prune_select: one decision per Gaussian.  With eff = sigmoid(opacity_raw[i]) * conf_flat[mask_index[i]] (mask_index NULL =
+ * identity), computed by the helper the pre-transform hands the rasterizer its opacity with (csrc/pretransform_math.h pre_opacity: the
+ * same bits), Gaussian i is DROPPED iff
+ *     eff < min_opacity                                                    (a NaN compares false: kept; a negative conf: dropped)
+ *  or max_world_scale > 0 and max_k exp(scaling[3 i + k]) > max_world_scale    (scaling NULL or max_world_scale <= 0: criterion off)
+ *  or also_drop != NULL and also_drop[i] != 0.
+ * dst_index[i] = the new row of a kept Gaussian — its rank among the kept ones, so order is preserved (depth ties are broken by Gaussian
+ * index) — or -1 for a dropped one.  count: device int32 words, DAS3R_PRUNE_COUNT_WORDS(P) of them; count[0] leaves as the number of kept
+ * rows, the others are scratch (per-workgroup counts; need not be zeroed).  Three launches on `stream` (flags + per-workgroup counts, a
+ * one-workgroup scan of the counts, ranks): nothing is handed from workgroup to workgroup inside a launch.  P == 0: count[0] = 0.
+ *
+ * das3r_prune_compact: dst[dst_index[i]] = src[i] for every row i with 0 <= dst_index[i] < kept, for up to 16 row-major tensors in ONE
+ * launch.  `tensors` is a HOST array.  row_bytes is a multiple of 4 (0: the tensor has no columns, nothing to move); rows are moved in
+ * 16-byte units where row_bytes and both pointers allow it, else 8, else 4.  Out of place: src and dst must not overlap (a later
+ * workgroup's destination could lie on an earlier one's unread source).  P * row_bytes / unit must stay below 2^32.  P == 0 or kept == 0:
+ * nothing is launched. */
+#define DAS3R_PRUNE_GROUP_ROWS 1024
+#define DAS3R_PRUNE_COUNT_WORDS(P) (1 + ((int64_t)(P) + DAS3R_PRUNE_GROUP_ROWS - 1) / DAS3R_PRUNE_GROUP_ROWS)
+typedef struct {
+    const void *src; /* [P] rows */
+    void *dst;       /* [kept] rows */
+    int64_t row_bytes;
+} das3r_prune_tensor;
+int das3r_prune_select(int32_t P, const float *opacity_raw, const float *conf_flat, const int64_t *mask_index, float min_opacity,
+                       const float *scaling, float max_world_scale, const uint8_t *also_drop, int32_t *dst_index, int32_t *count,
+                       das3r_stream_t stream);
+int das3r_prune_compact(int32_t P, int32_t kept, const int32_t *dst_index, int32_t n, const das3r_prune_tensor *tensors,
+                        das3r_stream_t stream);
+
 /* ---- introspection (used by the parity tests and the roofline accounting) ---- */
 
 /* Byte offsets of the saved intermediates inside geom / binning / img for given extents. */

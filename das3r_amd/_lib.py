@@ -88,7 +88,8 @@ EXPORTS = ("das3r_raster_forward", "das3r_raster_backward", "das3r_raster_backwa
            "das3r_has_experiments", "das3r_pair_counters", "das3r_debug_poison_lds", "das3r_debug_inject_fault", "das3r_debug_mutate",
            "das3r_pose_matrices_qt", "das3r_pose_chain_qt", "das3r_photometric_finish", "das3r_pretransform_backward_adam", "das3r_pretransform_pose_sums",
            "das3r_raster_count_live_pairs", "das3r_photometric_backward_finish", "das3r_pose_chain_qt_rearm", "das3r_ssim_map_forward", "das3r_ssim_map_backward",
-           "das3r_split_colour_rule", "das3r_split_colour_switch", "das3r_depth_l1_blocks", "das3r_depth_l1", "das3r_prune_select", "das3r_prune_compact")
+           "das3r_split_colour_rule", "das3r_split_colour_switch", "das3r_depth_l1_blocks", "das3r_depth_l1", "das3r_prune_select", "das3r_prune_compact",
+           "das3r_photometric_forward_exposure", "das3r_photometric_backward_finish_exposure", "das3r_exposure_grad_finish")
 
 _lib = None
 
@@ -163,6 +164,13 @@ def load():
     L.das3r_photometric_backward_finish.restype = C.c_int
     L.das3r_photometric_backward_finish.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.das3r_photometric_forward_exposure.restype = C.c_int   # per-frame exposure compensation (additive under ABI 16)
+    L.das3r_photometric_forward_exposure.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p]
+    L.das3r_photometric_backward_finish_exposure.restype = C.c_int
+    L.das3r_photometric_backward_finish_exposure.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 9
+    L.das3r_exposure_grad_finish.restype = C.c_int
+    L.das3r_exposure_grad_finish.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.das3r_depth_l1_blocks.restype = C.c_int64
     L.das3r_depth_l1_blocks.argtypes = [C.c_int32, C.c_int32]
     L.das3r_depth_l1.restype = C.c_int

@@ -10,6 +10,8 @@
 // pixel and channel, the four derivative maps the backward needs (dm/dmu1, dm/dmu2, dm/dE[a^2] = dm/dE[b^2], dm/dE[ab]); since
 // dL/dSSIM_map is the same constant for every pixel, the backward is the same separable convolution applied to those maps.
 // Reductions are deterministic: every tile writes its partial sums, the host side adds the few hundred rows.
+// Per-frame exposure compensation (opt-in; upstream 3DGS's learned 3 x 4 colour matrix per training image) is the EXPO instantiation of
+// the two kernels: the matrix is applied to the render as the halo tile is staged, and the backward also leaves dL/dE.
 #include "common.h"
 
 namespace das3r {
@@ -46,11 +48,32 @@ __device__ __forceinline__ void separable(const float (*halo)[PH][PH + 1], float
     }
 }
 
-__global__ void __launch_bounds__(256) photometric_forward_kernel(int H, int W, const float *__restrict__ render, const float *__restrict__ gt,
-                                                                  const float *__restrict__ stat, float lambda, GaussWin g,
-                                                                  float *__restrict__ partials /*[blocks][8]*/,
-                                                                  float *__restrict__ dmaps /*[4][3][H][W]*/,
-                                                                  float *__restrict__ ssim_map /*[3][H][W] or null (das3r_ssim_map_forward)*/) {
+// Per-frame exposure compensation (EXPO; das3r_photometric_forward_exposure): E is a 3x4 row-major matrix in device memory, and
+//     comp_c = sum_i r_i E[i][c] + E[c][3]
+// stands wherever the render did.  The chain below is written so that E = [I | 0] returns r_c exactly (every other term is an exact zero).
+struct Expo {
+    float m[12];
+};
+__device__ __forceinline__ Expo load_expo(const float *__restrict__ e) {
+    Expo E;
+#pragma unroll
+    for (int k = 0; k < 12; k++) E.m[k] = e[k];   // (uniform: scalar loads)
+    return E;
+}
+__device__ __forceinline__ float expo_comp(const Expo &E, const int c, const float r0, const float r1, const float r2) {
+    return fmaf(r0, E.m[0 * 4 + c], fmaf(r1, E.m[1 * 4 + c], fmaf(r2, E.m[2 * 4 + c], E.m[c * 4 + 3])));
+}
+
+// EXPO = false is the kernel as it has always been (photometric_forward_kernel below names that instantiation: no branch was added to it)
+template <bool EXPO>
+__global__ void __launch_bounds__(256) photometric_forward_kernel_t(int H, int W, const float *__restrict__ render, const float *__restrict__ gt,
+                                                         const float *__restrict__ stat, float lambda, GaussWin g,
+                                                         float *__restrict__ partials /*[blocks][8]*/,
+                                                         float *__restrict__ dmaps /*[4][3][H][W]*/,
+                                                         float *__restrict__ ssim_map /*[3][H][W] or null (das3r_ssim_map_forward)*/,
+                                                         const float *__restrict__ expo /*[12], EXPO only*/) {
+    Expo E;
+    if constexpr (EXPO) E = load_expo(expo);
     // (round 6) the three channels side by side: fifteen quantities go through ONE separable pass — three barriers per tile instead of nine,
     // and fifteen independent dot products per thread between them instead of five
     __shared__ float halo[15][PH][PH + 1];
@@ -74,11 +97,22 @@ __global__ void __launch_bounds__(256) photometric_forward_kernel(int H, int W, 
         const size_t p = (size_t)min(max(yy, 0), H - 1) * W + (size_t)min(max(xx, 0), W - 1);
         const float sm = in ? (stat != nullptr ? stat[p] : 1.f) : 0.f;
         float va[3], vb[3];
+        if constexpr (EXPO) {
+            float rv[3], gv[3];
 #pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const float rv = render[c * plane + p], gv = gt[c * plane + p];
-            va[c] = in ? rv * sm : 0.f;   // (outside the image: the zero padding of the reference's convolution)
-            vb[c] = in ? gv * sm : 0.f;
+            for (int c = 0; c < 3; c++) rv[c] = render[c * plane + p], gv[c] = gt[c * plane + p];
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                va[c] = in ? expo_comp(E, c, rv[0], rv[1], rv[2]) * sm : 0.f;
+                vb[c] = in ? gv[c] * sm : 0.f;
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const float rv = render[c * plane + p], gv = gt[c * plane + p];
+                va[c] = in ? rv * sm : 0.f;   // (outside the image: the zero padding of the reference's convolution)
+                vb[c] = in ? gv * sm : 0.f;
+            }
         }
         if (e < PH * PH) {
 #pragma unroll
@@ -131,6 +165,10 @@ __global__ void __launch_bounds__(256) photometric_forward_kernel(int H, int W, 
     if (tid < 5) partials[(size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 8 + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
 }
 
+// (the launch sites' names, which the library's profiler reports: the form without exposure keeps the name it has always had)
+constexpr auto photometric_forward_kernel = photometric_forward_kernel_t<false>;
+constexpr auto photometric_forward_exposure_kernel = photometric_forward_kernel_t<true>;
+
 // the few hundred rows of tile sums -> {loss, mse_r, mse_g, mse_b, psnr_frame} (what the host side of round 3 did with ~12 tiny
 // PyTorch kernels per iteration); one workgroup, rows added in a fixed order: deterministic
 __device__ __forceinline__ void finish_sums(const int nblocks, const float *__restrict__ partials, const float npix, const float lambda,
@@ -170,14 +208,20 @@ __global__ void __launch_bounds__(256) photometric_finish_kernel(int nblocks, co
     finish_sums(nblocks, partials, npix, lambda, out, red);
 }
 
-__global__ void __launch_bounds__(256) photometric_backward_kernel(int H, int W, const float *__restrict__ render, const float *__restrict__ gt,
-                                                                   const float *__restrict__ stat, float lambda, GaussWin g,
-                                                                   const float *__restrict__ dmaps, const float *__restrict__ grad_loss,
-                                                                   float *__restrict__ d_render, float *__restrict__ d_static,
-                                                                   const float *__restrict__ partials, int nblocks, float *__restrict__ out8,
-                                                                   // das3r_ssim_map_backward: gmap = dL/d(SSIM map) [3][H][W] (then stat may be null, lambda and
-                                                                   // grad_loss are not read, and d_b [3][H][W] receives dL/d(second image)); else both null
-                                                                   const float *__restrict__ gmap, float *__restrict__ d_b) {
+// EXPO = false is the kernel as it has always been (photometric_backward_kernel below).  EXPO (das3r_photometric_backward_finish_exposure; gmap and
+// d_b are null): comp is recomputed for the thread's pixel, the three g_c = dL/d image_c are formed first and then mixed into d_render and
+// d_static; the twelve terms of dL/dE are summed per tile — the forward's shuffle tree and LDS row — into epartials[tile][16] (null: skipped,
+// the held-out pose pass takes no exposure gradient).  No floating-point atomics.
+template <bool EXPO>
+__global__ void __launch_bounds__(256) photometric_backward_kernel_t(int H, int W, const float *__restrict__ render, const float *__restrict__ gt,
+                                                          const float *__restrict__ stat, float lambda, GaussWin g,
+                                                          const float *__restrict__ dmaps, const float *__restrict__ grad_loss,
+                                                          float *__restrict__ d_render, float *__restrict__ d_static,
+                                                          const float *__restrict__ partials, int nblocks, float *__restrict__ out8,
+                                                          // das3r_ssim_map_backward: gmap = dL/d(SSIM map) [3][H][W] (then stat may be null, lambda and
+                                                          // grad_loss are not read, and d_b [3][H][W] receives dL/d(second image)); else both null
+                                                          const float *__restrict__ gmap, float *__restrict__ d_b,
+                                                          const float *__restrict__ expo /*[12]*/, float *__restrict__ epartials /*[blocks][16] or null*/) {
     __shared__ float halo[12][PH][PH + 1];   // (round 6: the four derivative maps of the three channels through one separable pass)
     __shared__ float tmp[12][PH][PT + 1];
     const int tid = threadIdx.x, ty = tid / PT, tx = tid % PT;
@@ -224,6 +268,50 @@ __global__ void __launch_bounds__(256) photometric_backward_kernel(int H, int W,
     __syncthreads();
     float o[12];
     separable<12>(halo, tmp, g, tid, o);
+    if constexpr (EXPO) {
+        // The arithmetic below is the plain form's, operation for operation as the compiler contracts that form (explicit fmaf, contraction
+        // off), so that E = [I | 0] gives its d_render and d_static bit for bit whatever the optimizer makes of this instantiation.
+#pragma clang fp contract(off)
+        const Expo E = load_expo(expo);
+        float gc[3] = {0.f, 0.f, 0.f};
+        if (inside) {
+            const float one_minus_lambda = 1.f - lambda;
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const float R = expo_comp(E, c, Rv[0], Rv[1], Rv[2]), G = Gv[c];
+                const float a = R * s, b = G * s;
+                const float sgn = a > b ? 1.f : (a < b ? -1.f : 0.f);
+                const float l1 = one_minus_lambda * sgn;
+                const float ia = fmaf(b, o[4 * c + 3], fmaf(a + a, o[4 * c + 2], o[4 * c + 0]));
+                const float ib = fmaf(a, o[4 * c + 3], fmaf(b + b, o[4 * c + 2], o[4 * c + 1]));
+                const float da = scale * fmaf(-lambda, ia, l1);
+                const float db = scale * fmaf(-lambda, ib, -l1);
+                gc[c] = da;
+                ds += fmaf(R, da, G * db);
+            }
+#pragma unroll
+            for (int i = 0; i < 3; i++)   // dL/dr_i = static * sum_c E[i][c] g_c
+                d_render[i * plane + pix] = s * fmaf(E.m[4 * i + 0], gc[0], fmaf(E.m[4 * i + 1], gc[1], E.m[4 * i + 2] * gc[2]));
+            if (d_static != nullptr) d_static[pix] = ds;
+        }
+        if (epartials != nullptr) {   // (uniform)
+            __shared__ float ered[4][12];
+            const int lane = __lane_id(), wave = tid >> 6;
+#pragma unroll
+            for (int k = 0; k < 12; k++) {   // E[i][c] (k = 4 i + c, c < 3): g_c s r_i;  E[c][3] (k = 4 c + 3): g_c s   (outside the image: gc = 0)
+                const int i = k >> 2, c = k & 3;
+                float v = c < 3 ? gc[c] * s * Rv[i] : gc[i] * s;
+#pragma unroll
+                for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+                if (lane == 0) ered[wave][k] = v;
+            }
+            __syncthreads();
+            if (tid < 16)
+                epartials[(size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 16 + tid] =
+                    tid < 12 ? ered[0][tid] + ered[1][tid] + ered[2][tid] + ered[3][tid] : 0.f;
+        }
+        return;
+    }
 #pragma unroll
     for (int c = 0; c < 3; c++) {
         if (inside) {
@@ -243,6 +331,29 @@ __global__ void __launch_bounds__(256) photometric_backward_kernel(int H, int W,
         }
     }
     if (inside && d_static != nullptr) d_static[pix] = ds;
+}
+
+constexpr auto photometric_backward_kernel = photometric_backward_kernel_t<false>;
+constexpr auto photometric_backward_exposure_kernel = photometric_backward_kernel_t<true>;
+
+// dL/dE of one view: the tiles' rows of epartials added in a fixed order by ONE workgroup (sixteen row slots, each adding every sixteenth row in
+// index order, then the slots in index order) into grad_row[12] — row `uid` of the dense [n_train, 3, 4] gradient — after zero_row[12], the row
+// the previous view left there (may be null, may be the same row), has been zeroed: the pattern of das3r_pose_chain_qt_rearm.
+__global__ void __launch_bounds__(256) exposure_grad_finish_kernel(int nblocks, const float *__restrict__ epartials, float *grad_row,
+                                                                   float *zero_row /*(may alias grad_row: neither is __restrict__)*/) {
+    __shared__ float red[16][17];
+    const int tid = threadIdx.x, slot = tid >> 4, q = tid & 15;
+    float acc = 0.f;
+    for (int b = slot; b < nblocks; b += 16) acc += epartials[(size_t)b * 16 + q];
+    red[slot][q] = acc;
+    __syncthreads();
+    if (tid < 12) {
+        float v = 0.f;
+#pragma unroll
+        for (int k = 0; k < 16; k++) v += red[k][tid];
+        if (zero_row != nullptr) zero_row[tid] = 0.f;
+        grad_row[tid] = v;
+    }
 }
 
 static GaussWin make_window() {
@@ -273,7 +384,7 @@ extern "C" int das3r_photometric_forward(int32_t H, int32_t W, const float *rend
     }
     hipStream_t s = (hipStream_t)stream;
     DAS3R_LAUNCH(photometric_forward_kernel, dim3(div_up(W, PT), div_up(H, PT)), dim3(PT * PT), 0, s, H, W, render, gt, static_mask, lambda,
-                 make_window(), partials, dmaps, (float *)nullptr);
+                 make_window(), partials, dmaps, (float *)nullptr, (const float *)nullptr);
     KERNEL_CHECK(s, false, "photometric_forward");
     return DAS3R_OK;
 }
@@ -295,7 +406,8 @@ extern "C" int das3r_photometric_backward(int32_t H, int32_t W, const float *ren
     }
     hipStream_t s = (hipStream_t)stream;
     DAS3R_LAUNCH(photometric_backward_kernel, dim3(div_up(W, PT), div_up(H, PT)), dim3(PT * PT), 0, s, H, W, render, gt, static_mask,
-                 lambda, make_window(), dmaps, grad_loss, d_render, d_static, (const float *)nullptr, 0, (float *)nullptr, (const float *)nullptr, (float *)nullptr);
+                 lambda, make_window(), dmaps, grad_loss, d_render, d_static, (const float *)nullptr, 0, (float *)nullptr, (const float *)nullptr, (float *)nullptr,
+                 (const float *)nullptr, (float *)nullptr);
     KERNEL_CHECK(s, false, "photometric_backward");
     return DAS3R_OK;
 }
@@ -309,7 +421,8 @@ extern "C" int das3r_photometric_backward_finish(int32_t H, int32_t W, const flo
     }
     hipStream_t s = (hipStream_t)stream;
     DAS3R_LAUNCH(photometric_backward_kernel, dim3(div_up(W, PT), div_up(H, PT)), dim3(PT * PT), 0, s, H, W, render, gt, static_mask,
-                 lambda, make_window(), dmaps, grad_loss, d_render, d_static, partials, (int)das3r_photometric_blocks(H, W), out8, (const float *)nullptr, (float *)nullptr);
+                 lambda, make_window(), dmaps, grad_loss, d_render, d_static, partials, (int)das3r_photometric_blocks(H, W), out8, (const float *)nullptr, (float *)nullptr,
+                 (const float *)nullptr, (float *)nullptr);
     KERNEL_CHECK(s, false, "photometric_backward");
     return DAS3R_OK;
 }
@@ -322,7 +435,7 @@ extern "C" int das3r_ssim_map_forward(int32_t H, int32_t W, const float *img1, c
     if (H <= 0 || W <= 0 || !img1 || !img2 || !ssim_map || !dmaps || !partials) { set_error("das3r_ssim_map_forward: invalid argument"); return DAS3R_ERR_INVALID_ARG; }
     hipStream_t s = (hipStream_t)stream;
     DAS3R_LAUNCH(photometric_forward_kernel, dim3(div_up(W, PT), div_up(H, PT)), dim3(PT * PT), 0, s, H, W, img1, img2, (const float *)nullptr, 1.0f,
-                 make_window(), partials, dmaps, ssim_map);
+                 make_window(), partials, dmaps, ssim_map, (const float *)nullptr);
     KERNEL_CHECK(s, false, "ssim_map_forward");
     return DAS3R_OK;
 }
@@ -331,7 +444,61 @@ extern "C" int das3r_ssim_map_backward(int32_t H, int32_t W, const float *img1, 
     if (H <= 0 || W <= 0 || !img1 || !img2 || !dmaps || !grad_map || !d_img1 || !d_img2) { set_error("das3r_ssim_map_backward: invalid argument"); return DAS3R_ERR_INVALID_ARG; }
     hipStream_t s = (hipStream_t)stream;
     DAS3R_LAUNCH(photometric_backward_kernel, dim3(div_up(W, PT), div_up(H, PT)), dim3(PT * PT), 0, s, H, W, img1, img2, (const float *)nullptr, 1.0f,
-                 make_window(), dmaps, (const float *)nullptr, d_img1, (float *)nullptr, (const float *)nullptr, 0, (float *)nullptr, grad_map, d_img2);
+                 make_window(), dmaps, (const float *)nullptr, d_img1, (float *)nullptr, (const float *)nullptr, 0, (float *)nullptr, grad_map, d_img2,
+                 (const float *)nullptr, (float *)nullptr);
     KERNEL_CHECK(s, false, "ssim_map_backward");
+    return DAS3R_OK;
+}
+
+// Additive symbols under ABI 16 — per-frame exposure compensation (include/das3r_raster.h).  The entry points above are the form without.
+extern "C" int das3r_photometric_forward_exposure(int32_t H, int32_t W, const float *render, const float *gt, const float *static_mask, float lambda,
+                                                  const float *exposure, float *partials, float *dmaps, das3r_stream_t stream) {
+    if (H <= 0 || W <= 0 || !render || !gt || !static_mask || !partials || !dmaps) {
+        set_error("das3r_photometric_forward_exposure: invalid argument");
+        return DAS3R_ERR_INVALID_ARG;
+    }
+    if (!exposure) {
+        set_error("das3r_photometric_forward_exposure: exposure is NULL (das3r_photometric_forward is the form without exposure)");
+        return DAS3R_ERR_INVALID_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    DAS3R_LAUNCH(photometric_forward_exposure_kernel, dim3(div_up(W, PT), div_up(H, PT)), dim3(PT * PT), 0, s, H, W, render, gt, static_mask, lambda,
+                 make_window(), partials, dmaps, (float *)nullptr, exposure);
+    KERNEL_CHECK(s, false, "photometric_forward_exposure");
+    return DAS3R_OK;
+}
+
+extern "C" int das3r_photometric_backward_finish_exposure(int32_t H, int32_t W, const float *render, const float *gt, const float *static_mask,
+                                                          float lambda, const float *exposure, const float *dmaps, const float *grad_loss,
+                                                          float *d_render, float *d_static, const float *partials, float *out8, float *epartials,
+                                                          das3r_stream_t stream) {
+    if (H <= 0 || W <= 0 || !render || !gt || !static_mask || !dmaps || !grad_loss || !d_render || !d_static) {
+        set_error("das3r_photometric_backward_finish_exposure: invalid argument");
+        return DAS3R_ERR_INVALID_ARG;
+    }
+    if (!exposure) {
+        set_error("das3r_photometric_backward_finish_exposure: exposure is NULL (das3r_photometric_backward_finish is the form without exposure)");
+        return DAS3R_ERR_INVALID_ARG;
+    }
+    if ((partials == nullptr) != (out8 == nullptr)) {
+        set_error("das3r_photometric_backward_finish_exposure: partials and out8 go together (both NULL: no loss / PSNR reduction)");
+        return DAS3R_ERR_INVALID_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    DAS3R_LAUNCH(photometric_backward_exposure_kernel, dim3(div_up(W, PT), div_up(H, PT)), dim3(PT * PT), 0, s, H, W, render, gt, static_mask,
+                 lambda, make_window(), dmaps, grad_loss, d_render, d_static, partials, (int)das3r_photometric_blocks(H, W), out8, (const float *)nullptr,
+                 (float *)nullptr, exposure, epartials);
+    KERNEL_CHECK(s, false, "photometric_backward_exposure");
+    return DAS3R_OK;
+}
+
+extern "C" int das3r_exposure_grad_finish(int32_t H, int32_t W, const float *epartials, float *grad_row, float *zero_row, das3r_stream_t stream) {
+    if (H <= 0 || W <= 0 || !epartials || !grad_row) {
+        set_error("das3r_exposure_grad_finish: invalid argument");
+        return DAS3R_ERR_INVALID_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    DAS3R_LAUNCH(exposure_grad_finish_kernel, dim3(1), dim3(256), 0, s, (int)das3r_photometric_blocks(H, W), epartials, grad_row, zero_row);
+    KERNEL_CHECK(s, false, "exposure_grad_finish");
     return DAS3R_OK;
 }

@@ -245,7 +245,8 @@ def sequence_cost(seq_dir):
 
 def run_sequence_job(scene_id, iterations, device, frames=6, seq_dir=None, out_dir=None, fused=False, gt_mask_dir=None, dataset="sintel",
                      progress=None, seq=None, keep=None, checkpoint_every=0, resume=False, pipe=None, depth_l1_init=0.0, depth_l1_final=0.0,
-                     prune_from=0, prune_interval=0, prune_until=0, prune_min_opacity=0.005, prune_max_world_scale=0.0):
+                     prune_from=0, prune_interval=0, prune_until=0, prune_min_opacity=0.005, prune_max_world_scale=0.0,
+                     exposure_lr_init=0.0, exposure_lr_final=0.0, exposure_heldout="identity"):
     """One independent 'sequence': load a preprocessed DAS3R sequence directory (das3r_amd.io_formats.load_sequence) — or,
     without one, build a synthetic multi-frame scene —, optimise it with the train-step harness, report the held-out PSNR and,
     with out_dir, write what the reference writes (point_cloud/iteration_N/point_cloud.ply, pose/pose_N.npy:
@@ -260,6 +261,9 @@ def run_sequence_job(scene_id, iterations, device, frames=6, seq_dir=None, out_d
     resuming with other values raises train.ResumeMismatch (the one failure that is NOT turned into a failed record: it is a wrong command).
     prune_* (default: off): the pruning schedule — OptimParams.prune_from_iter / prune_interval / prune_until_iter / prune_min_opacity /
     prune_max_world_scale (das3r_amd.prune); kept in the checkpoints like the depth weights.  The record's n_splats is the final count.
+    exposure_lr_init / exposure_lr_final (default 0: off): per-frame exposure compensation — OptimParams.exposure_lr_init / _final; kept in the
+    checkpoints like the depth weights, and with out_dir the job writes exposure.json (frame name -> 3 x 4 matrix: io_formats.write_exposure_json).
+    exposure_heldout: "identity" (today's numbers) or "nearest" — which matrix the held-out pose pass and the held-out report use (train.heldout_exposure).
     progress: called at the job's stages and every few hundred iterations (Rendezvous.tick).  pipe: the `pipe` of training and of the held-out
     report (job_pipe; None: the default one)."""
     progress = progress or (lambda: None)
@@ -284,7 +288,8 @@ def run_sequence_job(scene_id, iterations, device, frames=6, seq_dir=None, out_d
         model, train_cams, test = build_from_sequence(seq, heldout=True, depth_targets=depth_l1_init > 0 or depth_l1_final > 0)
         opt = OptimParams(iterations=iterations, depth_l1_weight_init=float(depth_l1_init), depth_l1_weight_final=float(depth_l1_final),
                           prune_from_iter=int(prune_from), prune_interval=int(prune_interval), prune_until_iter=int(prune_until),
-                          prune_min_opacity=float(prune_min_opacity), prune_max_world_scale=float(prune_max_world_scale))
+                          prune_min_opacity=float(prune_min_opacity), prune_max_world_scale=float(prune_max_world_scale),
+                          exposure_lr_init=float(exposure_lr_init), exposure_lr_final=float(exposure_lr_final))
         start, loop_state = 1, None
         if resume and out_dir is not None:
             from .train import latest_checkpoint, load_checkpoint
@@ -300,9 +305,11 @@ def run_sequence_job(scene_id, iterations, device, frames=6, seq_dir=None, out_d
             dyn = {c.uid: (torch.from_numpy(masks[c.frame_index]).to(device) if masks[c.frame_index] is not None else None) for c in test}
         progress()
         stats = train(model, train_cams, opt, iterations, pipe=pipe, seed=scene_id, fused=fused, test_cameras=test, gt_dynamic_masks=dyn, on_progress=progress,
-                      start_iteration=start, loop_state=loop_state, checkpoint_every=checkpoint_every if out_dir is not None else 0, checkpoint_dir=out_dir)
+                      start_iteration=start, loop_state=loop_state, checkpoint_every=checkpoint_every if out_dir is not None else 0, checkpoint_dir=out_dir,
+                      **({"exposure_heldout": exposure_heldout} if exposure_heldout != "identity" else {}))
         progress()
-        rep = psnr_report(model, test, dynamic_masks=dyn, pipe=pipe, test_poses=True, iteration=iterations, log_dir=out_dir)
+        rep = psnr_report(model, test, dynamic_masks=dyn, pipe=pipe, test_poses=True, iteration=iterations, log_dir=out_dir,
+                          **({"exposure": exposure_heldout} if exposure_heldout != "identity" else {}))
         cams = train_cams
         if keep is not None:
             keep[scene_id] = (model, train_cams, test)
@@ -310,6 +317,10 @@ def run_sequence_job(scene_id, iterations, device, frames=6, seq_dir=None, out_d
             from .io_formats import save_model_ply, save_poses_npy
             save_model_ply(os.path.join(out_dir, "point_cloud", f"iteration_{iterations}", "point_cloud.ply"), model)
             save_poses_npy(os.path.join(out_dir, "pose", f"pose_{iterations}.npy"), [model.get_RT(i) for i in range(len(cams))])
+            if getattr(model, "_exposure", None) is not None:
+                from .io_formats import sequence_frame_names, write_exposure_json
+                names = sequence_frame_names(seq)
+                write_exposure_json(os.path.join(out_dir, "exposure.json"), [names[c.frame_index] for c in cams], model._exposure)
         # a report over zero views (ground-truth masks exist for the sequence but none of the held-out views has one) is no result:
         # ok = 0 keeps its NaN out of the table's mean
         import math
@@ -415,6 +426,11 @@ def prune_kwargs(args):
                 prune_min_opacity=args.prune_min_opacity, prune_max_world_scale=args.prune_max_world_scale)
 
 
+def exposure_kwargs(args):
+    """run_sequence_job's exposure keywords from a parsed command line."""
+    return dict(exposure_lr_init=args.exposure_lr_init, exposure_lr_final=args.exposure_lr_final, exposure_heldout=args.exposure_heldout)
+
+
 def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sequences", type=int, default=8)
@@ -447,6 +463,12 @@ def parser():
     ap.add_argument("--prune-min-opacity", type=float, default=0.005, help="an event drops the Gaussians rendered with sigmoid(opacity) * conf_static below "
                     "this (0.005: the reference's commented-out call; at or below 1/255 nothing that is left changes)")
     ap.add_argument("--prune-max-world-scale", type=float, default=0.0, help="and, when positive, those whose largest scale exceeds this in world units")
+    ap.add_argument("--exposure-lr-init", type=float, default=0.0, help="per-frame exposure compensation (off by default): learning rate of the 3 x 4 colour "
+                    "matrix every training view gets, at iteration 1 (0 with --exposure-lr-final 0: off; upstream 3DGS uses 0.01); with --out the job "
+                    "writes <sequence>/exposure.json")
+    ap.add_argument("--exposure-lr-final", type=float, default=0.0, help="its learning rate at the last iteration, log-linear in between (upstream 3DGS uses 0.001)")
+    ap.add_argument("--exposure-heldout", default="identity", choices=("identity", "nearest"), help="the matrix a held-out view is compared under: none "
+                    "(identity: the raw render) or that of the training frame with the nearest frame index")
     return ap
 
 
@@ -482,12 +504,12 @@ def main(argv=None):
                                          out_dir=os.path.join(args.out, dirs[s]) if args.out else None, fused=args.fused,
                                          gt_mask_dir=os.path.join(args.gt_dynamic_mask, dirs[s]) if args.gt_dynamic_mask else None,
                                          dataset=args.dataset, progress=tick, checkpoint_every=args.checkpoint_every, resume=args.resume, pipe=pipe,
-                                         depth_l1_init=args.depth_l1_init, depth_l1_final=args.depth_l1_final, **prune_kwargs(args))
+                                         depth_l1_init=args.depth_l1_init, depth_l1_final=args.depth_l1_final, **prune_kwargs(args), **exposure_kwargs(args))
     else:
         mine = assign(args.sequences, rank, world)
         job = lambda s: run_sequence_job(s, args.iterations, device, fused=args.fused, progress=tick, checkpoint_every=args.checkpoint_every,
                                          resume=args.resume, out_dir=os.path.join(args.out, f"seq_{s}") if args.out else None, pipe=pipe,
-                                         depth_l1_init=args.depth_l1_init, depth_l1_final=args.depth_l1_final, **prune_kwargs(args))
+                                         depth_l1_init=args.depth_l1_init, depth_l1_final=args.depth_l1_final, **prune_kwargs(args), **exposure_kwargs(args))
     # (default: two in flight with the fused kernels — the measured configuration; the reference's PyTorch glue runs its backward passes in
     #  autograd's one device thread, where two jobs would queue behind each other: one at a time unless asked for)
     records = run_jobs(mine, job, args.jobs_per_gpu if args.jobs_per_gpu else (2 if (use_gpu and args.fused) else 1), device)

@@ -13,6 +13,8 @@ whole conf_static tensor for one frame's mask gradient, a dozen scalar kernels f
         (ABI 11: the chain rule through the pre-transform AND the Adam step of xyz / rotation / scaling / opacity in one pass — those
          four gradients never reach memory; model.fuse_geometry_adam = False keeps das3r_pretransform_backward + gradients)
     FusedAdam.step (one launch: f_dc, f_rest, conf_static), FusedAdam.step(gate = psnr_frame) for the poses
+    (with per-frame exposure compensation on: the two loss calls are their _exposure forms, das3r_exposure_grad_finish follows them — the
+     one launch more — and the exposure group is an eighth tensor of the same FusedAdam launch)
 
 Gradients land where FusedAdam expects them (`p.grad`, or the compact SH gradient of fused._ShPrefix's contract); the pose gradient
 is written into row `uid` of two dense, otherwise zero buffers (torch's index backward produces exactly that dense gradient, and
@@ -53,7 +55,8 @@ def available(model, pipe):
             # the C-ABI takes plain pointers: every parameter must be a dense fp32 tensor (anything else keeps the autograd form, which
             # goes through .contiguous())
             and all(t.is_contiguous() and t.dtype == torch.float32 for t in (model._xyz, model._rotation, model._scaling, model._opacity,
-                                                                            model._features_dc, model._features_rest, model._conf_static, model.Q, model.T)))
+                                                                            model._features_dc, model._features_rest, model._conf_static, model.Q, model.T)
+                                                                           + ((model._exposure,) if getattr(model, "_exposure", None) is not None else ())))
 
 
 class _State:
@@ -68,6 +71,7 @@ class _State:
         self.one = torch.ones(1, device=dev)
         self.Qg, self.Tg = torch.zeros_like(model.Q), torch.zeros_like(model.T)
         self.tQg, self.tTg = (torch.zeros_like(model.test_Q), torch.zeros_like(model.test_T)) if model.test_Q is not None else (None, None)
+        self.Eg = None   # dense [n_train, 3, 4] exposure gradient, zero outside the row of the view that stepped last (train_step; exposure on only)
         self.means2D = torch.zeros(P, 3, device=dev, requires_grad=True)   # the reference's dummy leaf: only its .grad is ever used
         self.e = torch.empty(0, device=dev)
         idx = getattr(model, "_mask_index", None)
@@ -161,7 +165,7 @@ def _settings(st, cam, model, bg):
 
 
 def forward_backward(model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda_dssim, bg, geometry="grads", rearm_rows=None, antialiasing=False,
-                     depth_weight=0.0):
+                     depth_weight=0.0, exposure=None, exposure_grad=None):
     """Render `cam` with the pose (q_row, t_row: views of one row of Q / T), masked photometric loss against cam.original_image
     under `static_hw` [H, W], and the complete backward.  Gradients: model parameters' .grad (f_rest: compact or none, as in
     das3r_amd.render), the pose gradient into gq_row / gt_row, d loss / d static_hw returned.
@@ -174,15 +178,20 @@ def forward_backward(model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda
     with s = static_hw as a constant — the forward also renders the inverse-depth image, das3r_depth_l1 adds the term to out8 behind the
     photometric loss (out8[0] the total, out8[5] the pure term, out8[6] the weighted one), and the rasterizer's backward is
     das3r_raster_backward_depth.  0.0: none of that — the calls of a photometric step, one for one.
+    exposure (one view's [3, 4] matrix as a dense fp32 device tensor or view; None: none of this — the calls of today's step): the loss, the
+    MSEs, psnr_frame and d_static are those of losses.apply_exposure(render, E), evaluated inside the two loss kernels
+    (das3r_photometric_forward_exposure / _backward_finish_exposure); the package's "render" stays the raw render.  exposure_grad =
+    (grad_row, zero_row or None), views of rows of a dense [n_train, 3, 4] buffer: dL/dE is written to grad_row after zero_row has been
+    zeroed, by the one launch an exposure step adds (das3r_exposure_grad_finish); None: no exposure gradient is taken (the held-out pass).
     -> (out8 = {loss, mse x 3, psnr_frame, ...} device tensor, d_static [H, W], package)"""
     st = _state(model)
     with _on_device(st.dev):   # (the library's per-device state and the raw stream belong to the model's GPU, current or not)
         return _forward_backward(st, model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda_dssim, bg, geometry, rearm_rows, antialiasing,
-                                 float(depth_weight))
+                                 float(depth_weight), exposure, exposure_grad)
 
 
 def _forward_backward(st, model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda_dssim, bg, geometry, rearm_rows=None, antialiasing=False,
-                      depth_weight=0.0):
+                      depth_weight=0.0, exposure=None, exposure_grad=None):
     lib = _lib.load()
     dev, P = st.dev, st.P
     H, W = int(cam.image_height), int(cam.image_width)
@@ -234,11 +243,26 @@ def _forward_backward(st, model, cam, q_row, t_row, gq_row, gt_row, static_hw, l
     dmaps = torch.empty(4, 3, H, W, device=dev)
     out8 = torch.empty(8, device=dev)
     lam = float(lambda_dssim)
-    _lib.check(lib.das3r_photometric_forward(H, W, _p(image), _p(gt), _p(static_hw), C.c_float(lam), _p(partials), _p(dmaps), s), "das3r_photometric_forward")
     d_render, d_static = torch.empty_like(image), torch.empty(H, W, device=dev)
-    # (ABI 15: the loss / PSNR reduction of das3r_photometric_finish is the backward kernel's first workgroup's side duty — one launch less)
-    _lib.check(lib.das3r_photometric_backward_finish(H, W, _p(image), _p(gt), _p(static_hw), C.c_float(lam), _p(dmaps), _p(st.one), _p(d_render),
-                                                     _p(d_static), _p(partials), _p(out8), s), "das3r_photometric_backward_finish")
+    if exposure is None:
+        _lib.check(lib.das3r_photometric_forward(H, W, _p(image), _p(gt), _p(static_hw), C.c_float(lam), _p(partials), _p(dmaps), s), "das3r_photometric_forward")
+        # (ABI 15: the loss / PSNR reduction of das3r_photometric_finish is the backward kernel's first workgroup's side duty — one launch less)
+        _lib.check(lib.das3r_photometric_backward_finish(H, W, _p(image), _p(gt), _p(static_hw), C.c_float(lam), _p(dmaps), _p(st.one), _p(d_render),
+                                                         _p(d_static), _p(partials), _p(out8), s), "das3r_photometric_backward_finish")
+    else:   # ---- per-frame exposure compensation: the same two kernels with E applied inside, and one launch for the twelve sums of dL/dE
+        if tuple(exposure.shape) != (3, 4) or not exposure.is_contiguous() or exposure.dtype != torch.float32 or exposure.device != dev:
+            raise ValueError("fast_step.forward_backward: exposure must be a dense fp32 [3, 4] tensor on the model's device")
+        _lib.check(lib.das3r_photometric_forward_exposure(H, W, _p(image), _p(gt), _p(static_hw), C.c_float(lam), _p(exposure), _p(partials), _p(dmaps), s),
+                   "das3r_photometric_forward_exposure")
+        epartials = torch.empty(nb, 16, device=dev) if exposure_grad is not None else None
+        _lib.check(lib.das3r_photometric_backward_finish_exposure(H, W, _p(image), _p(gt), _p(static_hw), C.c_float(lam), _p(exposure), _p(dmaps),
+                                                                  _p(st.one), _p(d_render), _p(d_static), _p(partials), _p(out8),
+                                                                  _p(epartials) if epartials is not None else None, s),
+                   "das3r_photometric_backward_finish_exposure")
+        if exposure_grad is not None:
+            g_row, z_row = exposure_grad
+            _lib.check(lib.das3r_exposure_grad_finish(H, W, _p(epartials), _p(g_row), _p(z_row) if z_row is not None else None, s),
+                       "das3r_exposure_grad_finish")
     d_invdepth = None
     if depth:   # ---- the inverse-depth L1 term: value into out8 (behind the kernel above, which wrote it), gradient for the rasterizer's backward
         target, dmask = _dense_hw(cam, "invdepthmap", H, W), _dense_hw(cam, "depth_mask", H, W)
@@ -325,12 +349,20 @@ def train_step(model, cam, opt, iteration, pipe, background):
     with torch.no_grad(), _on_device(st.dev):   # (FusedAdam's launches too)
         # the dense pose gradients are zero outside the row of the view that stepped last; that row is zeroed by this step's pose chain launch
         prev = getattr(st, "dirty_uid", None)
+        expo = {}
+        E = getattr(model, "_exposure", None)
+        if E is not None:   # (None: the calls below are today's, one for one)
+            if st.Eg is None or st.Eg.shape != E.shape:
+                st.Eg = torch.zeros_like(E)
+            expo = dict(exposure=E.detach()[uid], exposure_grad=(st.Eg[uid], None if prev is None else st.Eg[prev]))
         out8, d_static, pkg = forward_backward(model, cam, model.Q[uid], model.T[uid], st.Qg[uid], st.Tg[uid], model._conf_static[uid],
                                                opt.lambda_dssim, background, geometry="adam" if getattr(model, "fuse_geometry_adam", True) else "grads",
                                                rearm_rows=None if prev is None else (st.Qg[prev], st.Tg[prev]),
-                                               antialiasing=bool(getattr(pipe, "antialiasing", False)), depth_weight=w_depth)
+                                               antialiasing=bool(getattr(pipe, "antialiasing", False)), depth_weight=w_depth, **expo)
         st.dirty_uid = uid
         model._conf_static.grad[uid] += d_static             # the loss sees conf_static twice: as opacity factor and as the frame's mask
+        if E is not None:
+            E.grad = st.Eg   # dense, zero outside row uid: the group steps inside the optimizer's one launch (rows of other views move by momentum)
         model.optimizer.step()
         model.optimizer.zero_grad(set_to_none=True)
         model.Q.grad, model.T.grad = st.Qg, st.Tg
@@ -339,10 +371,12 @@ def train_step(model, cam, opt, iteration, pipe, background):
     return out8[0], out8[4], pkg
 
 
-def test_pose_step(model, cam, static_hw, opt, background, pipe=None):
+def test_pose_step(model, cam, static_hw, opt, background, pipe=None, exposure=None):
     """One view of train_test_psnr.py's pass over the held-out views (das3r_amd.train.test_pose_pass): render with the test pose,
     loss, backward — and every gradient dropped: the Gaussian optimizer is zeroed without a step and optimizer_cam owns no
-    gradient here.  Reproduced for its cost; nothing changes."""
+    gradient here.  Reproduced for its cost; nothing changes.
+    exposure: the [3, 4] matrix the held-out policy gives this view (train.heldout_exposure), or None (identity: today's calls); its
+    gradient is never taken and the exposure group never steps here."""
     st = _state(model)
     uid = cam.uid
     if st.tQg is None:   # (the held-out poses were set after the first training step)
@@ -350,7 +384,8 @@ def test_pose_step(model, cam, static_hw, opt, background, pipe=None):
     with torch.no_grad(), _on_device(st.dev):
         out8, _d_static, _pkg = forward_backward(model, cam, model.test_Q[uid], model.test_T[uid], st.tQg[uid], st.tTg[uid], static_hw,
                                                  opt.lambda_dssim, background, geometry="pose",
-                                                 antialiasing=bool(getattr(pipe, "antialiasing", False)))
+                                                 antialiasing=bool(getattr(pipe, "antialiasing", False)),
+                                                 **({"exposure": exposure.detach().contiguous()} if exposure is not None else {}))
         model.optimizer.zero_grad(set_to_none=True)
         model.optimizer_cam.zero_grad(set_to_none=True)
     return out8

@@ -517,8 +517,64 @@ def ssim_map(img1, img2):
     return _SsimMap.apply(img1, img2)
 
 
-def masked_photometric_loss(render, gt, static, lambda_dssim):
+class _PhotometricExposure(torch.autograd.Function):
+    """_Photometric with the per-frame exposure matrix applied inside the two kernels (das3r_photometric_*_exposure); also returns dL/dE."""
+
+    @staticmethod
+    def forward(ctx, render, gt, static, lam, exposure):
+        lib = _lib.load()
+        dev = render.device
+        if dev.type != "cuda":
+            raise RuntimeError("das3r_amd.fused.masked_photometric_loss: tensors must live on a HIP device; there is no CPU path")
+        if render.dim() != 3 or render.shape[0] != 3 or gt.shape != render.shape or static.shape != render.shape[1:]:
+            raise ValueError("render / gt must be [3, H, W] and static [H, W]")
+        if tuple(exposure.shape) != (3, 4):
+            raise ValueError(f"exposure must be one view's [3, 4] matrix, got {tuple(exposure.shape)}")
+        render, gt, static = render.contiguous().float(), gt.contiguous().float(), static.contiguous().float()
+        E = exposure.detach().to(dev).contiguous().float()
+        H, W = int(render.shape[1]), int(render.shape[2])
+        nb = int(lib.das3r_photometric_blocks(H, W))
+        partials = torch.empty(nb, 8, device=dev)
+        dmaps = torch.empty(4, 3, H, W, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.das3r_photometric_forward_exposure(H, W, _p(render), _p(gt), _p(static), C.c_float(lam), _p(E), _p(partials), _p(dmaps), _stream(dev))
+        _lib.check(rc, "das3r_photometric_forward_exposure")
+        sums = partials[:, :5].sum(0)
+        n = float(H * W)
+        loss = ((1.0 - lam) * sums[0] + lam * sums[1]) / (3.0 * n)
+        mse = sums[2:5] / n
+        ctx.save_for_backward(render, gt, static, dmaps, E)
+        ctx.lam = float(lam)
+        ctx.mark_non_differentiable(mse)
+        return loss, mse
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_mse):
+        lib = _lib.load()
+        render, gt, static, dmaps, E = ctx.saved_tensors
+        dev = render.device
+        H, W = int(render.shape[1]), int(render.shape[2])
+        g = g_loss.reshape(1).contiguous().float()
+        d_render, d_static = torch.empty_like(render), torch.empty_like(static)
+        want_E = ctx.needs_input_grad[4]
+        epartials = torch.empty(int(lib.das3r_photometric_blocks(H, W)), 16, device=dev) if want_E else None
+        d_E = torch.empty(3, 4, device=dev) if want_E else None
+        with torch.cuda.device(dev):
+            rc = lib.das3r_photometric_backward_finish_exposure(H, W, _p(render), _p(gt), _p(static), C.c_float(ctx.lam), _p(E), _p(dmaps), _p(g),
+                                                                _p(d_render), _p(d_static), None, None, _p(epartials) if want_E else None, _stream(dev))
+            _lib.check(rc, "das3r_photometric_backward_finish_exposure")
+            if want_E:
+                _lib.check(lib.das3r_exposure_grad_finish(H, W, _p(epartials), _p(d_E), None, _stream(dev)), "das3r_exposure_grad_finish")
+        return d_render, None, d_static, None, d_E
+
+
+def masked_photometric_loss(render, gt, static, lambda_dssim, exposure=None):
     """-> (loss, mse[3]): DAS3R's iteration loss mean[(1 - lambda) |image - gt'| + lambda (1 - SSIM_map(image, gt'))] with
     image = render * static, gt' = gt * static, and the per-channel mean squared error of the same pair (for psnr_frame).
-    Differentiable in `render` and `static`; two HIP kernels instead of PyTorch's convolution / elementwise chains."""
-    return _Photometric.apply(render, gt, static, float(lambda_dssim))
+    Differentiable in `render` and `static`; two HIP kernels instead of PyTorch's convolution / elementwise chains.
+    exposure (one view's [3, 4] matrix E, a device tensor; None: the form above, call for call): image = comp * static with
+    comp = das3r_amd.losses.apply_exposure(render, E), evaluated inside the same two kernels; then also differentiable in `exposure`
+    (its twelve sums come out of the backward kernel per tile and are added in a fixed order by one more launch: bit-reproducible)."""
+    if exposure is None:
+        return _Photometric.apply(render, gt, static, float(lambda_dssim))
+    return _PhotometricExposure.apply(render, gt, static, float(lambda_dssim), exposure)

@@ -356,3 +356,41 @@ def save_poses_npy(path, pose7_by_colmap_id):
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     np.save(path, mats)
     return mats
+
+
+def sequence_frame_names(seq):
+    """The image name of every frame of a sequence dict: load_sequence's `names`, or — a synthetic sequence has none — the names
+    write_sequence_dir would give its frames."""
+    names = seq.get("names")
+    return list(names) if names else [f"frame_{i:04d}.png" for i in range(int(seq["images"].shape[0]))]
+
+
+def write_exposure_json(path, names, exposure):
+    """<out>/<sequence>/exposure.json of a job that trained with per-frame exposure compensation — upstream 3DGS's file: a dict from the
+    frame's image name to its 3 x 4 matrix as nested lists.  names: one per row of `exposure` ([n, 3, 4]).  Written under a temporary name
+    first."""
+    import json
+    rows = np.asarray(exposure.detach().cpu().numpy() if hasattr(exposure, "detach") else exposure, dtype=np.float64)
+    if rows.ndim != 3 or rows.shape[1:] != (3, 4) or rows.shape[0] != len(names):
+        raise ValueError(f"write_exposure_json: {len(names)} names for matrices of shape {rows.shape} (need [n, 3, 4])")
+    if len(set(names)) != len(names):
+        raise ValueError("write_exposure_json: frame names must be unique")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path + ".tmp", "w") as f:
+        json.dump({str(n): [[float(v) for v in row] for row in m] for n, m in zip(names, rows)}, f, indent=2)
+    os.replace(path + ".tmp", path)
+
+
+def read_exposure_json(path):
+    """-> {frame name: float32 array [3, 4]} from write_exposure_json's (upstream's) file."""
+    import json
+    with open(path) as f:
+        raw = json.load(f)
+    out = {}
+    for name, m in raw.items():
+        a = np.asarray(m, dtype=np.float32)
+        if a.shape != (3, 4):
+            raise ValueError(f"{path}: the matrix of {name!r} has shape {a.shape}, not (3, 4)")
+        out[name] = a
+    return out
+

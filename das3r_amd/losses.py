@@ -39,6 +39,27 @@ def depth_l1_weight(opt, iteration):
     return float(expon_lr_func(w0, w1, max_steps=opt.iterations)(iteration))
 
 
+def apply_exposure(image, E):
+    """Per-frame exposure compensation (upstream 3DGS's learned affine colour correction): image [3, H, W], E a 3 x 4 matrix ->
+        comp_c = sum_i image_i E[i][c] + E[c][3]
+    i.e. matmul(image.permute(1, 2, 0), E[:3, :3]).permute(2, 0, 1) + E[:3, 3, None, None].  The sum is written out term by term: with the exact ones and
+    zeros of E = [I | 0] it returns the image exactly.  Any dtype; the plain statement of what das3r_amd/csrc/photometric.hip computes."""
+    E = E.to(image.dtype)
+    rows = [image[0] * E[0, c] + image[1] * E[1, c] + image[2] * E[2, c] + E[c, 3] for c in range(3)]
+    return torch.stack(rows, 0)
+
+
+def exposure_enabled(opt):
+    """Does `opt` ask for per-frame exposure compensation?  Both rates positive: on; both 0 (the default): off; anything else is an error
+    (the schedule is log-linear)."""
+    e0, e1 = float(getattr(opt, "exposure_lr_init", 0.0)), float(getattr(opt, "exposure_lr_final", 0.0))
+    if e0 == 0.0 and e1 == 0.0:
+        return False
+    if e0 <= 0.0 or e1 <= 0.0:
+        raise ValueError(f"exposure_lr_init / exposure_lr_final must both be positive (a log-linear schedule) or both 0 (off); got {e0}, {e1}")
+    return True
+
+
 _WINDOWS = {}
 
 

@@ -19,7 +19,7 @@ import torch
 from torch import nn
 
 from .knn import distCUDA2
-from .losses import expon_lr_func, inverse_sigmoid, rgb_to_sh
+from .losses import expon_lr_func, exposure_enabled, inverse_sigmoid, rgb_to_sh
 
 
 @dataclass
@@ -48,6 +48,11 @@ class OptimParams:   # /root/reference/arguments/__init__.py:73-90 (densificatio
     prune_until_iter: int = 0
     prune_min_opacity: float = 0.005
     prune_max_world_scale: float = 0.0
+    # per-frame exposure compensation (upstream 3DGS's learned affine colour correction; not in the reference): a 3 x 4 matrix per training
+    # view, [I | 0] at the start, applied to the render before the loss (losses.apply_exposure); its learning rate runs log-linear from _init
+    # to _final over `iterations`.  Both 0: off — no parameter, no optimizer group.  Upstream: 0.01 -> 0.001.
+    exposure_lr_init: float = 0.0
+    exposure_lr_final: float = 0.0
 
 
 def depth_to_points(K, cam2world, depth):
@@ -71,6 +76,8 @@ class SplatModel:
         self.enable_test = False
         self.test_Q = self.test_T = None
         self.FoVx = self.FoVy = None
+        self._exposure = None          # [n_train, 3, 4] nn.Parameter while exposure compensation is on (training_setup), else None
+        self.exposure_frames = None    # frame index of every training view (train.build_from_sequence): the "nearest" held-out policy
 
     # ---- activations
     @property
@@ -167,6 +174,15 @@ class SplatModel:
             {"params": [self._rotation], "lr": opt.rotation_lr, "name": "rotation"},
             {"params": [self._conf_static], "lr": 3e-3, "name": "conf_static"},
         ]
+        e0, e1 = float(getattr(opt, "exposure_lr_init", 0.0)), float(getattr(opt, "exposure_lr_final", 0.0))
+        if exposure_enabled(opt):   # the eighth group: one 3 x 4 matrix per training view, [I | 0] unless restore() has put a checkpoint's there
+            if self._exposure is None or self._exposure.shape[0] != self.Q.shape[0]:
+                eye = torch.eye(3, 4, device=self._xyz.device)[None].repeat(self.Q.shape[0], 1, 1)
+                self._exposure = nn.Parameter(eye.contiguous())
+            groups.append({"params": [self._exposure], "lr": e0, "name": "exposure"})
+        else:
+            self._exposure = None
+        self._lr_exposure = expon_lr_func(e0, e1, max_steps=opt.iterations)
         cam = [{"params": [self.Q], "lr": 0.00003, "name": "pose_Q"}, {"params": [self.T], "lr": 0.00003, "name": "pose_T"}]
         if self.FoVx is not None:   # gaussian_model.py:253-254 (inert: module docstring)
             cam += [{"params": [self.FoVx], "lr": 0.0001, "name": "fovX"}, {"params": [self.FoVy], "lr": 0.0001, "name": "fovY"}]
@@ -204,8 +220,11 @@ class SplatModel:
     def capture_extras(self):
         """What the reference's capture() leaves out and a resumed job needs to continue EXACTLY (its checkpoints omit
         _conf_static, the camera optimizer and the held-out poses — a resumed reference run restarts those from their initial values)."""
-        return dict(conf_static=self._conf_static, aggregated_mask=self.aggregated_mask, optimizer_cam=self.optimizer_cam.state_dict(),
-                    test_Q=self.test_Q, test_T=self.test_T, FoVx=self.FoVx, FoVy=self.FoVy, max_sh_degree=self.max_sh_degree)
+        extras = dict(conf_static=self._conf_static, aggregated_mask=self.aggregated_mask, optimizer_cam=self.optimizer_cam.state_dict(),
+                      test_Q=self.test_Q, test_T=self.test_T, FoVx=self.FoVx, FoVy=self.FoVy, max_sh_degree=self.max_sh_degree)
+        if self._exposure is not None:   # (its Adam moments travel in the optimizer's state dict: capture())
+            extras["exposure"] = self._exposure
+        return extras
 
     def restore(self, model_args, opt, extras=None, fused=False, device=None):
         """Counterpart of GaussianModel.restore(model_args, training_args).  Also accepts a capture written by the reference (its
@@ -218,6 +237,12 @@ class SplatModel:
         self._xyz, self._features_dc, self._features_rest = par(xyz), par(f_dc), par(f_rest)
         self._scaling, self._rotation, self._opacity = par(scaling), par(rotation), par(opacity)
         self.Q, self.T = par(Q), par(T)
+        self._exposure = None
+        if extras is not None and extras.get("exposure") is not None:
+            if not exposure_enabled(opt):
+                raise ValueError("SplatModel.restore: the checkpoint holds exposure matrices, but exposure compensation is off in these "
+                                 "OptimParams (exposure_lr_init / exposure_lr_final)")
+            self._exposure = par(extras["exposure"])
         if extras is not None:
             self._conf_static = par(extras["conf_static"])
             self.aggregated_mask = extras["aggregated_mask"].to(dev)
@@ -261,3 +286,5 @@ class SplatModel:
                 g["lr"] = self._lr_xyz(iteration)
             elif g["name"] == "conf_static":
                 g["lr"] = self._lr_conf(iteration)
+            elif g["name"] == "exposure":
+                g["lr"] = self._lr_exposure(iteration)

@@ -161,11 +161,13 @@ def invdepth_median_rel_error(invdepth, depth):
 
 
 @torch.no_grad()
-def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=None, poses=None, write=True, fused=False, invdepth=None):
+def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=None, poses=None, write=True, fused=False, invdepth=None,
+               exposures=None):
     """render.py:72-86.  views: cameras carrying .pose7 (qw, qx, qy, qz, tx, ty, tz world-to-camera); poses: optional [N, 4, 4]
     world-to-camera matrices that override them.  fused: render_view_fused instead of the reference's PyTorch glue in front of the
     rasterizer (opt-in, like every fused form).  invdepth: a list that receives every view's inverse-depth image [1, H, W] (written as
-    invdepth/%05d.npy next to renders/ when `write`); None: colour only.  -> list of the rendered [3, H, W] tensors (on the device)."""
+    invdepth/%05d.npy next to renders/ when `write`); None: colour only.  exposures: per view a [3, 4] exposure matrix (applied to the
+    render: das3r_amd.losses.apply_exposure) or None.  -> list of the rendered [3, H, W] tensors (on the device)."""
     dev = model.get_xyz.device
     background = background if background is not None else torch.zeros(3, device=dev)
     render_path = os.path.join(model_path, name, f"ours_{iteration}", "renders")
@@ -180,6 +182,9 @@ def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=
         else:
             pkg = das3r_render(view, model, pipe, background, camera_pose=pose, variant="test", return_invdepth=want)
             img, inv = pkg["render"], pkg.get("invdepth")
+        if exposures is not None and exposures[idx] is not None:
+            from .losses import apply_exposure
+            img = apply_exposure(img, torch.as_tensor(exposures[idx], dtype=img.dtype, device=img.device))
         out.append(img)
         if want:
             invdepth.append(inv)
@@ -192,13 +197,17 @@ def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=
 
 
 def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=False, optimised_poses=False, device="cuda", write=True, fused=False,
-                depth=False, pipe=PIPE, prune_min_opacity=0.0, write_pruned_ply=False):
+                depth=False, pipe=PIPE, prune_min_opacity=0.0, write_pruned_ply=False, exposure="none"):
     """render.py:89-123: load the trained model, write pose_interpolated.npy, render the "interp" set.  seq: the sequence the model was
     trained on (its cameras).  depth: also the inverse-depth images (invdepth/%05d.npy) and, per view, the median relative error of
     1 / invdepth against the sequence's depth map (printed: a diagnostic).  pipe: PIPE, or pipe_from_args' (pipe.antialiasing: a model
     trained with antialiasing is rendered with it).  prune_min_opacity > 0: the loaded model is compacted first (das3r_amd.prune.prune_points:
     the Gaussians with sigmoid(opacity) * conf_static below it go; at or below 1/255 the renders do not change); write_pruned_ply: the
-    compacted model is saved as point_cloud/iteration_N/point_cloud_pruned.ply.  -> (iteration, list of rendered images)"""
+    compacted model is saved as point_cloud/iteration_N/point_cloud_pruned.ply.  exposure: "none" (the default: today's output) or "train" —
+    <model_path>/exposure.json (a job that trained with per-frame exposure compensation writes it) is loaded and every view whose frame
+    name it holds, i.e. every training view, is written compensated; the others stay raw.  -> (iteration, list of rendered images)"""
+    if exposure not in ("none", "train"):
+        raise ValueError(f'render_sets: exposure must be "none" or "train", got {exposure!r}')
     model, iteration = load_trained_model(model_path, iteration, sh_degree, device)
     if prune_min_opacity > 0:
         from .prune import prune_points, write_pruned_ply as save_pruned
@@ -223,7 +232,16 @@ def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=Fal
             frames = list(tr)
         poses = inter
     inv = [] if depth else None
-    imgs = render_set(model_path, "interp", iteration, views, model, pipe, bg, poses=poses, write=write, fused=fused, invdepth=inv)
+    exposures = None
+    if exposure == "train":
+        from .io_formats import read_exposure_json, sequence_frame_names
+        path = os.path.join(model_path, "exposure.json")
+        if not os.path.exists(path):
+            raise FileNotFoundError(f'exposure="train": no exposure.json under {model_path} (the job trained without exposure compensation)')
+        table, names = read_exposure_json(path), sequence_frame_names(seq)
+        exposures = [table.get(names[f]) for f in frames]
+    imgs = render_set(model_path, "interp", iteration, views, model, pipe, bg, poses=poses, write=write, fused=fused, invdepth=inv,
+                      exposures=exposures)
     if depth and seq.get("depths") is not None:
         for idx, (f, d) in enumerate(zip(frames, inv)):
             print(f"view {idx:05d} (frame {f}): median |1/invdepth - depth| / depth = {invdepth_median_rel_error(d, seq['depths'][f]):.4f}")
@@ -272,6 +290,8 @@ def parser():
                     "sigmoid(opacity) * conf_static below this (0: off; at or below 1/255 = 0.0039 the renders do not change)")
     ap.add_argument("--write-pruned-ply", action="store_true", help="with --prune-min-opacity: save the compacted model as "
                     "point_cloud/iteration_N/point_cloud_pruned.ply")
+    ap.add_argument("--exposure", default="none", choices=("none", "train"), help='"train": write the training views compensated with the matrices '
+                    "of <model-path>/exposure.json (a job trained with --exposure-lr-init / --exposure-lr-final); none: the raw renders")
     return ap
 
 
@@ -281,7 +301,8 @@ def main(argv=None):
     print("Rendering " + args.model_path)
     seq = load_sequence(args.source_path, device="cuda", dataset=args.dataset)
     it, imgs = render_sets(args.model_path, seq, args.iteration, args.sh_degree, args.white_background, args.optimised_poses, fused=args.fused,
-                           depth=args.depth, pipe=pipe_from_args(args), prune_min_opacity=args.prune_min_opacity, write_pruned_ply=args.write_pruned_ply)
+                           depth=args.depth, pipe=pipe_from_args(args), prune_min_opacity=args.prune_min_opacity, write_pruned_ply=args.write_pruned_ply,
+                           exposure=args.exposure)
     print(f"wrote {len(imgs)} images to {os.path.join(args.model_path, 'interp', f'ours_{it}', 'renders')}")
 
 

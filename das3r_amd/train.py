@@ -14,7 +14,7 @@ from types import SimpleNamespace
 import torch
 
 from .camera import focal2fov, projection_matrix
-from .losses import depth_l1, depth_l1_weight, l1_loss, psnr, ssim
+from .losses import apply_exposure, depth_l1, depth_l1_weight, exposure_enabled, l1_loss, psnr, ssim
 from .model import OptimParams, SplatModel
 from .render import das3r_render
 
@@ -75,9 +75,10 @@ def train_step(model: SplatModel, cam, opt: OptimParams, iteration, pipe, backgr
     image = pkg["render"]
     gt = cam.original_image
     static = model._conf_static[cam.uid]
+    expo = model._exposure[cam.uid] if getattr(model, "_exposure", None) is not None else None   # (None: today's step, call for call)
     if fused and fused_loss:   # opt-in: the masked L1 + SSIM loss and the frame MSE as one HIP kernel each way
         from .fused import masked_photometric_loss
-        loss, mse = masked_photometric_loss(image, gt, static, opt.lambda_dssim)
+        loss, mse = masked_photometric_loss(image, gt, static, opt.lambda_dssim, **({"exposure": expo} if expo is not None else {}))
         psnr_frame = (20 * torch.log10(1.0 / torch.sqrt(mse))).mean()
         if w_depth > 0.0:
             from .fused import depth_l1_loss
@@ -92,6 +93,8 @@ def train_step(model: SplatModel, cam, opt: OptimParams, iteration, pipe, backgr
                 model.optimizer_cam.step()
             model.optimizer_cam.zero_grad(set_to_none=True)
         return loss.detach(), psnr_frame.detach(), pkg
+    if expo is not None:   # (the package's "render" stays the raw render)
+        image = apply_exposure(image, expo)
     image = image * static
     gt = gt * static
     Ll1 = l1_loss(image, gt, reduce=False)
@@ -108,6 +111,33 @@ def train_step(model: SplatModel, cam, opt: OptimParams, iteration, pipe, backgr
             model.optimizer_cam.step()
         model.optimizer_cam.zero_grad(set_to_none=True)
     return loss.detach(), psnr_frame.detach(), pkg
+
+
+def exposure_rates(opt):
+    """(exposure_lr_init, exposure_lr_final) of `opt` as the pair the checkpoints keep; (0.0, 0.0): per-frame exposure compensation is off."""
+    exposure_enabled(opt)   # (raises on a half-set pair)
+    return (float(getattr(opt, "exposure_lr_init", 0.0)), float(getattr(opt, "exposure_lr_final", 0.0)))
+
+
+EXPOSURE_HELDOUT = ("identity", "nearest")
+
+
+def heldout_exposure(model, cam, policy="identity"):
+    """The exposure matrix a HELD-OUT view is rendered with: "identity" (the default) -> None, i.e. the raw render, today's numbers;
+    "nearest" -> the learned matrix of the training frame whose frame index is nearest to the view's (ties: the earlier frame), detached.
+    A model that trained without exposure compensation has no matrices: None under either policy.  "nearest" needs the frame indices —
+    model.exposure_frames (one per training view) and cam.frame_index, both set by build_from_sequence."""
+    if policy not in EXPOSURE_HELDOUT:
+        raise ValueError(f"held-out exposure policy must be one of {EXPOSURE_HELDOUT}, got {policy!r}")
+    E = getattr(model, "_exposure", None)
+    if policy == "identity" or E is None:
+        return None
+    frames, at = getattr(model, "exposure_frames", None), getattr(cam, "frame_index", None)
+    if frames is None or at is None or len(frames) != E.shape[0]:
+        raise ValueError('held-out exposure policy "nearest" needs model.exposure_frames (one frame index per training view) and the '
+                         "held-out camera's frame_index (train.build_from_sequence sets both)")
+    k = min(range(len(frames)), key=lambda j: (abs(int(frames[j]) - int(at)), j))
+    return E.detach()[k]
 
 
 def prune_schedule(opt):
@@ -127,6 +157,16 @@ def prune_due(schedule, iteration):
 
 class ResumeMismatch(ValueError):
     """A checkpoint is resumed with settings that would silently change the job's schedule."""
+
+
+def check_exposure_resume(loop_state, opt):
+    """Raises ResumeMismatch unless `opt` holds the exposure learning rates the checkpoint's job ran with (a checkpoint from before exposure
+    compensation has no entry: off)."""
+    was, now = tuple(float(v) for v in (loop_state.get("exposure") or (0.0, 0.0))), exposure_rates(opt)
+    if was != now:
+        raise ResumeMismatch(f"this checkpoint was written by a job with exposure learning rates {was[0]:g} -> {was[1]:g} (0 -> 0: off); it is "
+                             f"being resumed with {now[0]:g} -> {now[1]:g}, which would change the model mid-run: resume with the same "
+                             "--exposure-lr-init / --exposure-lr-final (OptimParams.exposure_lr_init / _final)")
 
 
 def save_checkpoint(path, model, iteration, loop_state=None):
@@ -163,19 +203,23 @@ def load_checkpoint(path, model, opt, fused=False, device=None):
     extras = torch.load(extras_path, map_location=device, weights_only=False) if os.path.exists(extras_path) else None
     if extras is not None and extras.get("iteration") != iteration:
         extras = None   # (a pair torn by a kill between the two renames: the extras belong to an older checkpoint of the same name — cannot happen with distinct iterations, kept as a guard)
+    if extras is not None and extras.get("loop") is not None:
+        check_exposure_resume(extras["loop"], opt)   # (before restore: a model that holds matrices cannot be restored with the feature off)
     model.restore(capture, opt, extras=extras["model"] if extras else None, fused=fused, device=device)
     return int(iteration), (extras["loop"] if extras else None)
 
 
 def train(model, cameras, opt: OptimParams, iterations, pipe=None, background=None, seed=0, log_every=0, fused=False,
           test_cameras=None, gt_dynamic_masks=None, on_progress=None, start_iteration=1, loop_state=None, checkpoint_every=0,
-          checkpoint_dir=None):
+          checkpoint_dir=None, exposure_heldout="identity"):
     """Random camera without replacement per epoch (train_gui.py:546-555).  With test_cameras: train_test_psnr.py's loop, which
     walks the held-out views whenever the training stack has run empty (test_pose_pass).  Returns dict(loss, psnr, iters_per_s).
     checkpoint_every / checkpoint_dir: write chkpnt<iteration>.pth every so many iterations (train_gui.py:626-628 --checkpoint_iterations);
     The weights of the depth term (opt.depth_l1_weight_init / _final) go into the checkpoint's loop state; resuming with other values raises
     ResumeMismatch.  The same holds for the pruning schedule (opt.prune_*: prune_schedule above) — an event (das3r_amd.prune.prune_points)
-    follows the optimizer steps of every iteration the schedule names, in all three step forms.
+    follows the optimizer steps of every iteration the schedule names, in all three step forms.  And for the rates of per-frame exposure
+    compensation (opt.exposure_lr_init / _final; the matrices themselves travel in the model's extras, their moments in the optimizer's
+    state).  exposure_heldout: the held-out pose pass's exposure policy (heldout_exposure).
     start_iteration / loop_state: continue a job from load_checkpoint's result — the iterations that follow are the ones the
     uninterrupted job would have run (same cameras in the same order, same schedules, same optimizer moments)."""
     pipe = pipe or SimpleNamespace(debug=False, compute_cov3D_python=False, convert_SHs_python=False)
@@ -185,7 +229,9 @@ def train(model, cameras, opt: OptimParams, iterations, pipe=None, background=No
     stack, ema, last_psnr = [], torch.zeros((), device=dev), torch.zeros((), device=dev)
     depth_l1 = (float(getattr(opt, "depth_l1_weight_init", 0.0)), float(getattr(opt, "depth_l1_weight_final", 0.0)))
     pruning = prune_schedule(opt)
+    exposure = exposure_rates(opt)
     if loop_state is not None:
+        check_exposure_resume(loop_state, opt)
         was_pruning = loop_state.get("prune")   # (a checkpoint from before pruning: off)
         was_pruning = None if was_pruning is None else tuple(was_pruning)
         if was_pruning != pruning:
@@ -217,7 +263,8 @@ def train(model, cameras, opt: OptimParams, iterations, pipe=None, background=No
             from .prune import prune_points
             prune_points(model, min_opacity=pruning[3], max_world_scale=pruning[4])
         if not stack and test_cameras and model.enable_test:
-            test_pose_pass(model, test_cameras, gt_dynamic_masks, opt, pipe, background, rng, fused=fused)
+            test_pose_pass(model, test_cameras, gt_dynamic_masks, opt, pipe, background, rng, fused=fused,
+                           **({"exposure": exposure_heldout} if exposure_heldout != "identity" else {}))
         ema = torch.lerp(ema, loss, 0.4)      # 0.4 loss + 0.6 ema, one kernel; stays on the device: a float() here would stall the host every iteration
         last_psnr = p
         if on_progress is not None and it % 256 == 0:   # (farm.Rendezvous.tick: this rank's main thread is getting somewhere)
@@ -233,7 +280,7 @@ def train(model, cameras, opt: OptimParams, iterations, pipe=None, background=No
                     library = _lib.learning()
             save_checkpoint(os.path.join(checkpoint_dir, f"chkpnt{it}.pth"), model, it,
                             dict(rng=rng.getstate(), stack=[c.uid for c in stack], ema=ema.detach().clone(), last_psnr=last_psnr.detach().clone(),
-                                 library=library, depth_l1=depth_l1, prune=pruning))
+                                 library=library, depth_l1=depth_l1, prune=pruning, exposure=exposure))
     if dev.type == "cuda":
         torch.cuda.current_stream(dev).synchronize()
     done = max(iterations - start_iteration + 1, 1)
@@ -252,14 +299,16 @@ def resize_mask_nearest(mask, H, W):
     return torch.nn.functional.interpolate(m, size=(H, W), mode="nearest")[0]
 
 
-def test_pose_pass(model, test_cams, gt_dynamic_masks, opt: OptimParams, pipe, background, rng, fused=False):
+def test_pose_pass(model, test_cams, gt_dynamic_masks, opt: OptimParams, pipe, background, rng, fused=False, exposure="identity"):
     """The pass over the held-out views train_test_psnr.py runs whenever the training stack runs empty (:109-147): every test
     view, in random order, is rendered with its test pose, the loss against the ground truth under (1 - gt_dynamic_mask) is
     back-propagated, the Gaussian optimizer's gradients are dropped WITHOUT a step, and optimizer_cam is stepped when the frame
     PSNR exceeds the gate.  optimizer_cam holds the TRAINING poses, whose gradients are None here, so no parameter changes
      — the pass costs time and nothing else; it is reproduced for the iterations/s of configs[4].
     fused: the same render + loss kernels as the training step (round 3: with the PyTorch glue this pass was more than half of a
-    DAVIS-shaped job — five 6.6 M-Gaussian views at ~40 ms each per 45 iterations of 3.7 ms), and no host sync on the gate."""
+    DAVIS-shaped job — five 6.6 M-Gaussian views at ~40 ms each per 45 iterations of 3.7 ms), and no host sync on the gate.
+    exposure: the held-out exposure policy (heldout_exposure; "identity": today's pass).  The pass never takes the exposure gradient and
+    never steps the exposure group — the Gaussian optimizer is zeroed without a step."""
     stack = list(test_cams)
     direct = False
     if fused:
@@ -271,19 +320,22 @@ def test_pose_pass(model, test_cams, gt_dynamic_masks, opt: OptimParams, pipe, b
             m = gt_dynamic_masks.get(cam.uid) if gt_dynamic_masks else None
             H, W = cam.image_height, cam.image_width
             static_hw = (1 - resize_mask_nearest(m, H, W)[0]).contiguous() if m is not None else _ones_hw(model, H, W)
-            fast_step.test_pose_step(model, cam, static_hw, opt, background, pipe)
+            E = heldout_exposure(model, cam, exposure)
+            fast_step.test_pose_step(model, cam, static_hw, opt, background, pipe, **({"exposure": E} if E is not None else {}))
             continue
+        E = heldout_exposure(model, cam, exposure)   # (detached: no gradient reaches the matrices)
         pkg = das3r_render(cam, model, pipe, background, camera_pose=model.get_RT_test(cam.uid), fused=fused)
         m = gt_dynamic_masks.get(cam.uid) if gt_dynamic_masks else None
         if fused:
             from .fused import masked_photometric_loss
             H, W = cam.image_height, cam.image_width
             static_hw = (1 - resize_mask_nearest(m, H, W)[0]) if m is not None else torch.ones(H, W, device=pkg["render"].device)
-            loss, mse = masked_photometric_loss(pkg["render"], cam.original_image, static_hw, opt.lambda_dssim)
+            loss, mse = masked_photometric_loss(pkg["render"], cam.original_image, static_hw, opt.lambda_dssim, **({"exposure": E} if E is not None else {}))
             psnr_frame = (20 * torch.log10(1.0 / torch.sqrt(mse))).mean()
         else:
             static = 1 - resize_mask_nearest(m, cam.image_height, cam.image_width) if m is not None else 1.0
-            image, gt = pkg["render"] * static, cam.original_image * static
+            comp = pkg["render"] if E is None else apply_exposure(pkg["render"], E)
+            image, gt = comp * static, cam.original_image * static
             psnr_frame = psnr(image, gt).mean()
             loss = ((1.0 - opt.lambda_dssim) * l1_loss(image, gt, reduce=False) + opt.lambda_dssim * (1.0 - ssim(image, gt, size_average=False))).mean()
         loss.backward(retain_graph=True)
@@ -306,7 +358,7 @@ def _ones_hw(model, H, W):
 
 @torch.no_grad()
 def psnr_report(model, cameras, dynamic_masks=None, pipe=None, background=None, test_poses=False, iteration=None, log_dir=None,
-                name="test"):
+                name="test", exposure="identity"):
     """Held-out report of train_test_psnr.py:241-302.  Per view: clamp the render to [0,1], mask render and ground truth with
     (1 - gt_dynamic_mask) — the mask nearest-resized to the render size (scene/cameras.py:60-67) —, L1 = mean |d|, PSNR = mean
     over channels of 20 log10(1 / sqrt(mse_c)) (utils/image_utils.py:17-19), both accumulated in float64.  ONLY views that have a
@@ -314,6 +366,8 @@ def psnr_report(model, cameras, dynamic_masks=None, pipe=None, background=None, 
     `dynamic_masks` given the averages run over the masked views; `dynamic_masks=None` is the harness's own mode for sequences
     without ground-truth masks (every view counts, unmasked).  test_poses: use model.get_RT_test (the reference's 'test' config)
     instead of the training poses.  log_dir: append the reference's line to <log_dir>/<name>_log.txt (:299-300).
+    exposure: the held-out exposure policy (heldout_exposure): "identity" reports the raw renders — today's numbers —, "nearest" the renders
+    compensated with the matrix of the nearest training frame (before the clamp).
     -> dict(l1, psnr, views, skipped)"""
     pipe = pipe or SimpleNamespace(debug=False, compute_cov3D_python=False, convert_SHs_python=False)
     dev = model.get_xyz.device
@@ -324,7 +378,9 @@ def psnr_report(model, cameras, dynamic_masks=None, pipe=None, background=None, 
     for cam in cameras:
         pose = model.get_RT_test(cam.uid) if test_poses else model.get_RT(cam.uid)
         with torch.no_grad():   # evaluation: the rasterizer then examines the forward's self-check itself (no backward will)
-            img = torch.clamp(das3r_render(cam, model, pipe, background, camera_pose=pose)["render"], 0.0, 1.0)
+            img = das3r_render(cam, model, pipe, background, camera_pose=pose)["render"]
+            E = heldout_exposure(model, cam, exposure)
+            img = torch.clamp(img if E is None else apply_exposure(img, E), 0.0, 1.0)
         gt = torch.clamp(cam.original_image, 0.0, 1.0)
         if dynamic_masks is not None:
             m = dynamic_masks.get(cam.uid) if hasattr(dynamic_masks, "get") else dynamic_masks[cam.uid]
@@ -489,6 +545,31 @@ def consistent_sequence(frames=22, W=512, H=208, focal=600.0, n_splats=20000, se
                 focal=focal, W=W, H=H, gt_dynamic_masks=masks)
 
 
+def apply_flicker(seq, seed=0, heldout=True):
+    """Auto-exposure / white-balance drift for a synthetic sequence, IN PLACE: every TRAINING frame's channels are multiplied by gains drawn
+    log-uniformly from [0.7, 0.95] and a bias from [0, 0.05] is added (per frame and channel) — frame_c <- gain_c frame_c + bias_c, exactly
+    the affine map per-frame exposure compensation can learn.  Held-out frames (build_from_sequence's split; heldout=False: there are none)
+    stay untouched.  No pixel leaves [0, 1] (0.95 + 0.05 <= 1: asserted), so nothing is clipped and the data really is affine.
+    -> the applied matrices [frames, 3, 4] (diag(gains) | bias; [I | 0] for held-out frames), on the sequence's device."""
+    images = seq["images"]
+    F = images.shape[0]
+    tr, te = (split_sequence(seq) if heldout else (list(range(F)), []))
+    if heldout and not te:
+        tr, te = list(range(F - 1)), [F - 1]
+    assert float(images.min()) >= 0.0 and float(images.max()) <= 1.0, "apply_flicker: images must lie in [0, 1]"
+    g = torch.Generator().manual_seed(1000 + int(seed))
+    lo, hi = math.log(0.7), math.log(0.95)
+    applied = torch.eye(3, 4)[None].repeat(F, 1, 1)
+    for i in tr:
+        gains = torch.exp(lo + (hi - lo) * torch.rand(3, generator=g))
+        bias = 0.05 * torch.rand(3, generator=g)
+        applied[i, :, :3] = torch.diag(gains)
+        applied[i, :, 3] = bias
+        images[i] = images[i] * gains.to(images.device).view(3, 1, 1) + bias.to(images.device).view(3, 1, 1)
+    assert float(images.min()) >= 0.0 and float(images.max()) <= 1.0, "apply_flicker: a pixel left [0, 1]"
+    return applied.to(images.device)
+
+
 def split_sequence(seq):
     """Held-out split of the reference (scene/dataset_readers.py:336-347, eval mode): frames with (idx + 5) % 10 == 0 are test
     views, the others training views.  -> (train index list, test index list)"""
@@ -517,6 +598,9 @@ def build_from_sequence(seq, sh_degree=3, heldout=False, depth_targets=False):
                                                 camera_center=seq["cam2world"][i][:3, 3], depth=depth)
     cams = [mk(u, i, seq["depths"][i] if depth_targets else None) for u, i in enumerate(tr)]
     model.init_fov(cams[0].FoVx, cams[0].FoVy)
+    model.exposure_frames = list(tr)   # (the "nearest" held-out exposure policy: heldout_exposure)
+    for c, i in zip(cams, tr):
+        c.frame_index = i
     if not heldout:
         return model, cams
     model.init_test_RT_seq(seq["w2c_pose7"][torch.tensor(te, device=dev)])

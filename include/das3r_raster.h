@@ -352,6 +352,26 @@ int das3r_photometric_backward_finish(int32_t H, int32_t W, const float *render,
                                       const float *dmaps, const float *grad_loss, float *d_render, float *d_static, const float *partials,
                                       float *out8, das3r_stream_t stream);
 
+/* ---- per-frame exposure compensation in the photometric loss (opt-in) ----------------------------------------------------
+ * Additive symbols under ABI 16.  `exposure` is a DEVICE pointer to one view's 3 x 4 row-major matrix E (upstream 3DGS's convention); with
+ *     comp_c(p) = sum_i render_i(p) E[i][c] + E[c][3]
+ * the loss, the MSEs, psnr_frame and d_static above are those of comp in the render's place; E = [I | 0] gives the values of the entry
+ * points without exposure bit for bit.  With g_c = dL/d image_c:
+ *     d_render_i(p) = static(p) sum_c E[i][c] g_c(p)          d_static(p) = sum_c (g_c comp_c + db_c gt_c)
+ *     dL/dE[i][c]   = sum_p g_c(p) static(p) render_i(p)      dL/dE[c][3] = sum_p g_c(p) static(p)
+ * das3r_photometric_backward_finish_exposure writes every tile's twelve sums to epartials[das3r_photometric_blocks(H, W)][16] (scratch; NULL:
+ * no exposure gradient is taken); partials / out8 as in das3r_photometric_backward_finish, or both NULL for no loss reduction.
+ * das3r_exposure_grad_finish: one workgroup zeroes zero_row[12] (NULL: nothing; may be grad_row) and then writes the rows of epartials, added
+ * in a fixed order, to grad_row[12] — row `uid` of a dense [n_train, 3, 4] gradient that is zero elsewhere.  No floating-point atomics:
+ * bit-identical from run to run.  A NULL `exposure` (the entry points above are the form without) or any other bad argument:
+ * DAS3R_ERR_INVALID_ARG with a das3r_last_error() message, nothing launched. */
+int das3r_photometric_forward_exposure(int32_t H, int32_t W, const float *render, const float *gt, const float *static_mask, float lambda,
+                                       const float *exposure, float *partials, float *dmaps, das3r_stream_t stream);
+int das3r_photometric_backward_finish_exposure(int32_t H, int32_t W, const float *render, const float *gt, const float *static_mask, float lambda,
+                                               const float *exposure, const float *dmaps, const float *grad_loss, float *d_render,
+                                               float *d_static, const float *partials, float *out8, float *epartials, das3r_stream_t stream);
+int das3r_exposure_grad_finish(int32_t H, int32_t W, const float *epartials, float *grad_row, float *zero_row, das3r_stream_t stream);
+
 /* ---- inverse-depth L1 term (depth-supervised training; opt-in) ------------------------------------------------------------
  * Additive symbols under ABI 16 (no struct and no existing entry point changes, as antialiasing and the split-colour rule were added).
  * With D = the rasterizer's inverse-depth image (das3r_raster_out.out_invdepth), D* = target, m = mask, s = static_mask (NULL = 1; taken as

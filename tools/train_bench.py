@@ -34,6 +34,8 @@ def main():
     ap.add_argument("--depth", default="noise", choices=("noise", "smooth"), help="depth maps of the synthetic sequence (das3r_amd.train.synthetic_sequence)")
     ap.add_argument("--depth-l1", nargs=2, type=float, default=(0.0, 0.0), metavar=("INIT", "FINAL"), help="time the depth-supervised step: weights of the "
                     "inverse-depth L1 term (OptimParams.depth_l1_weight_init / _final; upstream 3DGS: 1.0 0.01); the cameras then carry the sequence's depth maps")
+    ap.add_argument("--exposure-lr", nargs=2, type=float, default=(0.0, 0.0), metavar=("INIT", "FINAL"), help="time the step with per-frame exposure "
+                    "compensation: learning rates of the exposure group (OptimParams.exposure_lr_init / _final; upstream 3DGS: 0.01 0.001)")
     ap.add_argument("--dynamic-fraction", type=float, default=0.0, help="mark a rectangle of this share of every frame dynamic (dyna_avg = 1) before the "
                     "model is built (the synthetic sequences' own moving disc covers about 2 %% of a frame)")
     ap.add_argument("--prune-min-opacity", type=float, default=0.0, help="> 0: also time the step after one prune event at this threshold "
@@ -51,7 +53,8 @@ def main():
         seq["dyna_avg"][:, y0:y0 + h, x0:x0 + w] = 1.0
     w0, w1 = args.depth_l1
     model, cams = build_from_sequence(seq, depth_targets=w0 > 0 or w1 > 0)
-    opt = OptimParams(iterations=4000, depth_l1_weight_init=w0, depth_l1_weight_final=w1)
+    e0, e1 = args.exposure_lr
+    opt = OptimParams(iterations=4000, depth_l1_weight_init=w0, depth_l1_weight_final=w1, exposure_lr_init=e0, exposure_lr_final=e1)
     model.training_setup(opt, fused=args.fused_adam) if args.fused_adam else model.training_setup(opt)
     pipe = SimpleNamespace(debug=False, compute_cov3D_python=False, convert_SHs_python=False)
     bg = torch.zeros(3, device="cuda")
@@ -94,7 +97,7 @@ def main():
                        splats_after=info["after"], first_event_ms=round(event_ms, 3), before_ms=before, after_ms=after)
     out = {"train_step_ms": round(ms, 3), "splats": int(model.get_xyz.shape[0]), "frames": args.frames, "image": [args.W, args.H],
            "iters_per_s": round(1e3 / ms, 2), "fused_adam": bool(args.fused_adam), "fused_pre": bool(args.fused_pre),
-           "depth_l1": [w0, w1]}
+           "depth_l1": [w0, w1], "exposure_lr": [e0, e1]}
     if pruning is not None:
         out["prune"] = pruning
     if args.breakdown:

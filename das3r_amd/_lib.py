@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(_HERE, "libdas3r_hip.so")
 ABI_VERSION = 16
 NO_BACKWARD_IN_FLAG = 8   # das3r_raster_saved.flags bit 3 on the way in to das3r_raster_forward: no backward pass will follow
 ANTIALIAS_FLAG = 16       # das3r_raster_saved.flags bit 4: an antialiased forward (asked for on the way in, set again on the way out)
+AUX_MAX_CHANNELS = 8      # DAS3R_AUX_MAX_CHANNELS: channels per das3r_raster_aux_forward / _adjoint call
 
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
 
@@ -89,7 +90,8 @@ EXPORTS = ("das3r_raster_forward", "das3r_raster_backward", "das3r_raster_backwa
            "das3r_pose_matrices_qt", "das3r_pose_chain_qt", "das3r_photometric_finish", "das3r_pretransform_backward_adam", "das3r_pretransform_pose_sums",
            "das3r_raster_count_live_pairs", "das3r_photometric_backward_finish", "das3r_pose_chain_qt_rearm", "das3r_ssim_map_forward", "das3r_ssim_map_backward",
            "das3r_split_colour_rule", "das3r_split_colour_switch", "das3r_depth_l1_blocks", "das3r_depth_l1", "das3r_prune_select", "das3r_prune_compact",
-           "das3r_photometric_forward_exposure", "das3r_photometric_backward_finish_exposure", "das3r_exposure_grad_finish")
+           "das3r_photometric_forward_exposure", "das3r_photometric_backward_finish_exposure", "das3r_exposure_grad_finish",
+           "das3r_raster_aux_forward", "das3r_raster_aux_scratch_bytes", "das3r_raster_aux_adjoint")
 
 _lib = None
 
@@ -181,6 +183,13 @@ def load():
                                      C.c_void_p]
     L.das3r_prune_compact.restype = C.c_int
     L.das3r_prune_compact.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(PruneTensor), C.c_void_p]
+    L.das3r_raster_aux_forward.restype = C.c_int   # extra per-Gaussian channels over a forward's lists (additive under ABI 16)
+    L.das3r_raster_aux_forward.argtypes = [C.POINTER(RasterArgs), C.POINTER(RasterSaved), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.das3r_raster_aux_scratch_bytes.restype = C.c_size_t
+    L.das3r_raster_aux_scratch_bytes.argtypes = [C.c_int64, C.c_int32]
+    L.das3r_raster_aux_adjoint.restype = C.c_int
+    L.das3r_raster_aux_adjoint.argtypes = [C.POINTER(RasterArgs), C.POINTER(RasterSaved), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                           C.c_void_p]
     L.das3r_photometric_finish.restype = C.c_int
     L.das3r_photometric_finish.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
     L.das3r_adam_step_gated.restype = C.c_int

@@ -1020,6 +1020,58 @@ extern "C" size_t das3r_raster_backward_scratch_bytes(int64_t capacity) {
     return c * 9 * sizeof(float) + 16;
 }
 
+// ---- extra per-Gaussian channels over a forward's saved lists (render_aux.hip) ----
+// Both calls read the saved state only (ranges, lists, n_contrib, splat records, emission slots, tiles_touched / off_by_gid): any number of
+// them, before or after das3r_raster_backward / _depth, which read the same buffers and write none of what is read here.
+static int aux_validate(const char *who, const das3r_raster_args *a, const das3r_raster_saved *saved, int32_t C, const void *p0, const void *p1) {
+    if (!a || !saved) { set_error("%s: null args / saved state", who); return DAS3R_ERR_INVALID_ARG; }
+    if (C < 1 || C > DAS3R_AUX_MAX_CHANNELS) { set_error("%s: C = %d channels (1 .. %d per call)", who, C, DAS3R_AUX_MAX_CHANNELS); return DAS3R_ERR_INVALID_ARG; }
+    if (a->P < 0 || a->image_width <= 0 || a->image_height <= 0) { set_error("%s: bad extents P=%d W=%d H=%d", who, a->P, a->image_width, a->image_height); return DAS3R_ERR_INVALID_ARG; }
+    if (!p1 || (a->P > 0 && !p0)) { set_error("%s: null feature / image / gradient pointer", who); return DAS3R_ERR_INVALID_ARG; }
+    if (a->P > 0 && saved->num_rendered > 0 && (!saved->geom || !saved->binning || !saved->img)) { set_error("%s: saved buffers missing", who); return DAS3R_ERR_INVALID_ARG; }
+    return DAS3R_OK;
+}
+
+extern "C" int das3r_raster_aux_forward(const das3r_raster_args *a, const das3r_raster_saved *saved, int32_t C, const float *features, float *out,
+                                        das3r_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    int rc = aux_validate("das3r_raster_aux_forward", a, saved, C, features, out);
+    if (rc) return rc;
+    const int P = a->P, W = a->image_width, H = a->image_height;
+    if (P == 0 || saved->num_rendered <= 0) {   // nothing was blended: an empty image (upstream's empty scene)
+        HIP_TRY(hipMemsetAsync(out, 0, sizeof(float) * (size_t)C * (size_t)W * (size_t)H, s));
+        return DAS3R_OK;
+    }
+    if ((rc = das3r_raster_check(saved, stream))) return rc;   // a failed binning is an error, not a walk over bad lists
+    Layout L;
+    compute_layout(P, saved->capacity > 0 ? saved->capacity : saved->num_rendered, W, H, &L);
+    return launch_render_aux_forward(P, W, H, C, features, out, saved->geom, saved->binning, saved->img, L, saved->num_rendered, a->debug != 0, s);
+}
+
+// C floats per instance + 16 bytes (as das3r_raster_backward_scratch_bytes rounds its rows up)
+extern "C" size_t das3r_raster_aux_scratch_bytes(int64_t capacity, int32_t C) {
+    const size_t c = capacity > 0 ? (size_t)capacity : 1, ch = C > 0 ? (size_t)C : 1;
+    return c * ch * sizeof(float) + 16;
+}
+
+extern "C" int das3r_raster_aux_adjoint(const das3r_raster_args *a, const das3r_raster_saved *saved, int32_t C, const float *dL_dout, float *dL_dfeat,
+                                        int32_t accumulate, float *scratch, das3r_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    int rc = aux_validate("das3r_raster_aux_adjoint", a, saved, C, dL_dfeat, dL_dout);
+    if (rc) return rc;
+    const int P = a->P, W = a->image_width, H = a->image_height;
+    if (P == 0) return DAS3R_OK;   // dL_dfeat has no rows
+    if (saved->num_rendered <= 0) {
+        if (!accumulate) HIP_TRY(hipMemsetAsync(dL_dfeat, 0, sizeof(float) * (size_t)P * (size_t)C, s));
+        return DAS3R_OK;
+    }
+    if (!scratch) { set_error("das3r_raster_aux_adjoint: null scratch (das3r_raster_aux_scratch_bytes)"); return DAS3R_ERR_INVALID_ARG; }
+    if ((rc = das3r_raster_check(saved, stream))) return rc;
+    Layout L;
+    compute_layout(P, saved->capacity > 0 ? saved->capacity : saved->num_rendered, W, H, &L);
+    return launch_render_aux_adjoint(P, W, H, C, dL_dout, dL_dfeat, accumulate != 0, scratch, saved->geom, saved->binning, saved->img, L, saved->num_rendered, a->debug != 0, s);
+}
+
 extern "C" int das3r_has_experiments(void) {
 #ifdef DAS3R_EXPERIMENTS
     return 1;

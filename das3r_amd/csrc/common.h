@@ -372,6 +372,12 @@ int launch_depth_fold(int P, const char *geom, const Layout &L, float *partial, 
 // *quad_rows (out): false = partial[I][9], one row per instance; true = the stream kernel's rows[I][4][12] + existence bytes
 int launch_render_backward(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
                            float *partial, hipStream_t s, bool *quad_rows, int64_t num_rendered, uint32_t fwd_flags /*das3r_raster_saved.flags*/);
+// render_aux.hip: a caller's [P, C] rows composited over the saved lists of a forward (1 <= C <= DAS3R_AUX_MAX_CHANNELS), and the adjoint —
+// per-instance rows partial[capacity][C] through the emission slots, then the per-Gaussian sum (written, or added with `accumulate`)
+int launch_render_aux_forward(int P, int W, int H, int C, const float *feat, float *out, const char *geom, const char *binning, const char *img,
+                              const Layout &L, int64_t num_rendered, bool debug, hipStream_t s);
+int launch_render_aux_adjoint(int P, int W, int H, int C, const float *dL_dout, float *dL_dfeat, int accumulate, float *partial, const char *geom,
+                              const char *binning, const char *img, const Layout &L, int64_t num_rendered, bool debug, hipStream_t s);
 // pair_count.hip (measurement aid): out[0] += live pairs, out[1] += (pixel, list position) pairs below the pixel's n_contrib
 int launch_count_live_pairs(const das3r_raster_args *a, char *geom, char *binning, char *img, const Layout &L, unsigned long long *out, hipStream_t s);
 int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in *in, char *geom, char *binning, const Layout &L,

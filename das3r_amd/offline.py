@@ -115,16 +115,18 @@ class _EvalState:
 
 
 @torch.no_grad()
-def render_view_fused(model, view, pose7, background, pipe=PIPE, invdepth=False):
+def render_view_fused(model, view, pose7, background, pipe=PIPE, invdepth=False, features=None, alpha=False, return_state=False):
     """render_test of one view (gaussian_renderer/__init__.py:152-277) with the pose pre-transform INSIDE the rasterizer's per-Gaussian
     kernel (include/das3r_raster.h das3r_raster_in.pre, as the direct training iteration uses it): R xyz + t, quaternion product, exp,
     sigmoid x the per-Gaussian conf_static column — the dozen PyTorch kernels of the reference's glue (a boolean-mask gather of every
     tensor among them: 190 bytes of SH per Gaussian copied per view) are not launched and the camera-frame tensors never exist.
     Same arithmetic up to the rounding of the pre-transform (tests: within the parity bars of the glue form).  -> (image, radii), or with
-    invdepth (image, radii, inverse-depth image [1, H, W]: include/das3r_raster.h das3r_raster_out.out_invdepth)"""
+    invdepth (image, radii, inverse-depth image [1, H, W]: include/das3r_raster.h das3r_raster_out.out_invdepth).  features ([P, C] fp32) /
+    alpha: appended after those, in this order — the [C, H, W] image of the channels blended over this forward's lists
+    (rasterizer.composite_features) and the [1, H, W] coverage (rasterizer.alpha_of); return_state: last, the forward's RasterState."""
     import ctypes as C
     from . import _lib
-    from .rasterizer import _forward_full, _on_device, _stream, check_forward
+    from .rasterizer import RasterState, _forward_full, _on_device, _stream, alpha_of, check_forward, composite_features
     from .render import _settings
     st = model.__dict__.get("_das3r_eval")
     if st is None:
@@ -146,7 +148,16 @@ def render_view_fused(model, view, pose7, background, pipe=PIPE, invdepth=False)
     res = _forward_full(rs, xyz, st.packed_sh(model), st.e, op, sc, rot, st.e, pre=pre, invdepth=invdepth, no_backward=True,
                         antialiasing=bool(getattr(pipe, "antialiasing", False)))
     check_forward(res[6], dev)   # (no backward pass will examine this forward's binning self-check)
-    return (res[1], res[2], res[7]) if invdepth else (res[1], res[2])
+    out = (res[1], res[2], res[7]) if invdepth else (res[1], res[2])
+    if features is not None or alpha or return_state:
+        state = RasterState.of(res, rs)
+        if features is not None:
+            out = out + (composite_features(state, features),)
+        if alpha:
+            out = out + (alpha_of(state),)
+        if return_state:
+            out = out + (state,)
+    return out
 
 
 def invdepth_median_rel_error(invdepth, depth):
@@ -162,42 +173,62 @@ def invdepth_median_rel_error(invdepth, depth):
 
 @torch.no_grad()
 def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=None, poses=None, write=True, fused=False, invdepth=None,
-               exposures=None):
+               exposures=None, static_map=None, alpha=None):
     """render.py:72-86.  views: cameras carrying .pose7 (qw, qx, qy, qz, tx, ty, tz world-to-camera); poses: optional [N, 4, 4]
     world-to-camera matrices that override them.  fused: render_view_fused instead of the reference's PyTorch glue in front of the
     rasterizer (opt-in, like every fused form).  invdepth: a list that receives every view's inverse-depth image [1, H, W] (written as
     invdepth/%05d.npy next to renders/ when `write`); None: colour only.  exposures: per view a [3, 4] exposure matrix (applied to the
-    render: das3r_amd.losses.apply_exposure) or None.  -> list of the rendered [3, H, W] tensors (on the device)."""
+    render: das3r_amd.losses.apply_exposure) or None.  static_map / alpha: lists that receive every view's static-confidence map — the
+    loaded model's per-Gaussian conf_static column blended over the view's own lists, [1, H, W] — and its coverage map [1, H, W]
+    (written as static/%05d.npy and alpha/%05d.npy beside invdepth/, in the same format, when `write`); None: not computed.
+    -> list of the rendered [3, H, W] tensors (on the device)."""
     dev = model.get_xyz.device
     background = background if background is not None else torch.zeros(3, device=dev)
-    render_path = os.path.join(model_path, name, f"ours_{iteration}", "renders")
-    depth_path = os.path.join(model_path, name, f"ours_{iteration}", "invdepth")
-    want = invdepth is not None
+    base = os.path.join(model_path, name, f"ours_{iteration}")
+    render_path = os.path.join(base, "renders")
+    want, want_static, want_alpha = invdepth is not None, static_map is not None, alpha is not None
+    conf = None
+    if want_static:
+        conf = model._conf_static.detach().reshape(-1, 1).float().contiguous()
+        if conf.shape[0] != model.get_xyz.shape[0]:
+            raise RuntimeError("render_set(static_map=...) renders a LOADED model (one conf_static value per Gaussian: load_trained_model)")
     out = []
     for idx, view in enumerate(views):
         pose = view.pose7 if poses is None else tensor_from_camera(poses[idx], dev)
+        smap = amap = None
         if fused:
-            res = render_view_fused(model, view, pose, background, pipe, invdepth=want)
+            res = render_view_fused(model, view, pose, background, pipe, invdepth=want, features=conf, alpha=want_alpha)
             img, inv = res[0], (res[2] if want else None)
+            nxt = 3 if want else 2
+            if want_static:
+                smap, nxt = res[nxt], nxt + 1
+            if want_alpha:
+                amap = res[nxt]
         else:
-            pkg = das3r_render(view, model, pipe, background, camera_pose=pose, variant="test", return_invdepth=want)
-            img, inv = pkg["render"], pkg.get("invdepth")
+            pkg = das3r_render(view, model, pipe, background, camera_pose=pose, variant="test", return_invdepth=want, features=conf,
+                               return_alpha=want_alpha)
+            img, inv, smap, amap = pkg["render"], pkg.get("invdepth"), pkg.get("features"), pkg.get("alpha")
         if exposures is not None and exposures[idx] is not None:
             from .losses import apply_exposure
             img = apply_exposure(img, torch.as_tensor(exposures[idx], dtype=img.dtype, device=img.device))
         out.append(img)
         if want:
             invdepth.append(inv)
+        if want_static:
+            static_map.append(smap)
+        if want_alpha:
+            alpha.append(amap)
         if write:
             save_image(img, os.path.join(render_path, f"{idx:05d}.png"))
-            if want:
-                os.makedirs(depth_path, exist_ok=True)
-                np.save(os.path.join(depth_path, f"{idx:05d}.npy"), inv[0].detach().cpu().numpy())
+            for sub, m in (("invdepth", inv if want else None), ("static", smap), ("alpha", amap)):
+                if m is not None:
+                    os.makedirs(os.path.join(base, sub), exist_ok=True)
+                    np.save(os.path.join(base, sub, f"{idx:05d}.npy"), m[0].detach().cpu().numpy())
     return out
 
 
 def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=False, optimised_poses=False, device="cuda", write=True, fused=False,
-                depth=False, pipe=PIPE, prune_min_opacity=0.0, write_pruned_ply=False, exposure="none"):
+                depth=False, pipe=PIPE, prune_min_opacity=0.0, write_pruned_ply=False, exposure="none", static_map=False, alpha=False):
     """render.py:89-123: load the trained model, write pose_interpolated.npy, render the "interp" set.  seq: the sequence the model was
     trained on (its cameras).  depth: also the inverse-depth images (invdepth/%05d.npy) and, per view, the median relative error of
     1 / invdepth against the sequence's depth map (printed: a diagnostic).  pipe: PIPE, or pipe_from_args' (pipe.antialiasing: a model
@@ -205,7 +236,8 @@ def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=Fal
     the Gaussians with sigmoid(opacity) * conf_static below it go; at or below 1/255 the renders do not change); write_pruned_ply: the
     compacted model is saved as point_cloud/iteration_N/point_cloud_pruned.ply.  exposure: "none" (the default: today's output) or "train" —
     <model_path>/exposure.json (a job that trained with per-frame exposure compensation writes it) is loaded and every view whose frame
-    name it holds, i.e. every training view, is written compensated; the others stay raw.  -> (iteration, list of rendered images)"""
+    name it holds, i.e. every training view, is written compensated; the others stay raw.  static_map / alpha: also every view's
+    static-confidence map and coverage map (render_set: static/%05d.npy, alpha/%05d.npy).  -> (iteration, list of rendered images)"""
     if exposure not in ("none", "train"):
         raise ValueError(f'render_sets: exposure must be "none" or "train", got {exposure!r}')
     model, iteration = load_trained_model(model_path, iteration, sh_degree, device)
@@ -241,7 +273,7 @@ def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=Fal
         table, names = read_exposure_json(path), sequence_frame_names(seq)
         exposures = [table.get(names[f]) for f in frames]
     imgs = render_set(model_path, "interp", iteration, views, model, pipe, bg, poses=poses, write=write, fused=fused, invdepth=inv,
-                      exposures=exposures)
+                      exposures=exposures, static_map=[] if static_map else None, alpha=[] if alpha else None)
     if depth and seq.get("depths") is not None:
         for idx, (f, d) in enumerate(zip(frames, inv)):
             print(f"view {idx:05d} (frame {f}): median |1/invdepth - depth| / depth = {invdepth_median_rel_error(d, seq['depths'][f]):.4f}")
@@ -292,6 +324,9 @@ def parser():
                     "point_cloud/iteration_N/point_cloud_pruned.ply")
     ap.add_argument("--exposure", default="none", choices=("none", "train"), help='"train": write the training views compensated with the matrices '
                     "of <model-path>/exposure.json (a job trained with --exposure-lr-init / --exposure-lr-final); none: the raw renders")
+    ap.add_argument("--static-map", action="store_true", help="also write every view's static-confidence map (static/%%05d.npy next to renders/): the "
+                    "model's per-Gaussian conf_static blended over the view's own lists, at any view, without a second forward")
+    ap.add_argument("--alpha", action="store_true", help="also write every view's coverage map 1 - T (alpha/%%05d.npy next to renders/)")
     return ap
 
 
@@ -302,7 +337,7 @@ def main(argv=None):
     seq = load_sequence(args.source_path, device="cuda", dataset=args.dataset)
     it, imgs = render_sets(args.model_path, seq, args.iteration, args.sh_degree, args.white_background, args.optimised_poses, fused=args.fused,
                            depth=args.depth, pipe=pipe_from_args(args), prune_min_opacity=args.prune_min_opacity, write_pruned_ply=args.write_pruned_ply,
-                           exposure=args.exposure)
+                           exposure=args.exposure, static_map=args.static_map, alpha=args.alpha)
     print(f"wrote {len(imgs)} images to {os.path.join(args.model_path, 'interp', f'ours_{it}', 'renders')}")
 
 

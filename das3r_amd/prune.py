@@ -213,6 +213,39 @@ def prune_points(model, min_opacity=0.005, max_world_scale=0.0, also_drop=None, 
     return info
 
 
+@torch.no_grad()
+def contribution_scores(model, views, pipe=None, background=None):
+    """-> [P] fp32: every Gaussian's blending-weight mass over `views`, sum_views sum_pixels alpha_i T_i — how much of the rendered images
+    the Gaussian actually makes up (a Gaussian hidden behind others, or off every screen, scores 0 whatever its opacity: not what the opacity
+    threshold above measures).  Per view: one no-grad forward and one adjoint of a ones image over that forward's lists
+    (rasterizer.feature_adjoint: sum_pixels alpha T per Gaussian, no backward pass), accumulated in place after the first view.  No
+    floating-point atomics: the scores are bit-identical from run to run.
+    views: cameras; the pose is the view's own `.pose7` when it carries one, else the model's training pose of `view.uid`.  A training
+    model is rendered as in training (opacity x conf_static at the Gaussian's pixel), a loaded one as the offline renderer does
+    (variant "test").  The hand-off to the pruning event:
+
+        scores = contribution_scores(model, cameras, pipe, background)
+        prune_points(model, also_drop=scores < tau)        # tau: the caller's threshold, in units of pixels"""
+    from types import SimpleNamespace
+    from .rasterizer import feature_adjoint
+    from .render import das3r_render
+    pipe = pipe or SimpleNamespace(debug=False, compute_cov3D_python=False, convert_SHs_python=False)
+    dev = model._xyz.device
+    background = background if background is not None else torch.zeros(3, device=dev)
+    variant = "render" if hasattr(model, "aggregated_mask") else "test"
+    scores = torch.zeros(int(model._xyz.shape[0]), 1, dtype=torch.float32, device=dev)
+    ones = {}
+    for n, view in enumerate(views):
+        pose = getattr(view, "pose7", None)
+        pose = model.get_RT(view.uid) if pose is None else pose
+        state = das3r_render(view, model, pipe, background, camera_pose=pose, variant=variant, return_state=True)["raster_state"]
+        g = ones.get((state.H, state.W))
+        if g is None:
+            g = ones[(state.H, state.W)] = torch.ones(1, state.H, state.W, dtype=torch.float32, device=dev)
+        feature_adjoint(state, g, out=scores, accumulate=n > 0)
+    return scores.reshape(-1)
+
+
 def write_pruned_ply(path, model):
     """A loaded, pruned model back into the reference's PLY layout (io_formats.save_gaussians_ply)."""
     from .io_formats import save_gaussians_ply

@@ -327,6 +327,177 @@ def count_live_pairs(rs, P, M, num_rendered, geom, binning, img, capacity):
     return int(out[0]), int(out[1])
 
 
+class RasterState:
+    """What a forward leaves behind, as the aux-channel calls take it (include/das3r_raster.h das3r_raster_aux_forward / _adjoint): the three
+    saved buffers, num_rendered and the capacity (which also carries the forward's self-check ticket and flags), P, W, H and the device.
+    Valid as long as it is kept, for any number of `composite_features` / `feature_adjoint` / `alpha_of` calls, before or after the
+    forward's own backward pass.  `RasterState.of(res, rs)` wraps a `_forward_full` result."""
+    __slots__ = ("geom", "binning", "img", "num_rendered", "capacity", "P", "W", "H", "device")
+
+    def __init__(self, geom, binning, img, num_rendered, capacity, P, W, H, device):
+        self.geom, self.binning, self.img = geom, binning, img
+        self.num_rendered, self.capacity = int(num_rendered), capacity
+        self.P, self.W, self.H, self.device = int(P), int(W), int(H), torch.device(device)
+
+    @classmethod
+    def of(cls, res, rs):
+        """res: what `_forward_full` returned (num_rendered, color, radii, geom, binning, img, capacity, ...); rs: its settings."""
+        return cls(res[3], res[4], res[5], res[0], res[6], res[2].shape[0], rs.image_width, rs.image_height, res[1].device)
+
+    @property
+    def flags(self):
+        return int(getattr(self.capacity, "flags", 0))
+
+    def _c_args(self):
+        a = _lib.RasterArgs()
+        a.P, a.image_width, a.image_height = self.P, self.W, self.H
+        saved = _lib.RasterSaved()
+        saved.geom, saved.binning, saved.img = _ptr(self.geom), _ptr(self.binning), _ptr(self.img)
+        saved.num_rendered, saved.capacity = self.num_rendered, int(self.capacity)
+        if getattr(self.capacity, "check_tag", 0):
+            saved.check_word, saved.check_tag = self.capacity.check_word, self.capacity.check_tag
+        saved.flags = self.flags
+        return a, saved
+
+
+def _check_state(state):
+    if not isinstance(state, RasterState):
+        raise TypeError(f"expected a das3r_amd.rasterizer.RasterState, got {type(state).__name__}")
+
+
+def _needs_device(state):
+    if state.device.type != "cuda":
+        raise RuntimeError("das3r_amd rasterizer: the state must be that of a forward on a HIP device (torch device 'cuda'); there is no CPU path")
+
+
+def _check_rows(state, t, name, shape_hint):
+    """[P, C] / [C, H, W] fp32, dense, on the state's device — every mismatch is an error here, before the library is called."""
+    if not torch.is_tensor(t):
+        raise TypeError(f"{name} must be a tensor {shape_hint}")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32 (got {t.dtype})")
+
+
+def _check_features(state, features, name="features"):
+    _check_state(state)
+    _check_rows(state, features, name, "[P, C]")
+    if features.dim() != 2 or features.shape[1] < 1:
+        raise ValueError(f"{name} must have dimensions (num_points, C >= 1), got {tuple(features.shape)}")
+    if features.shape[0] != state.P:
+        raise ValueError(f"{name} has {features.shape[0]} rows, the forward rasterised {state.P} Gaussians")
+    if not features.is_contiguous():
+        raise ValueError(f"{name} must be contiguous (row-major [P, C]); call .contiguous()")
+    if features.device != state.device:
+        raise RuntimeError(f"{name} is on {features.device}, the forward ran on {state.device}")
+
+
+def _aux_forward(state, feat):
+    """One das3r_raster_aux_forward call: feat [P, C <= 8] -> [C, H, W]."""
+    _needs_device(state)
+    lib = _lib.load()
+    C_ = feat.shape[1]
+    out = torch.empty(C_, state.H, state.W, dtype=torch.float32, device=state.device)   # fully written by the call
+    a, saved = state._c_args()
+    with _on_device(state.device):
+        rc = lib.das3r_raster_aux_forward(C.byref(a), C.byref(saved), C_, _ptr(feat), C.c_void_p(out.data_ptr()), _stream(state.device))
+    _lib.check(rc, "das3r_raster_aux_forward")
+    return out
+
+
+def _aux_adjoint(state, grad, out, accumulate):
+    """One das3r_raster_aux_adjoint call: grad [C <= 8, H, W] -> out [P, C] (written, or added to)."""
+    _needs_device(state)
+    lib = _lib.load()
+    C_ = grad.shape[0]
+    nbytes = int(lib.das3r_raster_aux_scratch_bytes(max(int(state.capacity), 1), C_))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=state.device)   # per-instance rows, written before they are read
+    a, saved = state._c_args()
+    with _on_device(state.device):
+        rc = lib.das3r_raster_aux_adjoint(C.byref(a), C.byref(saved), C_, C.c_void_p(grad.data_ptr()), _ptr(out), int(bool(accumulate)),
+                                          C.c_void_p(scratch.data_ptr()), _stream(state.device))
+    _lib.check(rc, "das3r_raster_aux_adjoint")
+    return out
+
+
+class _CompositeFeatures(torch.autograd.Function):
+    """composite_features with its adjoint: the gradient goes to `features` alone (the geometry is constant in an aux channel)."""
+    @staticmethod
+    def forward(ctx, features, state):
+        ctx.state = state
+        return _composite(state, features)
+
+    @staticmethod
+    def backward(ctx, grad_image):
+        return feature_adjoint(ctx.state, grad_image), None
+
+
+def _composite(state, features):
+    n = features.shape[1]
+    if n <= _lib.AUX_MAX_CHANNELS:
+        return _aux_forward(state, features)
+    return torch.cat([_aux_forward(state, features[:, c0:c0 + _lib.AUX_MAX_CHANNELS].contiguous())
+                      for c0 in range(0, n, _lib.AUX_MAX_CHANNELS)], 0)
+
+
+def composite_features(state, features):
+    """features [P, C] fp32 (one row per Gaussian of the forward that left `state`) -> [C, H, W]: per pixel sum_k features[g_k] alpha_k T_k
+    over the splats the pixel's colour was blended from — same order, same alpha, same stop; no background term, an empty pixel is 0.
+    Nothing of the forward is repeated (no preprocess, emission or sort).  Differentiable with respect to `features` ONLY: alpha and T
+    are the forward's and constant here — no gradient reaches means, scales, rotations or opacities through an aux channel.  Tensors wider
+    than 8 channels take one library call per 8."""
+    _check_features(state, features)
+    if features.requires_grad and torch.is_grad_enabled():
+        return _CompositeFeatures.apply(features, state)
+    return _composite(state, features.detach())
+
+
+def feature_adjoint(state, grad_image, out=None, accumulate=False):
+    """The adjoint of composite_features: grad_image [C, H, W] -> [P, C] = sum over pixels of alpha T grad_image per Gaussian; with a ones
+    image and C = 1, every Gaussian's blending-weight mass in the view (das3r_amd.prune.contribution_scores).  out: a dense [P, C] fp32
+    tensor to write into; accumulate: add to `out` instead (needs `out`).  Rows of Gaussians that were not rendered are exactly 0.  No
+    floating-point atomics: bit-identical from run to run."""
+    _check_state(state)
+    _check_rows(state, grad_image, "grad_image", "[C, H, W]")
+    if grad_image.dim() != 3 or grad_image.shape[0] < 1 or tuple(grad_image.shape[1:]) != (state.H, state.W):
+        raise ValueError(f"grad_image must have dimensions (C >= 1, {state.H}, {state.W}), got {tuple(grad_image.shape)}")
+    if grad_image.device != state.device:
+        raise RuntimeError(f"grad_image is on {grad_image.device}, the forward ran on {state.device}")
+    n = grad_image.shape[0]
+    if out is None:
+        if accumulate:
+            raise ValueError("feature_adjoint(accumulate=True) needs the tensor to add to (out=)")
+        out = torch.empty(state.P, n, dtype=torch.float32, device=state.device)
+    else:
+        _check_features(state, out, "out")
+        if out.shape[1] != n:
+            raise ValueError(f"out has {out.shape[1]} channels, grad_image {n}")
+    grad_image = grad_image.detach().contiguous()
+    if n <= _lib.AUX_MAX_CHANNELS:
+        return _aux_adjoint(state, grad_image, out, accumulate)
+    for c0 in range(0, n, _lib.AUX_MAX_CHANNELS):
+        part = _aux_adjoint(state, grad_image[c0:c0 + _lib.AUX_MAX_CHANNELS],
+                            torch.empty(state.P, min(_lib.AUX_MAX_CHANNELS, n - c0), dtype=torch.float32, device=state.device), False)
+        if accumulate:
+            out[:, c0:c0 + part.shape[1]] += part
+        else:
+            out[:, c0:c0 + part.shape[1]] = part
+    return out
+
+
+def alpha_of(state):
+    """-> [1, H, W] = 1 - final_T: the coverage of the forward that left `state`, read out of its saved image buffer (the transmittance
+    every forward stores for its backward pass; include/das3r_raster.h das3r_raster_get_layout).  Exactly 0 where nothing was blended.
+    A view of what is there: no kernel of the library is launched."""
+    _check_state(state)
+    _needs_device(state)
+    npix = state.H * state.W
+    if state.P == 0 or state.img.numel() == 0:
+        return torch.zeros(1, state.H, state.W, dtype=torch.float32, device=state.device)
+    L = _lib.layout(state.P, int(state.capacity) if int(state.capacity) > 0 else state.num_rendered, state.W, state.H)
+    T = state.img[L["final_T"]:L["final_T"] + 4 * npix].view(torch.float32).reshape(1, state.H, state.W)
+    return 1.0 - T
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, antialiasing=False):
     return _apply(_RasterizeGaussians, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
                   antialiasing=antialiasing)
@@ -381,6 +552,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.num_rendered = num_rendered
         ctx.capacity = capacity
         _last.capacity = capacity   # GaussianRasterizer.forward: a render that no backward pass will follow checks itself
+        if getattr(_last, "want_state", False):   # (features= / return_alpha= / keep_state: the aux-channel calls work on this forward's lists)
+            _last.state = RasterState.of(res, raster_settings)
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, opacities, geomBuffer,
                               binningBuffer, imgBuffer)
         ctx.mark_non_differentiable(radii)
@@ -430,9 +603,12 @@ class _RasterizeGaussiansInvDepth(torch.autograd.Function):
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings):
+    def __init__(self, raster_settings, keep_state=False):
+        """keep_state: every forward leaves its `RasterState` in `self.state` (composite_features / feature_adjoint / alpha_of)."""
         super().__init__()
         self.raster_settings = raster_settings
+        self.keep_state = bool(keep_state)
+        self.state = None
 
     def markVisible(self, positions):
         with torch.no_grad():
@@ -452,14 +628,19 @@ class GaussianRasterizer(nn.Module):
             return present.bool()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, return_invdepth=False, antialiasing=False):
+                cov3D_precomp=None, return_invdepth=False, antialiasing=False, features=None, return_alpha=False):
         """-> (color [3, H, W], radii [P]); with return_invdepth, (color, radii, invdepth [1, H, W]) as upstream's newer rasterizer returns:
         per pixel sum_i (1/z_i) alpha_i T_i over the splats the colour is blended from, 0 where nothing is (no background term).  The
         colour and radii are the same bit for bit either way.  The inverse depth is differentiable (back to means3D, scales, rotations,
         opacities and means2D through alpha, and to means3D through 1/z).
         antialiasing: upstream's antialiasing mode (its 2D mip filter) — every splat is blended with its opacity times
-        sqrt(max(det(Sigma2D) / det(Sigma2D + 0.3 I), 2.5e-5)), and the backward differentiates that factor too.  Radii are unchanged."""
+        sqrt(max(det(Sigma2D) / det(Sigma2D + 0.3 I), 2.5e-5)), and the backward differentiates that factor too.  Radii are unchanged.
+        features ([P, C] fp32) / return_alpha: the extra results come after the others — (color, radii[, invdepth][, feature_image]
+        [, alpha]) — feature_image [C, H, W] = composite_features over this forward's lists (differentiable with respect to `features`
+        only: the geometry is constant in an aux channel), alpha [1, H, W] = alpha_of.  The colour, the radii and every gradient of a
+        colour loss are the same bit for bit; with both at their defaults the call is the one it was."""
         raster_settings = self.raster_settings
+        want_state = features is not None or return_alpha or self.keep_state
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
@@ -477,6 +658,18 @@ class GaussianRasterizer(nn.Module):
         if cov3D_precomp is None:
             cov3D_precomp = e
         _last.capacity = None
+        if want_state:
+            _last.want_state, _last.state = True, None
+        try:
+            return self._forward_checked(means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, return_invdepth,
+                                         antialiasing, features, return_alpha, want_state)
+        finally:
+            if want_state:
+                _last.want_state, _last.state = False, None
+
+    def _forward_checked(self, means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, return_invdepth, antialiasing,
+                         features, return_alpha, want_state):
+        raster_settings = self.raster_settings
         if return_invdepth:
             color, radii, invdepth = _apply(_RasterizeGaussiansInvDepth, means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                             cov3D_precomp, raster_settings, antialiasing=antialiasing)
@@ -488,4 +681,11 @@ class GaussianRasterizer(nn.Module):
             # self-check, so it is examined here, before the image is used (include/das3r_raster.h: das3r_raster_check)
             check_forward(_last.capacity, means3D.device)
         _last.capacity = None
-        return (color, radii, invdepth) if return_invdepth else (color, radii)
+        out = (color, radii, invdepth) if return_invdepth else (color, radii)
+        if want_state:
+            state = self.state = _last.state
+            if features is not None:
+                out = out + (composite_features(state, features),)
+            if return_alpha:
+                out = out + (alpha_of(state),)
+        return out

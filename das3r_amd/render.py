@@ -171,30 +171,49 @@ def rasterizer_inputs(cam, pc, pipe, bg_color, scaling_modifier=1.0, override_co
     return settings, kw
 
 
-def _mode_kw(pipe, return_invdepth):
+def _mode_kw(pipe, return_invdepth, features=None, return_alpha=False):
     """GaussianRasterizer.forward's keywords beyond upstream's eight tensors: only those that are on."""
     kw = {"return_invdepth": True} if return_invdepth else {}
     if bool(getattr(pipe, "antialiasing", False)):
         kw["antialiasing"] = True
+    if features is not None:
+        kw["features"] = features
+    if return_alpha:
+        kw["return_alpha"] = True
     return kw
 
 
 def das3r_render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, camera_pose=None,
-                 filtering=None, use_conf=True, fused=False, variant="render", return_invdepth=False):
+                 filtering=None, use_conf=True, fused=False, variant="render", return_invdepth=False, features=None, return_alpha=False,
+                 return_state=False):
     """viewpoint_camera: .FoVx .FoVy .image_height .image_width .projection_matrix (4x4, already transposed) [.camera_center for
     pipe.convert_SHs_python]; pc: splat model (das3r_amd.model.SplatModel or anything with the same attributes); pipe: .debug
     .compute_cov3D_python .convert_SHs_python; camera_pose: (7,) tensor (qw,qx,qy,qz,tx,ty,tz), may require grad.
     return_invdepth: render_pkg["invdepth"] = the [1, H, W] inverse-depth image (GaussianRasterizer.forward; differentiable).
-    pipe.antialiasing (where upstream's newer renderer reads it; absent = False): the rasterizer's antialiasing mode."""
+    pipe.antialiasing (where upstream's newer renderer reads it; absent = False): the rasterizer's antialiasing mode.
+    features ([P, C] fp32, one row per rasterised Gaussian — after `filtering`): render_pkg["features"] = the [C, H, W] image of those
+    channels blended over this render's own lists (rasterizer.composite_features: no second forward; differentiable with respect to
+    `features` only, the geometry is constant in an aux channel).  return_alpha: render_pkg["alpha"] = [1, H, W] coverage, 1 - final T.
+    return_state: render_pkg["raster_state"] = the forward's RasterState, for further composite_features / feature_adjoint calls."""
     settings, kw = rasterizer_inputs(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, camera_pose, filtering,
                                      use_conf, fused, variant)
-    out = GaussianRasterizer(raster_settings=settings)(**kw, **_mode_kw(pipe, return_invdepth))   # (upstream's call when both are off)
+    rasterizer = GaussianRasterizer(raster_settings=settings, keep_state=True) if return_state else GaussianRasterizer(raster_settings=settings)
+    out = rasterizer(**kw, **_mode_kw(pipe, return_invdepth, features, return_alpha))   # (upstream's call when all are off)
     image, radii = out[0], out[1]
     if variant == "confidence":
         return image   # (render_confidence returns the image alone: gaussian_renderer/__init__.py:510)
     pkg = {"render": image, "viewspace_points": kw["means2D"], "visibility_filter": radii > 0, "radii": radii}
+    nxt = 2
     if return_invdepth:
-        pkg["invdepth"] = out[2]
+        pkg["invdepth"] = out[nxt]
+        nxt += 1
+    if features is not None:
+        pkg["features"] = out[nxt]
+        nxt += 1
+    if return_alpha:
+        pkg["alpha"] = out[nxt]
+    if return_state:
+        pkg["raster_state"] = rasterizer.state
     return pkg
 
 

@@ -358,7 +358,7 @@ def _ones_hw(model, H, W):
 
 @torch.no_grad()
 def psnr_report(model, cameras, dynamic_masks=None, pipe=None, background=None, test_poses=False, iteration=None, log_dir=None,
-                name="test", exposure="identity"):
+                name="test", exposure="identity", static_mask="gt", static_threshold=0.5):
     """Held-out report of train_test_psnr.py:241-302.  Per view: clamp the render to [0,1], mask render and ground truth with
     (1 - gt_dynamic_mask) — the mask nearest-resized to the render size (scene/cameras.py:60-67) —, L1 = mean |d|, PSNR = mean
     over channels of 20 log10(1 / sqrt(mse_c)) (utils/image_utils.py:17-19), both accumulated in float64.  ONLY views that have a
@@ -368,21 +368,40 @@ def psnr_report(model, cameras, dynamic_masks=None, pipe=None, background=None, 
     instead of the training poses.  log_dir: append the reference's line to <log_dir>/<name>_log.txt (:299-300).
     exposure: the held-out exposure policy (heldout_exposure): "identity" reports the raw renders — today's numbers —, "nearest" the renders
     compensated with the matrix of the nearest training frame (before the clamp).
+    static_mask: "gt" (the default: the report above, value for value) or "rendered" — every view is masked with the model's OWN static
+    map instead of 1 - gt_dynamic_mask: the per-Gaussian static confidence (conf_static at each Gaussian's pixel) blended over the view's
+    lists (das3r_render(features=...): no second forward) >= static_threshold.  It exists at any view, held-out and interpolated ones
+    included, so every view counts and `dynamic_masks` is not consulted.  static_threshold = 0.5 is an interface default for a value the
+    user sets, not a tuned number.
     -> dict(l1, psnr, views, skipped)"""
+    if static_mask not in ("gt", "rendered"):
+        raise ValueError(f'psnr_report: static_mask must be "gt" or "rendered", got {static_mask!r}')
+    rendered = static_mask == "rendered"
     pipe = pipe or SimpleNamespace(debug=False, compute_cov3D_python=False, convert_SHs_python=False)
     dev = model.get_xyz.device
     background = background if background is not None else torch.zeros(3, device=dev)
     l1_sum = torch.zeros((), dtype=torch.float64, device=dev)
     psnr_sum = torch.zeros((), dtype=torch.float64, device=dev)
     lens = skipped = 0
+    conf = None
+    if rendered:   # the per-Gaussian static confidence: conf_static at the Gaussian's pixel (a loaded model stores it per Gaussian)
+        flat = model._conf_static.detach().reshape(-1)
+        if hasattr(model, "aggregated_mask"):
+            from .prune import mask_index
+            flat = flat[mask_index(model)]
+        conf = flat.reshape(-1, 1).float().contiguous()
     for cam in cameras:
         pose = model.get_RT_test(cam.uid) if test_poses else model.get_RT(cam.uid)
         with torch.no_grad():   # evaluation: the rasterizer then examines the forward's self-check itself (no backward will)
-            img = das3r_render(cam, model, pipe, background, camera_pose=pose)["render"]
+            pkg = das3r_render(cam, model, pipe, background, camera_pose=pose, **({"features": conf} if rendered else {}))
+            img = pkg["render"]
             E = heldout_exposure(model, cam, exposure)
             img = torch.clamp(img if E is None else apply_exposure(img, E), 0.0, 1.0)
         gt = torch.clamp(cam.original_image, 0.0, 1.0)
-        if dynamic_masks is not None:
+        if rendered:
+            static = (pkg["features"] >= static_threshold).to(img.dtype)   # [1, H, W]: the same mask on the three channels
+            img, gt = img * static, gt * static
+        elif dynamic_masks is not None:
             m = dynamic_masks.get(cam.uid) if hasattr(dynamic_masks, "get") else dynamic_masks[cam.uid]
             if m is None:
                 skipped += 1

@@ -421,6 +421,31 @@ int das3r_prune_select(int32_t P, const float *opacity_raw, const float *conf_fl
 int das3r_prune_compact(int32_t P, int32_t kept, const int32_t *dst_index, int32_t n, const das3r_prune_tensor *tensors,
                         das3r_stream_t stream);
 
+/* ---- extra per-Gaussian channels over a forward's lists (opt-in) --------------------------------------------------------------
+ * Additive symbols under ABI 16.  das3r_raster_aux_forward blends a caller's rows features[P][C] exactly as the forward blended its colours,
+ *     out[c][pixel] = sum_k features[g_k][c] alpha_k T_k        over the splats g_k the pixel's colour was blended from (same order, same
+ *                                                               alpha, same stop), no background term: an empty pixel is 0
+ * and das3r_raster_aux_adjoint is its adjoint,
+ *     dL_dfeat[i][c] (=, or += with accumulate != 0)  sum over pixels and the list entries of Gaussian i of  alpha T dL_dout[c][pixel];
+ * with dL_dout = 1 and C = 1 that is the blending-weight mass of every Gaussian in the view.  Both read what ANY forward enqueued on the
+ * stream left in `saved` (geom / binning / img, num_rendered, capacity, the self-check ticket): with or without das3r_raster_in.pre, with
+ * or without out_invdepth, antialiased or not (the factor is part of the saved opacity), an evaluation forward (flags bit 3), every
+ * binning path and forward kernel — any number of times while the caller keeps the three buffers, before or after
+ * das3r_raster_backward / _depth (neither call writes what the other reads).  No preprocess, emission or sort is repeated.
+ * THE GEOMETRY IS CONSTANT in these calls: alpha and T are the forward's, and no gradient reaches means, scales, rotations or opacities
+ * through an aux channel — the defined semantics, not an omission.
+ * args supplies P, image_width, image_height and debug only.  1 <= C <= DAS3R_AUX_MAX_CHANNELS per call (wider tensors: several calls).
+ * scratch: das3r_raster_aux_scratch_bytes(saved->capacity, C) bytes (one row of C sums per list entry; need not be zeroed).  dL_dfeat is
+ * fully written (zeros for a Gaussian that was not rendered) unless accumulate.  No floating-point atomics: bit-identical from run to run.
+ * A bad C or a NULL pointer: DAS3R_ERR_INVALID_ARG with a das3r_last_error() message before anything is launched; P == 0 or nothing
+ * rendered: `out` is zeroed (dL_dfeat too, unless accumulate).  The forward's binning self-check is examined first (das3r_raster_check). */
+#define DAS3R_AUX_MAX_CHANNELS 8
+int das3r_raster_aux_forward(const das3r_raster_args *args, const das3r_raster_saved *saved, int32_t C, const float *features /* [P,C] */,
+                             float *out /* [C,H,W] planar */, das3r_stream_t stream);
+size_t das3r_raster_aux_scratch_bytes(int64_t capacity, int32_t C);
+int das3r_raster_aux_adjoint(const das3r_raster_args *args, const das3r_raster_saved *saved, int32_t C, const float *dL_dout /* [C,H,W] */,
+                             float *dL_dfeat /* [P,C] */, int32_t accumulate, float *scratch, das3r_stream_t stream);
+
 /* ---- introspection (used by the parity tests and the roofline accounting) ---- */
 
 /* Byte offsets of the saved intermediates inside geom / binning / img for given extents. */

@@ -2,7 +2,8 @@
 """How far under the parity bars the kernels are.  On the GPU box:
     DAS3R_TOL_REPORT=$PWD/gpurun_out/tol.jsonl python -m pytest tests -m gpu -q ; python tools/tol_report.py gpurun_out/tol.jsonl
 tests/util.py appends one line per gradient check: the measured max-norm error and its bar, the number of elements beyond the bar
-(threshold flips at full size), and the fraction of elements that would miss element-wise bars 1x / 10x / 100x tighter."""
+(threshold flips at full size), and the fraction of elements that would miss element-wise bars 1x / 10x / 100x tighter;
+tests/loss_reference.py one line per budget check: the worst |got - float64| / budget of an output beside its multiplier K."""
 import collections
 import json
 import re
@@ -20,7 +21,8 @@ for r in rows:
     elif r["kind"] == "over_bar":
         if r["value"] > worst[k][2]:
             worst[k][2], worst[k][3] = int(r["value"]), int(r["tol"])
-print("worst max-norm error per test (bar; most elements beyond the bar in one tensor / its size):")
+if worst:
+    print("worst max-norm error per test (bar; most elements beyond the bar in one tensor / its size):")
 for k, (v, t, n, size) in sorted(worst.items(), key=lambda kv: -kv[1][0]):
     print(f"  {v:9.3e}  (bar {t:.0e}; {n} / {size})  {k[0]}::{k[1]}")
 for d in ("1", "10", "100"):
@@ -31,3 +33,15 @@ for d in ("1", "10", "100"):
     print(f"element-wise bars / {d}: {len(el)} checks, {sum(r['value'] > 0 for r in el)} with any element beyond; worst five:")
     for r in el[:5]:
         print(f"  {r['value']:9.3e} of the elements  {r['what'][:48]:48s} {test_of(r)}")
+budget = collections.defaultdict(lambda: [0.0, 0.0, "", 0])
+for r in rows:
+    if r["kind"] == "budget_ratio":
+        form, _, case = r["what"].partition(" [")
+        b = budget[(r["test"].split("::")[0].split("/")[-1], form)]
+        b[3] += 1
+        if r["value"] >= b[0]:
+            b[0], b[1], b[2] = r["value"], r["tol"], case.rstrip("]")
+if budget:
+    print("worst |got - float64| / budget per form and output (allowed multiple K; checks; the case it was met in):")
+    for (mod, form), (v, k, case, n) in sorted(budget.items()):
+        print(f"  {v:9.3f}  (K {k:g}; {n} checks)  {mod}  {form:28s} {case}")

@@ -246,7 +246,8 @@ def sequence_cost(seq_dir):
 def run_sequence_job(scene_id, iterations, device, frames=6, seq_dir=None, out_dir=None, fused=False, gt_mask_dir=None, dataset="sintel",
                      progress=None, seq=None, keep=None, checkpoint_every=0, resume=False, pipe=None, depth_l1_init=0.0, depth_l1_final=0.0,
                      prune_from=0, prune_interval=0, prune_until=0, prune_min_opacity=0.005, prune_max_world_scale=0.0,
-                     exposure_lr_init=0.0, exposure_lr_final=0.0, exposure_heldout="identity"):
+                     exposure_lr_init=0.0, exposure_lr_final=0.0, exposure_heldout="identity",
+                     thin_init_relative=None, thin_init_edge=None, thin_opacity="coverage", prune_thin_relative=None):
     """One independent 'sequence': load a preprocessed DAS3R sequence directory (das3r_amd.io_formats.load_sequence) — or,
     without one, build a synthetic multi-frame scene —, optimise it with the train-step harness, report the held-out PSNR and,
     with out_dir, write what the reference writes (point_cloud/iteration_N/point_cloud.ply, pose/pose_N.npy:
@@ -264,6 +265,10 @@ def run_sequence_job(scene_id, iterations, device, frames=6, seq_dir=None, out_d
     exposure_lr_init / exposure_lr_final (default 0: off): per-frame exposure compensation — OptimParams.exposure_lr_init / _final; kept in the
     checkpoints like the depth weights, and with out_dir the job writes exposure.json (frame name -> 3 x 4 matrix: io_formats.write_exposure_json).
     exposure_heldout: "identity" (today's numbers) or "nearest" — which matrix the held-out pose pass and the held-out report use (train.heldout_exposure).
+    thin_init_relative / thin_init_edge (at most one; default: off) / thin_opacity: voxel thinning at the start — build_from_sequence's thin_relative /
+    thin_edge / thin_opacity (das3r_amd.thin).  prune_thin_relative (default: off; needs the pruning schedule): every prune event also drops the
+    Gaussians that lose their voxel, the edge fixed at job start as this many pixel footprints (train.sequence_footprint) — OptimParams.prune_thin_edge.
+    All kept in the checkpoints like the pruning schedule.
     progress: called at the job's stages and every few hundred iterations (Rendezvous.tick).  pipe: the `pipe` of training and of the held-out
     report (job_pipe; None: the default one)."""
     progress = progress or (lambda: None)
@@ -285,11 +290,21 @@ def run_sequence_job(scene_id, iterations, device, frames=6, seq_dir=None, out_d
         masks = seq.get("gt_dynamic_masks")   # ground-truth masks only: the report skips views without one
         # Gaussians, training poses and conf_static from the TRAINING frames only; the held-out frames ((idx + 5) % 10 == 0) give
         # their poses and their images as ground truth (scene/__init__.py:88-93, dataset_readers.py:342-347)
-        model, train_cams, test = build_from_sequence(seq, heldout=True, depth_targets=depth_l1_init > 0 or depth_l1_final > 0)
+        if thin_init_relative is not None and thin_init_edge is not None:
+            raise ValueError("run_sequence_job: give thin_init_relative or thin_init_edge, not both")
+        thin_kw = {}
+        if thin_init_relative is not None or thin_init_edge is not None:
+            thin_kw = dict(thin_relative=thin_init_relative, thin_edge=thin_init_edge, thin_opacity=thin_opacity)
+        model, train_cams, test = build_from_sequence(seq, heldout=True, depth_targets=depth_l1_init > 0 or depth_l1_final > 0, **thin_kw)
+        prune_thin_edge = 0.0
+        if prune_thin_relative is not None:
+            from .train import sequence_footprint
+            prune_thin_edge = float(prune_thin_relative) * sequence_footprint(seq, heldout=True)
         opt = OptimParams(iterations=iterations, depth_l1_weight_init=float(depth_l1_init), depth_l1_weight_final=float(depth_l1_final),
                           prune_from_iter=int(prune_from), prune_interval=int(prune_interval), prune_until_iter=int(prune_until),
                           prune_min_opacity=float(prune_min_opacity), prune_max_world_scale=float(prune_max_world_scale),
-                          exposure_lr_init=float(exposure_lr_init), exposure_lr_final=float(exposure_lr_final))
+                          exposure_lr_init=float(exposure_lr_init), exposure_lr_final=float(exposure_lr_final),
+                          **({"prune_thin_edge": prune_thin_edge} if prune_thin_edge > 0.0 else {}))
         start, loop_state = 1, None
         if resume and out_dir is not None:
             from .train import latest_checkpoint, load_checkpoint
@@ -431,6 +446,16 @@ def exposure_kwargs(args):
     return dict(exposure_lr_init=args.exposure_lr_init, exposure_lr_final=args.exposure_lr_final, exposure_heldout=args.exposure_heldout)
 
 
+def thin_kwargs(args):
+    """run_sequence_job's voxel-thinning keywords from a parsed command line ({}: all off)."""
+    if args.thin_init_relative is None and args.thin_init_edge is None and args.prune_thin_relative is None:
+        return {}
+    if args.prune_thin_relative is not None and args.prune_interval <= 0:
+        raise SystemExit("--prune-thin-relative thins at the prune events: give a pruning schedule (--prune-from / --prune-interval / --prune-until)")
+    return dict(thin_init_relative=args.thin_init_relative, thin_init_edge=args.thin_init_edge, thin_opacity=args.thin_opacity,
+                prune_thin_relative=args.prune_thin_relative)
+
+
 def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sequences", type=int, default=8)
@@ -469,12 +494,22 @@ def parser():
     ap.add_argument("--exposure-lr-final", type=float, default=0.0, help="its learning rate at the last iteration, log-linear in between (upstream 3DGS uses 0.001)")
     ap.add_argument("--exposure-heldout", default="identity", choices=("identity", "nearest"), help="the matrix a held-out view is compared under: none "
                     "(identity: the raw render) or that of the training frame with the nearest frame index")
+    init = ap.add_mutually_exclusive_group()
+    init.add_argument("--thin-init-relative", type=float, default=None, help="voxel thinning at the start (off by default): of the confident pixels whose "
+                      "points share a voxel only the most confident becomes a Gaussian; the voxel's edge in multiples of the sequence's pixel "
+                      "footprint (median depth / focal)")
+    init.add_argument("--thin-init-edge", type=float, default=None, help="the same with the edge in world units")
+    ap.add_argument("--thin-opacity", default="coverage", choices=("coverage", "reference"), help="initial opacity of a survivor that stands for n pixels of F "
+                    "frames: 1 - (1 - 1/F)^n (coverage) or 1/F (reference)")
+    ap.add_argument("--prune-thin-relative", type=float, default=None, help="with a pruning schedule: every prune event also thins to one Gaussian per voxel "
+                    "(the highest effective opacity wins), the edge fixed at job start as this many pixel footprints (off by default)")
     return ap
 
 
 def main(argv=None):
     args = parser().parse_args(argv)
     pipe = job_pipe(args)
+    thin_kw = thin_kwargs(args)   # (here, not in a job: a wrong command ends the program)
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     local = int(os.environ.get("LOCAL_RANK", 0))
     from .hostpin import pin_to_ccx
@@ -504,12 +539,12 @@ def main(argv=None):
                                          out_dir=os.path.join(args.out, dirs[s]) if args.out else None, fused=args.fused,
                                          gt_mask_dir=os.path.join(args.gt_dynamic_mask, dirs[s]) if args.gt_dynamic_mask else None,
                                          dataset=args.dataset, progress=tick, checkpoint_every=args.checkpoint_every, resume=args.resume, pipe=pipe,
-                                         depth_l1_init=args.depth_l1_init, depth_l1_final=args.depth_l1_final, **prune_kwargs(args), **exposure_kwargs(args))
+                                         depth_l1_init=args.depth_l1_init, depth_l1_final=args.depth_l1_final, **prune_kwargs(args), **exposure_kwargs(args), **thin_kw)
     else:
         mine = assign(args.sequences, rank, world)
         job = lambda s: run_sequence_job(s, args.iterations, device, fused=args.fused, progress=tick, checkpoint_every=args.checkpoint_every,
                                          resume=args.resume, out_dir=os.path.join(args.out, f"seq_{s}") if args.out else None, pipe=pipe,
-                                         depth_l1_init=args.depth_l1_init, depth_l1_final=args.depth_l1_final, **prune_kwargs(args), **exposure_kwargs(args))
+                                         depth_l1_init=args.depth_l1_init, depth_l1_final=args.depth_l1_final, **prune_kwargs(args), **exposure_kwargs(args), **thin_kw)
     # (default: two in flight with the fused kernels — the measured configuration; the reference's PyTorch glue runs its backward passes in
     #  autograd's one device thread, where two jobs would queue behind each other: one at a time unless asked for)
     records = run_jobs(mine, job, args.jobs_per_gpu if args.jobs_per_gpu else (2 if (use_gpu and args.fused) else 1), device)

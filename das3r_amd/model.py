@@ -48,6 +48,10 @@ class OptimParams:   # /root/reference/arguments/__init__.py:73-90 (densificatio
     prune_until_iter: int = 0
     prune_min_opacity: float = 0.005
     prune_max_world_scale: float = 0.0
+    # voxel thinning at the prune events (das3r_amd.thin): with prune_thin_edge > 0 every event also drops the Gaussians that lose their
+    # voxel of that edge (world units; farm.py fixes it at job start from --prune-thin-relative and the sequence's pixel footprint), the
+    # score being the effective opacity.  0: off.
+    prune_thin_edge: float = 0.0
     # per-frame exposure compensation (upstream 3DGS's learned affine colour correction; not in the reference): a 3 x 4 matrix per training
     # view, [I | 0] at the start, applied to the render before the loss (losses.apply_exposure); its learning rate runs log-linear from _init
     # to _final over `iterations`.  Both 0: off — no parameter, no optimizer group.  Upstream: 0.01 -> 0.001.
@@ -133,16 +137,42 @@ class SplatModel:
             self.optimizer.set_active_sh_degree(self.active_sh_degree)
 
     # ---- initialisation from per-frame depth / confidence / dynamic maps
-    def create_from_frames(self, images, depths, confs, dyna_avg, K, cam2world, w2c_pose7, spatial_lr_scale=1.0, conf_thre=1.0):
-        """images (F,3,H,W) in [0,1]; depths/confs/dyna_avg (F,H,W); K (F,3,3); cam2world (F,4,4); w2c_pose7 (F,7)."""
+    def create_from_frames(self, images, depths, confs, dyna_avg, K, cam2world, w2c_pose7, spatial_lr_scale=1.0, conf_thre=1.0,
+                           thin_edge=None, thin_relative=None, thin_opacity="coverage"):
+        """images (F,3,H,W) in [0,1]; depths/confs/dyna_avg (F,H,W); K (F,3,3); cam2world (F,4,4); w2c_pose7 (F,7).
+        thin_edge (world units) / thin_relative (multiples of das3r_amd.thin.pixel_footprint over the confident pixels), at most one of them:
+        voxel thinning at the start (das3r_amd.thin) — of the confident pixels whose points share a voxel only the most confident becomes a
+        Gaussian, the others' bits in aggregated_mask are cleared; colours, distCUDA2 scales and rotations are built from the survivors, and
+        the opacity follows thin_opacity: "reference" = 1/F for everyone, "coverage" = 1 - (1 - 1/F)^count for a survivor that stands for
+        `count` pixels (thin.coverage_opacity; count == 1: the 1/F entry itself).  Neither given: today's initialisation, call for call;
+        self.thin_info is then None, else dict(edge, before, after, opacity), and self.thin_init None, else ("edge" | "relative", value,
+        thin_opacity) — the setting as given, which the checkpoints keep (train.thin_settings)."""
         dev = images.device
         self.spatial_lr_scale = spatial_lr_scale
         F = images.shape[0]
+        if thin_edge is not None and thin_relative is not None:
+            raise ValueError("create_from_frames: give thin_edge (world units) or thin_relative (pixel footprints), not both")
+        thinning = thin_edge is not None or thin_relative is not None
+        if thinning:
+            from . import thin
+            if thin_opacity not in thin.OPACITY_MODES:
+                raise ValueError(f"create_from_frames: thin_opacity must be one of {thin.OPACITY_MODES}, got {thin_opacity!r}")
+        self.thin_info = None
+        self.thin_init = (("edge", float(thin_edge)) if thin_edge is not None else ("relative", float(thin_relative))) + (thin_opacity,) if thinning else None
         pts = depth_to_points(K.float(), cam2world.float(), depths.float()).reshape(-1, 3)
         col = images.permute(0, 2, 3, 1).reshape(-1, 3)
         self.aggregated_mask = confs.reshape(-1) > torch.tensor(conf_thre).log()
         pts = pts[self.aggregated_mask].contiguous()
         col = col[self.aggregated_mask]
+        count = None
+        if thinning:
+            edge = float(thin_edge) if thin_edge is not None else float(thin_relative) * thin.pixel_footprint(depths, K, self.aggregated_mask)
+            keep, count, kept = thin.voxel_keep(pts, confs.reshape(-1)[self.aggregated_mask].float().contiguous(), edge=edge)
+            self.thin_info = dict(edge=edge, before=int(pts.shape[0]), after=kept, opacity=thin_opacity)
+            pixel = torch.nonzero(self.aggregated_mask, as_tuple=False).reshape(-1)[keep]
+            self.aggregated_mask = torch.zeros_like(self.aggregated_mask)
+            self.aggregated_mask[pixel] = True
+            pts, col, count = pts[keep].contiguous(), col[keep], count[keep]
         n = pts.shape[0]
         feats = torch.zeros(n, 3, (self.max_sh_degree + 1) ** 2, device=dev)
         feats[:, :3, 0] = rgb_to_sh(col)
@@ -150,7 +180,10 @@ class SplatModel:
         scales = torch.log(torch.sqrt(dist2))[..., None].repeat(1, 3)
         rots = torch.zeros(n, 4, device=dev)
         rots[:, 0] = 1
-        opac = inverse_sigmoid((1.0 / F) * torch.ones(n, 1, device=dev))
+        opac = (1.0 / F) * torch.ones(n, 1, device=dev)
+        if count is not None and thin_opacity == "coverage":
+            opac = thin.coverage_opacity(count, opac, F)
+        opac = inverse_sigmoid(opac)
         self._xyz = nn.Parameter(pts.requires_grad_(True))
         self._features_dc = nn.Parameter(feats[:, :, 0:1].transpose(1, 2).contiguous())
         self._features_rest = nn.Parameter(feats[:, :, 1:].transpose(1, 2).contiguous())

@@ -228,7 +228,7 @@ def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=
 
 
 def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=False, optimised_poses=False, device="cuda", write=True, fused=False,
-                depth=False, pipe=PIPE, prune_min_opacity=0.0, write_pruned_ply=False, exposure="none", static_map=False, alpha=False):
+                depth=False, pipe=PIPE, prune_min_opacity=0.0, write_pruned_ply=False, exposure="none", static_map=False, alpha=False, thin_edge=None, thin_relative=None):
     """render.py:89-123: load the trained model, write pose_interpolated.npy, render the "interp" set.  seq: the sequence the model was
     trained on (its cameras).  depth: also the inverse-depth images (invdepth/%05d.npy) and, per view, the median relative error of
     1 / invdepth against the sequence's depth map (printed: a diagnostic).  pipe: PIPE, or pipe_from_args' (pipe.antialiasing: a model
@@ -237,16 +237,32 @@ def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=Fal
     compacted model is saved as point_cloud/iteration_N/point_cloud_pruned.ply.  exposure: "none" (the default: today's output) or "train" —
     <model_path>/exposure.json (a job that trained with per-frame exposure compensation writes it) is loaded and every view whose frame
     name it holds, i.e. every training view, is written compensated; the others stay raw.  static_map / alpha: also every view's
-    static-confidence map and coverage map (render_set: static/%05d.npy, alpha/%05d.npy).  -> (iteration, list of rendered images)"""
+    static-confidence map and coverage map (render_set: static/%05d.npy, alpha/%05d.npy).  thin_edge (world units) / thin_relative (multiples of
+    the pixel footprint of `seq`'s depth maps and intrinsics: das3r_amd.thin.pixel_footprint over its confident pixels), at most one: the loaded
+    model is thinned to one Gaussian per voxel first (das3r_amd.thin.thin_model, after prune_min_opacity's event when both are given);
+    write_pruned_ply then saves the thinned model.  -> (iteration, list of rendered images)"""
     if exposure not in ("none", "train"):
         raise ValueError(f'render_sets: exposure must be "none" or "train", got {exposure!r}')
+    if thin_edge is not None and thin_relative is not None:
+        raise ValueError("render_sets: give thin_edge (world units) or thin_relative (pixel footprints), not both")
     model, iteration = load_trained_model(model_path, iteration, sh_degree, device)
     if prune_min_opacity > 0:
-        from .prune import prune_points, write_pruned_ply as save_pruned
+        from .prune import prune_points
         info = prune_points(model, min_opacity=prune_min_opacity)
         print(f"pruned {info['dropped']} of {info['before']} Gaussians below opacity {prune_min_opacity:g}")
-        if write_pruned_ply:
-            save_pruned(os.path.join(model_path, "point_cloud", f"iteration_{iteration}", "point_cloud_pruned.ply"), model)
+    if thin_edge is not None or thin_relative is not None:
+        from .thin import pixel_footprint, thin_model
+        edge = thin_edge
+        if edge is None:
+            if seq.get("depths") is None:
+                raise ValueError("render_sets(thin_relative=...): the sequence has no depth maps to take the pixel footprint from; give thin_edge")
+            confs = seq.get("confs")
+            edge = float(thin_relative) * pixel_footprint(seq["depths"], seq["K"], None if confs is None else confs > 0.0)
+        info = thin_model(model, edge)
+        print(f"thinned {info['dropped']} of {info['before']} Gaussians to one per voxel of edge {info['edge']:g}")
+    if write_pruned_ply and (prune_min_opacity > 0 or thin_edge is not None or thin_relative is not None):
+        from .prune import write_pruned_ply as save_pruned
+        save_pruned(os.path.join(model_path, "point_cloud", f"iteration_{iteration}", "point_cloud_pruned.ply"), model)
     inter = save_interpolate_pose(model_path, iteration)
     bg = torch.tensor([1.0, 1.0, 1.0] if white_background else [0.0, 0.0, 0.0], dtype=torch.float32, device=device)
     views = sequence_cameras(seq, device)
@@ -320,7 +336,12 @@ def parser():
                                                                 "render a model trained with it (farm --antialiasing) this way")
     ap.add_argument("--prune-min-opacity", type=float, default=0.0, help="compact the loaded model before rendering: drop the Gaussians with "
                     "sigmoid(opacity) * conf_static below this (0: off; at or below 1/255 = 0.0039 the renders do not change)")
-    ap.add_argument("--write-pruned-ply", action="store_true", help="with --prune-min-opacity: save the compacted model as "
+    thin = ap.add_mutually_exclusive_group()
+    thin.add_argument("--thin-edge", type=float, default=None, help="thin the loaded model to one Gaussian per voxel of this edge (world units) before "
+                      "rendering: the highest sigmoid(opacity) * conf_static of a voxel stays (after --prune-min-opacity's event when both are given)")
+    thin.add_argument("--thin-relative", type=float, default=None, help="the same with the edge in multiples of the pixel footprint (median depth / focal) "
+                      "of the sequence given with -s")
+    ap.add_argument("--write-pruned-ply", action="store_true", help="with --prune-min-opacity, --thin-edge or --thin-relative: save the compacted model as "
                     "point_cloud/iteration_N/point_cloud_pruned.ply")
     ap.add_argument("--exposure", default="none", choices=("none", "train"), help='"train": write the training views compensated with the matrices '
                     "of <model-path>/exposure.json (a job trained with --exposure-lr-init / --exposure-lr-final); none: the raw renders")
@@ -337,7 +358,9 @@ def main(argv=None):
     seq = load_sequence(args.source_path, device="cuda", dataset=args.dataset)
     it, imgs = render_sets(args.model_path, seq, args.iteration, args.sh_degree, args.white_background, args.optimised_poses, fused=args.fused,
                            depth=args.depth, pipe=pipe_from_args(args), prune_min_opacity=args.prune_min_opacity, write_pruned_ply=args.write_pruned_ply,
-                           exposure=args.exposure, static_map=args.static_map, alpha=args.alpha)
+                           exposure=args.exposure, static_map=args.static_map, alpha=args.alpha,
+                           **({"thin_edge": args.thin_edge, "thin_relative": args.thin_relative}
+                              if (args.thin_edge is not None or args.thin_relative is not None) else {}))
     print(f"wrote {len(imgs)} images to {os.path.join(args.model_path, 'interp', f'ours_{it}', 'renders')}")
 
 

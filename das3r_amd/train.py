@@ -155,6 +155,26 @@ def prune_due(schedule, iteration):
     return schedule is not None and schedule[0] <= iteration <= schedule[2] and iteration % schedule[1] == 0
 
 
+def thin_settings(model, opt):
+    """The voxel-thinning settings of a job as the tuple the checkpoints keep — (how the model was thinned at the start: model.thin_init, or
+    None; the edge the prune events thin with: opt.prune_thin_edge, 0.0 = off) — or None when both are off."""
+    init = getattr(model, "thin_init", None)
+    init = None if init is None else (str(init[0]), float(init[1]), str(init[2]))
+    edge = float(getattr(opt, "prune_thin_edge", 0.0) or 0.0)
+    return None if (init is None and edge <= 0.0) else (init, edge)
+
+
+def sequence_footprint(seq, heldout=True, conf_thre=1.0):
+    """das3r_amd.thin.pixel_footprint over the confident pixels of the TRAINING frames build_from_sequence(heldout=...) builds the model from."""
+    from .thin import pixel_footprint
+    F = seq["images"].shape[0]
+    tr, te = split_sequence(seq) if heldout else (list(range(F)), [])
+    if heldout and not te:
+        tr = list(range(F - 1))
+    sel = torch.tensor(tr, device=seq["images"].device)
+    return pixel_footprint(seq["depths"][sel], seq["K"][sel], seq["confs"][sel] > torch.tensor(conf_thre).log())
+
+
 class ResumeMismatch(ValueError):
     """A checkpoint is resumed with settings that would silently change the job's schedule."""
 
@@ -219,7 +239,8 @@ def train(model, cameras, opt: OptimParams, iterations, pipe=None, background=No
     ResumeMismatch.  The same holds for the pruning schedule (opt.prune_*: prune_schedule above) — an event (das3r_amd.prune.prune_points)
     follows the optimizer steps of every iteration the schedule names, in all three step forms.  And for the rates of per-frame exposure
     compensation (opt.exposure_lr_init / _final; the matrices themselves travel in the model's extras, their moments in the optimizer's
-    state).  exposure_heldout: the held-out pose pass's exposure policy (heldout_exposure).
+    state).  And for voxel thinning (thin_settings: how the model was thinned at the start, and opt.prune_thin_edge, with which every prune
+    event also passes das3r_amd.thin.voxel_keep's losers as also_drop).  exposure_heldout: the held-out pose pass's exposure policy (heldout_exposure).
     start_iteration / loop_state: continue a job from load_checkpoint's result — the iterations that follow are the ones the
     uninterrupted job would have run (same cameras in the same order, same schedules, same optimizer moments)."""
     pipe = pipe or SimpleNamespace(debug=False, compute_cov3D_python=False, convert_SHs_python=False)
@@ -230,8 +251,17 @@ def train(model, cameras, opt: OptimParams, iterations, pipe=None, background=No
     depth_l1 = (float(getattr(opt, "depth_l1_weight_init", 0.0)), float(getattr(opt, "depth_l1_weight_final", 0.0)))
     pruning = prune_schedule(opt)
     exposure = exposure_rates(opt)
+    thinning = thin_settings(model, opt)
+    if thinning is not None and thinning[1] > 0.0 and pruning is None:
+        raise ValueError("train: opt.prune_thin_edge thins at the prune events, and the pruning schedule is off (opt.prune_interval)")
     if loop_state is not None:
         check_exposure_resume(loop_state, opt)
+        was_thin = loop_state.get("thin")   # (a checkpoint from before voxel thinning: off)
+        was_thin = None if was_thin is None else (None if was_thin[0] is None else tuple(was_thin[0]), float(was_thin[1]))
+        if was_thin != thinning:
+            raise ResumeMismatch(f"this checkpoint was written by a job with the voxel-thinning settings {was_thin} ((how the model was thinned at "
+                                 f"the start, the prune events' edge); None: off); it is being resumed with {thinning}, which would change the "
+                                 "model mid-run: resume with the same --thin-init-* / --thin-opacity / --prune-thin-relative settings")
         was_pruning = loop_state.get("prune")   # (a checkpoint from before pruning: off)
         was_pruning = None if was_pruning is None else tuple(was_pruning)
         if was_pruning != pruning:
@@ -261,7 +291,12 @@ def train(model, cameras, opt: OptimParams, iterations, pipe=None, background=No
         loss, p, _ = train_step(model, cam, opt, it, pipe, background, fused=fused)
         if prune_due(pruning, it):
             from .prune import prune_points
-            prune_points(model, min_opacity=pruning[3], max_world_scale=pruning[4])
+            if thinning is not None and thinning[1] > 0.0:   # the event also drops the Gaussians that lose their voxel
+                from .thin import default_score, voxel_keep
+                keep_v, _, _ = voxel_keep(model._xyz.detach(), default_score(model), edge=thinning[1])
+                prune_points(model, min_opacity=pruning[3], max_world_scale=pruning[4], also_drop=~keep_v)
+            else:
+                prune_points(model, min_opacity=pruning[3], max_world_scale=pruning[4])
         if not stack and test_cameras and model.enable_test:
             test_pose_pass(model, test_cameras, gt_dynamic_masks, opt, pipe, background, rng, fused=fused,
                            **({"exposure": exposure_heldout} if exposure_heldout != "identity" else {}))
@@ -280,7 +315,7 @@ def train(model, cameras, opt: OptimParams, iterations, pipe=None, background=No
                     library = _lib.learning()
             save_checkpoint(os.path.join(checkpoint_dir, f"chkpnt{it}.pth"), model, it,
                             dict(rng=rng.getstate(), stack=[c.uid for c in stack], ema=ema.detach().clone(), last_psnr=last_psnr.detach().clone(),
-                                 library=library, depth_l1=depth_l1, prune=pruning, exposure=exposure))
+                                 library=library, depth_l1=depth_l1, prune=pruning, exposure=exposure, **({"thin": thinning} if thinning is not None else {})))
     if dev.type == "cuda":
         torch.cuda.current_stream(dev).synchronize()
     done = max(iterations - start_iteration + 1, 1)
@@ -597,8 +632,9 @@ def split_sequence(seq):
     return [i for i in range(F) if not is_test_index(i)], test
 
 
-def build_from_sequence(seq, sh_degree=3, heldout=False, depth_targets=False):
-    """depth_targets: the TRAINING cameras carry their frame's depth map as the depth term's target (make_camera(depth=...)); held-out
+def build_from_sequence(seq, sh_degree=3, heldout=False, depth_targets=False, thin_edge=None, thin_relative=None, thin_opacity="coverage"):
+    """thin_edge / thin_relative / thin_opacity: voxel thinning at the start (SplatModel.create_from_frames; off by default).
+    depth_targets: the TRAINING cameras carry their frame's depth map as the depth term's target (make_camera(depth=...)); held-out
     cameras never do.
     -> (model, cameras) from every frame, or with heldout=True -> (model, train cameras, test cameras): Gaussians, training
     poses and conf_static come from the TRAINING frames only (the reference builds them from scene.train_cameras:
@@ -611,7 +647,9 @@ def build_from_sequence(seq, sh_degree=3, heldout=False, depth_targets=False):
         tr, te = list(range(F - 1)), [F - 1]
     sel = torch.tensor(tr, device=dev)
     model = SplatModel(sh_degree).create_from_frames(seq["images"][sel], seq["depths"][sel], seq["confs"][sel], seq["dyna_avg"][sel],
-                                                     seq["K"][sel], seq["cam2world"][sel], seq["w2c_pose7"][sel])
+                                                     seq["K"][sel], seq["cam2world"][sel], seq["w2c_pose7"][sel],
+                                                     **(dict(thin_edge=thin_edge, thin_relative=thin_relative, thin_opacity=thin_opacity)
+                                                        if (thin_edge is not None or thin_relative is not None) else {}))
     K = seq["K"]   # per-frame focals (cameras.txt: scene/dataset_readers.py:139-147); principal point at the image centre
     mk = lambda uid, i, depth=None: make_camera(uid, seq["images"][i], float(K[i, 0, 0]), seq["W"], seq["H"], dev, focal_y=float(K[i, 1, 1]),
                                                 camera_center=seq["cam2world"][i][:3, 3], depth=depth)

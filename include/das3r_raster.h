@@ -421,6 +421,32 @@ int das3r_prune_select(int32_t P, const float *opacity_raw, const float *conf_fl
 int das3r_prune_compact(int32_t P, int32_t kept, const int32_t *dst_index, int32_t n, const das3r_prune_tensor *tensors,
                         das3r_stream_t stream);
 
+/* ---- voxel thinning: one Gaussian per cell of a voxel grid (opt-in) ------------------------------------------------------------
+ * Additive symbols under ABI 16 (csrc/thin.hip; the same rule in torch: das3r_amd/thin.py voxel_keep_torch, which the tests hold the kernels
+ * to bit for bit).  DAS3R starts with one Gaussian per confident pixel of every frame: a static surface seen in F frames is about F coincident
+ * Gaussians.  das3r_thin_voxels decides which of them stay; the surgery is das3r_prune_select(also_drop) + das3r_prune_compact.
+ *
+ * Cell of point i:  c_k = floorf(xyz[3 i + k] * inv_edge), k = 0, 1, 2 — ONE fp32 multiply per axis, no division, no offset, nothing
+ * contracted; inv_edge = fp32(1 / edge) is computed once by the host.  The point is PLACEABLE iff the three products are finite and every
+ * c_k lies in [-2^20, 2^20); its key is the 63-bit pack (c_0 + 2^20) << 42 | (c_1 + 2^20) << 21 | (c_2 + 2^20).  A point that is not
+ * placeable never merges with anything.
+ * Winner of a cell: the placeable point with the highest score[i]; equal scores (-0 equals +0) go to the lower index; a NaN score loses
+ * to every number, among NaNs the lower index wins.  score NULL: all scores equal, the lowest index of the cell wins.
+ *   keep[i]   1 for a winner and for a point that is not placeable, else 0
+ *   count[i]  the cell's population for a winner, 1 for a point that is not placeable, 0 for a dropped point
+ *   info[0]   the number kept;  info[1]  0, or 1 when the table was exhausted (impossible at the workspace size below: load factor <= 1/2;
+ *             a point that found no slot is then treated as not placeable)
+ * Nothing in the result depends on launch geometry, scheduling or the hash: two runs are bit-identical.
+ * workspace: das3r_thin_workspace_bytes(P) bytes, 8-byte aligned, need not be initialised: an open-addressing table of S slots, S the power
+ * of two >= max(2 P, 64), 20 bytes per slot (64-bit key, 64-bit best word, 32-bit population) + 4 bytes per point = 44 - 84 bytes per point;
+ * at 7.37 M points S = 2^24: 49.5 bytes per point.  Launches on `stream`: the memsets, an insert pass, a resolve pass (a thread per point
+ * each; bounded probing, no thread waits for another, integer vector atomics only).  P == 0: nothing is launched, info = {0, 0}.
+ * P < 0 or > 2^30 (das3r_thin_workspace_bytes: 0), a NULL pointer other than score, or inv_edge not finite or <= 0: DAS3R_ERR_INVALID_ARG with a
+ * das3r_last_error() message. */
+size_t das3r_thin_workspace_bytes(int32_t P);
+int das3r_thin_voxels(int32_t P, const float *xyz, const float *score /* or NULL */, float inv_edge, uint8_t *keep, int32_t *count,
+                      int32_t *info /* [2] */, char *workspace, das3r_stream_t stream);
+
 /* ---- extra per-Gaussian channels over a forward's lists (opt-in) --------------------------------------------------------------
  * Additive symbols under ABI 16.  das3r_raster_aux_forward blends a caller's rows features[P][C] exactly as the forward blended its colours,
  *     out[c][pixel] = sum_k features[g_k][c] alpha_k T_k        over the splats g_k the pixel's colour was blended from (same order, same

@@ -43,18 +43,27 @@ __global__ void __launch_bounds__(256) adam_kernel(const AdamTable T, float beta
     float gate_bc1 = 1.f, gate_bc2_sqrt = 1.f;
     if (GATED) {
         const bool go = gate[0] > threshold;
-        const float t = (float)(state[0] + 1);
+        const int32_t t = state[0] + 1;
         __syncthreads();   // (every thread has read the count)
         if (threadIdx.x == 0) {
             const int32_t before = __hip_atomic_fetch_add(&state[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (before == (int32_t)gridDim.x - 1) {
-                if (go) state[0] = (int32_t)t;
+                if (go) state[0] = t;
                 __hip_atomic_store(&state[1], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
         if (!go) return;
-        gate_bc1 = 1.f - powf(beta1, t);
-        gate_bc2_sqrt = sqrtf(1.f - powf(beta2, t));
+        // 1 - beta^t in double, rounded once: in fp32 the subtraction cancels (beta2 = 0.999, t = 2: three digits, one ulp of powf became
+        // 4e-6 of sqrt(bc2) and of the update — tests/test_gpu_adam_edges.py); the plain step gets both corrections from the host in double.
+        // beta^t by squaring: at most 31 rounds of three fp64 products (each 2^-53: ~1e-14 of beta^t at the end), uniform over the grid.
+        double p1 = 1.0, p2 = 1.0, b1 = (double)beta1, b2 = (double)beta2;
+#pragma unroll 1
+        for (uint32_t k = (uint32_t)(t > 0 ? t : 0); k != 0u; k >>= 1) {
+            if (k & 1u) { p1 *= b1; p2 *= b2; }
+            b1 *= b1; b2 *= b2;
+        }
+        gate_bc1 = (float)(1.0 - p1);
+        gate_bc2_sqrt = sqrtf((float)(1.0 - p2));
     }
     int t = 0;
 #pragma unroll 1

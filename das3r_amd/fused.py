@@ -289,6 +289,9 @@ class FusedAdam:
         lib = _lib.load()
         b1, b2 = self.betas
         entries, keep, dev = [], [], None
+        if gate is not None and sum(p.grad is not None or getattr(p, "_das3r_compact_grad", None) is not None
+                                    for g in self.param_groups for p in g["params"]) > 16:
+            raise RuntimeError("FusedAdam.step(gate=...): at most 16 tensors")   # (before any step is counted or gradient consumed)
         for g in self.param_groups:
             for p in g["params"]:
                 compact = getattr(p, "_das3r_compact_grad", None)   # (_ShPrefix: gradient of the active prefix)
@@ -385,8 +388,6 @@ class FusedAdam:
                 if gate is None:
                     rc = lib.das3r_adam_step(len(chunk), arr, C.c_float(b1), C.c_float(b2), C.c_float(self.eps), _stream(dev))
                 else:
-                    if len(entries) > 16:
-                        raise RuntimeError("FusedAdam.step(gate=...): at most 16 tensors")
                     if self._gate_state is None:
                         self._gate_state = torch.zeros(2, dtype=torch.int32, device=dev)
                     gt = gate.detach().reshape(1).float().contiguous()

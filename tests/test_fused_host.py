@@ -38,6 +38,22 @@ def test_step_passes_parameters_without_gradient_by_and_counts_nothing_for_them(
     assert opt.handles_compact_sh(rest) and not opt.handles_compact_sh(a)
 
 
+def test_gated_step_refuses_seventeen_tensors_before_it_counts_a_step():
+    """step(gate=...) is one launch of at most 16 tensors (the device-side step count is one per launch): seventeen are refused before a
+    step is counted or a compact gradient consumed — sixteen get as far as the device check."""
+    tensors = [torch.zeros(3 + i) for i in range(17)]
+    opt = _opt(*tensors)
+    for k, t in enumerate(tensors):
+        opt.state[t] = dict(step=k, exp_avg=torch.zeros_like(t), exp_avg_sq=torch.zeros_like(t))
+        t.grad = torch.ones_like(t)
+    with pytest.raises(RuntimeError, match="at most 16"):
+        opt.step(gate=torch.tensor(30.0), threshold=26.0)
+    assert [opt.state[t]["step"] for t in tensors] == list(range(17)) and opt._gate_state is None
+    tensors[16].grad = None
+    with pytest.raises(RuntimeError, match="HIP device"):
+        opt.step(gate=torch.tensor(30.0), threshold=26.0)
+
+
 def test_direct_iteration_is_only_taken_with_fused_optimizers_and_the_default_pipe(monkeypatch):
     from das3r_amd import fast_step
     pipe = SimpleNamespace(debug=False, compute_cov3D_python=False, convert_SHs_python=False)

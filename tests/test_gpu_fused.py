@@ -13,6 +13,60 @@ FWD_TOL = 4e-6        # relative to max(1, max|value|): same fp32 formulas, diff
 GRAD_TOL = 2e-5       # relative to the gradient's max magnitude (per-Gaussian grads)
 POSE_GRAD_TOL = 5e-4  # 28 sums over P terms accumulated in a different order
 ADAM_TOL = 1e-6       # relative to the parameter's max magnitude after 6 steps
+# The same comparison relative to the MOVEMENT max|p_after - p_before| of each tensor (ADAM_TOL is relative to |p|: with |p| ~ 3 and a pose
+# learning rate of 3e-5 it allows 5 % of four steps' movement).  Provenance: 4 x the worst deviation, over the tensors of a test, of
+# torch.optim.Adam in fp32 on the GPU from torch.optim.Adam in float64 on the CPU fed the same gradients, relative to that movement — each
+# test measures and prints it (_Adam64.check); FusedAdam plays no part in the numbers.  Measured on an MI355X, worst tensor of each test:
+ADAM_MOVE_TOL = dict(groups=3.2e-3,      # 4 x 7.93e-4 (f_rest at degree 3; 7.79e-4 .. 7.93e-4 over the degrees)
+                     single_sh=3.5e-3,   # 4 x 8.75e-4 (rest, degree 3)
+                     gate=5.8e-3,        # 4 x 1.45e-3 (pose_Q)
+                     gate_many=1.2e-2,   # 4 x 2.92e-3 (pose_T)
+                     compact=3.3e-3)     # 4 x 8.13e-4 (rest)
+# Moments against torch's (fp32, GPU).  FusedAdam hands the kernel the betas as fp32 and the kernel forms 1 - beta from those:
+# 1 - 0.9f = 0.100000024 where torch multiplies by 0.1f, 1 - 0.999f = 0.00099998713 where torch multiplies by 0.001f.
+#   exp_avg_sq, element-wise relative: 1.29e-5 (the ratio of the two 1 - beta2) + 3 roundings per step on either side over at most
+#   9 steps (2 x 9 x 3 x 2^-24 = 3.2e-6) = 1.61e-5
+#   exp_avg, relative to max|exp_avg|: per step 2.3e-7 of the increment plus 2 roundings on either side, (2.3e-7 + 4 x 2^-24) of
+#   |m| + |increment| <= ~2 max|m|; the errors of earlier steps decay with beta1, a geometric sum of at most 1 / (1 - beta1) = 10 terms:
+#   10 x 4.7e-7 x 2 = 9.4e-6 in the worst case
+ADAM_V_TOL = 1.7e-5
+ADAM_M_TOL = 1e-5
+
+
+class _Adam64:
+    """torch.optim.Adam in float64 on the CPU beside a test's two optimizers, fed the same gradients: the reference the movement bar is
+    measured against."""
+
+    def __init__(self, init, lrs):
+        self.init = {k: v.detach().double().cpu() for k, v in init.items()}
+        self.p = {k: torch.nn.Parameter(v.clone()) for k, v in self.init.items()}
+        self.opt = torch.optim.Adam([dict(params=[self.p[k]], lr=lrs[k]) for k in self.p], lr=0.0, eps=1e-15)
+
+    def step(self, grads, lr0=None):
+        for k, g in grads.items():
+            self.p[k].grad = g.detach().double().cpu()
+        if lr0 is not None:
+            self.opt.param_groups[0]["lr"] = lr0
+        self.opt.step()
+
+    def check(self, what, fused, torch32, moments):
+        """fused, torch32: {name: parameter}; moments: {name: ((exp_avg, exp_avg_sq) of FusedAdam, full shape; the state of torch's)}."""
+        worst = 0.0
+        for k in self.p:
+            p64, a, b = self.p[k].detach(), fused[k].detach().double().cpu(), torch32[k].detach().double().cpu()
+            move = float((p64 - self.init[k]).abs().max())
+            if move == 0:   # (SH coefficients above the active degree only: nothing steps)
+                assert torch.equal(a, self.init[k]) and torch.equal(b, self.init[k]), k
+                continue
+            dev32, dev = float((b - p64).abs().max()) / move, float((a - b).abs().max()) / move
+            worst = max(worst, dev32)
+            print(f"[{what} {k}] movement {move:.3e}; fp32 torch from float64: {dev32:.3e} of it; FusedAdam from fp32 torch: {dev:.3e} of it")
+            assert dev <= ADAM_MOVE_TOL[what], (what, k, dev)
+            (ma, va), st = moments[k]
+            mb, vb = st["exp_avg"], st["exp_avg_sq"]
+            assert float((ma - mb).abs().max()) <= ADAM_M_TOL * float(mb.abs().max()), (what, k, "exp_avg")
+            assert bool(((va - vb).abs() <= ADAM_V_TOL * vb).all()), (what, k, "exp_avg_sq", float(((va - vb).abs() / vb.clamp_min(1e-30)).max()))
+        print(f"[{what}] worst fp32-torch deviation {worst:.3e} of the movement; 4 x -> {4 * worst:.3e}")
 
 
 def _torch_pretransform(xyz, rot, scaling, opacity_raw, conf, mask, pose):
@@ -155,6 +209,7 @@ def test_fused_adam_matches_torch_adam(degree):
     for gdict in groups_b:
         gdict.pop("sh_rest", None)
     ta = torch.optim.Adam(groups_b, lr=0.0, eps=1e-15)
+    t64 = _Adam64(init, lrs)
     active = (degree + 1) ** 2 - 1
     g = torch.Generator().manual_seed(5)
     for step in range(6):
@@ -166,12 +221,14 @@ def test_fused_adam_matches_torch_adam(degree):
         if step == 3:                           # schedules change lr between steps
             for opt in (fa, ta):
                 opt.param_groups[0]["lr"] = 3.3e-5
+        t64.step({k: pa[k].grad for k in pa}, 3.3e-5 if step >= 3 else None)
         fa.step()
         ta.step()
         fa.zero_grad(set_to_none=True)
         ta.zero_grad(set_to_none=True)
     for k in pa:
         assert float((pa[k] - pb[k]).abs().max()) <= ADAM_TOL * float(pb[k].abs().max()), k
+    t64.check("groups", pa, pb, {k: (tuple(fa._full_moment(fa.state[pa[k]][key], pa[k]) for key in ("exp_avg", "exp_avg_sq")), ta.state[pb[k]]) for k in pa})
     assert torch.equal(pa["f_rest"][:, active:, :], init["f_rest"][:, active:, :])     # untouched, exactly
     st = fa.state[pa["f_rest"]]
     assert st["exp_avg"].shape[1] == active   # (round 6: the moments of an "sh_rest" tensor are kept for the active coefficients only)
@@ -251,15 +308,20 @@ def test_fused_adam_single_sh_tensor_matches_two_torch_groups(degree):
     fa = FusedAdam([dict(params=[pa], lr=2.5e-3, lr_rest=1.25e-4, name="f_dc", sh_all=True)], lr=0.0, eps=1e-15)
     fa.set_active_sh_degree(degree)
     ta = torch.optim.Adam([dict(params=[dc], lr=2.5e-3), dict(params=[rest], lr=1.25e-4)], lr=0.0, eps=1e-15)
+    t64 = _Adam64(dict(dc=full[:, :1], rest=full[:, 1:]), dict(dc=2.5e-3, rest=1.25e-4))
     active = (degree + 1) ** 2
     for step in range(5):
         gr = torch.randn(P, 16, 3, generator=g).cuda() * (10.0 ** (step - 2))
         gr[:, active:, :] = 0
         pa.grad, dc.grad, rest.grad = gr.clone(), gr[:, :1].clone(), gr[:, 1:].clone()
+        t64.step(dict(dc=dc.grad, rest=rest.grad))
         fa.step()
         ta.step()
     ref = torch.cat((dc, rest), 1).detach()
     assert float((pa.detach() - ref).abs().max()) <= ADAM_TOL * float(ref.abs().max())
+    sa = fa.state[pa]
+    t64.check("single_sh", dict(dc=pa[:, :1], rest=pa[:, 1:]), dict(dc=dc, rest=rest),
+              dict(dc=((sa["exp_avg"][:, :1], sa["exp_avg_sq"][:, :1]), ta.state[dc]), rest=((sa["exp_avg"][:, 1:], sa["exp_avg_sq"][:, 1:]), ta.state[rest])))
     assert torch.equal(pa.detach()[:, active:, :], full[:, active:, :])
 
 
@@ -274,6 +336,7 @@ def test_fused_adam_device_gate_matches_host_gated_torch_adam():
     fa = FusedAdam([dict(params=[qa], lr=3e-5, name="pose_Q"), dict(params=[ta], lr=3e-5, name="pose_T")], lr=0.0, eps=1e-15)
     tb_opt = torch.optim.Adam([dict(params=[qb], lr=3e-5), dict(params=[tb], lr=3e-5)], lr=0.0, eps=1e-15)
     gates = [20.0, 27.5, 26.0, 31.0, 12.0, 26.01, 40.0]     # threshold 26: open on steps 1, 3, 5, 6 (strictly greater)
+    t64 = _Adam64(dict(q=q0, t=t0), dict(q=3e-5, t=3e-5))
     for step, gv in enumerate(gates):
         gq, gt = torch.randn(7, 4, generator=g).cuda(), torch.randn(7, 3, generator=g).cuda()
         qa.grad, ta.grad, qb.grad, tb.grad = gq.clone(), gt.clone(), gq.clone(), gt.clone()
@@ -282,8 +345,10 @@ def test_fused_adam_device_gate_matches_host_gated_torch_adam():
         fa.step(gate=torch.tensor(gv, device="cuda"), threshold=26.0)
         if gv > 26.0:
             tb_opt.step()
+            t64.step(dict(q=gq, t=gt), 1e-5 if step >= 4 else None)
     assert int(fa._gate_state[0]) == 4
     assert float((qa - qb).abs().max()) <= 2e-6 * float(qb.abs().max()) and float((ta - tb).abs().max()) <= 2e-6 * float(tb.abs().max())
+    t64.check("gate", dict(q=qa, t=ta), dict(q=qb, t=tb), {k: ((fa.state[a]["exp_avg"], fa.state[a]["exp_avg_sq"]), tb_opt.state[b]) for k, a, b in (("q", qa, qb), ("t", ta, tb))})
     assert not torch.equal(qa.detach(), q0)
 
 
@@ -304,12 +369,14 @@ def test_compact_sh_gradient_accumulates_like_dot_grad():
     fa.set_active_sh_degree(degree)
     assert fa.handles_compact_sh(resta) and not fa.handles_compact_sh(dca)
     tb = torch.optim.Adam([dict(params=[dcb], lr=2.5e-3), dict(params=[restb], lr=1.25e-4)], lr=0.0, eps=1e-15)
+    t64 = _Adam64(dict(dc=dc0, rest=rest0), dict(dc=2.5e-3, rest=1.25e-4))
     for step in range(3):
         for w in (w1, w2 * (step + 1)):
             (active_sh_prefix(dca, resta, degree) * w).sum().backward()
             (torch.cat((dcb, restb), 1)[:, :K] * w).sum().backward()
         assert resta.grad is None and tuple(resta._das3r_compact_grad.shape) == (P, K - 1, 3)
         assert torch.allclose(resta._das3r_compact_grad, restb.grad[:, :K - 1], rtol=1e-6, atol=1e-7)
+        t64.step(dict(dc=dcb.grad, rest=restb.grad))
         fa.step()
         tb.step()
         assert getattr(resta, "_das3r_compact_grad", None) is None     # consumed: a stale gradient cannot be applied twice
@@ -317,6 +384,8 @@ def test_compact_sh_gradient_accumulates_like_dot_grad():
         tb.zero_grad(set_to_none=True)
     assert float((resta - restb).abs().max()) <= ADAM_TOL * float(restb.abs().max())
     assert float((dca - dcb).abs().max()) <= ADAM_TOL * float(dcb.abs().max())
+    t64.check("compact", dict(dc=dca, rest=resta), dict(dc=dcb, rest=restb),
+              {k: (tuple(fa._full_moment(fa.state[a][key], a) for key in ("exp_avg", "exp_avg_sq")), tb.state[b]) for k, a, b in (("dc", dca, dcb), ("rest", resta, restb))})
     assert torch.equal(resta.detach()[:, K - 1:], rest0[:, K - 1:])
     # a parked gradient of another width (degree changed without a step) is refused, not silently replaced
     (active_sh_prefix(dca, resta, 1) * w1).sum().backward()
@@ -415,15 +484,18 @@ def test_fused_adam_device_gate_with_many_workgroups():
     fa = FusedAdam([dict(params=[qa], lr=3e-5, name="pose_Q"), dict(params=[ta], lr=3e-5, name="pose_T")], lr=0.0, eps=1e-15)
     tb_opt = torch.optim.Adam([dict(params=[qb], lr=3e-5), dict(params=[tb], lr=3e-5)], lr=0.0, eps=1e-15)
     opened = 0
+    t64 = _Adam64(dict(q=q0, t=t0), dict(q=3e-5, t=3e-5))
     for step, gv in enumerate([30.0, 10.0, 26.5, 26.0, 27.0, 5.0, 5.0, 41.0, 28.0]):
         gq, gt = torch.randn(1500, 4, generator=g).cuda(), torch.randn(1500, 3, generator=g).cuda()
         qa.grad, ta.grad, qb.grad, tb.grad = gq.clone(), gt.clone(), gq.clone(), gt.clone()
         fa.step(gate=torch.tensor(gv, device="cuda"), threshold=26.0)
         if gv > 26.0:
             tb_opt.step()
+            t64.step(dict(q=gq, t=gt))
             opened += 1
         assert fa._gate_state.tolist() == [opened, 0], (step, fa._gate_state.tolist())
     assert float((qa - qb).abs().max()) <= 2e-6 * float(qb.abs().max()) and float((ta - tb).abs().max()) <= 2e-6 * float(tb.abs().max())
+    t64.check("gate_many", dict(q=qa, t=ta), dict(q=qb, t=tb), {k: ((fa.state[a]["exp_avg"], fa.state[a]["exp_avg_sq"]), tb_opt.state[b]) for k, a, b in (("q", qa, qb), ("t", ta, tb))})
 
 
 @pytest.mark.parametrize("hw", [(37, 53), (208, 512)])

@@ -3,7 +3,8 @@
     DAS3R_TOL_REPORT=$PWD/gpurun_out/tol.jsonl python -m pytest tests -m gpu -q ; python tools/tol_report.py gpurun_out/tol.jsonl
 tests/util.py appends one line per gradient check: the measured max-norm error and its bar, the number of elements beyond the bar
 (threshold flips at full size), and the fraction of elements that would miss element-wise bars 1x / 10x / 100x tighter;
-tests/loss_reference.py one line per budget check: the worst |got - float64| / budget of an output beside its multiplier K."""
+tests/loss_reference.py (and tests/adam_reference.py through it) one line per budget check: the worst |got - float64| / budget of an
+output beside its multiplier K."""
 import collections
 import json
 import re

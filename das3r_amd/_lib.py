@@ -66,6 +66,27 @@ class PruneTensor(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int64)]
 
 
+class PathPolicyState(C.Structure):
+    """include/das3r_raster.h das3r_path_policy_state: what the forwards of a shape have learnt (csrc/path_policy.h Verdict + Resume)."""
+    _fields_ = [("P", C.c_int32), ("W", C.c_int32), ("H", C.c_int32), ("last_I", C.c_int64), ("peak_I", C.c_int64), ("radix_left", C.c_int32),
+                ("backoff", C.c_int32), ("gen", C.c_uint32), ("seg_extra", C.c_int32), ("last_seg", C.c_int32), ("fine", C.c_int32),
+                ("forwards", C.c_uint32), ("clean", C.c_uint32), ("longest", C.c_uint32), ("resume_valid", C.c_int32), ("resume_fine", C.c_int32),
+                ("resume_forwards", C.c_uint32)]
+
+
+class PathPolicyInputs(C.Structure):
+    """include/das3r_raster.h das3r_path_policy_inputs: what a forward's plan reads besides the state."""
+    _fields_ = [("P", C.c_int32), ("W", C.c_int32), ("H", C.c_int32), ("ntiles", C.c_int32), ("tbits", C.c_int32), ("tile_passes", C.c_int32),
+                ("too_long", C.c_uint32), ("want_bits", C.c_uint32), ("forced", C.c_int32), ("onesweep", C.c_int32), ("capacity_hint", C.c_int64),
+                ("capacity_exact", C.c_int32)]
+
+
+class PathPolicyPlan(C.Structure):
+    """include/das3r_raster.h das3r_path_policy_plan."""
+    _fields_ = [("local", C.c_int32), ("seg", C.c_int32), ("seg_bits", C.c_int32), ("seg_passes", C.c_int32), ("speculate", C.c_int32),
+                ("decide_fine", C.c_int32), ("gen", C.c_uint32), ("cap", C.c_int64)]
+
+
 PRUNE_GROUP_ROWS = 1024   # DAS3R_PRUNE_GROUP_ROWS
 
 
@@ -92,7 +113,9 @@ EXPORTS = ("das3r_raster_forward", "das3r_raster_backward", "das3r_raster_backwa
            "das3r_split_colour_rule", "das3r_split_colour_switch", "das3r_depth_l1_blocks", "das3r_depth_l1", "das3r_prune_select", "das3r_prune_compact",
            "das3r_photometric_forward_exposure", "das3r_photometric_backward_finish_exposure", "das3r_exposure_grad_finish",
            "das3r_raster_aux_forward", "das3r_raster_aux_scratch_bytes", "das3r_raster_aux_adjoint",
-           "das3r_thin_workspace_bytes", "das3r_thin_voxels")
+           "das3r_thin_workspace_bytes", "das3r_thin_voxels",
+           "das3r_debug_path_policy_fresh", "das3r_debug_path_policy_plan", "das3r_debug_path_policy_count", "das3r_debug_path_policy_skew",
+           "das3r_debug_path_policy_hint", "das3r_debug_path_policy_forget", "das3r_debug_path_policy_resume", "das3r_debug_seg_dbits")
 
 _lib = None
 
@@ -201,6 +224,23 @@ def load():
     L.das3r_adam_step_gated.argtypes = [C.c_int32, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
     L.das3r_adam_step.restype = C.c_int
     L.das3r_adam_step.argtypes = [C.c_int32, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p]
+    ps = C.POINTER(PathPolicyState)   # the binning-path policy on a caller's own state (additive under ABI 16; host-only)
+    L.das3r_debug_path_policy_fresh.restype = None
+    L.das3r_debug_path_policy_fresh.argtypes = [ps, C.c_uint32]
+    L.das3r_debug_path_policy_plan.restype = None
+    L.das3r_debug_path_policy_plan.argtypes = [ps, C.POINTER(PathPolicyInputs), C.POINTER(PathPolicyPlan)]
+    L.das3r_debug_path_policy_count.restype = C.c_int
+    L.das3r_debug_path_policy_count.argtypes = [ps, C.POINTER(PathPolicyInputs), C.POINTER(PathPolicyPlan), C.c_int64]
+    L.das3r_debug_path_policy_skew.restype = C.c_int
+    L.das3r_debug_path_policy_skew.argtypes = [ps, C.c_uint32, C.c_uint32, C.c_int64, C.c_int32]
+    L.das3r_debug_path_policy_hint.restype = C.c_uint32
+    L.das3r_debug_path_policy_hint.argtypes = [ps]
+    L.das3r_debug_path_policy_forget.restype = None
+    L.das3r_debug_path_policy_forget.argtypes = [ps]
+    L.das3r_debug_path_policy_resume.restype = None
+    L.das3r_debug_path_policy_resume.argtypes = [ps, C.c_uint32, C.c_uint32]
+    L.das3r_debug_seg_dbits.restype = C.c_int
+    L.das3r_debug_seg_dbits.argtypes = [C.c_int32, C.c_int32]
     L.das3r_raster_get_layout.restype = C.c_int
     L.das3r_raster_get_layout.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(RasterLayout)]
     _lib = L

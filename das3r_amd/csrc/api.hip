@@ -331,6 +331,16 @@ static bool dhist_slots(hipStream_t s, uint32_t **use, uint32_t **next) {
     *next = e->buf + 256 * ((e->turn + 1u) & 1u);
     return true;
 }
+// The depth histogram of this forward (segkey.h): filled by the preprocess kernel, read by the emission.  Not segmented: none (nulls).
+// No slot: in the geometry buffer, zeroed by a memset, as before round 6 (*next stays null).
+static int seg_dhist_for(bool seg, hipStream_t s, char *geom, const Layout &L, uint32_t **use, uint32_t **next) {
+    *use = *next = nullptr;
+    if (seg && !dhist_slots(s, use, next)) {
+        *use = (uint32_t *)(geom + L.g_dhist);
+        HIP_TRY(hipMemsetAsync(*use, 0, 4 * 256, s));
+    }
+    return DAS3R_OK;
+}
 
 static int validate(const das3r_raster_args *a, const das3r_raster_in *in) {
     if (!a || !in) { set_error("null args"); return DAS3R_ERR_INVALID_ARG; }
@@ -380,6 +390,54 @@ extern "C" int das3r_split_colour_rule(int32_t has_sh, int32_t sh_degree, int32_
     return split_colour_rule(has_sh != 0, sh_degree, P, binning_path, no_backward != 0, forced) ? 1 : 0;
 }
 
+// The functions of path_policy.h on a caller's own state (include/das3r_raster.h): no HIP call, no look at this thread's PerDevice state or at
+// the switches — everything the policy reads is in the two structs.
+namespace {
+struct PolicyOnState {
+    Verdict v;
+    Resume r;
+    das3r_path_policy_state *s;
+    explicit PolicyOnState(das3r_path_policy_state *state) : s(state) { policy_state_from(*s, &v, &r); }
+    ~PolicyOnState() { policy_state_to(v, r, s); }
+    PolicyInputs inputs(const das3r_path_policy_inputs *in) {
+        return PolicyInputs{in->P, in->W, in->H, in->ntiles, in->tbits, in->tile_passes, in->too_long, in->want_bits, in->forced, in->onesweep != 0,
+                            in->capacity_hint, in->capacity_exact != 0, &r};
+    }
+};
+ForwardPlan plan_of(const das3r_path_policy_plan *p) {
+    return ForwardPlan{p->local != 0, p->seg != 0, p->seg_bits, p->seg_passes, p->speculate != 0, p->cap, p->decide_fine != 0, p->gen};
+}
+}  // namespace
+extern "C" void das3r_debug_path_policy_fresh(das3r_path_policy_state *state, uint32_t gen) { policy_state_to(Verdict::fresh(gen), Resume(), state); }
+extern "C" void das3r_debug_path_policy_plan(das3r_path_policy_state *state, const das3r_path_policy_inputs *in, das3r_path_policy_plan *out) {
+    PolicyOnState on(state);
+    const ForwardPlan p = plan_forward(on.v, on.inputs(in));
+    *out = das3r_path_policy_plan{p.local, p.seg, p.seg_bits, p.seg_passes, p.speculate, p.decide_fine, p.gen, p.cap};
+}
+extern "C" int das3r_debug_path_policy_count(das3r_path_policy_state *state, const das3r_path_policy_inputs *in, const das3r_path_policy_plan *plan, int64_t I) {
+    PolicyOnState on(state);
+    return learn_count(on.v, I, on.inputs(in), plan_of(plan)) ? 1 : 0;
+}
+extern "C" int das3r_debug_path_policy_skew(das3r_path_policy_state *state, uint32_t longest, uint32_t crowd16, int64_t cap, int32_t ntiles) {
+    PolicyOnState on(state);
+    return learn_skew(on.v, longest, crowd16, cap, ntiles) ? 1 : 0;
+}
+extern "C" uint32_t das3r_debug_path_policy_hint(const das3r_path_policy_state *state) {
+    Verdict v;
+    Resume r;
+    policy_state_from(*state, &v, &r);
+    return backward_hint(v, (uint32_t)BUCKET);
+}
+extern "C" void das3r_debug_path_policy_forget(das3r_path_policy_state *state) {
+    PolicyOnState on(state);
+    forget(on.v);
+}
+extern "C" void das3r_debug_path_policy_resume(das3r_path_policy_state *state, uint32_t fine, uint32_t forwards) {
+    PolicyOnState on(state);
+    resume(on.v, on.r, fine != 0u, forwards);
+}
+extern "C" int das3r_debug_seg_dbits(int32_t tbits, int32_t passes) { return seg_dbits((int)tbits, (int)passes); }
+
 extern "C" int das3r_raster_get_layout(int32_t P, int64_t num_rendered, int32_t W, int32_t H, das3r_raster_layout *out) {
     if (!out || P < 0 || num_rendered < 0 || W <= 0 || H <= 0) { set_error("das3r_raster_get_layout: invalid argument"); return DAS3R_ERR_INVALID_ARG; }
     Layout L;
@@ -398,18 +456,29 @@ struct Mailbox {
     uint32_t *dev = nullptr;
     uint32_t seq = 0;
 };
+// the words the host reads by index (the kernels are handed pointers: dev + MB_COUNT {count, flags, tag}, dev + MB_TOO_LONG {too long,
+// want bits}, dev + MB_LONGEST {longest, tag, crowding})
+enum MailboxWord : uint32_t {
+    MB_COUNT = 0,       // num_rendered of the forward whose tag is in MB_COUNT_TAG
+    MB_COUNT_TAG = 2,
+    MB_TOO_LONG = 10,   // != 0: a forward of the shape with that generation number met a list too long for LDS (path_policy.h)
+    MB_WANT_BITS = 11,  // != 0: the segmented path of that generation sorted a segment long enough to want more bucket bits
+    MB_FILTERED = 12,   // the tag of a forward whose preprocess kernel culled a point
+    MB_LONGEST = 13,    // list_skew_kernel: the longest tile list of the forward whose tag is in MB_SKEW_TAG
+    MB_SKEW_TAG = 14,
+    MB_CROWD16 = 15,    // ... and of 64 consecutive list entries, those in the tile's fullest quadrant, x 16
+};
+// the tag of the next hand-off through the mailbox (never 0: an empty word names nobody)
+static uint32_t next_tag(Mailbox *mb) { return ++mb->seq ? mb->seq : ++mb->seq; }
 // Everything the library remembers between calls, per host thread and per device (a thread that renders on two GPUs gets two
 // of these; nothing is shared between threads: any number of them may render concurrently, each on its own stream).
 constexpr uint32_t CHECK_SLOTS = 16, CHECK_WORD0 = 16, MAILBOX_BYTES = 4 * (CHECK_WORD0 + 2 * CHECK_SLOTS);
-constexpr uint32_t CROWDED16 = 23u * 16u;   // (api.hip bin_and_render)
-struct Verdict { int P, W, H; int64_t last_I, peak_I; int radix_left, backoff; uint32_t gen; int seg_extra; bool last_seg; bool fine; uint32_t forwards; uint32_t clean; uint32_t longest; };
 struct PerDevice {
     Mailbox mb;
     uint32_t pending[CHECK_SLOTS] = {};             // per slot: tag of the forward whose self-check word has not been examined yet
     unsigned long long *arrive_ring = nullptr;      // self re-arming arrival words of the preprocess kernel's count reduction
-    Verdict verdict = {0, 0, 0, -1, 0, 0, 64, 0};  // what the last forward of the current shape (P, W, H) taught us
-    bool pending_fine = false, pending_valid = false;   // das3r_raster_learning(set): handed to the next shape this thread meets
-    uint32_t pending_forwards = 0;
+    Verdict verdict;                                // what the last forward of the current shape (P, W, H) taught us (path_policy.h)
+    Resume resume;                                  // das3r_raster_learning(set): handed to the next shape this thread meets
     char *emit_ring = nullptr;                      // control words of the emission fused into the preprocess kernel
     bool emit_ring_dirty = false;
     uint32_t emit_last_tag = 0;
@@ -431,15 +500,24 @@ static int per_device(PerDevice **out) {
     *out = &T;
     return DAS3R_OK;
 }
-// spin until word `idx` carries `tag` (bounded: falls back to a stream synchronise, then gives up loudly)
-static int mailbox_wait(Mailbox *mb, int idx, uint32_t tag, hipStream_t s) {
+// spin until `*word` carries `tag` — bounded: a look at the stream now and then, at last a stream synchronise and one more look.
+// *seen = what the word held at that last look (the caller decides what a missing tag means)
+static int await_tag(volatile uint32_t *word, uint32_t tag, hipStream_t s, uint32_t *seen) {
     for (long spins = 0; spins < 200000000L; spins++) {
-        if (__atomic_load_n(&mb->host[idx], __ATOMIC_ACQUIRE) == tag) return DAS3R_OK;
+        if ((*seen = __atomic_load_n(word, __ATOMIC_ACQUIRE)) == tag) return DAS3R_OK;
         __builtin_ia32_pause();
         if ((spins & 0xFFFFF) == 0xFFFFF && hipStreamQuery(s) != hipErrorNotReady) break;   // stream drained (or failed): stop spinning
     }
     HIP_TRY(hipStreamSynchronize(s));
-    if (__atomic_load_n(&mb->host[idx], __ATOMIC_ACQUIRE) == tag) return DAS3R_OK;
+    *seen = __atomic_load_n(word, __ATOMIC_ACQUIRE);
+    return DAS3R_OK;
+}
+// wait for word `idx` to carry `tag`, or give up loudly
+static int mailbox_wait(Mailbox *mb, int idx, uint32_t tag, hipStream_t s) {
+    uint32_t seen = 0;
+    const int r = await_tag(&mb->host[idx], tag, s, &seen);
+    if (r) return r;
+    if (seen == tag) return DAS3R_OK;
     set_error("the device never delivered the result of this forward to the host mailbox");
     return DAS3R_ERR_HIP;
 }
@@ -453,15 +531,8 @@ static void stat_add(int i) { __atomic_fetch_add(&g_stats[i], 1ull, __ATOMIC_REL
 static int examine_check_slot(volatile uint32_t *slot, uint32_t tag, bool wait, hipStream_t s) {
     uint32_t seen = __atomic_load_n(&slot[1], __ATOMIC_ACQUIRE);
     if (seen != tag && wait) {
-        for (long spins = 0; spins < 200000000L && seen != tag; spins++) {
-            __builtin_ia32_pause();
-            seen = __atomic_load_n(&slot[1], __ATOMIC_ACQUIRE);
-            if ((spins & 0xFFFFF) == 0xFFFFF && hipStreamQuery(s) != hipErrorNotReady) break;   // stream drained (or failed): stop spinning
-        }
-        if (seen != tag) {
-            HIP_TRY(hipStreamSynchronize(s));
-            seen = __atomic_load_n(&slot[1], __ATOMIC_ACQUIRE);
-        }
+        const int r = await_tag(&slot[1], tag, s, &seen);
+        if (r) return r;
     }
     if (seen != tag) return 1;
     const uint32_t all_flags = slot[0], flags = all_flags & ~16u;
@@ -493,8 +564,7 @@ extern "C" int das3r_raster_forget_shapes(void) {
     PerDevice *T = nullptr;
     int r = per_device(&T);
     if (r) return r;
-    const uint32_t gen = T->verdict.gen;   // (generation numbers keep counting: a word a forward of the old shape still has on its way names nobody)
-    T->verdict = Verdict{0, 0, 0, -1, 0, 0, 64, gen};
+    forget(T->verdict);
     return DAS3R_OK;
 }
 
@@ -506,15 +576,11 @@ extern "C" int das3r_raster_learning(int32_t set, uint32_t state[2]) {
     int r = per_device(&T);
     if (r) return r;
     if (!set) {
-        state[0] = T->verdict.fine ? 1u : 0u;
-        state[1] = T->verdict.forwards;
+        state[0] = prefers_regions(T->verdict) ? 1u : 0u;
+        state[1] = forwards_seen(T->verdict);
         return DAS3R_OK;
     }
-    const uint32_t gen = T->verdict.gen;
-    T->verdict = Verdict{0, 0, 0, -1, 0, 0, 64, gen};
-    T->pending_fine = state[0] != 0u;
-    T->pending_forwards = state[1];
-    T->pending_valid = true;
+    resume(T->verdict, T->resume, state[0] != 0u, state[1]);
     return DAS3R_OK;
 }
 
@@ -598,84 +664,28 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
         // be issued on another non-blocking stream, which does not wait for this one.  Once per thread and device.
         HIP_TRY(hipStreamSynchronize(s));
     }
-    // Depth order: scenes with short tile lists (the 100 k-splat 1080p benchmark averages 32 entries per tile) skip the global
-    // depth sort — five of the eleven binning launches, each latency-bound at that size; the instances are emitted in index
-    // order and the compositing kernel sorts every tile's list itself (common.h: LocalBin).  Chosen from the instance count
-    // of the previous forward of the same shape, confirmed with this forward's count; a list that outgrows LDS is still sorted
-    // correctly (slowly) and sends the next forwards back to the global sort.
-    Verdict &verdict = T->verdict;
-    constexpr int64_t LOCAL_AVG = 384;   // mean list length up to which the local order wins (measured: 1 M splats at 1080p, mean 320: -4 %)
-    const uint32_t too_long = mb->host[10];   // != 0: a forward of the shape with that generation number met a list too long for LDS
-    if (too_long) mb->host[10] = 0;
-    const uint32_t want_bits = mb->host[11];  // != 0: the segmented path of that generation sorted a segment long enough to want more bucket bits
-    if (want_bits) mb->host[11] = 0;
-    if (verdict.P != P || verdict.W != W || verdict.H != H) {
-        const uint32_t gen = verdict.gen + 1u ? verdict.gen + 1u : 1u;
-        verdict = Verdict{P, W, H, -1, 0, 0, 64, gen};
-        if (T->pending_valid) {   // a resumed job: the forward-kernel choice and its schedule continue where the checkpoint left them
-            verdict.fine = T->pending_fine;
-            verdict.forwards = T->pending_forwards;
-            T->pending_valid = false;
-        }
-    }
-    // Skewed tile lists -> the forward kernel with four workgroups per tile (render_regions.hip; below, bin_and_render): decided from the
-    // tile ranges of the shape's FIRST forward and of every 512th after it — a one-workgroup kernel behind the binning leaves the longest
-    // list in the mailbox and the host waits for it (the first forward of a shape waits for its count anyway; afterwards one short wait
-    // per 512 forwards).  Which kernel runs in which forward thus depends on the data alone, never on timing: the two kernels round a
-    // pixel's T differently in the last bit, and a job must end bit-identical however it was scheduled.
-    const bool decide_fine = (verdict.forwards++ & 511u) == 0u;
-    // Every decision below starts a new GENERATION of the shape: the words the kernels raise (mailbox 10 / 11) name the generation they were
-    // launched under, and the host runs one or two forwards ahead of the device — the forward enqueued BEFORE a decision was taken raises
-    // the same word again a moment later, and answered a second time it turned "one more partition pass" straight into "global sort for
-    // 64 forwards" (round 6: seen as a smooth-depth train step of 1.29 ms instead of 1.18 on some boxes, its first 64 timed steps on the
-    // global sort; which box depended on how far ahead its host ran).
-    auto next_gen = [&]() { verdict.gen = verdict.gen + 1u ? verdict.gen + 1u : 1u; };
-    if (verdict.last_I < 0) {   // (a shape's first forward: nothing to learn from yet)
-    } else if (too_long == verdict.gen && !(verdict.last_seg && verdict.seg_extra == 0 && L.tile_passes < 3 && seg_dbits(L, L.tile_passes + 1) > 0)) {
-        // global sort for a while; longer every time it happens AGAIN SOON.  Round 6: a failure that comes after 256 or more clean forwards
-        // on the fast path is an occasional one — a view of 45 that looks at a wall head-on (DAVIS-shaped job: one forward in ~ 350) — and
-        // starts from the shortest stint again: the doubling never forgot, and by iteration 4000 such a job had spent 2 447 of its
-        // iterations on the global sort (binning 0.64 ms against 0.47), tools/probes/job_binning_paths.py
-        if (verdict.clean >= 256u) verdict.backoff = 64;
-        verdict.radix_left = verdict.backoff;
-        if (verdict.backoff < 4096) verdict.backoff *= 2;
-        verdict.clean = 0;
-        next_gen();
-    } else if (too_long == verdict.gen || want_bits == verdict.gen) {
-        verdict.seg_extra = 1;                  // the segmented path with one more partition pass of bucket bits from now on (this shape);
-                                                // a segment that is too long even then sends the shape back to the global sort (above)
-        next_gen();
-    }
-    const int forced = switches().binning;   // DAS3R_BINNING=local | radix | seg: force one (diagnostics, tests)
-    bool local = use_onesweep() && (forced == 1 || (forced == 0 && verdict.radix_left == 0 && verdict.last_I <= LOCAL_AVG * L.ntiles));
-    // Long lists (round 4): the segmented path — no global depth sort; the tile partition's passes carry a depth bucket in the key bits
-    // the tile ids leave free, and every (tile, bucket) segment is sorted inside LDS (segkey.h, segsort.hip).  Needs free key bits
-    // and segments that stay short on average; a segment that did not fit in LDS sends the shape back to the global sort for a
-    // while, like a list too long for the local order does (the same mailbox word and back-off).
-    // The buckets are global: they split a tile's list well when its depths are spread (random-depth benchmarks) and badly when a tile
-    // sees a thin depth band of a wide scene (every real scene: its Gaussians lie on surfaces).  A forward that had to rank a long
-    // segment says so (mailbox word 11), and the shape takes ONE MORE partition pass from then on: eight more bucket bits — a band
-    // that held 3 % of the scene's instances in 4 of 128 buckets is cut into a thousand (r4, coherent-depth 5 M-splat scene:
-    // segment sort 1.08 ms with two passes, see DESIGN.md with three).
-    constexpr int64_t SEG_AVG = 384;         // mean entries per segment up to which it is taken
-    const int seg_passes = L.tile_passes + ((forced == 3 || (forced == 0 && verdict.seg_extra)) ? 1 : 0);
-    const int seg_bits = (use_onesweep() && seg_passes <= 3) ? seg_dbits(L, seg_passes) : 0;
-    bool seg = !local && seg_bits > 0 && (forced >= 2 || (forced == 0 && verdict.radix_left == 0 && verdict.last_I >= 0 &&
-                                                           (verdict.last_I >> std::min(seg_bits, 20)) <= SEG_AVG * L.ntiles));
+    // Which binning path this forward takes, whether it speculates on its capacity and whether it looks at its tile lists: path_policy.h,
+    // from what the earlier forwards of the shape left in T->verdict and the two words their kernels may have raised since.
+    const uint32_t too_long = mb->host[MB_TOO_LONG];
+    if (too_long) mb->host[MB_TOO_LONG] = 0;
+    const uint32_t want_bits = mb->host[MB_WANT_BITS];
+    if (want_bits) mb->host[MB_WANT_BITS] = 0;
+    const PolicyInputs policy_in = {P, W, H, L.ntiles, L.tbits, L.tile_passes, too_long, want_bits, switches().binning /* DAS3R_BINNING */, use_onesweep(),
+                                    a->capacity_hint, switches().capacity_exact, &T->resume};
+    const ForwardPlan plan = plan_forward(T->verdict, policy_in);
+    bool local = plan.local;
+    const bool seg = plan.seg;
     const uint32_t *seg_dhist = nullptr;   // where this forward's depth histogram is (set with the preprocess launch, below)
     auto apply_seg = [&]() {   // (compute_layout starts every layout without buckets)
         L.dhist_ptr = seg_dhist;
         if (seg) {
-            L.dbits = seg_bits;
-            L.kbits = L.tbits + seg_bits;
+            L.dbits = plan.seg_bits;
+            L.kbits = L.tbits + plan.seg_bits;
             L.kshift = std::min(16, 32 - L.kbits);
-            L.part_passes = seg_passes;
+            L.part_passes = plan.seg_passes;
         }
     };
-    verdict.last_seg = seg;
-    if (local || seg) verdict.clean++;   // (a failure of this forward is reported to the next one: reset there)
-    if (forced == 0 && verdict.radix_left > 0) verdict.radix_left--;
-    const uint32_t count_tag = ++mb->seq ? mb->seq : ++mb->seq;
+    const uint32_t count_tag = next_tag(mb);
     unsigned long long *arrive = arrive_ring + (size_t)(count_tag % ARRIVE_SLOTS) * ARRIVE_WORDS;
     // The split preprocess: the fork event is recorded behind the geometry kernel (launch_preprocess); the colour kernel goes to the side
     // stream once the binning kernels are enqueued on s (join.launch()), and s waits for it (join.now()) in front of the first kernel that
@@ -730,7 +740,7 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
         }
         uint32_t *host_late = nullptr;
         if (cap > 0) {
-            late_tag = ++mb->seq ? mb->seq : ++mb->seq;
+            late_tag = next_tag(mb);
             const uint32_t slot = late_tag % CHECK_SLOTS;
             if ((r = check_slot(slot, true))) return r;   // (the forward that used the slot CHECK_SLOTS forwards ago)
             T->pending[slot] = late_tag;
@@ -740,42 +750,34 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
         }
         uint32_t *dead_keys = nullptr;
         if ((r = launch_binning(P, cap, W, H, out->radii, saved->geom, saved->binning, saved->img, L, fused_scan, host_late, late_tag,
-                                a->debug != 0, s, &dead_keys, emit_slot, mb->dev + 10, verdict.gen))) return r;
+                                a->debug != 0, s, &dead_keys, emit_slot, mb->dev + MB_TOO_LONG, plan.gen))) return r;
         if ((r = join.launch())) return r;   // the split preprocess: the colour kernel, beside the binning kernels enqueued above
-        LocalBin lb = {(float4 *)(saved->binning + L.b_ckpt), nullptr, nullptr, nullptr, nullptr, verdict.gen, (uint32_t)(P - 1), (uint32_t)cap};
-        if (decide_fine && cap > 0 && use_quad_lanes(L, lb)) {   // (shapes the one-workgroup-per-tile kernel would take: few tiles, long lists)
-            const uint32_t tag = ++mb->seq ? mb->seq : ++mb->seq;
-            if ((r = launch_list_skew(saved->img, saved->binning, saved->geom, L, (uint32_t)cap, (uint32_t)(P - 1), mb->dev + 13, tag, a->debug != 0, s))) return r;
-            if ((r = mailbox_wait(mb, 14, tag, s))) return r;
-            const int64_t longest = (int64_t)mb->host[13], mean = (verdict.last_I > 0 ? verdict.last_I : cap) / std::max(L.ntiles, 1);   // (the last forward's count; the capacity on a shape's first)
-            verdict.longest = (uint32_t)longest;   // (what the backward's grid is sized by until the next look: below)
-            const uint32_t crowd16 = mb->host[15];   // of 64 consecutive list entries, those in the tile's fullest quadrant, x 16 (render_regions.hip list_skew_kernel)
-            // skewed: 1.8 x the mean list, the measured crossover of the forward kernels (ledger (bd)); crowded: a stretch of a list sits in part of
-            // its tile (random depths: 20 of 64 in the fullest quadrant) — there the 2x2-region kernels win both ways whatever the skew (ledger (be))
-            verdict.fine = (longest > mean + (mean * 4) / 5 && longest >= 4096) || crowd16 >= CROWDED16;
+        LocalBin lb = {(float4 *)(saved->binning + L.b_ckpt), nullptr, nullptr, nullptr, nullptr, plan.gen, (uint32_t)(P - 1), (uint32_t)cap};
+        if (plan.decide_fine && cap > 0 && use_quad_lanes(L, lb)) {   // (shapes the one-workgroup-per-tile kernel would take: few tiles, long lists)
+            const uint32_t tag = next_tag(mb);
+            if ((r = launch_list_skew(saved->img, saved->binning, saved->geom, L, (uint32_t)cap, (uint32_t)(P - 1), mb->dev + MB_LONGEST, tag, a->debug != 0, s))) return r;
+            if ((r = mailbox_wait(mb, MB_SKEW_TAG, tag, s))) return r;
+            const uint32_t longest = mb->host[MB_LONGEST], crowd16 = mb->host[MB_CROWD16];
+            const int64_t mean = skew_mean(T->verdict, cap, L.ntiles);
+            const bool now_fine = learn_skew(T->verdict, longest, crowd16, cap, L.ntiles);
             if (switches().verbose) fprintf(stderr, "[das3r] tile lists: longest %lld, mean %lld, %.1f of 64 consecutive entries in one quadrant -> %s kernels\n", (long long)longest,
-                                            (long long)mean, crowd16 / 16.0, verdict.fine ? "2x2-region" : "block");
+                                            (long long)mean, crowd16 / 16.0, now_fine ? "2x2-region" : "block");
         }
-        lb.prefer_regions = verdict.fine;
+        const bool fine = prefers_regions(T->verdict);
+        lb.prefer_regions = fine;
         lb.tile_order = nullptr;
-        if (verdict.fine && cap > 0 && use_quad_lanes(L, lb) && L.ntiles <= 1024 && !switches().tile_lpt_off && (switches().render_fwd == 0 || switches().render_fwd == 5)) {
+        if (fine && cap > 0 && use_quad_lanes(L, lb) && L.ntiles <= 1024 && !switches().tile_lpt_off && (switches().render_fwd == 0 || switches().render_fwd == 5)) {
             // four workgroups per tile are 3 - 4 generations of workgroups on the chip, and a tile whose list is four times the mean (every
             // real sequence has them) that starts in the last generation adds its whole chain to the kernel: longest lists first
             if ((r = launch_tile_lpt(saved->img, L, (uint32_t)cap, a->debug != 0, s))) return r;
             lb.tile_order = (const uint32_t *)(saved->img + L.i_order);
         }
-        if (verdict.fine && cap > 0 && use_quad_lanes(L, lb)) {   // (the backward pass of this forward: render_bwd.hip)
-            // bits 8 - 15: buckets (common.h BUCKET = 1024 list positions) of the shape's longest tile list as last measured, + 2 of headroom — the
-            // bucket-parallel backward launches that many workgroups per tile instead of the AVERAGE list's (a tile of four times the mean then
-            // takes four buckets per workgroup, back to back, and the kernel ends with them: self-consistent job 0.409 -> 0.313 ms)
-            const uint32_t hint = std::min<uint32_t>(63u, verdict.longest / (uint32_t)BUCKET + 2u);
-            saved->flags |= 1u | (hint << 8);
-        }
+        if (fine && cap > 0 && use_quad_lanes(L, lb)) saved->flags |= backward_hint(T->verdict, (uint32_t)BUCKET);   // (for the backward pass of this forward: render_bwd.hip)
         if (local_order && cap > 0) {
             lb.point_list = (uint32_t *)(saved->binning + L.pub.point_list);
             lb.slot_list = (uint32_t *)(saved->binning + L.b_slot);
             lb.keys = dead_keys;
-            lb.host_flag = mb->dev + 10;
+            lb.host_flag = mb->dev + MB_TOO_LONG;
         }
         if ((r = join.now())) return r;   // (a redo finds the colours there already: nothing is pending the second time)
         return launch_render_forward(a, in->colors_precomp, out->out_color, saved->geom, saved->binning, saved->img, L, lb, s, out->out_invdepth,
@@ -784,20 +786,16 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
     // prefiltered: the caller's promise that no point fails the near-plane cull (upstream traps when one does: auxiliary.h in_frustum);
     // the preprocess kernel leaves this call's tag in mailbox word 12 when one did
     auto prefiltered_ok = [&]() -> int {
-        if (!a->prefiltered || mb->host[12] != count_tag) return DAS3R_OK;
+        if (!a->prefiltered || mb->host[MB_FILTERED] != count_tag) return DAS3R_OK;
         set_error("Point is filtered although prefiltered is set. This shouldn't happen!");
         return DAS3R_ERR_INVALID_ARG;
     };
     int64_t I, cap;
-    // Local order + a previous forward of the same shape: nothing else could be enqueued while the count is on its way, so
-    // the binning buffer is laid out for that forward's count + 25 % and the whole forward is enqueued before the host looks
-    // at the mailbox (the kernels clamp to the capacity).  Should the scene have grown past it, the binning and the
-    // compositing are redone with the exact size.  DAS3R_CAPACITY=exact switches the speculation off.
-    if ((local || seg) && verdict.last_I >= 0 && a->capacity_hint != -1 && !switches().capacity_exact) {   // (round 4: the segmented path too)
-        // headroom: 25 % over the last count, 5 % over the (slowly forgotten) largest one — a camera that moves between views
-        // of different density overflows rarely
-        cap = std::max(verdict.last_I + verdict.last_I / 4, verdict.peak_I + verdict.peak_I / 20) + 4096;
-        if (cap > (int64_t)0x7FFFFF00) cap = (int64_t)0x7FFFFF00;
+    // The speculative flow: the binning buffer is laid out for the plan's capacity and the whole forward is enqueued before the host looks
+    // at the mailbox (the kernels clamp to the capacity).  Should the scene have grown past it, the binning and the compositing are redone
+    // with the exact size.
+    if (plan.speculate) {
+        cap = plan.cap;
         compute_layout(P, cap, W, H, &L, shjac);
         apply_seg();
         saved->binning = alloc_binning(user, depth ? L.d_bytes : L.pub.binning_bytes);
@@ -833,10 +831,7 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
             emit_ring_dirty = false;
         } else {
             uint32_t *dhist = nullptr, *dhist_next = nullptr;
-            if (seg && !dhist_slots(s, &dhist, &dhist_next)) {   // the depth histogram of this forward (segkey.h): filled by the preprocess kernel, read by the emission
-                dhist = (uint32_t *)(saved->geom + L.g_dhist);   // (no slot: in the geometry buffer, zeroed by a memset, as before round 6)
-                HIP_TRY(hipMemsetAsync(dhist, 0, 4 * 256, s));
-            }
+            if ((rc = seg_dhist_for(seg, s, saved->geom, L, &dhist, &dhist_next))) return rc;
             seg_dhist = dhist;
             apply_seg();
             const SideStream *side = nullptr;
@@ -846,12 +841,11 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
             join.forked = side != nullptr;
             if ((rc = bin_and_render(cap, local, true, mb->dev, count_tag))) return rc;
         }
-        if ((rc = mailbox_wait(mb, 2, count_tag, s))) return rc;
+        if ((rc = mailbox_wait(mb, MB_COUNT_TAG, count_tag, s))) return rc;
         if ((rc = prefiltered_ok())) return rc;
-        I = (int64_t)mb->host[0];
-        if (I > (int64_t)0x7FFFFF00) { set_error("num_rendered %lld exceeds 2^31", (long long)I); return DAS3R_ERR_OVERFLOW; }
-        verdict.last_I = I;
-        verdict.peak_I = std::max(I, verdict.peak_I - verdict.peak_I / 1024);
+        I = (int64_t)mb->host[MB_COUNT];
+        if (I > CAPACITY_MAX) { set_error("num_rendered %lld exceeds 2^31", (long long)I); return DAS3R_ERR_OVERFLOW; }
+        (void)learn_count(T->verdict, I, policy_in, plan);   // (enqueued already: this forward keeps its path)
         if (I > cap) {
             cap = I;
             compute_layout(P, cap, W, H, &L, shjac);
@@ -864,23 +858,18 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
         }
     } else {
         uint32_t *dhist = nullptr, *dhist_next = nullptr;
-        if (seg && !dhist_slots(s, &dhist, &dhist_next)) {   // the depth histogram of this forward (segkey.h): filled by the preprocess kernel, read by the emission
-            dhist = (uint32_t *)(saved->geom + L.g_dhist);
-            HIP_TRY(hipMemsetAsync(dhist, 0, 4 * 256, s));
-        }
+        if ((rc = seg_dhist_for(seg, s, saved->geom, L, &dhist, &dhist_next))) return rc;
         seg_dhist = dhist;
         const SideStream *side = nullptr;
         if ((rc = split_side((local || seg) ? 1 : 0, &side))) return rc;
         if ((rc = launch_preprocess(a, in, out->radii, saved->geom, saved->img, nullptr, 0, L, arrive, mb->dev, count_tag, s, nullptr, dhist, dhist_next, aa, side))) return rc;
         join.forked = side != nullptr;
         if (!local && !seg && (rc = launch_depth_sort(P, saved->geom, L, 0, nullptr, 0, a->debug != 0, s))) return rc;
-        if ((rc = mailbox_wait(mb, 2, count_tag, s))) return rc;    // usually there already: preprocess finished long ago
+        if ((rc = mailbox_wait(mb, MB_COUNT_TAG, count_tag, s))) return rc;    // usually there already: preprocess finished long ago
         if ((rc = prefiltered_ok())) return rc;
-        I = cap = (int64_t)mb->host[0];
-        if (cap > (int64_t)0x7FFFFF00) { set_error("num_rendered %lld exceeds 2^31", (long long)cap); return DAS3R_ERR_OVERFLOW; }
-        verdict.last_I = I;
-        verdict.peak_I = std::max(I, verdict.peak_I - verdict.peak_I / 1024);
-        if (local && forced == 0 && I > LOCAL_AVG * L.ntiles) {   // the scene grew: global sort after all
+        I = cap = (int64_t)mb->host[MB_COUNT];
+        if (cap > CAPACITY_MAX) { set_error("num_rendered %lld exceeds 2^31", (long long)cap); return DAS3R_ERR_OVERFLOW; }
+        if (learn_count(T->verdict, I, policy_in, plan)) {   // the scene grew: global sort after all
             local = false;
             if ((rc = join.now())) return rc;   // (the sort scatters the depth keys the colour kernel reads)
             if ((rc = launch_depth_sort(P, saved->geom, L, 0, nullptr, 0, a->debug != 0, s))) return rc;
@@ -906,6 +895,28 @@ static bool shjac_saved(const das3r_raster_args *a, const das3r_raster_in *in, c
     return (saved->flags & SHJAC_SAVED_FLAG) != 0 && in->shs != nullptr && a->sh_degree >= 2;
 }
 
+// What das3r_raster_backward (depth_pass false; dL_dinvdepth not looked at) and das3r_raster_backward_depth ask of their pointers.
+static int backward_validate(const char *who, const das3r_raster_in *in, const das3r_raster_saved *saved, const float *dL_dpix, bool depth_pass,
+                             const float *dL_dinvdepth, const das3r_raster_grads *g) {
+    const bool chained = g && g->chain;   // (ABI 14: dL/d(camera-frame means, opacities, scales, rotations) are then not produced — may be NULL)
+    if (!saved || !saved->geom || !saved->img || !dL_dpix || (depth_pass && !dL_dinvdepth) || !g || !g->dL_dmeans2D ||
+        (!chained && (!g->dL_dopacities || !g->dL_dmeans3D)) || (saved->num_rendered > 0 && !g->scratch)) {
+        set_error("%s: null saved state / %sgradient buffer", who, depth_pass ? "upstream gradient / " : "");
+        return DAS3R_ERR_INVALID_ARG;
+    }
+    if (depth_pass && !(saved->flags & DEPTH_SAVED_FLAG)) {
+        set_error("%s: the saved state is not that of a forward with out_invdepth (das3r_raster_saved.flags bit 1 is clear)", who);
+        return DAS3R_ERR_INVALID_ARG;
+    }
+    const bool has_sh = in->shs != nullptr, has_cov = in->cov3D_precomp != nullptr;
+    if ((has_sh && !g->dL_dshs) || (!has_sh && !g->dL_dcolors_precomp) || (has_cov && !g->dL_dcov3D) ||
+        (!has_cov && !chained && (!g->dL_dscales || !g->dL_drotations))) {
+        set_error("%s: gradient buffer missing for a provided input", who);
+        return DAS3R_ERR_INVALID_ARG;
+    }
+    return DAS3R_OK;
+}
+
 extern "C" int das3r_raster_backward(const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_saved *saved,
                                      const float *dL_dpix, const das3r_raster_grads *g, das3r_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
@@ -913,18 +924,7 @@ extern "C" int das3r_raster_backward(const das3r_raster_args *a, const das3r_ras
     if (rc) return rc;
     const int P = a->P;
     if (P == 0) return DAS3R_OK;
-    const bool chained = g && g->chain;   // (ABI 14: dL/d(camera-frame means, opacities, scales, rotations) are then not produced — may be NULL)
-    if (!saved || !saved->geom || !saved->img || !dL_dpix || !g || !g->dL_dmeans2D || (!chained && (!g->dL_dopacities || !g->dL_dmeans3D)) ||
-        (saved && saved->num_rendered > 0 && !g->scratch)) {
-        set_error("das3r_raster_backward: null saved state / gradient buffer");
-        return DAS3R_ERR_INVALID_ARG;
-    }
-    const bool has_sh = in->shs != nullptr, has_cov = in->cov3D_precomp != nullptr;
-    if ((has_sh && !g->dL_dshs) || (!has_sh && !g->dL_dcolors_precomp) || (has_cov && !g->dL_dcov3D) ||
-        (!has_cov && !chained && (!g->dL_dscales || !g->dL_drotations))) {
-        set_error("das3r_raster_backward: gradient buffer missing for a provided input");
-        return DAS3R_ERR_INVALID_ARG;
-    }
+    if ((rc = backward_validate("das3r_raster_backward", in, saved, dL_dpix, false, nullptr, g))) return rc;
     // the forward's binning self-check first: nothing is launched on the strength of an invalid image / list
     if ((rc = das3r_raster_check(saved, stream))) return rc;
     Layout L;
@@ -952,22 +952,7 @@ extern "C" int das3r_raster_backward_depth(const das3r_raster_args *a, const das
     if (rc) return rc;
     const int P = a->P;
     if (P == 0) return DAS3R_OK;
-    const bool chained = g && g->chain;
-    if (!saved || !saved->geom || !saved->img || !dL_dpix || !dL_dinvdepth || !g || !g->dL_dmeans2D || (!chained && (!g->dL_dopacities || !g->dL_dmeans3D)) ||
-        (saved->num_rendered > 0 && !g->scratch)) {
-        set_error("das3r_raster_backward_depth: null saved state / upstream gradient / gradient buffer");
-        return DAS3R_ERR_INVALID_ARG;
-    }
-    if (!(saved->flags & DEPTH_SAVED_FLAG)) {
-        set_error("das3r_raster_backward_depth: the saved state is not that of a forward with out_invdepth (das3r_raster_saved.flags bit 1 is clear)");
-        return DAS3R_ERR_INVALID_ARG;
-    }
-    const bool has_sh = in->shs != nullptr, has_cov = in->cov3D_precomp != nullptr;
-    if ((has_sh && !g->dL_dshs) || (!has_sh && !g->dL_dcolors_precomp) || (has_cov && !g->dL_dcov3D) ||
-        (!has_cov && !chained && (!g->dL_dscales || !g->dL_drotations))) {
-        set_error("das3r_raster_backward_depth: gradient buffer missing for a provided input");
-        return DAS3R_ERR_INVALID_ARG;
-    }
+    if ((rc = backward_validate("das3r_raster_backward_depth", in, saved, dL_dpix, true, dL_dinvdepth, g))) return rc;
     const int kind = switches().render_bwd;
     if (kind == 2 || kind == 3 || kind == 5) {
         set_error("das3r_raster_backward_depth: DAS3R_RENDER_BWD=%s has no inverse-depth form", kind == 3 ? "scan" : (kind == 2 ? "mfma" : "stream"));

@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "../../include/das3r_raster.h"
+#include "path_policy.h"
 #include "pretransform_math.h"
 
 #define TILE_X 16
@@ -234,8 +235,8 @@ struct Layout {
     const uint32_t *dhist_ptr;  // round 6: where this forward's depth histogram really is (a library-owned slot: api.hip dhist_slots); null = geom + g_dhist
     size_t i_order;   // img buffer, u32[ntiles]: the tiles longest list first (render_regions.hip tile_lpt_kernel; round 6)
 };
-// depth-bucket bits `passes` partition passes (at most three) have room for beside the tile ids (<= 0: none)
-static inline int seg_dbits(const Layout &L, int passes) { return 8 * (passes < 3 ? passes : 3) - L.tbits; }
+// depth-bucket bits `passes` partition passes (at most three) have room for beside the tile ids (<= 0: none): path_policy.h
+static inline int seg_dbits(const Layout &L, int passes) { return seg_dbits(L.tbits, passes); }
 
 // Local depth order (short tile lists): the binning skips the global depth sort, the tile lists arrive in index order and
 // the forward compositing kernel sorts each one by (depth bits, index) itself (render_common.h: local_sort_tile) — in LDS up
@@ -248,7 +249,7 @@ struct LocalBin {
     uint32_t flag_value;                // names the shape (P, W, H) this forward belongs to, never 0
     uint32_t last_g, cap;               // P - 1 and the instances the lists hold: bounds for safe_index / safe_range (always set)
     // round 6: the forward kernel with four workgroups per tile (render_regions.hip) instead of one (render_lanes.hip): chosen by the host for
-    // shapes whose tile lists are skewed (api.hip Verdict::fine, decided from the tile ranges themselves: launch_list_skew)
+    // shapes whose tile lists are skewed (path_policy.h Verdict::fine, decided from the tile ranges themselves: launch_list_skew, learn_skew)
     bool prefer_regions;
     const uint32_t *tile_order;         // with prefer_regions: the tiles, longest list first (tile_lpt_kernel); null: the locality order
 };

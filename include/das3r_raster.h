@@ -566,6 +566,48 @@ int das3r_has_experiments(void);
 int das3r_split_colour_rule(int32_t has_sh, int32_t sh_degree, int32_t P, int32_t binning_path, int32_t no_backward, int32_t forced);
 int das3r_split_colour_switch(void);
 
+/* ---- the binning-path policy on a caller's own state (test aid) ------------------------------------------------------------------
+ * Additive symbols under ABI 16 (no struct and no existing entry point changes).  What das3r_raster_forward learns about a shape and what
+ * its next forward does with it — binning path, back-off to the global sort, speculative capacity, compositing kernels — is host
+ * arithmetic (csrc/path_policy.h); these calls run exactly those functions on the state struct the caller passes, so that a test can
+ * script any sequence of forwards (inputs, delivered count, mailbox words) and look at every plan and every resulting state.
+ * Host-only: no device needed, no HIP call, and neither the calling thread's library state nor the DAS3R_* switches are looked at or
+ * changed (what the policy reads of them is in das3r_path_policy_inputs).  Flags are 0 / 1. */
+typedef struct {
+    int32_t P, W, H;              /* the shape the state is about */
+    int64_t last_I, peak_I;       /* the last forward's count (-1: none yet), the slowly forgotten largest one */
+    int32_t radix_left, backoff;  /* forwards still to spend on the global sort, and what the next failure costs */
+    uint32_t gen;                 /* generation: what the kernels' mailbox words name (never 0 once a shape was met) */
+    int32_t seg_extra, last_seg, fine;
+    uint32_t forwards, clean, longest;
+    int32_t resume_valid, resume_fine;   /* das3r_raster_learning(set): waiting for the next shape */
+    uint32_t resume_forwards;
+} das3r_path_policy_state;
+typedef struct {
+    int32_t P, W, H, ntiles, tbits, tile_passes;   /* tbits: bits of a tile id; tile_passes = (tbits + 7) / 8 */
+    uint32_t too_long, want_bits;                  /* the two mailbox words as read before the forward (0: not raised) */
+    int32_t forced;                                /* DAS3R_BINNING: 0 unset, 1 local, -1 radix, 2 seg, 3 seg3 */
+    int32_t onesweep;                              /* 1 except with DAS3R_SORT=classic of an experiments build */
+    int64_t capacity_hint;                         /* das3r_raster_args.capacity_hint */
+    int32_t capacity_exact;                        /* DAS3R_CAPACITY=exact */
+} das3r_path_policy_inputs;
+typedef struct {
+    int32_t local, seg, seg_bits, seg_passes;      /* local order / segmented path (neither: global sort); bucket bits and passes of the latter */
+    int32_t speculate, decide_fine;
+    uint32_t gen;
+    int64_t cap;                                   /* with speculate */
+} das3r_path_policy_plan;
+void das3r_debug_path_policy_fresh(das3r_path_policy_state *state, uint32_t gen);   /* the state of a thread that has met no shape */
+void das3r_debug_path_policy_plan(das3r_path_policy_state *state, const das3r_path_policy_inputs *in, das3r_path_policy_plan *plan);
+/* the forward's count has arrived; 1: a forward that planned the local order at its exact size takes the global sort after all */
+int das3r_debug_path_policy_count(das3r_path_policy_state *state, const das3r_path_policy_inputs *in, const das3r_path_policy_plan *plan, int64_t I);
+/* a forward with plan.decide_fine has measured its tile lists; returns state->fine */
+int das3r_debug_path_policy_skew(das3r_path_policy_state *state, uint32_t longest, uint32_t crowd16, int64_t cap, int32_t ntiles);
+uint32_t das3r_debug_path_policy_hint(const das3r_path_policy_state *state);   /* das3r_raster_saved.flags bits 0 and 8 - 15 of a `fine` forward */
+void das3r_debug_path_policy_forget(das3r_path_policy_state *state);           /* das3r_raster_forget_shapes */
+void das3r_debug_path_policy_resume(das3r_path_policy_state *state, uint32_t fine, uint32_t forwards);   /* das3r_raster_learning(set) */
+int das3r_debug_seg_dbits(int32_t tbits, int32_t passes);   /* depth-bucket bits `passes` partition passes leave beside tbits bits of tile id */
+
 int das3r_abi_version(void);
 const char *das3r_last_error(void);
 

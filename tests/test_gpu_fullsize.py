@@ -140,7 +140,7 @@ def test_steady_state_full_size_vs_oracle(name):
     assert _launches(kernels, "segment_sort_kernel") == 1, kernels
     assert _launches(kernels, "depth_hist_kernel") == 0, kernels
     # round 6: the compositing kernels follow the lists — random depths (`ds`): one workgroup per tile forward, the block walk backward;
-    # a depth slab that crowds into part of its tile (`dsc`, every real sequence; api.hip CROWDED16): the 2x2-region kernels both ways
+    # a depth slab that crowds into part of its tile (`dsc`, every real sequence; path_policy.h CROWDED16): the 2x2-region kernels both ways
     fwd, bwd = ("render_forward_regions_kernel", "render_backward_regions_kernel") if name == "dsc" else ("render_forward_lanes_kernel", "render_backward_blk_kernel")
     assert _launches(kernels, fwd) == 1 and _launches(kernels, "render_forward_") == 1, kernels
     assert _launches(kernels, bwd) == 1 and _launches(kernels, "render_backward_") == 1, kernels

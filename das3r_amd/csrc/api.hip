@@ -917,75 +917,105 @@ static int backward_validate(const char *who, const das3r_raster_in *in, const d
     return DAS3R_OK;
 }
 
-extern "C" int das3r_raster_backward(const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_saved *saved,
-                                     const float *dL_dpix, const das3r_raster_grads *g, das3r_stream_t stream) {
+// What das3r_raster_backward_focal adds to a backward (focal_grad.hip); null for the two entries that do not.
+struct FocalOut {
+    float *sums, *per_splat, *workspace;
+};
+
+// The backward pass of das3r_raster_backward (depth_pass false), das3r_raster_backward_depth (true) and das3r_raster_backward_focal (either,
+// with `focal`): the launches of the first two are what they were, the third puts one per-Gaussian kernel and its finish between the
+// compositing passes (+ the depth fold) and the per-Gaussian backward — before grads->chain's Adam step touches the parameters it reads.
+//
+// ABI 16, the depth pass: the backward of (colour, inverse depth).  The colour pass is das3r_raster_backward's; the depth pass is the same compositing backward
+// (the same kernel: the choice depends on the lists and the flags only) on the colour (1/z, 0, 0) with background 0, upstream gradient
+// (dL/dinvdepth, 0, 0) and the depth checkpoints — preprocess_bwd.hip depth_pass_inputs_kernel / depth_fold_kernel say why that is the
+// backward of the fourth channel.  Its geometry sums are added to the colour pass's rows, its colour sums become dL/dz, which the per-Gaussian
+// kernel adds to dL/dmeans3D (before the chain, with grads->chain).  Everything it writes besides grads and scratch is in the binning
+// buffer's depth part (Layout::d_*), which only a forward with out_invdepth has: das3r_raster_saved.flags bit 1 says so.
+static int backward_body(const char *who, const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_saved *saved, const float *dL_dpix,
+                         bool depth_pass, const float *dL_dinvdepth, const das3r_raster_grads *g, const FocalOut *focal, das3r_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     int rc = validate(a, in);
     if (rc) return rc;
     const int P = a->P;
-    if (P == 0) return DAS3R_OK;
-    if ((rc = backward_validate("das3r_raster_backward", in, saved, dL_dpix, false, nullptr, g))) return rc;
+    if (P == 0) {
+        if (focal) HIP_TRY(hipMemsetAsync(focal->sums, 0, 2 * sizeof(float), s));   // (per_splat has no element)
+        return DAS3R_OK;
+    }
+    if ((rc = backward_validate(who, in, saved, dL_dpix, depth_pass, dL_dinvdepth, g))) return rc;
+    if (depth_pass) {
+        const int kind = switches().render_bwd;
+        if (kind == 2 || kind == 3 || kind == 5) {
+            set_error("%s: DAS3R_RENDER_BWD=%s has no inverse-depth form", who, kind == 3 ? "scan" : (kind == 2 ? "mfma" : "stream"));
+            return DAS3R_ERR_INVALID_ARG;
+        }
+    }
     // the forward's binning self-check first: nothing is launched on the strength of an invalid image / list
     if ((rc = das3r_raster_check(saved, stream))) return rc;
     Layout L;
     compute_layout(P, saved->capacity > 0 ? saved->capacity : saved->num_rendered, a->image_width, a->image_height, &L, shjac_saved(a, in, saved));
     // scratch = per-instance partial sums [num_rendered, 9]; no accumulator needs zeroing (no atomics anywhere)
     float *partial = g->scratch;
-    bool quad_rows = false;
-    if (saved->num_rendered > 0) {
-        if (!saved->binning) { set_error("das3r_raster_backward: binning buffer missing"); return DAS3R_ERR_INVALID_ARG; }
-        if ((rc = launch_render_backward(a, dL_dpix, saved->geom, saved->binning, saved->img, L, partial, s, &quad_rows, saved->num_rendered, saved->flags))) return rc;
-    }
-    return launch_preprocess_backward(a, in, saved->geom, saved->binning, L, g, partial, s, quad_rows, nullptr, (saved->flags & ANTIALIAS_FLAG) != 0);
-}
-
-// ABI 16: the backward of (colour, inverse depth).  The colour pass is das3r_raster_backward's; the depth pass is the same compositing backward
-// (the same kernel: the choice depends on the lists and the flags only) on the colour (1/z, 0, 0) with background 0, upstream gradient
-// (dL/dinvdepth, 0, 0) and the depth checkpoints — preprocess_bwd.hip depth_pass_inputs_kernel / depth_fold_kernel say why that is the
-// backward of the fourth channel.  Its geometry sums are added to the colour pass's rows, its colour sums become dL/dz, which the per-Gaussian
-// kernel adds to dL/dmeans3D (before the chain, with grads->chain).  Everything it writes besides grads and scratch is in the binning
-// buffer's depth part (Layout::d_*), which only a forward with out_invdepth has: das3r_raster_saved.flags bit 1 says so.
-extern "C" int das3r_raster_backward_depth(const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_saved *saved,
-                                           const float *dL_dpix, const float *dL_dinvdepth, const das3r_raster_grads *g, das3r_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
-    int rc = validate(a, in);
-    if (rc) return rc;
-    const int P = a->P;
-    if (P == 0) return DAS3R_OK;
-    if ((rc = backward_validate("das3r_raster_backward_depth", in, saved, dL_dpix, true, dL_dinvdepth, g))) return rc;
-    const int kind = switches().render_bwd;
-    if (kind == 2 || kind == 3 || kind == 5) {
-        set_error("das3r_raster_backward_depth: DAS3R_RENDER_BWD=%s has no inverse-depth form", kind == 3 ? "scan" : (kind == 2 ? "mfma" : "stream"));
-        return DAS3R_ERR_INVALID_ARG;
-    }
-    if ((rc = das3r_raster_check(saved, stream))) return rc;
-    Layout L;
-    compute_layout(P, saved->capacity > 0 ? saved->capacity : saved->num_rendered, a->image_width, a->image_height, &L, shjac_saved(a, in, saved));
-    float *partial = g->scratch;
     const float *dz = nullptr;
     bool quad_rows = false;
     if (saved->num_rendered > 0) {
-        if (!saved->binning) { set_error("das3r_raster_backward_depth: binning buffer missing"); return DAS3R_ERR_INVALID_ARG; }
-        const size_t c = L.capacity > 0 ? (size_t)L.capacity : 1;
-        float *partial_depth = (float *)((char *)g->scratch + align_up(c * 9 * sizeof(float) + 16));
+        if (!saved->binning) { set_error("%s: binning buffer missing", who); return DAS3R_ERR_INVALID_ARG; }
         if ((rc = launch_render_backward(a, dL_dpix, saved->geom, saved->binning, saved->img, L, partial, s, &quad_rows, saved->num_rendered, saved->flags))) return rc;
-        if ((rc = launch_depth_pass_inputs(P, a->image_width * a->image_height, saved->geom, L, saved->binning, dL_dinvdepth, s, a->debug != 0))) return rc;
-        Layout Ld = L;   // the depth pass reads its splat records and checkpoints from the binning buffer's depth part
-        Ld.pub.xy = L.d_recs;
-        Ld.pub.conic_opacity = L.d_recs + 16;
-        Ld.pub.rgbd = L.d_recs + 32;
-        Ld.b_ckpt = L.d_ckpt;
-        das3r_raster_args ad = *a;
-        ad.bg = (const float *)(saved->binning + L.d_bg);
-        bool quad_rows_d = false;
-        if ((rc = launch_render_backward(&ad, (const float *)(saved->binning + L.d_dpix), saved->binning, saved->binning, saved->img, Ld, partial_depth, s,
-                                         &quad_rows_d, saved->num_rendered, saved->flags))) return rc;
-        float *dzw = (float *)(saved->binning + L.d_dz);
-        if ((rc = launch_depth_fold(P, saved->geom, L, partial, partial_depth, dzw, s, a->debug != 0))) return rc;
-        dz = dzw;
+        if (depth_pass) {
+            const size_t c = L.capacity > 0 ? (size_t)L.capacity : 1;
+            float *partial_depth = (float *)((char *)g->scratch + align_up(c * 9 * sizeof(float) + 16));
+            if ((rc = launch_depth_pass_inputs(P, a->image_width * a->image_height, saved->geom, L, saved->binning, dL_dinvdepth, s, a->debug != 0))) return rc;
+            Layout Ld = L;   // the depth pass reads its splat records and checkpoints from the binning buffer's depth part
+            Ld.pub.xy = L.d_recs;
+            Ld.pub.conic_opacity = L.d_recs + 16;
+            Ld.pub.rgbd = L.d_recs + 32;
+            Ld.b_ckpt = L.d_ckpt;
+            das3r_raster_args ad = *a;
+            ad.bg = (const float *)(saved->binning + L.d_bg);
+            bool quad_rows_d = false;
+            if ((rc = launch_render_backward(&ad, (const float *)(saved->binning + L.d_dpix), saved->binning, saved->binning, saved->img, Ld, partial_depth, s,
+                                             &quad_rows_d, saved->num_rendered, saved->flags))) return rc;
+            float *dzw = (float *)(saved->binning + L.d_dz);
+            if ((rc = launch_depth_fold(P, saved->geom, L, partial, partial_depth, dzw, s, a->debug != 0))) return rc;
+            dz = dzw;
+        }
     }
+    const bool aa = (saved->flags & ANTIALIAS_FLAG) != 0;
+    // (nothing rendered: tiles_touched is all zero, the kernel reads no row and writes the zeros)
+    if (focal && (rc = launch_focal_grad(a, in, saved->geom, L, partial, quad_rows, aa, focal->sums, focal->per_splat, focal->workspace, s))) return rc;
     // (the depth pass's opacity sums were folded into `partial` above: the antialiasing factor's derivative is applied once, to the total)
-    return launch_preprocess_backward(a, in, saved->geom, saved->binning, L, g, partial, s, quad_rows, dz, (saved->flags & ANTIALIAS_FLAG) != 0);
+    return launch_preprocess_backward(a, in, saved->geom, saved->binning, L, g, partial, s, quad_rows, dz, aa);
+}
+
+extern "C" int das3r_raster_backward(const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_saved *saved,
+                                     const float *dL_dpix, const das3r_raster_grads *g, das3r_stream_t stream) {
+    return backward_body("das3r_raster_backward", a, in, saved, dL_dpix, false, nullptr, g, nullptr, stream);
+}
+
+extern "C" int das3r_raster_backward_depth(const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_saved *saved,
+                                           const float *dL_dpix, const float *dL_dinvdepth, const das3r_raster_grads *g, das3r_stream_t stream) {
+    return backward_body("das3r_raster_backward_depth", a, in, saved, dL_dpix, true, dL_dinvdepth, g, nullptr, stream);
+}
+
+// Additive under ABI 16: the whole backward (das3r_raster_backward, or with dL_dinvdepth das3r_raster_backward_depth — the same launches, the
+// same gradients bit for bit) plus dL/d(log-focal offsets) of the same loss: focal_grad.hip.  Refused before anything is launched: NULL sums /
+// workspace, and with dL_dinvdepth the forced DAS3R_RENDER_BWD forms das3r_raster_backward_depth refuses.
+extern "C" size_t das3r_raster_focal_workspace_bytes(int32_t P) { return focal_workspace_bytes(P); }
+extern "C" int das3r_raster_backward_focal(const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_saved *saved, const float *dL_dpix,
+                                           const float *dL_dinvdepth, const das3r_raster_grads *g, float *sums, float *per_splat, float *workspace,
+                                           das3r_stream_t stream) {
+    if (!sums || !workspace) {
+        set_error("das3r_raster_backward_focal: null sums / workspace");
+        return DAS3R_ERR_INVALID_ARG;
+    }
+    const bool depth_pass = dL_dinvdepth != nullptr;
+    const int kind = switches().render_bwd;
+    if (depth_pass && (kind == 2 || kind == 3 || kind == 5)) {
+        set_error("das3r_raster_backward_focal: DAS3R_RENDER_BWD=%s has no inverse-depth form", kind == 3 ? "scan" : (kind == 2 ? "mfma" : "stream"));
+        return DAS3R_ERR_INVALID_ARG;
+    }
+    const FocalOut focal = {sums, per_splat, workspace};
+    return backward_body("das3r_raster_backward_focal", a, in, saved, dL_dpix, depth_pass, dL_dinvdepth, g, &focal, stream);
 }
 
 // das3r_raster_backward_scratch_bytes' rows twice: the colour pass's and the depth pass's (whose first column is the per-instance depth sum)

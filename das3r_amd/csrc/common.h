@@ -369,6 +369,11 @@ int launch_render_forward(const das3r_raster_args *a, const float *colors_precom
 // (dL/dinvdepth, 0, 0) and zero background; then the fold of its per-instance sums into the colour pass's and the per-Gaussian dL/dz.
 int launch_depth_pass_inputs(int P, int npix, const char *geom, const Layout &L, char *binning, const float *dL_dinvdepth, hipStream_t s, bool debug);
 int launch_depth_fold(int P, const char *geom, const Layout &L, float *partial, const float *partial_depth, float *dz, hipStream_t s, bool debug);
+// focal_grad.hip (das3r_raster_backward_focal): dL/d(log-focal offsets) from the rows the compositing backward (and the depth fold) left in
+// `partial`, before the per-Gaussian backward runs; workspace: focal_workspace_bytes(P) bytes, one row of two sums per workgroup
+size_t focal_workspace_bytes(int P);
+int launch_focal_grad(const das3r_raster_args *a, const das3r_raster_in *in, const char *geom, const Layout &L, const float *partial, bool quad_rows,
+                      bool aa /*ANTIALIAS_FLAG*/, float *sums /*[2]*/, float *per_splat /*[P,2] or null*/, float *workspace, hipStream_t s);
 // partial: [num_rendered, 9] per-instance sums written by the render backward, gathered by the preprocess backward
 // *quad_rows (out): false = partial[I][9], one row per instance; true = the stream kernel's rows[I][4][12] + existence bytes
 int launch_render_backward(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,

@@ -18,7 +18,12 @@ whole conf_static tensor for one frame's mask gradient, a dozen scalar kernels f
 
 Gradients land where FusedAdam expects them (`p.grad`, or the compact SH gradient of fused._ShPrefix's contract); the pose gradient
 is written into row `uid` of two dense, otherwise zero buffers (torch's index backward produces exactly that dense gradient, and
-Adam's moments of the other rows decay with it).  Semantics are those of das3r_amd.train.train_step(fused=True) — the tests hold
+Adam's moments of the other rows decay with it).  With a trainable field of view (OptimParams.fov_lr > 0) the step reads FoVx / FoVy back ONCE per iteration — tanfov and the projection
+matrix are host-side arguments of the C-ABI — which is a host synchronise the default step does not have (its cost: docs/ledger.md, the
+focal-gradient entry); the rasterizer's backward is then das3r_raster_backward_focal, and its two sums go to FoVx.grad / FoVy.grad through
+-1 / sin(FoV).  At fov_lr = 0 none of that runs.
+
+Semantics are those of das3r_amd.train.train_step(fused=True) — the tests hold
 both to the float64 trainer and to each other — and nothing here is reachable unless the caller opted into the fused kernels.
 """
 import ctypes as C
@@ -139,6 +144,30 @@ def _dense_hw(cam, name, H, W):
     return cache[1]
 
 
+def _read_fov(model):
+    """(FoVx, FoVy) of the model as host floats when its field of view is being trained (model.fov_lr > 0), else None: ONE device-to-host
+    copy, which waits for everything enqueued before it."""
+    if not float(getattr(model, "fov_lr", 0.0) or 0.0) > 0.0:
+        return None
+    fx, fy = torch.stack((model.FoVx.detach(), model.FoVy.detach())).tolist()
+    return float(fx), float(fy)
+
+
+def _settings_fov(st, cam, model, bg, fov):
+    """_settings with the field of view and the projection rebuilt from the model's (das3r_amd.render._settings(model_fov=True): the same
+    matrix from the same floats); not cached — the values move with every step."""
+    from .camera import projection_matrix
+    dev = st.dev
+    fx, fy = fov
+    pm = cam.get_projection_matrix(fx, fy) if hasattr(cam, "get_projection_matrix") else projection_matrix(0.01, 100.0, fx, fy).transpose(0, 1)
+    ident = torch.eye(4, device=dev)
+    proj = ident.unsqueeze(0).bmm(pm.to(dev).unsqueeze(0)).squeeze(0)
+    return GaussianRasterizationSettings(
+        image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(fx * 0.5), tanfovy=math.tan(fy * 0.5), bg=bg,
+        scale_modifier=1.0, viewmatrix=ident.contiguous(), projmatrix=proj.contiguous(), sh_degree=model.active_sh_degree,
+        campos=torch.zeros(3, device=dev), prefiltered=False, debug=False)
+
+
 def _settings(st, cam, model, bg):
     """GaussianRasterizationSettings of render() for this camera (gaussian_renderer/__init__.py:53-78): identity view matrix,
     projmatrix = I @ P^T, campos = 0.  Built once per (image size, FoV, projection-matrix tensor, SH degree, background tensor) —
@@ -165,8 +194,11 @@ def _settings(st, cam, model, bg):
 
 
 def forward_backward(model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda_dssim, bg, geometry="grads", rearm_rows=None, antialiasing=False,
-                     depth_weight=0.0, exposure=None, exposure_grad=None):
-    """Render `cam` with the pose (q_row, t_row: views of one row of Q / T), masked photometric loss against cam.original_image
+                     depth_weight=0.0, exposure=None, exposure_grad=None, fov=None, focal_grad=False):
+    """fov ((FoVx, FoVy) host floats, _read_fov; None: the camera's, today's calls): render with that field of view and the projection built
+    from it.  focal_grad (needs fov): the rasterizer's backward is das3r_raster_backward_focal and the package carries "focal_sums", the [2]
+    device tensor dL/d(log-focal offsets) of the loss.
+    Render `cam` with the pose (q_row, t_row: views of one row of Q / T), masked photometric loss against cam.original_image
     under `static_hw` [H, W], and the complete backward.  Gradients: model parameters' .grad (f_rest: compact or none, as in
     das3r_amd.render), the pose gradient into gq_row / gt_row, d loss / d static_hw returned.
     geometry: what becomes of the gradients of xyz / rotation / scaling / opacity, which exist in camera space when the rasterizer's backward
@@ -187,12 +219,14 @@ def forward_backward(model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda
     st = _state(model)
     with _on_device(st.dev):   # (the library's per-device state and the raw stream belong to the model's GPU, current or not)
         return _forward_backward(st, model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda_dssim, bg, geometry, rearm_rows, antialiasing,
-                                 float(depth_weight), exposure, exposure_grad)
+                                 float(depth_weight), exposure, exposure_grad, fov, focal_grad)
 
 
 def _forward_backward(st, model, cam, q_row, t_row, gq_row, gt_row, static_hw, lambda_dssim, bg, geometry, rearm_rows=None, antialiasing=False,
-                      depth_weight=0.0, exposure=None, exposure_grad=None):
+                      depth_weight=0.0, exposure=None, exposure_grad=None, fov=None, focal_grad=False):
     lib = _lib.load()
+    if focal_grad and fov is None:
+        raise ValueError("fast_step.forward_backward: focal_grad needs the field of view the step renders with (fov=)")
     dev, P = st.dev, st.P
     H, W = int(cam.image_height), int(cam.image_width)
     s = _stream(dev)
@@ -225,7 +259,7 @@ def _forward_backward(st, model, cam, q_row, t_row, gq_row, gt_row, static_hw, l
         shs = _packed_sh(st, model, K)
     else:
         shs = _packed_sh(st, model, 1 + model._features_rest.shape[1])
-    rs = _settings(st, cam, model, bg)
+    rs = _settings(st, cam, model, bg) if fov is None else _settings_fov(st, cam, model, bg, fov)
     e = st.e
     depth = depth_weight > 0.0
     if depth and geometry == "pose":
@@ -283,9 +317,9 @@ def _forward_backward(st, model, cam, q_row, t_row, gq_row, gt_row, static_hw, l
         chain.g_conf_flat, chain.g_small, chain.slots = g_conf.data_ptr(), st.g_small.data_ptr(), slots
         chain.beta1, chain.beta2, chain.eps = opt_.betas[0], opt_.betas[1], opt_.eps
         conf_grad = g_conf
-    g_means2D, _g_colors, g_opac, g_means3D, _g_cov, g_sh, g_scales, g_rot = _backward_impl(
-        rs, I, d_render, means3D, shs, e, opac, scales, rotations, e, geom, binning, img, cap, pre=pre, chain=chain,
-        **({"grad_invdepth": d_invdepth} if depth else {}))
+    bwd = _backward_impl(rs, I, d_render, means3D, shs, e, opac, scales, rotations, e, geom, binning, img, cap, pre=pre, chain=chain,
+                         **({"grad_invdepth": d_invdepth} if depth else {}), **({"focal": True} if focal_grad else {}))
+    g_means2D, _g_colors, g_opac, g_means3D, _g_cov, g_sh, g_scales, g_rot = bwd[:8]
     # ---- pre-transform backward, pose chain rule
     if chain is not None:
         del keep
@@ -333,6 +367,8 @@ def _forward_backward(st, model, cam, q_row, t_row, gq_row, gt_row, static_hw, l
     pkg = _Pkg(render=image, viewspace_points=st.means2D, radii=radii)
     if depth:
         pkg["invdepth"] = invdepth
+    if focal_grad:
+        pkg["focal_sums"] = bwd[8]
     return out8, d_static, pkg
 
 
@@ -355,6 +391,9 @@ def train_step(model, cam, opt, iteration, pipe, background):
             if st.Eg is None or st.Eg.shape != E.shape:
                 st.Eg = torch.zeros_like(E)
             expo = dict(exposure=E.detach()[uid], exposure_grad=(st.Eg[uid], None if prev is None else st.Eg[prev]))
+        fov = _read_fov(model)   # (None at fov_lr = 0: nothing below differs from today's step)
+        if fov is not None:
+            expo.update(fov=fov, focal_grad=True)
         out8, d_static, pkg = forward_backward(model, cam, model.Q[uid], model.T[uid], st.Qg[uid], st.Tg[uid], model._conf_static[uid],
                                                opt.lambda_dssim, background, geometry="adam" if getattr(model, "fuse_geometry_adam", True) else "grads",
                                                rearm_rows=None if prev is None else (st.Qg[prev], st.Tg[prev]),
@@ -366,6 +405,10 @@ def train_step(model, cam, opt, iteration, pipe, background):
         model.optimizer.step()
         model.optimizer.zero_grad(set_to_none=True)
         model.Q.grad, model.T.grad = st.Qg, st.Tg
+        if fov is not None:   # dL/dFoV = -dL/ds / sin(FoV): the two tensors step inside the gated launch of the poses
+            from .model import fov_grad_from_log_focal
+            sums = pkg["focal_sums"]
+            model.FoVx.grad, model.FoVy.grad = fov_grad_from_log_focal(sums[0], fov[0]), fov_grad_from_log_focal(sums[1], fov[1])
         model.optimizer_cam.step(gate=out8[4], threshold=opt.psnr_threshold)
         model.optimizer_cam.zero_grad(set_to_none=True)
     return out8[0], out8[4], pkg
@@ -376,7 +419,8 @@ def test_pose_step(model, cam, static_hw, opt, background, pipe=None, exposure=N
     loss, backward — and every gradient dropped: the Gaussian optimizer is zeroed without a step and optimizer_cam owns no
     gradient here.  Reproduced for its cost; nothing changes.
     exposure: the [3, 4] matrix the held-out policy gives this view (train.heldout_exposure), or None (identity: today's calls); its
-    gradient is never taken and the exposure group never steps here."""
+    gradient is never taken and the exposure group never steps here.  With a trainable field of view (model.fov_lr > 0) the view is rendered
+    with the model's FoVx / FoVy (one read-back); no focal gradient is computed."""
     st = _state(model)
     uid = cam.uid
     if st.tQg is None:   # (the held-out poses were set after the first training step)
@@ -385,7 +429,8 @@ def test_pose_step(model, cam, static_hw, opt, background, pipe=None, exposure=N
         out8, _d_static, _pkg = forward_backward(model, cam, model.test_Q[uid], model.test_T[uid], st.tQg[uid], st.tTg[uid], static_hw,
                                                  opt.lambda_dssim, background, geometry="pose",
                                                  antialiasing=bool(getattr(pipe, "antialiasing", False)),
-                                                 **({"exposure": exposure.detach().contiguous()} if exposure is not None else {}))
+                                                 **({"exposure": exposure.detach().contiguous()} if exposure is not None else {}),
+                                                 **({"fov": _read_fov(model)} if float(getattr(model, "fov_lr", 0.0) or 0.0) > 0.0 else {}))
         model.optimizer.zero_grad(set_to_none=True)
         model.optimizer_cam.zero_grad(set_to_none=True)
     return out8

@@ -394,3 +394,39 @@ def read_exposure_json(path):
         out[name] = a
     return out
 
+
+
+FOV_JSON_KEYS = ("FoVx", "FoVy", "focal_x", "focal_y", "iteration")
+
+
+def write_fov_json(path, FoVx, FoVy, width, height, iteration):
+    """<out>/<sequence>/fov.json of a job that trained its field of view (OptimParams.fov_lr > 0): {"FoVx", "FoVy"} in radians, the focal
+    lengths {"focal_x", "focal_y"} = (width, height) / (2 tan(FoV / 2)) in pixels of the training images, and the iteration they are from.
+    Written under a temporary name first."""
+    import json
+    import math
+    fx, fy = float(FoVx), float(FoVy)
+    if not (0.0 < fx < math.pi and 0.0 < fy < math.pi):
+        raise ValueError(f"write_fov_json: fields of view ({fx}, {fy}) outside (0, pi)")
+    rec = {"FoVx": fx, "FoVy": fy, "focal_x": float(width) / (2.0 * math.tan(0.5 * fx)), "focal_y": float(height) / (2.0 * math.tan(0.5 * fy)),
+           "iteration": int(iteration)}
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path + ".tmp", "w") as f:
+        json.dump(rec, f, indent=2)
+    os.replace(path + ".tmp", path)
+    return rec
+
+
+def read_fov_json(path):
+    """-> write_fov_json's dict; a file without one of its keys or with a field of view outside (0, pi) is an error."""
+    import json
+    import math
+    with open(path) as f:
+        raw = json.load(f)
+    missing = [k for k in FOV_JSON_KEYS if k not in raw]
+    if missing:
+        raise ValueError(f"{path}: missing {missing}")
+    out = {k: (int(raw[k]) if k == "iteration" else float(raw[k])) for k in FOV_JSON_KEYS}
+    if not (0.0 < out["FoVx"] < math.pi and 0.0 < out["FoVy"] < math.pi):
+        raise ValueError(f"{path}: fields of view ({out['FoVx']}, {out['FoVy']}) outside (0, pi)")
+    return out

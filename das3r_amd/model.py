@@ -8,9 +8,12 @@ conf_static = 1 - dyna_avg with shape (frames, H, W); the two Adam optimizers (l
 groups and LRs and the exponential schedules (:228-323; defaults /root/reference/arguments/__init__.py:73-90);
 oneupSHdegree (:199-201); pose parameters Q/T as (frames,4)/(frames,3) tensors (:149-184); the held-out views' poses
 test_Q/test_T with their own optimizer (:132-147,263-268) and the FoVx/FoVy "parameters" of the camera optimizer (:163-166,
-253-254).  The last two are INERT in the reference and therefore here: render() turns FoV into Python floats with math.tan, so
-no gradient ever reaches FoVx/FoVy (Adam skips parameters whose .grad is None and never creates state for them),
-and the test-pose pass of train_test_psnr.py steps optimizer_cam — which holds Q/T, not test_Q/test_T — so optimizer_cam_test is
+253-254).  The last two are INERT in the reference and therefore here BY DEFAULT: render() turns FoV into Python floats with
+math.tan, so no gradient ever reaches FoVx/FoVy (Adam skips parameters whose .grad is None and never creates state for
+them).  OptimParams.fov_lr > 0 makes the field of view trainable: das3r_render then renders with the model's FoVx / FoVy and hands the
+rasterizer log_focal = (-log tan(FoVx / 2), -log tan(FoVy / 2)), whose gradient a kernel of its own computes beside the backward pass
+(das3r_raster_backward_focal), so autograd reaches FoVx / FoVy (dL/dFoV = -dL/ds / sin(FoV)); the two groups take fov_lr and step with
+the camera optimizer under its PSNR gate.  At fov_lr = 0 (the default) everything is as in the reference.  The test-pose pass of train_test_psnr.py steps optimizer_cam — which holds Q/T, not test_Q/test_T — so optimizer_cam_test is
 built and never stepped (C5).  They are kept so that optimizer groups, their order and their state match the reference's.
 """
 from dataclasses import dataclass
@@ -57,6 +60,22 @@ class OptimParams:   # /root/reference/arguments/__init__.py:73-90 (densificatio
     # to _final over `iterations`.  Both 0: off — no parameter, no optimizer group.  Upstream: 0.01 -> 0.001.
     exposure_lr_init: float = 0.0
     exposure_lr_final: float = 0.0
+    # trainable field of view (the reference builds the two optimizer groups and never feeds them: module docstring): the learning rate of
+    # the fovX / fovY groups.  0: off — the groups stay inert at the reference's 1e-4, every render takes the camera's field of view.
+    fov_lr: float = 0.0
+
+
+def log_focal_of(fovx, fovy):
+    """(-log tan(FoVx / 2), -log tan(FoVy / 2)) as a [2] tensor: the log-focal offsets GaussianRasterizer(...)(..., log_focal=...) takes, up to
+    the constant log(W / 2), log(H / 2).  Differentiable: ds/dFoV = -1 / sin(FoV)."""
+    return torch.stack((-torch.log(torch.tan(0.5 * fovx)), -torch.log(torch.tan(0.5 * fovy))))
+
+
+def fov_grad_from_log_focal(g_s, fov):
+    """dL/dFoV from dL/ds of s = -log tan(FoV / 2) — what autograd does through log_focal_of, for the step that has no autograd
+    (das3r_amd/fast_step.py).  fov: a host float or a tensor."""
+    import math
+    return g_s * (-1.0 / (math.sin(fov) if isinstance(fov, float) else torch.sin(fov)))
 
 
 def depth_to_points(K, cam2world, depth):
@@ -80,6 +99,7 @@ class SplatModel:
         self.enable_test = False
         self.test_Q = self.test_T = None
         self.FoVx = self.FoVy = None
+        self.fov_lr = 0.0              # OptimParams.fov_lr of the last training_setup: > 0 = das3r_render renders with, and trains, FoVx / FoVy
         self._exposure = None          # [n_train, 3, 4] nn.Parameter while exposure compensation is on (training_setup), else None
         self.exposure_frames = None    # frame index of every training view (train.build_from_sequence): the "nearest" held-out policy
 
@@ -217,8 +237,15 @@ class SplatModel:
             self._exposure = None
         self._lr_exposure = expon_lr_func(e0, e1, max_steps=opt.iterations)
         cam = [{"params": [self.Q], "lr": 0.00003, "name": "pose_Q"}, {"params": [self.T], "lr": 0.00003, "name": "pose_T"}]
-        if self.FoVx is not None:   # gaussian_model.py:253-254 (inert: module docstring)
-            cam += [{"params": [self.FoVx], "lr": 0.0001, "name": "fovX"}, {"params": [self.FoVy], "lr": 0.0001, "name": "fovY"}]
+        self.fov_lr = float(getattr(opt, "fov_lr", 0.0) or 0.0)
+        if not (self.fov_lr >= 0.0 and self.fov_lr < float("inf")):
+            raise ValueError(f"OptimParams.fov_lr must be finite and >= 0 (got {self.fov_lr})")
+        if self.fov_lr > 0.0 and self.FoVx is None:
+            raise RuntimeError("OptimParams.fov_lr > 0 trains the model's field of view: call SplatModel.init_fov(FoVx, FoVy) first "
+                               "(build_from_sequence does)")
+        if self.FoVx is not None:   # gaussian_model.py:253-254 (inert unless fov_lr > 0: module docstring)
+            fov_lr = self.fov_lr if self.fov_lr > 0.0 else 0.0001
+            cam += [{"params": [self.FoVx], "lr": fov_lr, "name": "fovX"}, {"params": [self.FoVy], "lr": fov_lr, "name": "fovY"}]
         cam_test = None
         if self.enable_test:        # gaussian_model.py:263-268 (built, never stepped: module docstring)
             cam_test = [{"params": [self.test_Q], "lr": 0.00003, "name": "test_pose_Q"},
@@ -227,8 +254,9 @@ class SplatModel:
             from .fused import FusedAdam
             groups[2]["sh_rest"] = True
             self.optimizer = FusedAdam(groups, lr=0.0, eps=1e-15)
-            self.optimizer_cam = FusedAdam(cam[:2], lr=0.0, eps=1e-15)   # stepped with a device-side PSNR gate (train.py); the
-            #                                                                inert FoV groups have nothing to fuse
+            # stepped with a device-side PSNR gate (train.py); the FoV groups while inert have nothing to fuse, trained (fov_lr > 0) they
+            # are two more tensors of the same gated launch
+            self.optimizer_cam = FusedAdam(cam if self.fov_lr > 0.0 else cam[:2], lr=0.0, eps=1e-15)
         else:
             self.optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
             self.optimizer_cam = torch.optim.Adam(cam, lr=0.0, eps=1e-15)

@@ -94,6 +94,17 @@ def sequence_cameras(seq, device="cuda"):
     return cams
 
 
+def apply_fov(views, fovx, fovy):
+    """Give every camera the field of view (radians) of a job that trained it — <model_path>/fov.json — and the projection built from it
+    (train.make_camera's matrix at those values).  In place; -> views."""
+    from .camera import projection_matrix
+    for v in views:
+        dev = v.projection_matrix.device
+        v.FoVx, v.FoVy = float(fovx), float(fovy)
+        v.projection_matrix = projection_matrix(0.01, 100.0, float(fovx), float(fovy)).transpose(0, 1).to(dev)
+    return views
+
+
 PIPE = SimpleNamespace(debug=False, compute_cov3D_python=False, convert_SHs_python=False)
 
 
@@ -228,7 +239,8 @@ def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=
 
 
 def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=False, optimised_poses=False, device="cuda", write=True, fused=False,
-                depth=False, pipe=PIPE, prune_min_opacity=0.0, write_pruned_ply=False, exposure="none", static_map=False, alpha=False, thin_edge=None, thin_relative=None):
+                depth=False, pipe=PIPE, prune_min_opacity=0.0, write_pruned_ply=False, exposure="none", static_map=False, alpha=False, thin_edge=None, thin_relative=None,
+                camera_fov=False):
     """render.py:89-123: load the trained model, write pose_interpolated.npy, render the "interp" set.  seq: the sequence the model was
     trained on (its cameras).  depth: also the inverse-depth images (invdepth/%05d.npy) and, per view, the median relative error of
     1 / invdepth against the sequence's depth map (printed: a diagnostic).  pipe: PIPE, or pipe_from_args' (pipe.antialiasing: a model
@@ -240,7 +252,9 @@ def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=Fal
     static-confidence map and coverage map (render_set: static/%05d.npy, alpha/%05d.npy).  thin_edge (world units) / thin_relative (multiples of
     the pixel footprint of `seq`'s depth maps and intrinsics: das3r_amd.thin.pixel_footprint over its confident pixels), at most one: the loaded
     model is thinned to one Gaussian per voxel first (das3r_amd.thin.thin_model, after prune_min_opacity's event when both are given);
-    write_pruned_ply then saves the thinned model.  -> (iteration, list of rendered images)"""
+    write_pruned_ply then saves the thinned model.  A model directory that holds fov.json (a job that trained its field of view: farm
+    --fov-lr) is rendered with that field of view; camera_fov: ignore the file and keep the cameras' own.  Without the file: today's output.
+    -> (iteration, list of rendered images)"""
     if exposure not in ("none", "train"):
         raise ValueError(f'render_sets: exposure must be "none" or "train", got {exposure!r}')
     if thin_edge is not None and thin_relative is not None:
@@ -266,6 +280,12 @@ def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=Fal
     inter = save_interpolate_pose(model_path, iteration)
     bg = torch.tensor([1.0, 1.0, 1.0] if white_background else [0.0, 0.0, 0.0], dtype=torch.float32, device=device)
     views = sequence_cameras(seq, device)
+    fov_path = os.path.join(model_path, "fov.json")
+    if not camera_fov and os.path.exists(fov_path):
+        from .io_formats import read_fov_json
+        fov = read_fov_json(fov_path)
+        apply_fov(views, fov["FoVx"], fov["FoVy"])
+        print(f"rendering with the trained field of view of {fov_path}: focal {fov['focal_x']:.3f} x {fov['focal_y']:.3f} px")
     frames = list(range(len(views)))   # (the sequence frame of each view: its depth map)
     poses = None
     if optimised_poses:
@@ -345,6 +365,8 @@ def parser():
                     "point_cloud/iteration_N/point_cloud_pruned.ply")
     ap.add_argument("--exposure", default="none", choices=("none", "train"), help='"train": write the training views compensated with the matrices '
                     "of <model-path>/exposure.json (a job trained with --exposure-lr-init / --exposure-lr-final); none: the raw renders")
+    ap.add_argument("--camera-fov", action="store_true", help="keep the cameras' own field of view even when <model-path>/fov.json (a job trained with "
+                    "farm --fov-lr) holds a trained one")
     ap.add_argument("--static-map", action="store_true", help="also write every view's static-confidence map (static/%%05d.npy next to renders/): the "
                     "model's per-Gaussian conf_static blended over the view's own lists, at any view, without a second forward")
     ap.add_argument("--alpha", action="store_true", help="also write every view's coverage map 1 - T (alpha/%%05d.npy next to renders/)")
@@ -358,7 +380,7 @@ def main(argv=None):
     seq = load_sequence(args.source_path, device="cuda", dataset=args.dataset)
     it, imgs = render_sets(args.model_path, seq, args.iteration, args.sh_degree, args.white_background, args.optimised_poses, fused=args.fused,
                            depth=args.depth, pipe=pipe_from_args(args), prune_min_opacity=args.prune_min_opacity, write_pruned_ply=args.write_pruned_ply,
-                           exposure=args.exposure, static_map=args.static_map, alpha=args.alpha,
+                           exposure=args.exposure, static_map=args.static_map, alpha=args.alpha, **({"camera_fov": True} if args.camera_fov else {}),
                            **({"thin_edge": args.thin_edge, "thin_relative": args.thin_relative}
                               if (args.thin_edge is not None or args.thin_relative is not None) else {}))
     print(f"wrote {len(imgs)} images to {os.path.join(args.model_path, 'interp', f'ours_{it}', 'renders')}")

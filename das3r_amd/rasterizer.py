@@ -242,9 +242,14 @@ def _forward_full(rs, means3D, sh, colors_precomp, opacities, scales, rotations,
 
 
 def _backward_impl(rs, num_rendered, grad_out_color, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                   geom, binning, img, capacity=None, _scratch_misalign=0, pre=None, chain=None, grad_invdepth=None):
+                   geom, binning, img, capacity=None, _scratch_misalign=0, pre=None, chain=None, grad_invdepth=None, focal=False,
+                   focal_per_splat=False, _fill=None):
     """grad_invdepth ([1, H, W] or None): also the backward of the forward's inverse-depth image (ABI 16, das3r_raster_backward_depth; the
-    forward must have been made with invdepth=True).  grad_out_color may then be None (zero)."""
+    forward must have been made with invdepth=True).  grad_out_color may then be None (zero).
+    focal: the same backward through das3r_raster_backward_focal — the result gains (sums [2], per_splat [P, 2] or None): dL/d(log-focal
+    offsets) of the same loss and, with focal_per_splat, every splat's share of it (include/das3r_raster.h).
+    (_fill: tests fill everything the library is said to write without reading — the scratch, and with focal sums, per_splat and the
+    workspace — with this value before the call.)"""
     ticket = capacity
     capacity = int(num_rendered) if capacity is None else int(capacity)
     lib = _lib.load()
@@ -263,7 +268,8 @@ def _backward_impl(rs, num_rendered, grad_out_color, means3D, sh, colors_precomp
     g_scales, g_rot = (None, None) if (has_cov or chain is not None) else (z(P, 3), z(P, 4))
     g_cov = z(P, 6) if has_cov else None
     if P == 0:
-        return g_means2D, g_colors, g_opac, g_means3D, g_cov, g_sh, g_scales, g_rot
+        out = (g_means2D, g_colors, g_opac, g_means3D, g_cov, g_sh, g_scales, g_rot)
+        return out + (torch.zeros(2, dtype=torch.float32, device=device), z(0, 2) if focal_per_splat else None) if focal else out
     # per-instance partial sums, written by the render backward and added per Gaussian (no atomics, no memset by the caller)
     # (_scratch_misalign: tests hand the library a scratch buffer that is only 4-byte aligned — a C caller may)
     depth = grad_invdepth is not None
@@ -292,10 +298,26 @@ def _backward_impl(rs, num_rendered, grad_out_color, means3D, sh, colors_precomp
     dL = grad_out_color.contiguous() if grad_out_color is not None else torch.zeros(3, H, W, dtype=torch.float32, device=device)
     if dL.dtype != torch.float32:
         dL = dL.float()
+    dD = None
     if depth:
         dD = grad_invdepth.contiguous()
         if dD.dtype != torch.float32:
             dD = dD.float()
+    if _fill is not None:
+        scratch[int(_scratch_misalign):][:int(nbytes) // 4 * 4].view(torch.float32).fill_(_fill)
+    if focal:   # (sums, per_splat and the workspace are written in full by the library)
+        sums, per = z(2), (z(P, 2) if focal_per_splat else None)
+        work = torch.empty(int(lib.das3r_raster_focal_workspace_bytes(P)), dtype=torch.uint8, device=device)
+        if _fill is not None:
+            for t in (sums, per, work.view(torch.float32)):
+                if t is not None:
+                    t.fill_(_fill)
+        with _on_device(device):
+            rc = lib.das3r_raster_backward_focal(C.byref(a), C.byref(i), C.byref(saved), C.c_void_p(dL.data_ptr()), _ptr(dD), C.byref(g),
+                                                 C.c_void_p(sums.data_ptr()), _ptr(per), C.c_void_p(work.data_ptr()), _stream(device))
+        _lib.check(rc, "das3r_raster_backward_focal")
+        return g_means2D, g_colors, g_opac, g_means3D, g_cov, g_sh, g_scales, g_rot, sums, per
+    if depth:
         with _on_device(device):
             rc = lib.das3r_raster_backward_depth(C.byref(a), C.byref(i), C.byref(saved), C.c_void_p(dL.data_ptr()), C.c_void_p(dD.data_ptr()),
                                                  C.byref(g), _stream(device))
@@ -498,7 +520,12 @@ def alpha_of(state):
     return 1.0 - T
 
 
-def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, antialiasing=False):
+def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, antialiasing=False,
+                        log_focal=None):
+    """log_focal ([2] tensor or None): see GaussianRasterizer.forward's docstring."""
+    if log_focal is not None:
+        return _apply(_RasterizeGaussiansFocal, _check_log_focal(log_focal, means3D.device), False, means3D, means2D, sh, colors_precomp, opacities,
+                      scales, rotations, cov3Ds_precomp, raster_settings, antialiasing=antialiasing)
     return _apply(_RasterizeGaussians, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
                   antialiasing=antialiasing)
 
@@ -565,15 +592,18 @@ class _RasterizeGaussians(torch.autograd.Function):
         return _RasterizeGaussians._backward(ctx, grad_out_color, None)
 
     @staticmethod
-    def _backward(ctx, grad_out_color, grad_invdepth):
+    def _backward(ctx, grad_out_color, grad_invdepth, focal=False):
+        """focal: through das3r_raster_backward_focal; the tuple then ends with dL/d(log-focal offsets) [2] (or None)."""
         rs = ctx.raster_settings
         if grad_out_color is None and grad_invdepth is None:   # (grads are not materialised) nothing flows back
-            return (None,) * 9
+            return (None,) * (10 if focal else 9)
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, opacities, geomBuffer, binningBuffer,
          imgBuffer) = ctx.saved_tensors
         args = (rs, ctx.num_rendered, grad_out_color, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 geomBuffer, binningBuffer, imgBuffer, ctx.capacity)
         kw = {} if grad_invdepth is None else {"grad_invdepth": grad_invdepth}   # (None: today's das3r_raster_backward call)
+        if focal:
+            kw["focal"] = True
         if rs.debug:
             cpu_args = cpu_deep_copy_tuple(args)
             try:
@@ -584,10 +614,37 @@ class _RasterizeGaussians(torch.autograd.Function):
                 raise ex
         else:
             out = _backward_impl(*args, **kw)
-        g_means2D, g_colors, g_opac, g_means3D, g_cov, g_sh, g_scales, g_rot = out
+        g_means2D, g_colors, g_opac, g_means3D, g_cov, g_sh, g_scales, g_rot = out[:8]
+        tail = (out[8],) if focal else ()
         return (g_means3D, g_means2D, g_sh if sh.numel() else None, g_colors if colors_precomp.numel() else None, g_opac,
                 g_scales if scales.numel() else None, g_rot if rotations.numel() else None,
-                g_cov if cov3Ds_precomp.numel() else None, None)
+                g_cov if cov3Ds_precomp.numel() else None, None) + tail
+
+
+def _check_log_focal(log_focal, device):
+    if not torch.is_tensor(log_focal) or log_focal.numel() != 2 or log_focal.dtype != torch.float32:
+        raise ValueError("log_focal must be a float32 tensor of 2 elements (log-focal offsets in x and y)")
+    if log_focal.device != device:
+        raise RuntimeError(f"log_focal is on {log_focal.device}, expected {device}")
+    return log_focal
+
+
+class _RasterizeGaussiansFocal(torch.autograd.Function):
+    """_RasterizeGaussians / _RasterizeGaussiansInvDepth with one more input, log_focal [2]: its value is not read (like the dummy means2D — the
+    caller built raster_settings from the same field of view); when it takes a gradient the backward is das3r_raster_backward_focal and
+    returns dL/d(log-focal offsets) for it, otherwise today's calls."""
+    @staticmethod
+    def forward(ctx, log_focal, invdepth, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
+        ctx.focal_shape = log_focal.shape
+        return _RasterizeGaussians._forward(ctx, bool(invdepth), means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _grad_radii, grad_invdepth=None):
+        if not ctx.needs_input_grad[0]:
+            return (None, None) + _RasterizeGaussians._backward(ctx, grad_out_color, grad_invdepth)
+        out = _RasterizeGaussians._backward(ctx, grad_out_color, grad_invdepth, focal=True)
+        g_focal = out[9]
+        return (None if g_focal is None else g_focal.reshape(ctx.focal_shape), None) + out[:9]
 
 
 class _RasterizeGaussiansInvDepth(torch.autograd.Function):
@@ -609,6 +666,16 @@ class GaussianRasterizer(nn.Module):
         self.raster_settings = raster_settings
         self.keep_state = bool(keep_state)
         self.state = None
+
+    def __call__(self, *args, log_focal=None, **kwargs):
+        """The module call takes one keyword more than forward(): log_focal (forward's docstring).  None: nn.Module's call, as it was."""
+        if log_focal is None:
+            return super().__call__(*args, **kwargs)
+        _last.log_focal = log_focal
+        try:
+            return super().__call__(*args, **kwargs)
+        finally:
+            _last.log_focal = None
 
     def markVisible(self, positions):
         with torch.no_grad():
@@ -638,8 +705,15 @@ class GaussianRasterizer(nn.Module):
         features ([P, C] fp32) / return_alpha: the extra results come after the others — (color, radii[, invdepth][, feature_image]
         [, alpha]) — feature_image [C, H, W] = composite_features over this forward's lists (differentiable with respect to `features`
         only: the geometry is constant in an aux channel), alpha [1, H, W] = alpha_of.  The colour, the radii and every gradient of a
-        colour loss are the same bit for bit; with both at their defaults the call is the one it was."""
+        colour loss are the same bit for bit; with both at their defaults the call is the one it was.
+        log_focal ([2] fp32 tensor; a keyword of the module CALL — rasterizer(..., log_focal=t), see __call__ — so that this method keeps the
+        parameters it had): log-focal offsets (s_x, s_y) of the camera, e.g. (-log tan(FoVx / 2), -log tan(FoVy / 2)).  Like the
+        dummy means2D its VALUE is not read — raster_settings (tanfov, projmatrix) must have been built from the same field of view.  When
+        it requires grad the backward pass returns dL/ds for it (das3r_raster_backward_focal: the rendering with tanfov e^(-s) and the
+        clip-x / clip-y columns of projmatrix scaled by e^(s), every discrete decision held fixed), with and without return_invdepth /
+        antialiasing; every other gradient is the same bit for bit.  None: the functions and library calls are the ones they were."""
         raster_settings = self.raster_settings
+        log_focal, _last.log_focal = getattr(_last, "log_focal", None), None   # (handed over by __call__; consumed here)
         want_state = features is not None or return_alpha or self.keep_state
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
@@ -662,20 +736,23 @@ class GaussianRasterizer(nn.Module):
             _last.want_state, _last.state = True, None
         try:
             return self._forward_checked(means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, return_invdepth,
-                                         antialiasing, features, return_alpha, want_state)
+                                         antialiasing, features, return_alpha, want_state, log_focal)
         finally:
             if want_state:
                 _last.want_state, _last.state = False, None
 
     def _forward_checked(self, means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, return_invdepth, antialiasing,
-                         features, return_alpha, want_state):
+                         features, return_alpha, want_state, log_focal=None):
         raster_settings = self.raster_settings
-        if return_invdepth:
+        if log_focal is not None and return_invdepth:
+            color, radii, invdepth = _apply(_RasterizeGaussiansFocal, _check_log_focal(log_focal, means3D.device), True, means3D, means2D, shs,
+                                            colors_precomp, opacities, scales, rotations, cov3D_precomp, raster_settings, antialiasing=antialiasing)
+        elif return_invdepth:
             color, radii, invdepth = _apply(_RasterizeGaussiansInvDepth, means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                             cov3D_precomp, raster_settings, antialiasing=antialiasing)
         else:
             color, radii = rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                               raster_settings, antialiasing=antialiasing)
+                                               raster_settings, antialiasing=antialiasing, **({} if log_focal is None else {"log_focal": log_focal}))
         if not color.requires_grad and getattr(_last, "capacity", None) is not None:
             # evaluation (torch.no_grad, or no input that takes a gradient): no backward pass will examine this forward's binning
             # self-check, so it is examined here, before the image is used (include/das3r_raster.h: das3r_raster_check)

@@ -106,7 +106,15 @@ def rasterizer_inputs(cam, pc, pipe, bg_color, scaling_modifier=1.0, override_co
         means2D.retain_grad()
     except Exception:  # noqa: BLE001
         pass
-    settings = _settings(cam, pc, pipe, bg_color, scaling_modifier, device, model_fov=variant == "no_soft")
+    # OptimParams.fov_lr > 0 (SplatModel.training_setup): the "render" variant takes the field of view from the model, as no_soft does, and
+    # hands the rasterizer its log-focal offsets — a [2] tensor whose value is not read and whose gradient the backward pass fills
+    # (GaussianRasterizer(...)(..., log_focal=...)), so that autograd reaches pc.FoVx / pc.FoVy
+    train_fov = variant == "render" and float(getattr(pc, "fov_lr", 0.0) or 0.0) > 0.0
+    settings = _settings(cam, pc, pipe, bg_color, scaling_modifier, device, model_fov=variant == "no_soft" or train_fov)
+    extra = {}
+    if train_fov:
+        from .model import log_focal_of
+        extra["log_focal"] = log_focal_of(pc.FoVx, pc.FoVy)
     cov_python = bool(getattr(pipe, "compute_cov3D_python", False))
     sh_python = bool(getattr(pipe, "convert_SHs_python", False))
 
@@ -136,7 +144,7 @@ def rasterizer_inputs(cam, pc, pipe, bg_color, scaling_modifier=1.0, override_co
         else:
             shs = pc.get_features
         return settings, dict(means3D=means3D, means2D=means2D, shs=shs, colors_precomp=None, opacities=opacity, scales=scales,
-                              rotations=rotations, cov3D_precomp=None)
+                              rotations=rotations, cov3D_precomp=None, **extra)
 
     w2c = camera_from_tensor(camera_pose)
     pts = pc._xyz.clone()[filtering]
@@ -151,7 +159,7 @@ def rasterizer_inputs(cam, pc, pipe, bg_color, scaling_modifier=1.0, override_co
     elif variant == "render" and use_conf:
         opacity = opacity * pc._conf_static.reshape(-1, 1)[pc.aggregated_mask]
     kw = dict(means3D=means3D, means2D=means2D, shs=None, colors_precomp=None, opacities=opacity, scales=None, rotations=None,
-              cov3D_precomp=None)
+              cov3D_precomp=None, **extra)
     if cov_python:
         kw["cov3D_precomp"] = (pc.get_covariance(scaling_modifier) if hasattr(pc, "get_covariance")
                                else covariance_from_scaling_rotation(pc.get_scaling, scaling_modifier, pc._rotation))
@@ -194,7 +202,10 @@ def das3r_render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, ove
     features ([P, C] fp32, one row per rasterised Gaussian — after `filtering`): render_pkg["features"] = the [C, H, W] image of those
     channels blended over this render's own lists (rasterizer.composite_features: no second forward; differentiable with respect to
     `features` only, the geometry is constant in an aux channel).  return_alpha: render_pkg["alpha"] = [1, H, W] coverage, 1 - final T.
-    return_state: render_pkg["raster_state"] = the forward's RasterState, for further composite_features / feature_adjoint calls."""
+    return_state: render_pkg["raster_state"] = the forward's RasterState, for further composite_features / feature_adjoint calls.
+    With OptimParams.fov_lr > 0 (pc.fov_lr) the "render" variant takes the field of view and the projection from pc.FoVx / pc.FoVy instead
+    of the camera's — training, held-out passes and reports alike — and a backward pass leaves dL/dFoV on them (one host read-back of the
+    two values per render: the settings are host floats)."""
     settings, kw = rasterizer_inputs(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, camera_pose, filtering,
                                      use_conf, fused, variant)
     rasterizer = GaussianRasterizer(raster_settings=settings, keep_state=True) if return_state else GaussianRasterizer(raster_settings=settings)

@@ -201,6 +201,24 @@ int das3r_raster_backward_depth(const das3r_raster_args *args, const das3r_raste
  * first column is the per-instance sum over pixels of alpha T dL/dinvdepth. */
 size_t das3r_raster_backward_depth_scratch_bytes(int64_t capacity);
 
+/* Additive under ABI 16: a backward pass that also returns the gradient of its loss with respect to two log-focal offsets s = (s_x, s_y).
+ * The forward at s is the forward with tanfovx e^(-s_x), tanfovy e^(-s_y) and the clip-x / clip-y columns of projmatrix (elements 4r and
+ * 4r + 1) scaled by e^(s_x) / e^(s_y); sums[0 .. 1] = dL/ds at s = 0 for L = <dL_dpix, colour> (+ <dL_dinvdepth, inverse depth>), every
+ * discrete decision of the forward held fixed (cull, radius, tile rectangle, lists, the 1/255 and T < 1e-4 cut-offs, the EWA clamp flags; a
+ * clamped ray is a constant, as it is for dL/dmeans3D).  With s_x = -log tan(FoVx / 2): dL/dFoVx = -sums[0] / sin(FoVx).
+ * It is the whole backward: with dL_dinvdepth == NULL das3r_raster_backward, otherwise das3r_raster_backward_depth — the same launches, the
+ * same gradient tensors bit for bit, grads->scratch sized by the matching *_scratch_bytes — with one per-Gaussian kernel and its one-workgroup
+ * finish in front of the per-Gaussian backward (with grads->chain: before the Adam step touches the parameters).
+ * per_splat ([P,2] or NULL): every splat's own contribution, exact zeros for a splat that reached no tile; sums is their sum in a fixed order
+ * (no float atomics: bit-identical from run to run).  workspace: das3r_raster_focal_workspace_bytes(P) bytes, 4-byte aligned.  Neither sums,
+ * per_splat nor workspace needs initialising.  P == 0 or nothing rendered: sums = 0, per_splat = 0.
+ * NULL sums / workspace, and with dL_dinvdepth whatever das3r_raster_backward_depth refuses: DAS3R_ERR_INVALID_ARG before anything is launched. */
+size_t das3r_raster_focal_workspace_bytes(int32_t P);
+int das3r_raster_backward_focal(const das3r_raster_args *args, const das3r_raster_in *in, const das3r_raster_saved *saved,
+                                const float *dL_dpix /* [3,H,W] */, const float *dL_dinvdepth /* [H,W], or NULL: colour only */,
+                                const das3r_raster_grads *grads, float *sums /* [2] */, float *per_splat /* [P,2] or NULL */, float *workspace,
+                                das3r_stream_t stream);
+
 /* das3r_raster_forward returns as soon as its kernels are enqueued.  Its binning kernels check themselves (a bounded wait on
  * another workgroup that timed out, an index out of range, counts that do not add up) and leave one word for the host; this call
  * waits (bounded) for that word of the forward that produced `saved` and returns DAS3R_ERR_HIP if the forward's image and lists are

@@ -87,6 +87,25 @@ class PathPolicyPlan(C.Structure):
                 ("decide_fine", C.c_int32), ("gen", C.c_uint32), ("cap", C.c_int64)]
 
 
+class Switches(C.Structure):
+    """include/das3r_raster.h das3r_switches: the DAS3R_* switches as parsed (csrc/kernel_choice.h Switches)."""
+    _fields_ = [(n, C.c_int32) for n in
+                ("sort_ipl", "sort_classic", "rect_upstream", "verbose", "binning", "capacity_exact", "fused_emit_off", "no_sh_stage", "render_fwd",
+                 "render_bwd", "render_bwd_mb", "render_bwd_atomic", "render_bwd_pix", "render_bwd_occ", "render_bwd_strips", "tile_chunk",
+                 "scan_items", "deterministic", "tile_lpt_off", "bwd_reduce_set", "bwd_reduce_shfl", "ablate_set", "ablate", "tickets",
+                 "bwd_pad_lds", "fwd_pad_lds", "bwd_buckets", "fwd_no_prefetch", "split_colour", "tile_strip")]
+
+
+class BwdChoice(C.Structure):
+    """include/das3r_raster.h das3r_bwd_choice."""
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "mb", "slices", "pix", "occ", "strips", "atomic_flush")]
+
+
+class FwdChoice(C.Structure):
+    """include/das3r_raster.h das3r_fwd_choice."""
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "quad_lanes", "row_private", "tile_lpt")]
+
+
 PRUNE_GROUP_ROWS = 1024   # DAS3R_PRUNE_GROUP_ROWS
 
 
@@ -115,7 +134,9 @@ EXPORTS = ("das3r_raster_forward", "das3r_raster_backward", "das3r_raster_backwa
            "das3r_raster_aux_forward", "das3r_raster_aux_scratch_bytes", "das3r_raster_aux_adjoint",
            "das3r_thin_workspace_bytes", "das3r_thin_voxels", "das3r_raster_focal_workspace_bytes", "das3r_raster_backward_focal",
            "das3r_debug_path_policy_fresh", "das3r_debug_path_policy_plan", "das3r_debug_path_policy_count", "das3r_debug_path_policy_skew",
-           "das3r_debug_path_policy_hint", "das3r_debug_path_policy_forget", "das3r_debug_path_policy_resume", "das3r_debug_seg_dbits")
+           "das3r_debug_path_policy_hint", "das3r_debug_path_policy_forget", "das3r_debug_path_policy_resume", "das3r_debug_seg_dbits",
+           "das3r_debug_parse_switches", "das3r_debug_choose_backward", "das3r_debug_choose_forward", "das3r_debug_has_invdepth_form",
+           "das3r_debug_kernel_name")
 
 _lib = None
 
@@ -246,6 +267,17 @@ def load():
     L.das3r_debug_path_policy_resume.argtypes = [ps, C.c_uint32, C.c_uint32]
     L.das3r_debug_seg_dbits.restype = C.c_int
     L.das3r_debug_seg_dbits.argtypes = [C.c_int32, C.c_int32]
+    sw = C.POINTER(Switches)   # the switches and the compositing-kernel choice on a caller's own values (additive under ABI 16; host-only)
+    L.das3r_debug_parse_switches.restype = None
+    L.das3r_debug_parse_switches.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int32, C.c_int32, sw]
+    L.das3r_debug_choose_backward.restype = None
+    L.das3r_debug_choose_backward.argtypes = [sw, C.c_int64, C.c_int32, C.c_uint32, C.POINTER(BwdChoice)]
+    L.das3r_debug_choose_forward.restype = None
+    L.das3r_debug_choose_forward.argtypes = [sw, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(FwdChoice)]
+    L.das3r_debug_has_invdepth_form.restype = C.c_int
+    L.das3r_debug_has_invdepth_form.argtypes = [C.c_int32, C.c_int32]
+    L.das3r_debug_kernel_name.restype = C.c_char_p
+    L.das3r_debug_kernel_name.argtypes = [C.c_int32, C.c_int32]
     L.das3r_raster_get_layout.restype = C.c_int
     L.das3r_raster_get_layout.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(RasterLayout)]
     _lib = L

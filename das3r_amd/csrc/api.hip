@@ -52,65 +52,12 @@ static bool g_sw_loaded = false;
 static int g_inject_fault = 0;
 static int g_mutate = 0;
 static void load_switches() {
-    Switches w;
-    memset(&w, 0, sizeof(w));
-    auto env = [](const char *k) -> const char * { const char *e = getenv(k); return (e && e[0]) ? e : nullptr; };
-    const char *e;
-    // Switches that select between CORRECT code paths (tests force each of them) are read in every build.  Those that exist for
-    // timing experiments only — some of them produce wrong results by design (DAS3R_ABLATE) — are read only by an experiments
-    // build (make EXPERIMENTS=1): a stray environment variable cannot change what the shipped library computes.  Fault injection
-    // for the self-check tests is a call (das3r_debug_inject_fault), not an environment variable.
 #ifdef DAS3R_EXPERIMENTS
-    if ((e = env("DAS3R_SORT_IPL"))) { const int v = atoi(e); w.sort_ipl = (v == 4 || v == 8 || v == 16) ? v : 0; }
-    w.sort_classic = (e = env("DAS3R_SORT")) && e[0] == 'c';
-    w.no_sh_stage = getenv("DAS3R_NO_SH_STAGE") != nullptr;
-    if ((e = env("DAS3R_ABLATE"))) { w.ablate_set = true; w.ablate = atoi(e); }
-    if ((e = env("DAS3R_BWD_PAD_LDS"))) w.bwd_pad_lds = atoi(e);
-    if ((e = env("DAS3R_FWD_PAD_LDS"))) w.fwd_pad_lds = atoi(e);
-    if ((e = env("DAS3R_SCAN_ITEMS"))) { const int v = atoi(e); w.scan_items = (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) ? v : 0; }
-    w.fwd_no_prefetch = (e = env("DAS3R_FWD_PREFETCH")) && e[0] == '0';
+    const bool experiments = true;
+#else
+    const bool experiments = false;
 #endif
-    w.rect_upstream = (e = env("DAS3R_RECT")) && e[0] == 'u';
-    w.verbose = env("DAS3R_VERBOSE") != nullptr;
-    if ((e = env("DAS3R_BINNING"))) w.binning = e[0] == 'l' ? 1 : (e[0] == 'r' ? -1 : (e[0] == 's' ? (strchr(e, '3') ? 3 : 2) : 0));
-    w.capacity_exact = (e = env("DAS3R_CAPACITY")) && e[0] == 'e';
-    w.fused_emit_off = (e = env("DAS3R_FUSED_EMIT")) && e[0] == '0';
-    if ((e = env("DAS3R_SPLIT_COLOUR"))) w.split_colour = e[0] == '0' ? -1 : (e[0] == '1' ? 1 : 0);   // (A-B runs, tests: the split preprocess off / on)
-    w.tile_lpt_off = (e = env("DAS3R_TILE_LPT")) && e[0] == '0';   // (A-B runs: the region forward in the locality order of the other kernels)
-    if ((e = env("DAS3R_RENDER"))) w.render_fwd = e[0] == 'q' ? 1 : (e[0] == 'r' ? 2 : (e[0] == 'l' ? 3 : (e[0] == 's' ? 4 : (e[0] == 'f' ? 5 : 0))));
-    if ((e = env("DAS3R_RENDER_BWD"))) {   // dpp | mfma | scan[a][64|128|256|512]
-        w.render_bwd = e[0] == 'd' ? 1 : (e[0] == 'm' ? 2 : (strncmp(e, "stream", 6) == 0 ? 5 : (e[0] == 's' ? 3 : (e[0] == 'b' ? 6 : (e[0] == 'f' ? 7 : 0)))));
-        if (w.render_bwd == 6) {
-            const char *d = e;
-            while (*d && (*d < '0' || *d > '9')) d++;
-            w.render_bwd_mb = *d ? atoi(d) : 128;
-            const char *pp = strchr(e, 'p');
-            w.render_bwd_pix = pp ? atoi(pp + 1) : 0;
-            const char *po = strchr(e, 'o');
-            w.render_bwd_occ = po ? atoi(po + 1) : 5;
-        }
-        if (w.render_bwd == 7) {   // fine[<entries per round>]: render_bwd_rgn.hip
-            const char *d = e;
-            while (*d && (*d < '0' || *d > '9')) d++;
-            w.render_bwd_mb = *d ? atoi(d) : 128;
-            w.render_bwd_pix = strchr(e, 'q') ? 9 : (strchr(e, 's') ? 8 : 0);
-        }
-        if (w.render_bwd == 3) {
-            const char *d = e;
-            while (*d && (*d < '0' || *d > '9')) d++;
-            w.render_bwd_mb = (*d ? atoi(d) : 256) + (strncmp(e, "scana", 5) == 0 ? 1000 : 0);
-        }
-    }
-    if ((e = env("DAS3R_BWD_REDUCE"))) { w.bwd_reduce_set = true; w.bwd_reduce_shfl = e[0] == 's'; }
-    w.tickets = -1;
-    if ((e = env("DAS3R_TICKETS"))) w.tickets = e[0] == 'a' ? 0 : (e[0] == 'n' ? 1 << 30 : ((e[0] >= '1' && e[0] <= '9') ? atoi(e) : -1));
-    w.deterministic = (e = env("DAS3R_DETERMINISTIC")) && e[0] != '0';
-    w.bwd_buckets = -1;
-    if ((e = env("DAS3R_BWD_BUCKETS"))) w.bwd_buckets = atoi(e);
-    w.tile_strip = 8;
-    w.tile_chunk = -1;
-    if ((e = env("DAS3R_TILE_CHUNK"))) { const int v = atoi(e); w.tile_chunk = (v >= 0 && v <= 64 && (v & (v - 1)) == 0) ? v : -1; }
-    if ((e = env("DAS3R_TILE_STRIP"))) w.tile_strip = std::max(0, std::min(63, atoi(e)));   // (7-bit field of render_common.h pack_tiles, kept below its sign bit)
+    Switches w = parse_switches(getenv, experiments);   // what every DAS3R_* spelling means: kernel_choice.h
     w.inject_fault = g_inject_fault;   // (not an environment variable: das3r_debug_inject_fault)
     w.mutate = g_mutate;               // (likewise: das3r_debug_mutate)
     g_sw = w;
@@ -438,6 +385,34 @@ extern "C" void das3r_debug_path_policy_resume(das3r_path_policy_state *state, u
 }
 extern "C" int das3r_debug_seg_dbits(int32_t tbits, int32_t passes) { return seg_dbits((int)tbits, (int)passes); }
 
+// The functions of kernel_choice.h on a caller's own switches (include/das3r_raster.h): no HIP call, no look at the process environment or at
+// the switches the library itself last read.
+extern "C" void das3r_debug_parse_switches(const char *const *names, const char *const *values, int32_t n, int32_t experiments, das3r_switches *out) {
+    auto lookup = [&](const char *name) -> const char * {
+        for (int32_t i = 0; i < n; i++)
+            if (strcmp(names[i], name) == 0) return values[i];
+        return nullptr;
+    };
+    switches_to(parse_switches(lookup, experiments != 0), out);
+}
+extern "C" void das3r_debug_choose_backward(const das3r_switches *sw, int64_t num_rendered, int32_t ntiles, uint32_t fwd_flags, das3r_bwd_choice *out) {
+    const BwdChoice c = choose_backward(switches_from(*sw), num_rendered, ntiles, fwd_flags);
+    *out = das3r_bwd_choice{c.kernel, c.mb, c.slices, c.pix, c.occ, c.strips, c.atomic_flush};
+}
+extern "C" void das3r_debug_choose_forward(const das3r_switches *sw, int32_t ntiles, int64_t capacity, int32_t local_lists, int32_t prefer_regions,
+                                           das3r_fwd_choice *out) {
+    const Switches w = switches_from(*sw);
+    const bool local = local_lists != 0, regions = prefer_regions != 0;
+    *out = das3r_fwd_choice{choose_forward(w, ntiles, capacity, local, regions), quad_lanes(w, ntiles, capacity, local), row_private(w, capacity, ntiles),
+                            tile_lpt_wanted(w, ntiles, capacity, local, regions)};
+}
+extern "C" int das3r_debug_has_invdepth_form(int32_t backward, int32_t kernel) {
+    return (backward ? bwd_has_invdepth_form((BwdKernel)kernel) : fwd_has_invdepth_form((FwdKernel)kernel)) ? 1 : 0;
+}
+extern "C" const char *das3r_debug_kernel_name(int32_t backward, int32_t kernel) {
+    return backward ? bwd_kernel_name((BwdKernel)kernel) : fwd_kernel_name((FwdKernel)kernel);
+}
+
 extern "C" int das3r_raster_get_layout(int32_t P, int64_t num_rendered, int32_t W, int32_t H, das3r_raster_layout *out) {
     if (!out || P < 0 || num_rendered < 0 || W <= 0 || H <= 0) { set_error("das3r_raster_get_layout: invalid argument"); return DAS3R_ERR_INVALID_ARG; }
     Layout L;
@@ -599,8 +574,8 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
         set_error("das3r_raster_forward: null output/allocator");
         return DAS3R_ERR_INVALID_ARG;
     }
-    if (out->out_invdepth && switches().render_fwd == 4) {   // ABI 16: every forward kernel the library picks has an inverse-depth form, not the forced slices
-        set_error("das3r_raster_forward: DAS3R_RENDER=slices has no inverse-depth form (das3r_raster_out.out_invdepth)");
+    if (out->out_invdepth && !fwd_has_invdepth_form(switches().render_fwd)) {   // ABI 16: every forward kernel the library picks has an inverse-depth form, not the forced slices
+        set_error("das3r_raster_forward: DAS3R_RENDER=%s has no inverse-depth form (das3r_raster_out.out_invdepth)", fwd_kernel_name(switches().render_fwd));
         return DAS3R_ERR_INVALID_ARG;
     }
     const int P = a->P, W = a->image_width, H = a->image_height;
@@ -753,7 +728,13 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
                                 a->debug != 0, s, &dead_keys, emit_slot, mb->dev + MB_TOO_LONG, plan.gen))) return r;
         if ((r = join.launch())) return r;   // the split preprocess: the colour kernel, beside the binning kernels enqueued above
         LocalBin lb = {(float4 *)(saved->binning + L.b_ckpt), nullptr, nullptr, nullptr, nullptr, plan.gen, (uint32_t)(P - 1), (uint32_t)cap};
-        if (plan.decide_fine && cap > 0 && use_quad_lanes(L, lb)) {   // (shapes the one-workgroup-per-tile kernel would take: few tiles, long lists)
+        // The three questions below — look at the list skew? order the tiles longest first? leave the backward its hint? — are asked with
+        // local_lists = false, "by shape", on every binning path: lb.point_list is only set further down, so that is what these sites have always
+        // answered.  launch_render_forward, which sees the pointer, passes the truth, and on the local-order path never takes the lanes /
+        // regions kernels the answers here are about; the hint's bit 0 still steers that forward's BACKWARD (kernel_choice.h choose_backward).
+        // Kept as it is: changing it changes which kernels a training run takes.
+        const bool by_shape = cap > 0 && quad_lanes(switches(), L.ntiles, L.capacity, /*local_lists=*/false);
+        if (plan.decide_fine && by_shape) {   // (shapes the one-workgroup-per-tile kernel would take: few tiles, long lists)
             const uint32_t tag = next_tag(mb);
             if ((r = launch_list_skew(saved->img, saved->binning, saved->geom, L, (uint32_t)cap, (uint32_t)(P - 1), mb->dev + MB_LONGEST, tag, a->debug != 0, s))) return r;
             if ((r = mailbox_wait(mb, MB_SKEW_TAG, tag, s))) return r;
@@ -766,13 +747,11 @@ extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_
         const bool fine = prefers_regions(T->verdict);
         lb.prefer_regions = fine;
         lb.tile_order = nullptr;
-        if (fine && cap > 0 && use_quad_lanes(L, lb) && L.ntiles <= 1024 && !switches().tile_lpt_off && (switches().render_fwd == 0 || switches().render_fwd == 5)) {
-            // four workgroups per tile are 3 - 4 generations of workgroups on the chip, and a tile whose list is four times the mean (every
-            // real sequence has them) that starts in the last generation adds its whole chain to the kernel: longest lists first
+        if (tile_lpt_wanted(switches(), L.ntiles, L.capacity, /*local_lists=*/false, fine)) {   // longest lists first (kernel_choice.h says why)
             if ((r = launch_tile_lpt(saved->img, L, (uint32_t)cap, a->debug != 0, s))) return r;
             lb.tile_order = (const uint32_t *)(saved->img + L.i_order);
         }
-        if (fine && cap > 0 && use_quad_lanes(L, lb)) saved->flags |= backward_hint(T->verdict, (uint32_t)BUCKET);   // (for the backward pass of this forward: render_bwd.hip)
+        if (fine && by_shape) saved->flags |= backward_hint(T->verdict, (uint32_t)BUCKET);   // (for the backward pass of this forward: kernel_choice.h choose_backward)
         if (local_order && cap > 0) {
             lb.point_list = (uint32_t *)(saved->binning + L.pub.point_list);
             lb.slot_list = (uint32_t *)(saved->binning + L.b_slot);
@@ -922,6 +901,14 @@ struct FocalOut {
     float *sums, *per_splat, *workspace;
 };
 
+// the depth pass runs the compositing backward a second time: a forced kernel must have an inverse-depth form (kernel_choice.h)
+static int refuse_bwd_without_invdepth(const char *who) {
+    const BwdKernel k = switches().render_bwd;
+    if (bwd_has_invdepth_form(k)) return DAS3R_OK;
+    set_error("%s: DAS3R_RENDER_BWD=%s has no inverse-depth form", who, bwd_kernel_name(k));
+    return DAS3R_ERR_INVALID_ARG;
+}
+
 // The backward pass of das3r_raster_backward (depth_pass false), das3r_raster_backward_depth (true) and das3r_raster_backward_focal (either,
 // with `focal`): the launches of the first two are what they were, the third puts one per-Gaussian kernel and its finish between the
 // compositing passes (+ the depth fold) and the per-Gaussian backward — before grads->chain's Adam step touches the parameters it reads.
@@ -943,13 +930,7 @@ static int backward_body(const char *who, const das3r_raster_args *a, const das3
         return DAS3R_OK;
     }
     if ((rc = backward_validate(who, in, saved, dL_dpix, depth_pass, dL_dinvdepth, g))) return rc;
-    if (depth_pass) {
-        const int kind = switches().render_bwd;
-        if (kind == 2 || kind == 3 || kind == 5) {
-            set_error("%s: DAS3R_RENDER_BWD=%s has no inverse-depth form", who, kind == 3 ? "scan" : (kind == 2 ? "mfma" : "stream"));
-            return DAS3R_ERR_INVALID_ARG;
-        }
-    }
+    if (depth_pass && (rc = refuse_bwd_without_invdepth(who))) return rc;
     // the forward's binning self-check first: nothing is launched on the strength of an invalid image / list
     if ((rc = das3r_raster_check(saved, stream))) return rc;
     Layout L;
@@ -1009,10 +990,9 @@ extern "C" int das3r_raster_backward_focal(const das3r_raster_args *a, const das
         return DAS3R_ERR_INVALID_ARG;
     }
     const bool depth_pass = dL_dinvdepth != nullptr;
-    const int kind = switches().render_bwd;
-    if (depth_pass && (kind == 2 || kind == 3 || kind == 5)) {
-        set_error("das3r_raster_backward_focal: DAS3R_RENDER_BWD=%s has no inverse-depth form", kind == 3 ? "scan" : (kind == 2 ? "mfma" : "stream"));
-        return DAS3R_ERR_INVALID_ARG;
+    if (depth_pass) {   // (before the saved state is looked at, under this entry's own name)
+        const int rc = refuse_bwd_without_invdepth("das3r_raster_backward_focal");
+        if (rc) return rc;
     }
     const FocalOut focal = {sums, per_splat, workspace};
     return backward_body("das3r_raster_backward_focal", a, in, saved, dL_dpix, depth_pass, dL_dinvdepth, g, &focal, stream);
@@ -1030,7 +1010,7 @@ extern "C" size_t das3r_raster_backward_depth_scratch_bytes(int64_t capacity) {
 extern "C" size_t das3r_raster_backward_scratch_bytes(int64_t capacity) {
     const size_t c = capacity > 0 ? (size_t)capacity : 1;
 #ifdef DAS3R_EXPERIMENTS
-    if (switches().render_bwd == 5) return std::max(c * 9 * sizeof(float) + 16, stream_scratch_bytes(capacity));
+    if (switches().render_bwd == BWD_STREAM) return std::max(c * 9 * sizeof(float) + 16, stream_scratch_bytes(capacity));
 #endif
     return c * 9 * sizeof(float) + 16;
 }

@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "../../include/das3r_raster.h"
+#include "kernel_choice.h"
 #include "path_policy.h"
 #include "pretransform_math.h"
 
@@ -18,39 +19,7 @@ namespace das3r {
 
 void set_error(const char *fmt, ...);
 
-// Experiment / diagnostic switches, read from the environment ONCE — at the first call into the library and
-// again whenever das3r_reload_switches() is called (tests and tools flip them between calls) — not on every launch.
-struct Switches {
-    int sort_ipl;          // DAS3R_SORT_IPL = 4 | 8 | 16: keys per lane of the radix passes (0: by size)
-    bool sort_classic;     // DAS3R_SORT=classic: histogram + row scan + scatter per digit instead of the one-sweep passes
-    bool rect_upstream;    // DAS3R_RECT=upstream: bin over upstream's 3-sigma square (bit-exact list tests)
-    bool verbose;          // DAS3R_VERBOSE
-    int binning;           // DAS3R_BINNING=local | radix | seg | seg3: 1 | -1 | 2 | 3 (0: chosen per scene; seg3 = seg with one more partition pass of bucket bits)
-    bool capacity_exact;   // DAS3R_CAPACITY=exact: never lay the binning buffer out speculatively
-    bool fused_emit_off;   // DAS3R_FUSED_EMIT=0
-    bool no_sh_stage;      // DAS3R_NO_SH_STAGE
-    int render_fwd;        // DAS3R_RENDER=quad | rows | lanes | slices | fine: 1 | 2 | 3 | 4 | 5 (0: by list length and tile count)
-    int render_bwd;        // DAS3R_RENDER_BWD=dpp | mfma | scan... | stream | blk...: 1 | 2 | 3 | 5 | 6 (0: by list length)
-    int render_bwd_mb;     // scan64 / scan128 / scan256, blk64 / blk128 / blk256: entries per round; scana256 / scana512: 1000 + entries, atomic flush
-    int tile_chunk;        // DAS3R_TILE_CHUNK: tiles per chunk of the XCD round robin (render_common.h); -1 = default, 0 = contiguous eighths
-    int scan_items;        // DAS3R_SCAN_ITEMS = 1 | 2 | 4 | 8 | 16: ranks per thread of the scan + emission kernel (0: by size)
-    bool deterministic;    // DAS3R_DETERMINISTIC=1: bit-identical gradients run to run (the block-walk backward for every list length:
-                           // the pixel-per-lane kernel meets its four waves with LDS float atomics, whose order varies)
-    int render_bwd_occ;    // blk...o<4|5>: workgroups per CU the kernel is compiled for (register cap)
-    bool tile_lpt_off;     // DAS3R_TILE_LPT=0
-    int render_bwd_pix;    // blk...p<0|1|2>: where render_bwd_blk.hip keeps the per-pixel values (render_blk.h)
-    bool bwd_reduce_set, bwd_reduce_shfl;   // DAS3R_BWD_REDUCE=shfl | dpp (reference reduction of the pixel-per-lane kernel)
-    bool ablate_set;       // DAS3R_ABLATE (perf experiments on the pixel-per-lane kernel)
-    int ablate;
-    int tickets;           // DAS3R_TICKETS=always | never | <bound>: 0 | 1 << 30 | bound (-1: from the device's CU count)
-    int bwd_pad_lds, fwd_pad_lds;   // DAS3R_BWD_PAD_LDS / DAS3R_FWD_PAD_LDS: extra dynamic LDS (occupancy experiments)
-    int bwd_buckets;       // DAS3R_BWD_BUCKETS=0 | <slices>: bucket-parallel backward off / forced with that many slices (-1: by list length)
-    int inject_fault;
-    int mutate;            // das3r_debug_mutate (tests): 1 = the block-walk backward evaluates exp(power) (1 + 1e-4) — a biased kernel the parity tests must catch
-    bool fwd_no_prefetch;   // DAS3R_FWD_PREFETCH=0: the rows forward kernel without its software prefetch (A-B runs)
-    int split_colour;      // DAS3R_SPLIT_COLOUR=0 | 1: the split preprocess (preprocess.hip) forced off (-1) / on (1) where it can run; unset (0): by shape (api.hip split_colour_rule)
-    int tile_strip;   // DAS3R_TILE_STRIP: rows per strip of the compositing kernels' tile order (0 = row-major)      // DAS3R_INJECT_FAULT: bits OR-ed into the binning self-check word of every forward (fault-injection tests)
-};
+// The experiment / diagnostic switches as last read from the environment: kernel_choice.h Switches / parse_switches
 const Switches &switches();
 
 #define HIP_TRY(expr)                                                                          \
@@ -188,11 +157,7 @@ static inline int tile_bits(int ntiles) {
     return b < 1 ? 1 : b;
 }
 
-// Long tile lists are cut into BUCKETs of list positions: the forward compositing kernels leave every pixel's (T, C) at the bucket
-// boundaries in the binning buffer (checkpoints: render_common.h), so that the backward pass can replay the buckets of a tile
-// in parallel workgroups (render_bwd_scan.hip) — the DAS3R shape has 416 tiles with ~14 k entries each: one workgroup per tile
-// leaves the chip at 1.6 waves per SIMD.
-constexpr int BUCKET = 1024;
+// (BUCKET, the list positions between two checkpoints of a long tile list: kernel_choice.h)
 constexpr int SPLAT_REC = 4;   // float4s per Gaussian record (xyh, conic+opacity, rgb+depth, pad): 64 bytes, one cache-line gather
 
 // das3r_raster_saved.flags bit 1 (ABI 16): the forward was given out_invdepth, its binning buffer holds Layout::d_* (bits 0 and 8 - 15: api.hip)
@@ -309,8 +274,6 @@ int launch_onesweep_depth_sort(int P, char *geom, const Layout &L, int part, uin
                                hipStream_t s);
 int launch_onesweep_partition(int64_t cap, char *geom, char *binning, const Layout &L, uint32_t **keys_final, bool debug, hipStream_t s,
                               uint32_t *ghist_override = nullptr, uint32_t *err_override = nullptr);
-bool use_row_private(int64_t instances, int ntiles);  // forward: 4x4-block-per-row kernel for long tile lists (render_rows.hip)
-bool use_quad_lanes(const Layout &L, const LocalBin &lb);   // forward: four lanes per pixel for few tiles with long lists (render_lanes.hip)
 // das3r_raster_in.pre -> the device-side view the per-Gaussian kernels take by value (pretransform_math.h); all null when the caller handed
 // over camera-frame tensors
 inline PreXform pre_xform(const das3r_raster_in *in) {
@@ -339,13 +302,14 @@ size_t stream_scratch_bytes(int64_t capacity);
 int launch_render_backward_stream(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
                                   float *scratch, hipStream_t s);
 // slices > 1: bucket-parallel replay (grid = tiles x slices; needs the forward's checkpoints)
+// c: kernel_choice.h choose_backward (entries per round, slices, and what each kernel's forms are picked by)
 int launch_render_backward_scan(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
-                                float *partial, int mb, int slices, hipStream_t s);
+                                float *partial, const BwdChoice &c, hipStream_t s);
 // 4x4 block per DPP row, pixel state in registers, fp32 accumulators (render_bwd_blk.hip)
 int launch_render_backward_blk(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
-                               float *partial, int mb, int slices, hipStream_t s);
+                               float *partial, const BwdChoice &c, hipStream_t s);
 int launch_render_backward_regions(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
-                               float *partial, int mb, int slices, hipStream_t s);   // render_bwd_rgn.hip
+                               float *partial, const BwdChoice &c, hipStream_t s);   // render_bwd_rgn.hip
 constexpr int LOCAL_MAX = 1024;   // longest tile list the forward kernels sort in LDS
 // chained kernels (scan, radix passes) order their workgroups by ticket unless every workgroup of the grid is resident at once
 // (api.hip: grid_is_resident)

@@ -174,7 +174,7 @@ static inline bool learn_skew(Verdict &v, uint32_t longest32, uint32_t crowd16, 
     return v.fine;
 }
 
-// das3r_raster_saved.flags of a forward composited with the 2x2-region kernels, for the backward pass of that forward (render_bwd.hip):
+// das3r_raster_saved.flags of a forward composited with the 2x2-region kernels, for the backward pass of that forward (kernel_choice.h choose_backward):
 // bit 0, and in bits 8 - 15 the buckets (`bucket` list positions each: common.h BUCKET) of the shape's longest tile list as last
 // measured, + 2 of headroom — the bucket-parallel backward launches that many workgroups per tile instead of the AVERAGE list's (a tile
 // of four times the mean then takes four buckets per workgroup, back to back, and the kernel ends with them: self-consistent job

@@ -19,7 +19,7 @@
 // tests of every compositing kernel.
 //
 // Few tiles with long lists (the DAS3R training shape: 416 tiles of ~11 k entries) leave one workgroup per tile at 1.6 waves per SIMD, so
-// both kernels have a second form for them (aux_long_lists: the rule of render_lanes.hip use_quad_lanes, on the instance count):
+// both kernels have a second form for them (aux_long_lists: the rule of kernel_choice.h quad_lanes, on the instance count):
 //   forward  SPLIT: four workgroups per tile, one per quadrant; the four waves of a workgroup share its 64 pixels and take a quarter of
 //            every staged batch each, starting from T = 1; the blend is a composition of segments — (T, sum) o (T', sum') =
 //            (T T', sum + T sum') — so the waves meet once per batch in LDS (four transmittances per pixel, multiplied in wave order)
@@ -334,7 +334,7 @@ __global__ void __launch_bounds__(256) aux_gather_kernel(int P, int C, const uin
     (const uint2 *)(img + L.pub.ranges), (const uint32_t *)(binning + L.pub.point_list), W, H, L.tiles_x, pack_tiles(L),  \
         (const float4 *)(geom + L.pub.xy), (const float4 *)(geom + L.pub.conic_opacity), (const uint32_t *)(img + L.pub.n_contrib)
 
-// few tiles, long lists (render_lanes.hip use_quad_lanes' shapes; from the instance COUNT: the same scene takes the same kernels however
+// few tiles, long lists (kernel_choice.h quad_lanes' shapes; from the instance COUNT: the same scene takes the same kernels however
 // its buffer was sized): the forward with four workgroups per tile, the adjoint bucket-parallel
 static bool aux_long_lists(const Layout &L, int64_t num_rendered) { return L.ntiles <= 1024 && num_rendered >= (int64_t)1024 * L.ntiles; }
 

@@ -165,64 +165,25 @@ __global__ void __launch_bounds__(256) render_backward_kernel(
 int launch_render_backward(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
                            float *partial, hipStream_t s, bool *quad_rows, int64_t num_rendered, uint32_t fwd_flags) {
     *quad_rows = false;
-    // Which decomposition (DAS3R_RENDER_BWD=dpp | mfma | scan<N> | scana<N> | stream forces one; measurements: DESIGN.md §4):
-    //   dpp     pixel per lane, cross-lane reduction on the vector ALU (this file): lists of a few hundred entries per tile
-    //   fine    every DPP row of a wave on a 2x2 region's list, four pixel steps per batch (render_bwd_rgn.hip): long, spatially coherent lists
-    //   blk     every DPP row of a wave on its own 4x4 block: lanes = 16 splats of the block's culled list, time = its 16 pixels,
-    //           recurrences as DPP row scans, sums in fp32 registers (render_bwd_blk.hip): everything but short lists
-    //   scan    lanes = 4 pixels x 16 splats of the QUADRANT's list, sums as split-bf16 products on the matrix cores
-    //           (render_bwd_scan.hip): round 2's kernel for long lists, kept as the reference for blk
-    //   stream  the same arithmetic, every wave streaming the tile's list on its own (render_bwd_stream.hip; experimental)
-    //   mfma    pixel per lane + LDS-transposed slab -> fp32 matrix cores (render_bwd_mfma.hip; superseded by scan)
+    // which decomposition, how many entries per round and how many workgroups per tile: kernel_choice.h
     const Switches &sw = switches();
-    int kind = sw.render_bwd;
-    int mb = sw.render_bwd_mb ? sw.render_bwd_mb : 256;
-    if (kind == 0) {
-        // measured (render backward, ms; tools/gpu_perf.py): 100 k splats at 1080p, mean list 32: dpp 0.071 / blk64 0.068 / scan128 0.129;
-        // 1 M splats, mean 320: dpp 0.532 / scan128 0.476 / blk128p1 0.381; DAS3R shape (13 800, bucket-parallel): dpp 1.89 / scan128 0.78 /
-        // blk192 0.497.  Round 2's crossover between dpp and the quadrant walk was a mean list of 192; the block walk culls per 4x4
-        // block and is ahead from ~100 entries per tile on (tools/gpu_perf.py --workloads c4:<P>: DESIGN.md section 5).
-        const int64_t mean_list = num_rendered / std::max(L.ntiles, 1);   // (the count, not the capacity: the same scene takes the same kernel however its buffer was sized)
-        const bool long_lists = mean_list >= 96;
-        kind = (sw.bwd_reduce_set || sw.ablate_set || !long_lists) ? 1 : 6;
-        mb = mean_list >= 1024 ? 192 : 128;
-        // round 6: long lists that the forward found spatially coherent or skewed (das3r_raster_saved.flags bit 0: the depth maps of a real
-        // sequence) take the 2x2-region walk — self-consistent Sintel-shaped job: backward 0.548 -> 0.414 ms, dsc 0.865 -> 0.590; random depths
-        // stay on the block walk (ds 0.50 against 0.55, noise-depth train step 0.344 against 0.369)
-        if (kind == 6 && mean_list >= 1024 && L.ntiles <= 1024 && (fwd_flags & 1u) && !sw.ablate_set) {
-            kind = 7;
-            mb = 128;
-        }
-        if (sw.deterministic && kind == 1) {   // short lists too on the block walk: every sum has a fixed order (rows 0..3 of a wave, waves 0..3)
-            kind = 6;
-            mb = 64;
-        }
-    }
+    const BwdChoice c = choose_backward(sw, num_rendered, L.ntiles, fwd_flags);
+    switch (c.kernel) {
 #ifdef DAS3R_EXPERIMENTS
-    if (kind == 5) {
-        *quad_rows = true;
-        return launch_render_backward_stream(a, dL_dpix, geom, binning, img, L, partial, s);
-    }
-    if (kind == 2) return launch_render_backward_mfma(a, dL_dpix, geom, binning, img, L, partial, s);
+        case BWD_STREAM:
+            *quad_rows = true;
+            return launch_render_backward_stream(a, dL_dpix, geom, binning, img, L, partial, s);
+        case BWD_MFMA: return launch_render_backward_mfma(a, dL_dpix, geom, binning, img, L, partial, s);
 #else
-    if (kind == 5 || kind == 2) {
-        set_error("DAS3R_RENDER_BWD=%s: this library was built without the superseded kernels (make EXPERIMENTS=1)", kind == 5 ? "stream" : "mfma");
-        return DAS3R_ERR_INVALID_ARG;
-    }
+        case BWD_STREAM:
+        case BWD_MFMA:
+            set_error("DAS3R_RENDER_BWD=%s: this library was built without the superseded kernels (make EXPERIMENTS=1)", bwd_kernel_name(c.kernel));
+            return DAS3R_ERR_INVALID_ARG;
 #endif
-    if (kind == 3 || kind == 6 || kind == 7) {
-        // long lists are replayed bucket by bucket in parallel workgroups (checkpoints from the forward: common.h BUCKET); slices =
-        // buckets of an average tile, so that a tile's workgroups take about one bucket each
-        int slices = sw.bwd_buckets;
-        if (slices < 0) slices = (int)std::min<int64_t>(32, std::max<int64_t>(1, num_rendered / ((int64_t)BUCKET * std::max(L.ntiles, 1))));
-        if (slices > 1 && mb > 256) slices = 1;
-        // round 6: skewed lists (das3r_raster_saved.flags bits 8 - 15: buckets of the longest list the forward last measured) — a workgroup per
-        // bucket of the LONGEST tile; the workgroups of shorter tiles that have no bucket leave before they load anything
-        const int hint = (int)((fwd_flags >> 8) & 0xFFu);
-        if (sw.bwd_buckets < 0 && kind == 7 && slices > 1 && hint > slices) slices = std::min(hint, 64);
-        if (kind == 6) return launch_render_backward_blk(a, dL_dpix, geom, binning, img, L, partial, mb, slices, s);
-        if (kind == 7) return launch_render_backward_regions(a, dL_dpix, geom, binning, img, L, partial, mb, slices, s);
-        return launch_render_backward_scan(a, dL_dpix, geom, binning, img, L, partial, mb, slices, s);
+        case BWD_BLK: return launch_render_backward_blk(a, dL_dpix, geom, binning, img, L, partial, c, s);
+        case BWD_REGIONS: return launch_render_backward_regions(a, dL_dpix, geom, binning, img, L, partial, c, s);
+        case BWD_SCAN: return launch_render_backward_scan(a, dL_dpix, geom, binning, img, L, partial, c, s);
+        default: break;   // BWD_DPP: below
     }
     const bool use_dpp = !sw.bwd_reduce_shfl;   // "shfl" selects the ds_bpermute reference reduction (diagnostics)
     const int ablate = sw.ablate;               // perf experiments only: bit0 = no partial stores, bit2 = no cross-lane reduction

@@ -347,7 +347,8 @@ __global__ void __launch_bounds__(256, OCC) render_backward_blk_kernel(
 }
 
 int launch_render_backward_blk(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
-                               float *partial, int mb, int slices, hipStream_t s) {
+                               float *partial, const BwdChoice &c, hipStream_t s) {
+    const int mb = c.mb, slices = c.slices;
 #define ARGS                                                                                                              \
     (const uint2 *)(img + L.pub.ranges), (const uint32_t *)(binning + L.pub.point_list), a->image_width, a->image_height, \
         L.tiles_x, pack_tiles(L), (const float4 *)(geom + L.pub.xy), (const float4 *)(geom + L.pub.conic_opacity),             \
@@ -360,9 +361,8 @@ int launch_render_backward_blk(const das3r_raster_args *a, const float *dL_dpix,
         else DAS3R_LAUNCH((render_backward_blk_kernel<MBV, PIX, 0, OCC, false>), dim3(xcd_grid(L), 1), dim3(TILE_PIX), 0, s, ARGS);                   \
     } while (0)
     // DAS3R_RENDER_BWD=blk<entries per round>[p<PIX>][o<workgroups per CU>]: blk128 (registers), blk128p1 (constants in LDS), blk160p1o4 ...
-    // default (no DAS3R_RENDER_BWD): constants in LDS for 128-entry rounds (1 M splats at 1080p: 0.381 vs 0.407 ms), registers for 192
-    // (DAS3R shape: 0.497 vs 0.534 ms)
-    const int pix = switches().render_bwd == 6 ? switches().render_bwd_pix : (mb == 128 ? 1 : 0), occ = switches().render_bwd_occ == 4 ? 4 : 5;
+    // (what an unforced launch gets: kernel_choice.h choose_backward)
+    const int pix = c.pix, occ = c.occ;
 #define BY_PIX(MBV, OCC) do { if (pix == 2) GO(MBV, 2, OCC); else if (pix == 1) GO(MBV, 1, OCC); else GO(MBV, 0, OCC); } while (0)
     if (switches().mutate == 1) {   // the mutated kernel (a test aid: include/das3r_raster.h das3r_debug_mutate), in the two shipped default forms
         if (slices > 1) DAS3R_LAUNCH((render_backward_blk_kernel<192, 0, 32, 4, true>), dim3(xcd_grid(L), slices), dim3(TILE_PIX), 0, s, ARGS);

@@ -384,7 +384,8 @@ __global__ void __launch_bounds__(256, OCC) render_backward_regions_kernel(
 }
 
 int launch_render_backward_regions(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
-                                   float *partial, int mb, int slices, hipStream_t s) {
+                                   float *partial, const BwdChoice &c, hipStream_t s) {
+    const int mb = c.mb, slices = c.slices;
 #define ARGS                                                                                                              \
     (const uint2 *)(img + L.pub.ranges), (const uint32_t *)(binning + L.pub.point_list), a->image_width, a->image_height, \
         L.tiles_x, pack_tiles(L), (const float4 *)(geom + L.pub.xy), (const float4 *)(geom + L.pub.conic_opacity),             \
@@ -404,8 +405,8 @@ int launch_render_backward_regions(const das3r_raster_args *a, const float *dL_d
     } else
 #endif
     if (switches().mutate == 1) DAS3R_LAUNCH((render_backward_regions_kernel<128, 5, true>), dim3(xcd_grid(L), std::max(slices, 1)), dim3(TILE_PIX), 0, s, ARGS);
-    else if (switches().render_bwd_pix == 9) GQ(128, 5, 0);   // fine128q: strips, a wave per quadrant (A-B runs)
-    else if (switches().render_bwd_pix == 8) GQ(128, 5, 1);   // fine128s: strips, interleaved
+    else if (c.strips == STRIPS_QUADRANT) GQ(128, 5, 0);      // fine128q: strips, a wave per quadrant (A-B runs)
+    else if (c.strips == STRIPS_INTERLEAVED) GQ(128, 5, 1);   // fine128s: strips, interleaved
     else if (mb == 64) GO(64, 5);
     else if (mb == 96) GO(96, 5);
     else if (mb == 160) GO(160, 4);

@@ -388,7 +388,8 @@ __global__ void __launch_bounds__(256, (MB <= 128 ? 4 : 2)) render_backward_scan
 }
 
 int launch_render_backward_scan(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
-                                float *partial, int mb, int slices, hipStream_t s) {
+                                float *partial, const BwdChoice &c, hipStream_t s) {
+    const int mb = c.atomic_flush ? 256 : c.mb, slices = c.slices;   // (the atomic flush has one form: 256 entries per round, whatever the spelling asked for)
 #define ARGS                                                                                                              \
     (const uint2 *)(img + L.pub.ranges), (const uint32_t *)(binning + L.pub.point_list), a->image_width, a->image_height, \
         L.tiles_x, pack_tiles(L), (const float4 *)(geom + L.pub.xy), (const float4 *)(geom + L.pub.conic_opacity),             \
@@ -397,7 +398,7 @@ int launch_render_backward_scan(const das3r_raster_args *a, const float *dL_dpix
         (uint32_t)(a->P - 1), (uint32_t)L.capacity, (const float4 *)(binning + L.b_ckpt), pair_counters()
 #define GO(MBV, AT, AB) DAS3R_LAUNCH((render_backward_scan_kernel<MBV, AT, AB>), dim3(xcd_grid(L), slices > 1 ? slices : 1), dim3(TILE_PIX), 0, s, ARGS)
     const int abl = switches().ablate_set ? switches().ablate : 0;
-    // mb: 64 / 128 / 256 private accumulator regions; 1256: 256 entries per round with the atomic flush
+    // mb: 64 / 128 / 256 private accumulator regions; scana<N>: 256 entries per round with the atomic flush
     if (mb == 128 && abl == 1) GO(128, false, 1);
     else if (mb == 128 && abl == 2) GO(128, false, 2);
     else if (mb == 128 && abl == 3) GO(128, false, 3);
@@ -405,7 +406,7 @@ int launch_render_backward_scan(const das3r_raster_args *a, const float *dL_dpix
     else if (mb == 128 && abl == 8) GO(128, false, 8);
     else if (mb == 64) GO(64, false, 0);
     else if (mb == 128) GO(128, false, 0);
-    else if (mb >= 1000) GO(256, true, 0);
+    else if (c.atomic_flush) GO(256, true, 0);
     else GO(256, false, 0);
 #undef GO
 #undef ARGS

@@ -114,20 +114,20 @@ __global__ void __launch_bounds__(256) render_forward_kernel(const uint2 *__rest
 int launch_render_forward(const das3r_raster_args *a, const float *colors_precomp, float *out_color, char *geom, char *binning,
                           char *img, const Layout &L, const LocalBin &lb, hipStream_t s, float *out_invdepth, float4 *dckpt) {
     (void)colors_precomp;  // precomputed colours were copied into rgbd by the preprocess kernel
-    if (use_quad_lanes(L, lb))
-    {   // one workgroup per tile (lanes), or four (regions) where the tile lists are skewed: the host has been told by the forwards before this one
-        const int f = switches().render_fwd;
-        if (f == 4) {
-            if (out_invdepth) {   // (das3r_raster_forward refuses this combination before it launches anything; kept as a guard)
-                set_error("DAS3R_RENDER=slices has no inverse-depth form (das3r_raster_out.out_invdepth)");
-                return DAS3R_ERR_INVALID_ARG;
-            }
-            return launch_render_forward_slices(a, out_color, geom, binning, img, L, lb, s);
-        }
-        if (f == 5 || (f == 0 && lb.prefer_regions)) return launch_render_forward_regions(a, out_color, geom, binning, img, L, lb, s, out_invdepth, dckpt);
-        return launch_render_forward_lanes(a, out_color, geom, binning, img, L, lb, s, out_invdepth, dckpt);
+    // which kernel: kernel_choice.h (lb.point_list != null: lists in local depth order, which only this kernel and the rows kernel sort)
+    const FwdKernel k = choose_forward(switches(), L.ntiles, L.capacity, lb.point_list != nullptr, lb.prefer_regions);
+    if (out_invdepth && !fwd_has_invdepth_form(k)) {   // (das3r_raster_forward refuses this combination before it launches anything; kept as a guard)
+        set_error("DAS3R_RENDER=%s has no inverse-depth form (das3r_raster_out.out_invdepth)", fwd_kernel_name(k));
+        return DAS3R_ERR_INVALID_ARG;
     }
-    if (use_row_private(L.capacity, L.ntiles)) return launch_render_forward_rows(a, out_color, geom, binning, img, L, lb, s, out_invdepth, dckpt);
+    switch (k) {
+        case FWD_SLICES: return launch_render_forward_slices(a, out_color, geom, binning, img, L, lb, s);
+        // one workgroup per tile (lanes), or four (regions) where the tile lists are skewed: the host has been told by the forwards before this one
+        case FWD_REGIONS: return launch_render_forward_regions(a, out_color, geom, binning, img, L, lb, s, out_invdepth, dckpt);
+        case FWD_LANES: return launch_render_forward_lanes(a, out_color, geom, binning, img, L, lb, s, out_invdepth, dckpt);
+        case FWD_ROWS: return launch_render_forward_rows(a, out_color, geom, binning, img, L, lb, s, out_invdepth, dckpt);
+        default: break;   // FWD_QUAD: below
+    }
     const int pad_lds = switches().fwd_pad_lds;   // occupancy experiments
 #define ARGS                                                                                                                    \
     (const uint2 *)(img + L.pub.ranges), (const uint32_t *)(binning + L.pub.point_list), a->image_width, a->image_height, L.tiles_x, \

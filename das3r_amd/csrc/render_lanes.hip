@@ -153,14 +153,7 @@ __global__ void __launch_bounds__(LN_THREADS) __attribute__((amdgpu_waves_per_eu
     }
 }
 
-// Few tiles (fewer waves than the SIMDs can interleave with one pixel per lane), lists from the global sort: see the head of the file.
-bool use_quad_lanes(const Layout &L, const LocalBin &lb) {
-    if (lb.point_list != nullptr) return false;   // (lists in local depth order: render_rows.hip sorts them itself)
-    const int forced = switches().render_fwd;
-    if (forced) return forced >= 3;
-    return L.ntiles <= 1024 && L.capacity >= (int64_t)1024 * L.ntiles;
-}
-
+// (taken for few tiles with long lists from the global sort: kernel_choice.h quad_lanes)
 int launch_render_forward_lanes(const das3r_raster_args *a, float *out_color, char *geom, char *binning, char *img, const Layout &L, const LocalBin &lb,
                                 hipStream_t s, float *out_invdepth, float4 *dckpt) {
 #define ARGS                                                                                                                                   \

@@ -7,7 +7,7 @@
 // wave cut the iteration count to 0.73-0.78x (1080p) and 0.47x (DAS3R shape): the four rows of a wave process four
 // DIFFERENT splats in one pass of the instruction stream.  Measured: forward 1.12 -> 0.84 ms on the 5 M-splat DAS3R-shaped
 // scene, 0.294 -> 0.273 ms at 1 M splats / 1080p, 0.045 -> 0.050 ms at 100 k (list building dominates short lists, hence the
-// switch in use_row_private()).
+// switch in kernel_choice.h row_private()).
 //
 // Per batch of 256 LDS-staged splats every wave builds four compacted index lists (one per row: ballot + mbcnt prefix, u8
 // indices in LDS), then iterates i = 0 .. longest list; a row whose list is exhausted idles (predicated off).  The per-pixel
@@ -285,14 +285,7 @@ __global__ void __launch_bounds__(256) FWD_WAVES(PREFETCH || DEPTH) render_forwa
     }
 }
 
-// The row lists cost ~200 instructions per wave and batch to build: worth it once a tile's list is long.  DAS3R_RENDER=quad /
-// rows forces one of the two forward kernels (A-B runs, tests).
-bool use_row_private(int64_t instances, int ntiles) {
-    const int forced = switches().render_fwd;
-    if (forced == 1 || forced == 2) return forced == 2;   // (3: render_lanes.hip where it applies, else by length)
-    return instances >= (int64_t)128 * ntiles;
-}
-
+// (taken once a tile's list is long: kernel_choice.h row_private)
 int launch_render_forward_rows(const das3r_raster_args *a, float *out_color, char *geom, char *binning, char *img, const Layout &L,
                                const LocalBin &lb, hipStream_t s, float *out_invdepth, float4 *dckpt) {
 #define ARGS                                                                                                              \

@@ -626,6 +626,38 @@ void das3r_debug_path_policy_forget(das3r_path_policy_state *state);           /
 void das3r_debug_path_policy_resume(das3r_path_policy_state *state, uint32_t fine, uint32_t forwards);   /* das3r_raster_learning(set) */
 int das3r_debug_seg_dbits(int32_t tbits, int32_t passes);   /* depth-bucket bits `passes` partition passes leave beside tbits bits of tile id */
 
+/* ---- the switches and the compositing-kernel choice on a caller's own values (test aid) -------------------------------------------
+ * Additive symbols under ABI 16.  What every DAS3R_* spelling means and which compositing kernel a forward and a backward launch is host
+ * arithmetic (csrc/kernel_choice.h); these calls run exactly those functions.  Host-only: no device needed, no HIP call; neither the process
+ * environment nor the switches the library itself last read are looked at or changed.  Flags are 0 / 1.
+ * Kernel kinds: forward 0 auto, 1 quad, 2 rows, 3 lanes, 4 slices, 5 fine (regions); backward 0 auto, 1 dpp, 2 mfma, 3 scan, 5 stream, 6 blk,
+ * 7 fine (regions). */
+typedef struct {
+    int32_t sort_ipl, sort_classic, rect_upstream, verbose, binning, capacity_exact, fused_emit_off, no_sh_stage;
+    int32_t render_fwd, render_bwd;                    /* the forced kernel kinds (0: none) */
+    int32_t render_bwd_mb, render_bwd_atomic;          /* entries per round of a DAS3R_RENDER_BWD spelling (0: none given); scana... */
+    int32_t render_bwd_pix, render_bwd_occ;            /* blk...p<N>, blk...o<N> */
+    int32_t render_bwd_strips;                         /* fine...q: 1, fine...s: 2 */
+    int32_t tile_chunk, scan_items, deterministic, tile_lpt_off, bwd_reduce_set, bwd_reduce_shfl, ablate_set, ablate, tickets;
+    int32_t bwd_pad_lds, fwd_pad_lds, bwd_buckets, fwd_no_prefetch, split_colour, tile_strip;
+} das3r_switches;
+typedef struct {
+    int32_t kernel, mb, slices;                        /* kind (never 0), entries per round, workgroups per tile of the bucket-parallel replay */
+    int32_t pix, occ, strips, atomic_flush;            /* the forms of blk (pix, occ), of the region walk (strips) and of scan (atomic_flush) */
+} das3r_bwd_choice;
+typedef struct {
+    int32_t kernel, quad_lanes, row_private, tile_lpt; /* kind (never 0); the predicates behind it; the tiles longest list first */
+} das3r_fwd_choice;
+/* parses the n (name, value) pairs as if they were the environment; experiments: also the variables only `make EXPERIMENTS=1` builds read */
+void das3r_debug_parse_switches(const char *const *names, const char *const *values, int32_t n, int32_t experiments, das3r_switches *out);
+/* fwd_flags: das3r_raster_saved.flags of the forward */
+void das3r_debug_choose_backward(const das3r_switches *sw, int64_t num_rendered, int32_t ntiles, uint32_t fwd_flags, das3r_bwd_choice *out);
+/* local_lists: the tile lists are in local depth order; prefer_regions: das3r_path_policy_state.fine */
+void das3r_debug_choose_forward(const das3r_switches *sw, int32_t ntiles, int64_t capacity, int32_t local_lists, int32_t prefer_regions,
+                                das3r_fwd_choice *out);
+int das3r_debug_has_invdepth_form(int32_t backward, int32_t kernel);      /* can the (backward != 0: backward) kernel kind run with an inverse-depth map */
+const char *das3r_debug_kernel_name(int32_t backward, int32_t kernel);    /* the kind's name in DAS3R_RENDER / DAS3R_RENDER_BWD and in error messages */
+
 int das3r_abi_version(void);
 const char *das3r_last_error(void);
 

@@ -1,10 +1,11 @@
-// api.hip — the C-ABI entry points of libdas3r_hip.so (include/das3r_raster.h) and the buffer layout.
+// api.hip — the C-ABI entry points of libdas3r_hip.so (include/das3r_raster.h) except das3r_raster_forward / _check / das3r_get_stats
+// (forward.hip), the switches, the residency rule, the profiler and the buffer layout.
 #include <stdarg.h>
 #include <string.h>
 
 #include <vector>
 
-#include "common.h"
+#include "host_state.h"
 #include <algorithm>
 
 namespace das3r {
@@ -72,11 +73,10 @@ const Switches &switches() {
 // The bound is taken from the device the call runs on (compute partitions have fewer CUs) and stays below what it holds
 // (>= 3 workgroups per CU of the heaviest of these kernels).  DAS3R_TICKETS=always switches the short cut off.
 // Round 6: "the whole grid is resident" presumes that the grid has the device to itself.  The library knows when it does
-// not: every host thread that renders on a device registers there (per_device(), below; un-registered when the thread ends), and
+// not: every host thread that renders on a device registers there (forward.hip per_device(); un-registered when the thread ends), and
 // once a second thread has, every chained kernel of that device takes its tickets — whatever farm.run_jobs or the environment say
 // (a DAS3R_TICKETS bound set by hand still wins: it is an experiment switch, and says so once on stderr).  Two PROCESSES on one GPU
 // are not seen from here: tools/jobs_per_gpu.py's process mode sets DAS3R_TICKETS=always for its children.
-constexpr int MAX_DEVICES = 64;
 static int g_threads_on_device[MAX_DEVICES] = {};
 struct ThreadRegistrar {
     bool on[MAX_DEVICES] = {};
@@ -89,6 +89,7 @@ struct ThreadRegistrar {
     }
 };
 static thread_local ThreadRegistrar g_registrar;
+void register_rendering_thread(int dev) { g_registrar.add(dev); }
 bool grid_is_resident(int nblocks) {
     const int forced = switches().tickets;
     int dev = 0;
@@ -110,57 +111,6 @@ bool grid_is_resident(int nblocks) {
         cached_limit = cus * 2;   // the heaviest chained kernels get 3 workgroups per CU
     }
     return nblocks <= cached_limit;
-}
-
-// The split preprocess (preprocess.hip: geometry kernel on the caller's stream, SH colour kernel on a side stream beside the binning chain):
-// taken or not from the call's SHAPE alone, never from a timing, so that a job computes with the same kernels however it was scheduled (both
-// forms store the same bits; the rule keeps the launch sequence reproducible too).
-//   binning_path   0 the global depth sort (it scatters the depth keys the colour kernel reads: fused kernel)
-//                  1 index-order emission with a binning chain of its own (local order, segmented): the window the colour kernel fills
-//                  2 emission fused into the preprocess kernel (P <= 196 k, the whole grid resident: no chain to run beside)
-//   forced         Switches::split_colour: -1 never, 1 wherever it can run (SH given, active degree >= 1, path 1), 0 by shape:
-// active degree >= 2 (rows of 108 / 192 bytes and the nine Jacobian planes: at degree 0 / 1 the colour is 12 / 48 bytes of input, nothing to
-// hide), P >= SPLIT_MIN_P (below that the colour kernel is a few microseconds, of the order of the fork and the join themselves), and a
-// forward a backward may follow (flags bit 3 clear on the way in).  An evaluation forward keeps the fused kernel: its callers wait for every
-// view, and where the stream has run dry before the call — the no-grad glue render, bench.py's eval_forward — the six host calls of the fork
-// and the join are on the critical path themselves: 3.11 -> 3.18 ms per view measured, against 0.657 -> 0.648 on the fused evaluation path.
-constexpr int SPLIT_MIN_P = 1 << 18;
-bool split_colour_rule(bool has_sh, int sh_degree, int P, int binning_path, bool no_backward, int forced) {
-    if (!has_sh || sh_degree < 1 || binning_path != 1 || forced < 0 || P <= 0) return false;
-    if (forced > 0) return true;
-    return sh_degree >= 2 && P >= SPLIT_MIN_P && !no_backward;
-}
-
-// One side stream and its two events per (host thread, device, caller stream), created at the first split forward of the stream and destroyed
-// with the thread.  K jobs in flight (farm.run_jobs: K host threads, each on its own stream) get one each; the hardware queue count is the
-// runtime's business.  (A side stream of the lowest priority the device offers measured the same as this one: ledger.)
-struct SideStreams {
-    struct Entry { int dev; hipStream_t caller; SideStream ss; };
-    std::vector<Entry> all;
-    ~SideStreams() {
-        for (auto &e : all) {
-            (void)hipEventDestroy(e.ss.fork);
-            (void)hipEventDestroy(e.ss.join);
-            (void)hipStreamDestroy(e.ss.stream);
-        }
-    }
-};
-static int side_stream_for(hipStream_t s, SideStream *out) {
-    static thread_local SideStreams streams;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    for (auto &e : streams.all)
-        if (e.dev == dev && e.caller == s) { *out = e.ss; return DAS3R_OK; }
-    SideStream ss = {nullptr, nullptr, nullptr, 0};
-    int cus = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    ss.colour_blocks = COLOUR_WGS_PER_CU * (cus > 0 ? cus : 1);
-    HIP_TRY(hipStreamCreateWithFlags(&ss.stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&ss.fork, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&ss.join, hipEventDisableTiming));
-    streams.all.push_back(SideStreams::Entry{dev, s, ss});
-    *out = ss;
-    return DAS3R_OK;
 }
 
 int sort_ipl_override() { return switches().sort_ipl; }
@@ -250,71 +200,6 @@ void compute_layout(int P, int64_t I, int W, int H, Layout *L, bool shjac) {
     L->pub.ranges = take(8 * (size_t)(L->ntiles > 0 ? L->ntiles : 1));
     L->i_order = take(4 * (size_t)(L->ntiles > 0 ? L->ntiles : 1));
     L->pub.img_bytes = o;
-}
-
-// Depth histograms of the segmented path (segkey.h), round 6: two 256-word slots per (host thread, device, stream), used in turn.  A forward's
-// preprocess kernel accumulates into one and ZEROES THE OTHER for the next forward of the stream — the memset that used to precede every
-// forward (a launch of its own: 5 us of every DAS3R-shaped iteration) is gone.  Launches of one stream are ordered, so the slot a forward
-// zeroes is read by nobody (the previous forward's emission has finished), and the slot it reads stays as it is until the NEXT forward's
-// preprocess kernel, however often its own emission is redone.  Should a slot ever be dirty — an aborted forward — the buckets come out
-// less even for one forward and exact all the same: any histogram gives a monotone map, the same one in every workgroup.
-static bool dhist_slots(hipStream_t s, uint32_t **use, uint32_t **next) {
-    struct Slot { int dev; hipStream_t stream; uint32_t *buf; uint32_t turn; };
-    static thread_local std::vector<Slot> slots;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return false;
-    Slot *e = nullptr;
-    for (auto &c : slots)
-        if (c.dev == dev && c.stream == s) e = &c;
-    if (!e) {
-        uint32_t *buf = nullptr;
-        if (hipMalloc((void **)&buf, 2 * 256 * sizeof(uint32_t)) != hipSuccess) return false;
-        if (hipMemsetAsync(buf, 0, 2 * 256 * sizeof(uint32_t), s) != hipSuccess) return false;   // (on the stream whose kernels use it: ordered)
-        slots.push_back(Slot{dev, s, buf, 0u});
-        e = &slots.back();
-    }
-    e->turn++;
-    *use = e->buf + 256 * (e->turn & 1u);
-    *next = e->buf + 256 * ((e->turn + 1u) & 1u);
-    return true;
-}
-// The depth histogram of this forward (segkey.h): filled by the preprocess kernel, read by the emission.  Not segmented: none (nulls).
-// No slot: in the geometry buffer, zeroed by a memset, as before round 6 (*next stays null).
-static int seg_dhist_for(bool seg, hipStream_t s, char *geom, const Layout &L, uint32_t **use, uint32_t **next) {
-    *use = *next = nullptr;
-    if (seg && !dhist_slots(s, use, next)) {
-        *use = (uint32_t *)(geom + L.g_dhist);
-        HIP_TRY(hipMemsetAsync(*use, 0, 4 * 256, s));
-    }
-    return DAS3R_OK;
-}
-
-static int validate(const das3r_raster_args *a, const das3r_raster_in *in) {
-    if (!a || !in) { set_error("null args"); return DAS3R_ERR_INVALID_ARG; }
-    if (a->P < 0 || a->image_width <= 0 || a->image_height <= 0) { set_error("bad extents P=%d W=%d H=%d", a->P, a->image_width, a->image_height); return DAS3R_ERR_INVALID_ARG; }
-    if ((int64_t)((a->image_width + TILE_X - 1) / TILE_X) * ((a->image_height + TILE_Y - 1) / TILE_Y) >= (1ll << 22)) {   // render_common.h pack_tiles
-        set_error("image of %d x %d pixels has 2^22 tiles or more", a->image_width, a->image_height);
-        return DAS3R_ERR_INVALID_ARG;
-    }
-    if (a->P == 0) return DAS3R_OK;
-    if (!a->bg || !a->viewmatrix || !a->projmatrix || !a->campos) { set_error("bg/viewmatrix/projmatrix/campos must be device pointers"); return DAS3R_ERR_INVALID_ARG; }
-    if (in->pre) {   // ABI 14: raw parameters + pose; the camera-frame tensors are not looked at
-        const das3r_pretransform *p = in->pre;
-        if (!p->xyz || !p->rot || !p->scaling || !p->opacity_raw || !p->conf_flat || !p->R || !p->t || !p->Lq) { set_error("das3r_raster_in.pre: xyz / rot / scaling / opacity_raw / conf_flat / R / t / Lq are required"); return DAS3R_ERR_INVALID_ARG; }
-        if (in->cov3D_precomp) { set_error("das3r_raster_in.pre excludes cov3D_precomp"); return DAS3R_ERR_INVALID_ARG; }
-    } else if (!in->means3D || !in->opacities) { set_error("means3D/opacities are required"); return DAS3R_ERR_INVALID_ARG; }
-    if ((in->shs != nullptr) == (in->colors_precomp != nullptr)) { set_error("Please provide excatly one of either SHs or precomputed colors!"); return DAS3R_ERR_INVALID_ARG; }
-    const bool sr = in->pre != nullptr || (in->scales != nullptr && in->rotations != nullptr);
-    if ((!in->pre && (in->scales != nullptr) != (in->rotations != nullptr)) || sr == (in->cov3D_precomp != nullptr)) {
-        set_error("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!");
-        return DAS3R_ERR_INVALID_ARG;
-    }
-    if (in->shs) {
-        if (a->sh_degree < 0 || a->sh_degree > 3) { set_error("sh_degree must be 0..3 (got %d)", a->sh_degree); return DAS3R_ERR_INVALID_ARG; }
-        if (a->M < (a->sh_degree + 1) * (a->sh_degree + 1) || a->M > 16) { set_error("M=%d incompatible with sh_degree=%d (need (D+1)^2 <= M <= 16)", a->M, a->sh_degree); return DAS3R_ERR_INVALID_ARG; }
-    }
-    if (a->tanfovx <= 0.f || a->tanfovy <= 0.f) { set_error("tanfov must be positive"); return DAS3R_ERR_INVALID_ARG; }
-    return DAS3R_OK;
 }
 
 }  // namespace das3r
@@ -421,118 +306,6 @@ extern "C" int das3r_raster_get_layout(int32_t P, int64_t num_rendered, int32_t 
     return DAS3R_OK;
 }
 
-// Host mailbox: a pinned, device-visible block per host thread and device.  The scan kernel stores {count, flags} and then the
-// tag of the call (system-scope release) into words 0..2; word 10 is raised by a compositing kernel that met a tile list too
-// long for its LDS sort; the last binning kernel of a forward stores {self-check word, tag} into one of CHECK_SLOTS two-word
-// slots from word 16 on (slot = tag % CHECK_SLOTS).  The host polls the tags — no D2H copy kernel, no event, no parked thread
-// (hipEventSynchronize's wake-up alone cost ~100 us per forward, a third of a 100 k-splat step).
-struct Mailbox {
-    volatile uint32_t *host = nullptr;
-    uint32_t *dev = nullptr;
-    uint32_t seq = 0;
-};
-// the words the host reads by index (the kernels are handed pointers: dev + MB_COUNT {count, flags, tag}, dev + MB_TOO_LONG {too long,
-// want bits}, dev + MB_LONGEST {longest, tag, crowding})
-enum MailboxWord : uint32_t {
-    MB_COUNT = 0,       // num_rendered of the forward whose tag is in MB_COUNT_TAG
-    MB_COUNT_TAG = 2,
-    MB_TOO_LONG = 10,   // != 0: a forward of the shape with that generation number met a list too long for LDS (path_policy.h)
-    MB_WANT_BITS = 11,  // != 0: the segmented path of that generation sorted a segment long enough to want more bucket bits
-    MB_FILTERED = 12,   // the tag of a forward whose preprocess kernel culled a point
-    MB_LONGEST = 13,    // list_skew_kernel: the longest tile list of the forward whose tag is in MB_SKEW_TAG
-    MB_SKEW_TAG = 14,
-    MB_CROWD16 = 15,    // ... and of 64 consecutive list entries, those in the tile's fullest quadrant, x 16
-};
-// the tag of the next hand-off through the mailbox (never 0: an empty word names nobody)
-static uint32_t next_tag(Mailbox *mb) { return ++mb->seq ? mb->seq : ++mb->seq; }
-// Everything the library remembers between calls, per host thread and per device (a thread that renders on two GPUs gets two
-// of these; nothing is shared between threads: any number of them may render concurrently, each on its own stream).
-constexpr uint32_t CHECK_SLOTS = 16, CHECK_WORD0 = 16, MAILBOX_BYTES = 4 * (CHECK_WORD0 + 2 * CHECK_SLOTS);
-struct PerDevice {
-    Mailbox mb;
-    uint32_t pending[CHECK_SLOTS] = {};             // per slot: tag of the forward whose self-check word has not been examined yet
-    unsigned long long *arrive_ring = nullptr;      // self re-arming arrival words of the preprocess kernel's count reduction
-    Verdict verdict;                                // what the last forward of the current shape (P, W, H) taught us (path_policy.h)
-    Resume resume;                                  // das3r_raster_learning(set): handed to the next shape this thread meets
-    char *emit_ring = nullptr;                      // control words of the emission fused into the preprocess kernel
-    bool emit_ring_dirty = false;
-    uint32_t emit_last_tag = 0;
-};
-static int per_device(PerDevice **out) {
-    static thread_local PerDevice state[MAX_DEVICES];
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= MAX_DEVICES) { set_error("device ordinal %d not supported", dev); return DAS3R_ERR_INVALID_ARG; }
-    PerDevice &T = state[dev];
-    g_registrar.add(dev);   // (grid_is_resident: a second rendering thread on the device switches the ticket-free short cut off)
-    if (!T.mb.host) {
-        uint32_t *h = nullptr;
-        HIP_TRY(hipHostMalloc((void **)&h, MAILBOX_BYTES, hipHostMallocMapped));
-        memset(h, 0, MAILBOX_BYTES);
-        HIP_TRY(hipHostGetDevicePointer((void **)&T.mb.dev, h, 0));
-        T.mb.host = h;
-    }
-    *out = &T;
-    return DAS3R_OK;
-}
-// spin until `*word` carries `tag` — bounded: a look at the stream now and then, at last a stream synchronise and one more look.
-// *seen = what the word held at that last look (the caller decides what a missing tag means)
-static int await_tag(volatile uint32_t *word, uint32_t tag, hipStream_t s, uint32_t *seen) {
-    for (long spins = 0; spins < 200000000L; spins++) {
-        if ((*seen = __atomic_load_n(word, __ATOMIC_ACQUIRE)) == tag) return DAS3R_OK;
-        __builtin_ia32_pause();
-        if ((spins & 0xFFFFF) == 0xFFFFF && hipStreamQuery(s) != hipErrorNotReady) break;   // stream drained (or failed): stop spinning
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    *seen = __atomic_load_n(word, __ATOMIC_ACQUIRE);
-    return DAS3R_OK;
-}
-// wait for word `idx` to carry `tag`, or give up loudly
-static int mailbox_wait(Mailbox *mb, int idx, uint32_t tag, hipStream_t s) {
-    uint32_t seen = 0;
-    const int r = await_tag(&mb->host[idx], tag, s, &seen);
-    if (r) return r;
-    if (seen == tag) return DAS3R_OK;
-    set_error("the device never delivered the result of this forward to the host mailbox");
-    return DAS3R_ERR_HIP;
-}
-
-// Examine the self-check word a forward's last binning kernel left in `slot` = {flags, tag} of a host mailbox (bit 1 look-back
-// timeout, 2 index out of range -> write suppressed, 8 counts do not add up to the histogram; 16 = a stalled look-back was rescued,
-// granule.h: informational).  wait: spin (bounded) until the word of `tag` is there.  Returns 1 when the slot does not hold
-// `tag`'s word (not there yet, or — after CHECK_SLOTS later forwards, each of which examines the slot before reusing it — gone).
-static unsigned long long g_stats[4] = {0, 0, 0, 0};   // forwards, self-check words examined, rescued look-back polls, failed self-checks
-static void stat_add(int i) { __atomic_fetch_add(&g_stats[i], 1ull, __ATOMIC_RELAXED); }
-static int examine_check_slot(volatile uint32_t *slot, uint32_t tag, bool wait, hipStream_t s) {
-    uint32_t seen = __atomic_load_n(&slot[1], __ATOMIC_ACQUIRE);
-    if (seen != tag && wait) {
-        const int r = await_tag(&slot[1], tag, s, &seen);
-        if (r) return r;
-    }
-    if (seen != tag) return 1;
-    const uint32_t all_flags = slot[0], flags = all_flags & ~16u;
-    if (all_flags & 0x80000000u) return DAS3R_OK;   // this forward's failure has been reported already (by the backward pass / das3r_raster_check)
-    stat_add(1);
-    if (all_flags & 16u) stat_add(2);
-    if (flags) stat_add(3);
-    if ((all_flags & 16u) && switches().verbose) fprintf(stderr, "das3r: a look-back poll needed the read-modify-write path\n");
-    if (flags) {
-        slot[0] = all_flags | 0x80000000u;   // reported once: the thread that made the forward will not report it again at its next call
-        set_error("a forward's binning failed its self-check (flags 0x%x); its output is invalid", flags);
-        return DAS3R_ERR_HIP;
-    }
-    return DAS3R_OK;
-}
-
-// The self-check of the forward that produced `saved`, for callers that want it BEFORE they consume the image (the forward
-// itself returns as soon as everything is enqueued; das3r_raster_backward runs this first).  Waits, bounded, for the word.
-extern "C" int das3r_raster_check(const das3r_raster_saved *saved, das3r_stream_t stream) {
-    if (!saved) { set_error("das3r_raster_check: null saved state"); return DAS3R_ERR_INVALID_ARG; }
-    if (!saved->check_word || !saved->check_tag) return DAS3R_OK;   // P == 0, nothing rendered, or a caller that dropped the ticket
-    const int r = examine_check_slot((volatile uint32_t *)saved->check_word, saved->check_tag, true, (hipStream_t)stream);
-    return r < 0 ? r : DAS3R_OK;
-}
-
 // ABI 13: what the calling thread's library state has LEARNT about shapes on the current device is forgotten (counts, binning path, forward
 // kernel choice); the mailbox, rings and tickets stay.  See include/das3r_raster.h.
 extern "C" int das3r_raster_forget_shapes(void) {
@@ -559,313 +332,12 @@ extern "C" int das3r_raster_learning(int32_t set, uint32_t state[2]) {
     return DAS3R_OK;
 }
 
-extern "C" void das3r_get_stats(uint64_t out[4]) {
-    for (int i = 0; i < 4; i++) out[i] = (uint64_t)__atomic_load_n(&g_stats[i], __ATOMIC_RELAXED);
-}
-
-extern "C" int64_t das3r_raster_forward(const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_out *out,
-                                        das3r_alloc_fn alloc_geom, das3r_alloc_fn alloc_binning, das3r_alloc_fn alloc_img,
-                                        void *user, das3r_raster_saved *saved, das3r_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
-    stat_add(0);
-    int rc = validate(a, in);
-    if (rc) return rc;
-    if (!out || !out->out_color || (a->P > 0 && !out->radii) || !alloc_geom || !alloc_binning || !alloc_img || !saved) {
-        set_error("das3r_raster_forward: null output/allocator");
-        return DAS3R_ERR_INVALID_ARG;
-    }
-    if (out->out_invdepth && !fwd_has_invdepth_form(switches().render_fwd)) {   // ABI 16: every forward kernel the library picks has an inverse-depth form, not the forced slices
-        set_error("das3r_raster_forward: DAS3R_RENDER=%s has no inverse-depth form (das3r_raster_out.out_invdepth)", fwd_kernel_name(switches().render_fwd));
-        return DAS3R_ERR_INVALID_ARG;
-    }
-    const int P = a->P, W = a->image_width, H = a->image_height;
-    const bool depth = out->out_invdepth != nullptr;   // ABI 16: the binning buffer also holds Layout::d_* (d_bytes instead of binning_bytes)
-    // the geometry buffer also holds Layout::g_shjac (flags bit 2) — unless the caller said that no backward will read it (flags bit 3 on the
-    // way in, read before the struct is cleared below)
-    const bool shjac = in->shs != nullptr && a->sh_degree >= 2 && !(saved->flags & NO_BACKWARD_IN_FLAG);
-    const bool no_backward = (saved->flags & NO_BACKWARD_IN_FLAG) != 0;
-    const bool aa = (saved->flags & ANTIALIAS_FLAG) != 0;   // (bit 4 on the way in: an antialiased forward; set again on the way out)
+// The layout of a finished forward's buffers: for the capacity they were laid out for (a caller that kept only num_rendered: for that).
+// (rasterizer.py alpha_of asks das3r_raster_get_layout the same way.)
+static Layout saved_layout(const das3r_raster_args *a, const das3r_raster_saved *saved, bool shjac = false) {
     Layout L;
-    compute_layout(P, 0, W, H, &L, shjac);
-    saved->geom = alloc_geom(user, L.pub.geom_bytes);
-    saved->img = alloc_img(user, L.pub.img_bytes);
-    saved->binning = nullptr;
-    saved->num_rendered = 0;
-    saved->capacity = 0;
-    saved->check_word = nullptr;
-    saved->check_tag = 0;
-    saved->flags = aa ? ANTIALIAS_FLAG : 0u;
-    if (!saved->geom || !saved->img) { set_error("scratch allocation failed (geom %zu B, img %zu B)", L.pub.geom_bytes, L.pub.img_bytes); return DAS3R_ERR_ALLOC; }
-    if (P == 0) {
-        // upstream:rasterize_points.cu skips the rasterizer when P == 0: the image stays zero (background NOT applied)
-        HIP_TRY(hipMemsetAsync(out->out_color, 0, sizeof(float) * 3 * (size_t)W * H, s));
-        if (out->out_invdepth) HIP_TRY(hipMemsetAsync(out->out_invdepth, 0, sizeof(float) * (size_t)W * H, s));
-        HIP_TRY(hipMemsetAsync(saved->img + L.pub.ranges, 0, 8 * (size_t)L.ntiles, s));
-        saved->binning = alloc_binning(user, 256);
-        return 0;
-    }
-    // Host <-> device hand-offs of one forward (all through the pinned mailbox, no copies, no events):
-    //   * num_rendered (sum of tiles_touched) leaves with the preprocess kernel, five kernels before the device needs it, so
-    //     the binning buffer is sized exactly and the host practically never waits (upstream blocks on a cudaMemcpy in the
-    //     middle of every forward); on the local-order path nothing waits for it at all (speculative capacity, below);
-    //   * the binning self-check word is delivered by the last binning kernel into a slot of the mailbox; saved->check_word /
-    //     check_tag name it.  It is examined by das3r_raster_backward (before anything is launched) and das3r_raster_check, which
-    //     wait for it, and — for callers that use neither — without waiting at the start of this thread's later forwards;
-    //     debug mode waits for it before returning.
-    PerDevice *T = nullptr;
-    if ((rc = per_device(&T))) return rc;
-    Mailbox *mb = &T->mb;
-    auto check_slot = [&](uint32_t i, bool wait) -> int {
-        if (!T->pending[i]) return DAS3R_OK;
-        const int r = examine_check_slot(mb->host + CHECK_WORD0 + 2 * i, T->pending[i], wait, s);
-        if (r == 1) return DAS3R_OK;   // not there yet: look again next time
-        T->pending[i] = 0;
-        return r;
-    };
-    for (uint32_t i = 0; i < CHECK_SLOTS; i++)
-        if ((rc = check_slot(i, false))) return rc;
-    uint32_t late_tag = 0;
-    // per-thread ring of self re-arming arrival words for the count reduction of the preprocess kernel
-    unsigned long long *&arrive_ring = T->arrive_ring;
-    constexpr uint32_t ARRIVE_SLOTS = 16, ARRIVE_WORDS = 8 + 64 * 8;   // per call: top word + 64 sub-counters, one 64-byte line each
-    if (!arrive_ring) {
-        HIP_TRY(hipMalloc((void **)&arrive_ring, ARRIVE_SLOTS * ARRIVE_WORDS * sizeof(unsigned long long)));
-        // on the CALLER'S stream, in front of the kernel that counts in it: hipMemset runs on the null stream, which a non-blocking stream
-        // does not wait for — with a second job keeping the GPU busy (round 5: farm.run_jobs) the fill could land AFTER the first preprocess
-        // kernel of this thread had started counting, the last arriver never saw its total, and the forward ended with "the device never
-        // delivered the result of this forward to the host mailbox" (one first-forward in a few dozen two-job runs)
-        HIP_TRY(hipMemsetAsync(arrive_ring, 0, ARRIVE_SLOTS * ARRIVE_WORDS * sizeof(unsigned long long), s));
-        // ... and COMPLETE before this call goes on: the ring belongs to the thread, not to the stream — the same thread's next forward may
-        // be issued on another non-blocking stream, which does not wait for this one.  Once per thread and device.
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    // Which binning path this forward takes, whether it speculates on its capacity and whether it looks at its tile lists: path_policy.h,
-    // from what the earlier forwards of the shape left in T->verdict and the two words their kernels may have raised since.
-    const uint32_t too_long = mb->host[MB_TOO_LONG];
-    if (too_long) mb->host[MB_TOO_LONG] = 0;
-    const uint32_t want_bits = mb->host[MB_WANT_BITS];
-    if (want_bits) mb->host[MB_WANT_BITS] = 0;
-    const PolicyInputs policy_in = {P, W, H, L.ntiles, L.tbits, L.tile_passes, too_long, want_bits, switches().binning /* DAS3R_BINNING */, use_onesweep(),
-                                    a->capacity_hint, switches().capacity_exact, &T->resume};
-    const ForwardPlan plan = plan_forward(T->verdict, policy_in);
-    bool local = plan.local;
-    const bool seg = plan.seg;
-    const uint32_t *seg_dhist = nullptr;   // where this forward's depth histogram is (set with the preprocess launch, below)
-    auto apply_seg = [&]() {   // (compute_layout starts every layout without buckets)
-        L.dhist_ptr = seg_dhist;
-        if (seg) {
-            L.dbits = plan.seg_bits;
-            L.kbits = L.tbits + plan.seg_bits;
-            L.kshift = std::min(16, 32 - L.kbits);
-            L.part_passes = plan.seg_passes;
-        }
-    };
-    const uint32_t count_tag = next_tag(mb);
-    unsigned long long *arrive = arrive_ring + (size_t)(count_tag % ARRIVE_SLOTS) * ARRIVE_WORDS;
-    // The split preprocess: the fork event is recorded behind the geometry kernel (launch_preprocess); the colour kernel goes to the side
-    // stream once the binning kernels are enqueued on s (join.launch()), and s waits for it (join.now()) in front of the first kernel that
-    // reads a colour, `clamped` or a Jacobian plane — the compositing forward.  Whatever is pending on the side stream when this function
-    // returns, on EVERY way out, s waits for: once the call's work on s is complete the side stream touches neither the caller's tensors
-    // nor the geometry buffer.  (A way out between the fork and the launch leaves nothing on the side stream.)
-    struct Join {
-        hipStream_t s;
-        const das3r_raster_args *a;
-        const das3r_raster_in *in;
-        char *const *geom;
-        const Layout *L;
-        SideStream side;
-        bool forked, pending;
-        int launch() {
-            if (!forked) return DAS3R_OK;
-            forked = false;
-            pending = true;   // (from the first call that touches the side stream on)
-            return launch_sh_colour(a, in, *geom, *L, &side);
-        }
-        int now() {
-            const int r = launch();
-            if (r) return r;
-            if (!pending) return DAS3R_OK;
-            pending = false;
-            HIP_TRY(hipStreamWaitEvent(s, side.join, 0));
-            return DAS3R_OK;
-        }
-        ~Join() {
-            if (pending) (void)hipStreamWaitEvent(s, side.join, 0);
-        }
-    } join = {s, a, in, &saved->geom, &L, {nullptr, nullptr, nullptr, 0}, false, false};
-    auto split_side = [&](int binning_path, const SideStream **side) -> int {   // *side: null = the fused kernel
-        *side = nullptr;
-        if (!split_colour_rule(in->shs != nullptr, a->sh_degree, P, binning_path, no_backward, switches().split_colour)) return DAS3R_OK;
-        const int r = side_stream_for(s, &join.side);
-        if (r) return r;
-        *side = &join.side;
-        return DAS3R_OK;
-    };
-    // everything behind the count: scan + emission, partition, tile ranges, compositing (L laid out for `cap`, buffer allocated)
-    auto bin_and_render = [&](int64_t cap, bool local_order, bool ctrl_zeroed, uint32_t *count_out = nullptr, uint32_t count_out_tag = 0,
-                              uint32_t *emit_slot = nullptr /*the preprocess kernel has emitted the instances already*/) -> int {
-        int r;
-        const bool fused_scan = use_onesweep();   // scan + emission in one kernel; the classic path scans, then emits
-        const bool seg = L.dbits > 0;             // segmented path: index-order emission with depth buckets, lists sorted by segment_sort_kernel
-        if (!emit_slot) {
-            if (fused_scan) {
-                if ((r = launch_binning_scan_emit(P, cap, out->radii, saved->geom, saved->binning, L, ctrl_zeroed, count_out, count_out_tag, a->debug != 0,
-                                                  s, local_order || seg))) return r;
-            } else if ((r = launch_scan(P, saved->geom, L, nullptr, 0, a->debug != 0, s))) return r;
-        }
-        uint32_t *host_late = nullptr;
-        if (cap > 0) {
-            late_tag = next_tag(mb);
-            const uint32_t slot = late_tag % CHECK_SLOTS;
-            if ((r = check_slot(slot, true))) return r;   // (the forward that used the slot CHECK_SLOTS forwards ago)
-            T->pending[slot] = late_tag;
-            host_late = mb->dev + CHECK_WORD0 + 2 * slot;
-            saved->check_word = (void *)(mb->host + CHECK_WORD0 + 2 * slot);
-            saved->check_tag = late_tag;
-        }
-        uint32_t *dead_keys = nullptr;
-        if ((r = launch_binning(P, cap, W, H, out->radii, saved->geom, saved->binning, saved->img, L, fused_scan, host_late, late_tag,
-                                a->debug != 0, s, &dead_keys, emit_slot, mb->dev + MB_TOO_LONG, plan.gen))) return r;
-        if ((r = join.launch())) return r;   // the split preprocess: the colour kernel, beside the binning kernels enqueued above
-        LocalBin lb = {(float4 *)(saved->binning + L.b_ckpt), nullptr, nullptr, nullptr, nullptr, plan.gen, (uint32_t)(P - 1), (uint32_t)cap};
-        // The three questions below — look at the list skew? order the tiles longest first? leave the backward its hint? — are asked with
-        // local_lists = false, "by shape", on every binning path: lb.point_list is only set further down, so that is what these sites have always
-        // answered.  launch_render_forward, which sees the pointer, passes the truth, and on the local-order path never takes the lanes /
-        // regions kernels the answers here are about; the hint's bit 0 still steers that forward's BACKWARD (kernel_choice.h choose_backward).
-        // Kept as it is: changing it changes which kernels a training run takes.
-        const bool by_shape = cap > 0 && quad_lanes(switches(), L.ntiles, L.capacity, /*local_lists=*/false);
-        if (plan.decide_fine && by_shape) {   // (shapes the one-workgroup-per-tile kernel would take: few tiles, long lists)
-            const uint32_t tag = next_tag(mb);
-            if ((r = launch_list_skew(saved->img, saved->binning, saved->geom, L, (uint32_t)cap, (uint32_t)(P - 1), mb->dev + MB_LONGEST, tag, a->debug != 0, s))) return r;
-            if ((r = mailbox_wait(mb, MB_SKEW_TAG, tag, s))) return r;
-            const uint32_t longest = mb->host[MB_LONGEST], crowd16 = mb->host[MB_CROWD16];
-            const int64_t mean = skew_mean(T->verdict, cap, L.ntiles);
-            const bool now_fine = learn_skew(T->verdict, longest, crowd16, cap, L.ntiles);
-            if (switches().verbose) fprintf(stderr, "[das3r] tile lists: longest %lld, mean %lld, %.1f of 64 consecutive entries in one quadrant -> %s kernels\n", (long long)longest,
-                                            (long long)mean, crowd16 / 16.0, now_fine ? "2x2-region" : "block");
-        }
-        const bool fine = prefers_regions(T->verdict);
-        lb.prefer_regions = fine;
-        lb.tile_order = nullptr;
-        if (tile_lpt_wanted(switches(), L.ntiles, L.capacity, /*local_lists=*/false, fine)) {   // longest lists first (kernel_choice.h says why)
-            if ((r = launch_tile_lpt(saved->img, L, (uint32_t)cap, a->debug != 0, s))) return r;
-            lb.tile_order = (const uint32_t *)(saved->img + L.i_order);
-        }
-        if (fine && by_shape) saved->flags |= backward_hint(T->verdict, (uint32_t)BUCKET);   // (for the backward pass of this forward: kernel_choice.h choose_backward)
-        if (local_order && cap > 0) {
-            lb.point_list = (uint32_t *)(saved->binning + L.pub.point_list);
-            lb.slot_list = (uint32_t *)(saved->binning + L.b_slot);
-            lb.keys = dead_keys;
-            lb.host_flag = mb->dev + MB_TOO_LONG;
-        }
-        if ((r = join.now())) return r;   // (a redo finds the colours there already: nothing is pending the second time)
-        return launch_render_forward(a, in->colors_precomp, out->out_color, saved->geom, saved->binning, saved->img, L, lb, s, out->out_invdepth,
-                                     depth ? (float4 *)(saved->binning + L.d_ckpt) : nullptr);
-    };
-    // prefiltered: the caller's promise that no point fails the near-plane cull (upstream traps when one does: auxiliary.h in_frustum);
-    // the preprocess kernel leaves this call's tag in mailbox word 12 when one did
-    auto prefiltered_ok = [&]() -> int {
-        if (!a->prefiltered || mb->host[MB_FILTERED] != count_tag) return DAS3R_OK;
-        set_error("Point is filtered although prefiltered is set. This shouldn't happen!");
-        return DAS3R_ERR_INVALID_ARG;
-    };
-    int64_t I, cap;
-    // The speculative flow: the binning buffer is laid out for the plan's capacity and the whole forward is enqueued before the host looks
-    // at the mailbox (the kernels clamp to the capacity).  Should the scene have grown past it, the binning and the compositing are redone
-    // with the exact size.
-    if (plan.speculate) {
-        cap = plan.cap;
-        compute_layout(P, cap, W, H, &L, shjac);
-        apply_seg();
-        saved->binning = alloc_binning(user, depth ? L.d_bytes : L.pub.binning_bytes);
-        if (!saved->binning) { set_error("scratch allocation failed (binning %zu B)", L.pub.binning_bytes); return DAS3R_ERR_ALLOC; }
-        // The count is not needed before the end of this call: the preprocess kernel skips its count reduction and the scan
-        // delivers it.  When the preprocess grid is resident as a whole (P <= 196 k) the scan and the emission run inside the
-        // preprocess kernel itself (EmitArgs, common.h) and the separate scan + emit kernel is not launched at all; their
-        // control words live in a library-owned ring slot per forward, zero at rest.  DAS3R_FUSED_EMIT=0 switches that off.
-        char *&emit_ring = T->emit_ring;
-        bool &emit_ring_dirty = T->emit_ring_dirty;
-        uint32_t &emit_last_tag = T->emit_last_tag;
-        constexpr size_t EMIT_SLOT_BYTES = sizeof(uint32_t) * EMIT_SLOT_WORDS + sizeof(unsigned long long) * EMIT_STATUS_GRANULES;
-        const bool fused_emit = local && grid_is_resident(div_up(P, 256)) && !switches().fused_emit_off;
-        uint32_t *emit_slot = nullptr;
-        if (fused_emit) {
-            if (!emit_ring) {
-                HIP_TRY(hipMalloc((void **)&emit_ring, ARRIVE_SLOTS * EMIT_SLOT_BYTES));
-                emit_ring_dirty = true;
-            }
-            if (emit_ring_dirty || count_tag < emit_last_tag) {   // first use, an aborted forward, or the tags wrapped around
-                HIP_TRY(hipMemsetAsync(emit_ring, 0, ARRIVE_SLOTS * EMIT_SLOT_BYTES, s));
-                emit_ring_dirty = false;
-            }
-            emit_last_tag = count_tag;
-            emit_slot = (uint32_t *)(emit_ring + (size_t)(count_tag % ARRIVE_SLOTS) * EMIT_SLOT_BYTES);
-            const EmitArgs em = {(unsigned long long *)(emit_slot + EMIT_SLOT_WORDS), count_tag, emit_slot + 64, emit_slot,
-                                 (uint32_t *)(saved->binning + L.b_keyA), (uint32_t *)(saved->binning + L.b_gid_of),
-                                 (uint32_t *)(saved->geom + L.g_off_by_gid), (uint32_t)cap, L.tbits, (uint32_t *)(saved->geom + L.g_count), mb->dev};
-            emit_ring_dirty = true;   // until the last binning kernel of this forward is enqueued (it re-arms the slot)
-            if ((rc = launch_preprocess(a, in, out->radii, saved->geom, saved->img, saved->binning + L.b_ghist, L.b_ctrl_bytes, L, nullptr, mb->dev,
-                                        count_tag, s, &em, nullptr, nullptr, aa))) return rc;
-            if ((rc = bin_and_render(cap, true, true, nullptr, 0, emit_slot))) return rc;
-            emit_ring_dirty = false;
-        } else {
-            uint32_t *dhist = nullptr, *dhist_next = nullptr;
-            if ((rc = seg_dhist_for(seg, s, saved->geom, L, &dhist, &dhist_next))) return rc;
-            seg_dhist = dhist;
-            apply_seg();
-            const SideStream *side = nullptr;
-            if ((rc = split_side(1, &side))) return rc;
-            if ((rc = launch_preprocess(a, in, out->radii, saved->geom, saved->img, saved->binning + L.b_ghist, L.b_ctrl_bytes, L, nullptr, mb->dev,
-                                        count_tag, s, nullptr, dhist, dhist_next, aa, side))) return rc;
-            join.forked = side != nullptr;
-            if ((rc = bin_and_render(cap, local, true, mb->dev, count_tag))) return rc;
-        }
-        if ((rc = mailbox_wait(mb, MB_COUNT_TAG, count_tag, s))) return rc;
-        if ((rc = prefiltered_ok())) return rc;
-        I = (int64_t)mb->host[MB_COUNT];
-        if (I > CAPACITY_MAX) { set_error("num_rendered %lld exceeds 2^31", (long long)I); return DAS3R_ERR_OVERFLOW; }
-        (void)learn_count(T->verdict, I, policy_in, plan);   // (enqueued already: this forward keeps its path)
-        if (I > cap) {
-            cap = I;
-            compute_layout(P, cap, W, H, &L, shjac);
-            saved->binning = alloc_binning(user, depth ? L.d_bytes : L.pub.binning_bytes);
-            if (!saved->binning) { set_error("scratch allocation failed (binning %zu B)", L.pub.binning_bytes); return DAS3R_ERR_ALLOC; }
-            apply_seg();
-            HIP_TRY(hipMemsetAsync(saved->geom + L.g_ghist, 0, L.g_ctrl_bytes, s));          // tickets and look-back words of the scan
-            HIP_TRY(hipMemsetAsync(saved->img + L.pub.ranges, 0, 8 * (size_t)L.ntiles, s));
-            if ((rc = bin_and_render(cap, local, false))) return rc;
-        }
-    } else {
-        uint32_t *dhist = nullptr, *dhist_next = nullptr;
-        if ((rc = seg_dhist_for(seg, s, saved->geom, L, &dhist, &dhist_next))) return rc;
-        seg_dhist = dhist;
-        const SideStream *side = nullptr;
-        if ((rc = split_side((local || seg) ? 1 : 0, &side))) return rc;
-        if ((rc = launch_preprocess(a, in, out->radii, saved->geom, saved->img, nullptr, 0, L, arrive, mb->dev, count_tag, s, nullptr, dhist, dhist_next, aa, side))) return rc;
-        join.forked = side != nullptr;
-        if (!local && !seg && (rc = launch_depth_sort(P, saved->geom, L, 0, nullptr, 0, a->debug != 0, s))) return rc;
-        if ((rc = mailbox_wait(mb, MB_COUNT_TAG, count_tag, s))) return rc;    // usually there already: preprocess finished long ago
-        if ((rc = prefiltered_ok())) return rc;
-        I = cap = (int64_t)mb->host[MB_COUNT];
-        if (cap > CAPACITY_MAX) { set_error("num_rendered %lld exceeds 2^31", (long long)cap); return DAS3R_ERR_OVERFLOW; }
-        if (learn_count(T->verdict, I, policy_in, plan)) {   // the scene grew: global sort after all
-            local = false;
-            if ((rc = join.now())) return rc;   // (the sort scatters the depth keys the colour kernel reads)
-            if ((rc = launch_depth_sort(P, saved->geom, L, 0, nullptr, 0, a->debug != 0, s))) return rc;
-        }
-        compute_layout(P, cap, W, H, &L, shjac);
-        apply_seg();
-        saved->binning = alloc_binning(user, depth ? L.d_bytes : L.pub.binning_bytes);
-        if (!saved->binning) { set_error("scratch allocation failed (binning %zu B)", L.pub.binning_bytes); return DAS3R_ERR_ALLOC; }
-        if (!local && !seg && (rc = launch_depth_sort(P, saved->geom, L, 1, saved->binning + L.b_ghist, L.b_ctrl_bytes, a->debug != 0, s))) return rc;
-        if ((rc = bin_and_render(cap, local, !local && !seg))) return rc;
-    }
-    if (a->debug && late_tag && (rc = check_slot(late_tag % CHECK_SLOTS, true))) return rc;   // debug: report this forward's self-check word right away
-    saved->num_rendered = I;
-    saved->capacity = cap;
-    if (depth) saved->flags |= DEPTH_SAVED_FLAG;
-    if (shjac) saved->flags |= SHJAC_SAVED_FLAG;
-    return I;
+    compute_layout(a->P, saved->capacity > 0 ? saved->capacity : saved->num_rendered, a->image_width, a->image_height, &L, shjac);
+    return L;
 }
 
 // flags bit 2: the forward left the SH colour's Jacobian for the per-Gaussian backward (Layout::g_shjac), which then reads it instead of
@@ -933,8 +405,7 @@ static int backward_body(const char *who, const das3r_raster_args *a, const das3
     if (depth_pass && (rc = refuse_bwd_without_invdepth(who))) return rc;
     // the forward's binning self-check first: nothing is launched on the strength of an invalid image / list
     if ((rc = das3r_raster_check(saved, stream))) return rc;
-    Layout L;
-    compute_layout(P, saved->capacity > 0 ? saved->capacity : saved->num_rendered, a->image_width, a->image_height, &L, shjac_saved(a, in, saved));
+    const Layout L = saved_layout(a, saved, shjac_saved(a, in, saved));
     // scratch = per-instance partial sums [num_rendered, 9]; no accumulator needs zeroing (no atomics anywhere)
     float *partial = g->scratch;
     const float *dz = nullptr;
@@ -1038,8 +509,7 @@ extern "C" int das3r_raster_aux_forward(const das3r_raster_args *a, const das3r_
         return DAS3R_OK;
     }
     if ((rc = das3r_raster_check(saved, stream))) return rc;   // a failed binning is an error, not a walk over bad lists
-    Layout L;
-    compute_layout(P, saved->capacity > 0 ? saved->capacity : saved->num_rendered, W, H, &L);
+    const Layout L = saved_layout(a, saved);
     return launch_render_aux_forward(P, W, H, C, features, out, saved->geom, saved->binning, saved->img, L, saved->num_rendered, a->debug != 0, s);
 }
 
@@ -1062,8 +532,7 @@ extern "C" int das3r_raster_aux_adjoint(const das3r_raster_args *a, const das3r_
     }
     if (!scratch) { set_error("das3r_raster_aux_adjoint: null scratch (das3r_raster_aux_scratch_bytes)"); return DAS3R_ERR_INVALID_ARG; }
     if ((rc = das3r_raster_check(saved, stream))) return rc;
-    Layout L;
-    compute_layout(P, saved->capacity > 0 ? saved->capacity : saved->num_rendered, W, H, &L);
+    const Layout L = saved_layout(a, saved);
     return launch_render_aux_adjoint(P, W, H, C, dL_dout, dL_dfeat, accumulate != 0, scratch, saved->geom, saved->binning, saved->img, L, saved->num_rendered, a->debug != 0, s);
 }
 
@@ -1149,8 +618,7 @@ extern "C" int das3r_raster_count_live_pairs(const das3r_raster_args *a, const d
     if (a->P == 0 || saved->num_rendered <= 0) return DAS3R_OK;
     if (!saved->geom || !saved->binning || !saved->img) { set_error("das3r_raster_count_live_pairs: saved buffers missing"); return DAS3R_ERR_INVALID_ARG; }
     hipStream_t s = (hipStream_t)stream;
-    Layout L;
-    compute_layout(a->P, saved->capacity > 0 ? saved->capacity : saved->num_rendered, a->image_width, a->image_height, &L);
+    const Layout L = saved_layout(a, saved);
     unsigned long long *dev = nullptr;
     HIP_TRY(hipMalloc((void **)&dev, 2 * sizeof(unsigned long long)));
     int rc = DAS3R_OK;

@@ -160,7 +160,7 @@ static inline int tile_bits(int ntiles) {
 // (BUCKET, the list positions between two checkpoints of a long tile list: kernel_choice.h)
 constexpr int SPLAT_REC = 4;   // float4s per Gaussian record (xyh, conic+opacity, rgb+depth, pad): 64 bytes, one cache-line gather
 
-// das3r_raster_saved.flags bit 1 (ABI 16): the forward was given out_invdepth, its binning buffer holds Layout::d_* (bits 0 and 8 - 15: api.hip)
+// das3r_raster_saved.flags bit 1 (ABI 16): the forward was given out_invdepth, its binning buffer holds Layout::d_* (bits 0 and 8 - 15: forward.hip look_at_lists)
 constexpr uint32_t DEPTH_SAVED_FLAG = 2u;
 // das3r_raster_saved.flags bit 2: the forward wrote the SH colour's Jacobian w.r.t. the view direction into the geometry buffer
 // (Layout::g_shjac; SH given and the active degree >= 2, where its 36 bytes are fewer than the coefficients the backward would re-read)
@@ -197,7 +197,7 @@ struct Layout {
     int part_passes;            // passes of the instance partition: tile_passes, or one more when the segmented path wants more bucket bits
     size_t g_dhist;
     size_t g_shjac;   // f32[9][P] behind everything else of the geometry buffer: plane 3c + k = d(rgb_c)/d(dir_k) (preprocess.hip); 0 = none
-    const uint32_t *dhist_ptr;  // round 6: where this forward's depth histogram really is (a library-owned slot: api.hip dhist_slots); null = geom + g_dhist
+    const uint32_t *dhist_ptr;  // round 6: where this forward's depth histogram really is (a library-owned slot: forward.hip dhist_slots); null = geom + g_dhist
     size_t i_order;   // img buffer, u32[ntiles]: the tiles longest list first (render_regions.hip tile_lpt_kernel; round 6)
 };
 // depth-bucket bits `passes` partition passes (at most three) have room for beside the tile ids (<= 0: none): path_policy.h
@@ -220,7 +220,7 @@ struct LocalBin {
 };
 void compute_layout(int P, int64_t I, int W, int H, Layout *L, bool shjac = false);
 
-// Emission fused into the preprocess kernel (speculative local-order path, grid resident: api.hip).  status == null: off.
+// Emission fused into the preprocess kernel (speculative local-order path, grid resident: forward.hip flow_fused_emit).  status == null: off.
 // The control words live in a library-owned ring slot that is zero at rest (ghist, err: re-armed by tile_ranges_kernel) or
 // versioned by the forward's tag (status granules), because nothing runs before this kernel that could zero them.
 struct EmitArgs {
@@ -242,7 +242,7 @@ constexpr int EMIT_STATUS_GRANULES = 1024;             // >= resident grid + its
 // arrive: a zeroed 64-bit device word (self re-arming); host_out / tag: pinned mailbox that receives num_rendered
 // The split preprocess (preprocess.hip): a library-owned non-blocking stream beside the caller's, and the two events of the fork (recorded on
 // the caller's stream behind the geometry kernel; the side stream waits for it) and of the join (recorded on the side stream behind the colour
-// kernel; the caller's stream waits for it in front of the compositing kernel).  One per (host thread, device, caller stream): api.hip.
+// kernel; the caller's stream waits for it in front of the compositing kernel).  One per (host thread, device, caller stream): forward.hip PerStream.
 constexpr int COLOUR_WGS_PER_CU = 4;   // persistent grid of sh_colour_kernel (preprocess.hip says why four)
 struct SideStream {
     hipStream_t stream;
@@ -316,7 +316,7 @@ constexpr int LOCAL_MAX = 1024;   // longest tile list the forward kernels sort 
 bool grid_is_resident(int nblocks);
 bool use_onesweep();  // DAS3R_SORT=classic selects the three-kernel radix passes (diagnostics / A-B)
 bool use_tight_rect();  // DAS3R_RECT=upstream bins over upstream's 3-sigma square (bit-exact list tests)
-// host_late / tag: pinned mailbox the last binning kernel copies the self-check word to (see api.hip)
+// host_late / tag: pinned mailbox the last binning kernel copies the self-check word to (see mailbox.h)
 int launch_binning(int P, int64_t I, int W, int H, const int32_t *radii, char *geom, char *binning, char *img, const Layout &L,
                    bool fused_scan, uint32_t *host_late, uint32_t tag, bool debug, hipStream_t s, uint32_t **dead_keys = nullptr,
                    uint32_t *emit_slot = nullptr /*fused emission: {err, pad, ghist} ring slot, re-armed by the last kernel*/,

@@ -96,7 +96,7 @@ struct Switches {
     int inject_fault;      // das3r_debug_inject_fault (not an environment variable): bits OR-ed into the binning self-check word of every forward (fault-injection tests)
     int mutate;            // das3r_debug_mutate (tests): 1 = the block-walk backward evaluates exp(power) (1 + 1e-4) — a biased kernel the parity tests must catch
     bool fwd_no_prefetch;  // DAS3R_FWD_PREFETCH=0: the rows forward kernel without its software prefetch (A-B runs)
-    int split_colour;      // DAS3R_SPLIT_COLOUR=0 | 1: the split preprocess (preprocess.hip) forced off (-1) / on (1) where it can run; unset (0): by shape (api.hip split_colour_rule)
+    int split_colour;      // DAS3R_SPLIT_COLOUR=0 | 1: the split preprocess (preprocess.hip) forced off (-1) / on (1) where it can run; unset (0): by shape (forward.hip split_colour_rule)
     int tile_strip;        // DAS3R_TILE_STRIP: rows per strip of the compositing kernels' tile order (0 = row-major)
 };
 

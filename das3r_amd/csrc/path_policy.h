@@ -1,7 +1,7 @@
 // path_policy.h — what a forward LEARNS about a shape (P, W, H) and what the next forward of the shape does with it: which binning path it
 // takes (local order, segmented with N partition passes, global radix sort), when a shape backs off to the global sort and for how
 // long, whether it speculates on its capacity, and which compositing kernels its tile lists call for.  Pure host arithmetic on a
-// caller-owned Verdict: no HIP, no switches(), no error reporting — api.hip (das3r_raster_forward) reads the mailbox words and the
+// caller-owned Verdict: no HIP, no switches(), no error reporting — forward.hip (das3r_raster_forward) reads the mailbox words and the
 // switches, calls in here at the places named below, and launches what the plan says.  Compiles with a plain C++17 compiler
 // (das3r_debug_path_policy_*: the CPU tests drive every transition through it, tests/test_path_policy_host.py).
 #pragma once
@@ -17,7 +17,7 @@ constexpr uint32_t CROWDED16 = 23u * 16u;     // of 64 consecutive list entries,
 constexpr uint32_t FINE_PERIOD = 512;         // forwards of a shape between two looks at its tile lists (a power of two: plan_forward)
 constexpr int BACKOFF_MIN = 64, BACKOFF_MAX = 4096;   // forwards on the global sort after a failure: doubled from MIN while failures come soon, up to MAX
 constexpr uint32_t CLEAN_RESET = 256;         // clean fast-path forwards after which a failure counts as an occasional one (back to BACKOFF_MIN)
-constexpr int64_t CAPACITY_MAX = 0x7FFFFF00;  // instances a binning buffer is laid out for at most (api.hip refuses a larger count: DAS3R_ERR_OVERFLOW)
+constexpr int64_t CAPACITY_MAX = 0x7FFFFF00;  // instances a binning buffer is laid out for at most (forward.hip refuses a larger count: DAS3R_ERR_OVERFLOW)
 
 // depth-bucket bits `passes` partition passes (at most three) have room for beside `tbits` bits of tile id (<= 0: none)
 static inline int seg_dbits(int tbits, int passes) { return 8 * (passes < 3 ? passes : 3) - tbits; }

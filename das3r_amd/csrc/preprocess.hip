@@ -31,13 +31,13 @@ namespace das3r {
     uint32_t *__restrict__ host_out, uint32_t tag, const EmitArgs em, \
     uint32_t *__restrict__ dhist /*segmented binning path: 256-bin depth histogram of this forward, zeroed by the caller (segkey.h); else null*/, \
     uint32_t dhist_mask /*a pseudo-random 1 / (mask + 1) of the workgroups contribute (`sampled` below): a sample is all the bucket map needs*/, \
-    uint32_t *__restrict__ dhist_next /*round 6: the library's OTHER histogram slot, zeroed here for the next forward of this stream (api.hip dhist_slots); else null*/, \
+    uint32_t *__restrict__ dhist_next /*round 6: the library's OTHER histogram slot, zeroed here for the next forward of this stream (forward.hip dhist_slots); else null*/, \
     const PreXform pre /*xyz != null (round 6, das3r_raster_in.pre): the raw parameters + the pose; means3D / scales / rotations / opacities are not read*/, \
     float *__restrict__ shjac /*[9][P] or null: the colour's Jacobian w.r.t. the view direction, plane 3c + k = d(rgb_c)/d(dir_k) (Layout::g_shjac)*/
 // GEOM: the geometry half of the split form (below, preprocess_geometry_kernel): no colour is read or evaluated, `clamped` and the Jacobian
 // planes are not stored — they belong to sh_colour_kernel — and the record's third float4 leaves as (0, 0, 0, depth), to be overwritten.
 // GEOM = false is the fused form: geometry and colour of a splat in one lane, one launch — the only form for precomputed colours, SH degree
-// 0, the emission fused in (em.status != null), the global depth sort and evaluation forwards (api.hip split_colour_rule).
+// 0, the emission fused in (em.status != null), the global depth sort and evaluation forwards (forward.hip split_colour_rule).
 template <bool HAS_SH, bool HAS_COV, bool STAGE, bool AA = false, bool GEOM = false>
 __global__ void __launch_bounds__(256) preprocess_kernel(PRE_PARAMS) {
     const int gidx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -219,7 +219,7 @@ __global__ void __launch_bounds__(256) preprocess_kernel(PRE_PARAMS) {
     } else if ((tight_rect & 2) && live) {
         // prefiltered = true is the caller's promise that no point is culled here; upstream:auxiliary.h in_frustum prints "Point is
         // filtered although prefiltered is set" and traps.  Here the forward fails with that message: the tag of this call in word 12
-        // of the host mailbox, examined by das3r_raster_forward once the count has arrived (api.hip)
+        // of the host mailbox, examined by das3r_raster_forward once the count has arrived (forward.hip read_count)
         __hip_atomic_store(host_out + 12, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         __threadfence_system();
     }
@@ -276,7 +276,7 @@ __global__ void __launch_bounds__(256) preprocess_kernel(PRE_PARAMS) {
     // num_rendered = sum of tiles_touched does not depend on the depth order: deliver it to the host NOW, five kernels before the
     // scan that needs it on the device, so that the host can size the binning buffer exactly without ever waiting for the sort.
     // One 64-bit atomic per workgroup carries (workgroups done << 40 | tiles); the last arriver owns the total, re-arms the
-    // counters for their next use and writes {count, tag} to the pinned mailbox (see api.hip).
+    // counters for their next use and writes {count, tag} to the pinned mailbox (see mailbox.h).
     // Fused emission (speculative local-order path, the whole grid resident: common.h EmitArgs): the index-order scan of
     // tiles_touched and the (tile id, splat) instances of scan_emit.hip, without its launch, its drain and its second trip to the
     // records — this workgroup's splats are still in registers.
@@ -363,7 +363,7 @@ __global__ void __launch_bounds__(256) preprocess_kernel(PRE_PARAMS) {
         }
         return;
     }
-    // (arrive == null: the caller does not need the count early — speculative capacity, api.hip — and lets the scan deliver it)
+    // (arrive == null: the caller does not need the count early — speculative capacity, forward.hip — and lets the scan deliver it)
     if (arrive == nullptr) return;
     uint32_t wsum = live ? tiles_out : 0u;
 #pragma unroll
@@ -394,7 +394,7 @@ __global__ void __launch_bounds__(256) preprocess_kernel(PRE_PARAMS) {
     }
 }
 
-// The split form (api.hip SideStream): the forward's critical path needs the geometry only — the binning reads rectangles, counts and depth
+// The split form (forward.hip Join): the forward's critical path needs the geometry only — the binning reads rectangles, counts and depth
 // keys, never a colour — so this kernel does everything preprocess_kernel does except the colour, on the caller's stream, and
 // sh_colour_kernel evaluates the SH rows on a side stream BESIDE the latency-bound binning chain, joined in front of the compositing kernel.
 // Who writes which bytes of the 64-byte record, and when:
@@ -421,7 +421,7 @@ constexpr auto preprocess_geometry_kernel = preprocess_kernel<false, HAS_COV, fa
 // beside two 52 KB workgroups of a partition pass.
 // Two things keep it from slowing the binning chain it runs beside more than it must (1 M splats, ms per step, parent 0.867 - 0.870;
 // docs/ledger.md (ca) has every run):
-//   * a persistent grid of COLOUR_WGS_PER_CU workgroups per CU, each taking slices of 64 splats in turn (api.hip SideStream::colour_blocks):
+//   * a persistent grid of COLOUR_WGS_PER_CU workgroups per CU, each taking slices of 64 splats in turn (forward.hip side_stream_for: SideStream::colour_blocks):
 //     one workgroup per slice (15 625 of them) 0.855, eight per CU 0.854 - 0.858, four 0.851 - 0.853, two 0.857 — the bytes in flight stay
 //     bounded and the chain's workgroups are not dispatched in between thousands of these;
 //   * the SH rows are read and the planes stored with the non-temporal hint — each byte is touched once, and without the hint the 250 MB
@@ -531,7 +531,7 @@ int launch_preprocess(const das3r_raster_args *a, const das3r_raster_in *in, int
         (uint32_t *)(geom + L.pub.tiles_touched), (uint32_t *)(geom + L.g_rect), (use_tight_rect() ? 1 : 0) | (a->prefiltered ? 2 : 0), (uint32_t *)(geom + L.g_ghist), (uint32_t)(L.g_ctrl_bytes / 4),                 \
         (uint32_t *)(img + L.pub.ranges), (uint32_t)(2 * L.ntiles), (uint32_t *)binning_ctrl, (uint32_t)(binning_ctrl_bytes / 4), arrive, host_out, tag, em, dhist, dhist_mask, dhist_next, pre, shjac
     const bool stage = has_sh && a->M == 16 && a->sh_degree >= 2 && ((uintptr_t)in->shs & 15) == 0 && !switches().no_sh_stage;
-    if (side != nullptr) {   // the split form (api.hip split_colour_rule: SH given, no fused emission, a binning path that keeps the depth keys)
+    if (side != nullptr) {   // the split form (forward.hip split_colour_rule: SH given, no fused emission, a binning path that keeps the depth keys)
         if (!has_sh || emit != nullptr) { set_error("launch_preprocess: the split form needs SH rows and a binning chain of its own"); return DAS3R_ERR_INVALID_ARG; }
         if (has_cov) {
             if (aa) DAS3R_LAUNCH((preprocess_geometry_kernel<true, true>), grid, block, 0, s, ARGS);
@@ -582,7 +582,7 @@ int launch_sh_colour(const das3r_raster_args *a, const das3r_raster_in *in, char
     if (stage) DAS3R_LAUNCH((sh_colour_kernel<true>), cgrid, cblock, 0, side->stream, COLOUR_ARGS);
     else DAS3R_LAUNCH((sh_colour_kernel<false>), cgrid, cblock, 0, side->stream, COLOUR_ARGS);
 #undef COLOUR_ARGS
-    HIP_TRY(hipEventRecord(side->join, side->stream));   // (the caller's stream waits for it in front of the compositing kernel: api.hip)
+    HIP_TRY(hipEventRecord(side->join, side->stream));   // (the caller's stream waits for it in front of the compositing kernel: forward.hip colour_join)
     KERNEL_CHECK(side->stream, a->debug, "sh_colour");
     return DAS3R_OK;
 }

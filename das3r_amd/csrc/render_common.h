@@ -196,7 +196,7 @@ __device__ __forceinline__ uint32_t blend_batch_end(const PixelBlend &px, const 
     return px.lastf >= 0.0f ? batch_first + (uint32_t)px.lastf + 1u : last_contributor;
 }
 
-// A failed binning (look-back timeout: reported through the self-check word, api.hip) may leave garbage in the tile lists.
+// A failed binning (look-back timeout: reported through the self-check word, mailbox.h) may leave garbage in the tile lists.
 // Every index read from them is kept in bounds, so that the failure surfaces as the error it is and not as a memory fault.
 __device__ __forceinline__ uint2 safe_range(uint2 r, const uint32_t cap) {
     r.y = min(r.y, cap);

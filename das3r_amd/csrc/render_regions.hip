@@ -302,7 +302,7 @@ __global__ void __launch_bounds__(RG_THREADS) __attribute__((amdgpu_waves_per_eu
 }
 
 // Two numbers about a forward's tile lists, delivered to the host (pinned mailbox: {longest, tag, crowding}) — what the choice between the
-// compositing kernels for long lists is made from (api.hip): the LONGEST list (one workgroup per tile lasts as long as its longest tile), and
+// compositing kernels for long lists is made from (forward.hip look_at_lists): the LONGEST list (one workgroup per tile lasts as long as its longest tile), and
 // how CROWDED a stretch of a list is on the screen: of 64 consecutive entries from the middle of every list of >= 256 entries, how many have
 // their centre in the most popular 8x8 quadrant of the tile (mean over the tiles, in 1/64).  A tile's list is in depth order; on random depths
 // the four quadrants share a stretch evenly (the fullest holds ~20 of 64), on the depth maps of a real sequence a depth slab is a band or a

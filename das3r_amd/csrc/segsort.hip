@@ -14,7 +14,7 @@
 // in place: a segment is read and written by its owner only.
 // A segment that does not end inside the LDS span (a wall parallel to the image plane: thousands of equal depths in one tile) is
 // sorted by the same workgroup with a bitonic network over global memory — slow, exact — and the host is told through the mailbox
-// word the local depth order uses, so that the next forwards of this shape take the global sort for a while (api.hip).
+// word the local depth order uses, so that the next forwards of this shape take the global sort for a while (forward.hip reads it, path_policy.h decides).
 #include "granule.h"
 #include "segkey.h"
 

@@ -6,7 +6,7 @@ in real DAS3R training.  "Densification on" is therefore a synthetic stress of t
 §8d): every `every` steps the 5 % of the splats with the largest view-space gradient grow the scene — the smaller half of them
 is cloned, the larger half split in two (what densify_and_clone / densify_and_split did, gaussian_model.py:511-551) — until P
 has grown from P0 to 1.3 P0.  Each event changes P, so the library's shape cache resets, the binning buffer is sized
-exactly again and the speculative capacity starts over (api.hip).
+exactly again and the speculative capacity starts over (forward.hip, path_policy.h).
 
 Works on the tensors the rasterizer takes (activated scales, raw quaternions); harness code, not part of the drop-in surface.
 """

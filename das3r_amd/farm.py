@@ -362,7 +362,7 @@ def run_jobs(items, job, jobs_per_gpu=1, device=None, pin=None):
     < 8 % of the HBM bandwidth, its per-Gaussian / binning / Adam / loss kernels by HBM or latency at < 18 % VALU issue, strictly one
     after the other on one stream (profiles/r04_train_step_fused.json).  Independent sequences have nothing to wait for in each other:
     K host threads per rank, each with its OWN HIP stream (torch's current stream is per thread), its own model and its own library
-    state (api.hip: thread_local per-device state, host mailbox, allocator callbacks) pull sequences from the rank's list, and the
+    state (forward.hip: thread_local per-device state, host mailbox, allocator callbacks) pull sequences from the rank's list, and the
     hardware interleaves one job's compositing with another's streaming kernels.  ctypes and torch release the GIL inside their calls;
     what the threads share of the interpreter is the glue between calls.  Results come back in the order of `items`; an exception of a
     job is raised here (run_sequence_job itself never raises: failures are per-sequence records).

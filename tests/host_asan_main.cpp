@@ -62,6 +62,12 @@ int main() {
     CHECK(das3r_raster_forward(&a, &in, &out, no_alloc, no_alloc, no_alloc, nullptr, &saved, nullptr) == DAS3R_ERR_INVALID_ARG);   // M too small for the degree
     a.M = 16;
     CHECK(das3r_raster_forward(&a, &in, nullptr, no_alloc, no_alloc, no_alloc, nullptr, &saved, nullptr) == DAS3R_ERR_INVALID_ARG);   // no outputs
+    das3r_raster_out out2 = out;
+    out2.out_color = dummy;
+    out2.radii = (int32_t *)dummy;
+    CHECK(das3r_raster_forward(&a, &in, &out2, no_alloc, no_alloc, no_alloc, nullptr, nullptr, nullptr) == DAS3R_ERR_INVALID_ARG);   // no saved state
+    CHECK(strstr(das3r_last_error(), "null output/allocator") != nullptr);
+    CHECK(das3r_raster_forward(&a, nullptr, &out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == DAS3R_ERR_INVALID_ARG && strcmp(das3r_last_error(), "null args") == 0);
     das3r_raster_grads g;
     memset(&g, 0, sizeof(g));
     CHECK(das3r_raster_backward(&a, &in, nullptr, dummy, &g, nullptr) == DAS3R_ERR_INVALID_ARG);

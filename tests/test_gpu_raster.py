@@ -724,7 +724,7 @@ def test_segmented_binning_is_chosen_for_long_lists_and_backs_off(monkeypatch):
 @pytest.mark.parametrize("render", ["quad", "rows"])
 @pytest.mark.parametrize("name", ["basic_deg3", "long_lists", "deep", "depth_ties", "ragged_image"])
 def test_depth_orders_agree(name, render, monkeypatch):
-    """Global depth sort vs the local depth order (tile lists sorted by the compositing kernel, api.hip): the lists are
+    """Global depth sort vs the local depth order (tile lists sorted by the compositing kernel, forward.hip): the lists are
     identical, so image, radii and num_rendered must be too, and the gradients up to the order of the per-wave LDS adds
     (the emission slots — rows of the backward pass's partial sums — are numbered in index instead of depth order)."""
     sc, mode = util.scene_variant(name)
@@ -744,7 +744,7 @@ def test_depth_orders_agree(name, render, monkeypatch):
 
 def test_speculative_capacity_is_redone_when_the_scene_grows(monkeypatch):
     """A forward of a shape seen before lays the binning buffer out for the previous count + 25 % and enqueues everything
-    before it knows its own count (api.hip).  When the scene has grown past that (here: the scale modifier goes from 0.15
+    before it knows its own count (forward.hip).  When the scene has grown past that (here: the scale modifier goes from 0.15
     to 1), the binning and the compositing are redone with the exact size: image, radii, count and gradients must equal those
     of a forward that never speculated (DAS3R_CAPACITY=exact)."""
     from das3r_amd import GaussianRasterizationSettings, rasterizer

@@ -3,7 +3,7 @@ sources with `hipcc -fsanitize=address -fno-gpu-sanitize` (host instrumented, de
 tests/host_asan_main.cpp, which drives every entry point that works without a GPU (layout arithmetic over a sweep of shapes,
 argument validation of forward / backward / check / mark_visible with the upstream error strings, profiler and counter
 bookkeeping), and runs it: ASan aborts on any bad access, the program exits non-zero on a wrong answer.  ~2 minutes to build:
-only api.hip (where all the host logic lives) and the launchers it links against are compiled."""
+only api.hip and forward.hip (where all the host logic lives) and the launchers they link against are compiled."""
 import os
 import shutil
 import subprocess

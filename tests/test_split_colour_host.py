@@ -1,5 +1,5 @@
 """CPU tests of the split preprocess (geometry kernel on the caller's stream, SH colour kernel on the library's side stream: preprocess.hip,
-api.hip): the DAS3R_SPLIT_COLOUR switch is parsed, the choice between the split and the fused form is a pure function of the call's shape,
+forward.hip): the DAS3R_SPLIT_COLOUR switch is parsed, the choice between the split and the fused form is a pure function of the call's shape,
 the ABI did not move, and the per-kernel table folds the two new kernel names into the preprocess entry."""
 import ctypes
 

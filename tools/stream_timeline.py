@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-step kernel timeline from a rocprofv3 --kernel-trace CSV dump, for steps whose kernels run on MORE THAN ONE stream (the split
-preprocess: das3r_amd/csrc/api.hip SideStream).  tools/timeline.py adds durations and gaps along one in-order stream; here every kernel
+preprocess: das3r_amd/csrc/forward.hip Join).  tools/timeline.py adds durations and gaps along one in-order stream; here every kernel
 of a step is placed by its start and end stamps relative to the step's first kernel, so that a kernel that runs beside others shows as
 an interval, and the step's critical path is read off the stamps instead of summed.
 

@@ -536,6 +536,51 @@ extern "C" int das3r_raster_aux_adjoint(const das3r_raster_args *a, const das3r_
     return launch_render_aux_adjoint(P, W, H, C, dL_dout, dL_dfeat, accumulate != 0, scratch, saved->geom, saved->binning, saved->img, L, saved->num_rendered, a->debug != 0, s);
 }
 
+// ---- the aux channels' and the coverage image's gradients to the geometry (render_aux_bwd.hip) ----
+// Additive under ABI 16.  The whole backward of L = <dL_dout, aux image> + <dL_dalpha, 1 - final_T> for the forward that left `saved`: one
+// compositing kernel (rows 3..8 of the nine-float rows, 0..2 zero; with dL_dfeatures the [capacity, C] feature rows on the same walk), the
+// gather for dL_dfeatures, then the per-Gaussian backward exactly as a colour loss runs it (quad_rows false, no depth term, the forward's
+// antialiasing flag).  Scratch: the nine-float rows as das3r_raster_backward_scratch_bytes rounds them, then the feature rows.
+extern "C" size_t das3r_raster_aux_backward_scratch_bytes(int64_t capacity, int32_t C) {
+    const size_t c = capacity > 0 ? (size_t)capacity : 1, ch = C > 0 ? (size_t)C : 0;
+    return align_up(c * 9 * sizeof(float) + 16) + c * ch * sizeof(float) + 16;
+}
+
+extern "C" int das3r_raster_aux_backward(const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_saved *saved, int32_t C,
+                                         const float *features, const float *dL_dout, const float *dL_dalpha, float *dL_dfeatures,
+                                         const das3r_raster_grads *g, das3r_stream_t stream) {
+    static const char who[] = "das3r_raster_aux_backward";
+    hipStream_t s = (hipStream_t)stream;
+    if (!a || !in || !saved || !g) { set_error("%s: null args / inputs / saved state / grads", who); return DAS3R_ERR_INVALID_ARG; }
+    if (C < 0 || C > DAS3R_AUX_MAX_CHANNELS) { set_error("%s: C = %d channels (0 .. %d per call)", who, C, DAS3R_AUX_MAX_CHANNELS); return DAS3R_ERR_INVALID_ARG; }
+    if (C == 0 && !dL_dalpha) { set_error("%s: C = 0 channels and null dL_dalpha: no loss term", who); return DAS3R_ERR_INVALID_ARG; }
+    if (C == 0 && dL_dfeatures) { set_error("%s: dL_dfeatures with C = 0 channels", who); return DAS3R_ERR_INVALID_ARG; }
+    if (C > 0 && (!dL_dout || (a->P > 0 && !features))) { set_error("%s: null features / dL_dout with C = %d channels", who, C); return DAS3R_ERR_INVALID_ARG; }
+    if (g->chain) { set_error("%s: grads->chain is not supported here (the chained backward belongs to the colour loss)", who); return DAS3R_ERR_INVALID_ARG; }
+    if (!g->scratch) { set_error("%s: null scratch (das3r_raster_aux_backward_scratch_bytes)", who); return DAS3R_ERR_INVALID_ARG; }
+    int rc = validate(a, in);
+    if (rc) return rc;
+    const int P = a->P, W = a->image_width, H = a->image_height;
+    if (P == 0) return DAS3R_OK;   // no gradient has a row
+    if ((rc = backward_validate(who, in, saved, /*dL_dpix: not this entry's*/ reinterpret_cast<const float *>(g->scratch), false, nullptr, g))) return rc;
+    if (saved->num_rendered > 0 && !saved->binning) { set_error("%s: binning buffer missing", who); return DAS3R_ERR_INVALID_ARG; }
+    // the forward's binning self-check first: nothing is launched on the strength of an invalid image / list
+    if ((rc = das3r_raster_check(saved, stream))) return rc;
+    const Layout L = saved_layout(a, saved, shjac_saved(a, in, saved));
+    float *partial = g->scratch;
+    if (saved->num_rendered > 0) {
+        const size_t c = L.capacity > 0 ? (size_t)L.capacity : 1;
+        float *partial_f = dL_dfeatures ? (float *)((char *)g->scratch + align_up(c * 9 * sizeof(float) + 16)) : nullptr;
+        if ((rc = launch_render_aux_backward(P, W, H, C, features, dL_dout, dL_dalpha, partial, partial_f, saved->geom, saved->binning, saved->img, L,
+                                             a->debug != 0, s))) return rc;
+        if (dL_dfeatures && (rc = launch_aux_gather(P, C, partial_f, dL_dfeatures, saved->geom, L, a->debug != 0, s))) return rc;
+    } else if (dL_dfeatures) {
+        HIP_TRY(hipMemsetAsync(dL_dfeatures, 0, sizeof(float) * (size_t)P * (size_t)C, s));
+    }
+    // (nothing rendered: tiles_touched is all zero, the kernel reads no row and writes the zeros; columns 0..2 are zero: so is dL/d(colour, SH))
+    return launch_preprocess_backward(a, in, saved->geom, saved->binning, L, g, partial, s, false, nullptr, (saved->flags & ANTIALIAS_FLAG) != 0);
+}
+
 extern "C" int das3r_has_experiments(void) {
 #ifdef DAS3R_EXPERIMENTS
     return 1;

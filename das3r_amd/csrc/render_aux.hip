@@ -9,9 +9,9 @@
 //   out[c][pixel]  = sum_k f[g_k][c] alpha_k T_k          over the list positions k < n_contrib[pixel]      (no background term)
 //   dL/df[g][c]    = sum_pixels sum_{k: g_k = g} alpha_k T_k dL/dout[c][pixel]
 //
-// The geometry is CONSTANT here: alpha and T come from the saved records, and no gradient reaches means, scales, rotations or
-// opacities through an aux channel (the documented semantics).  That is also why the adjoint needs no back-to-front replay:
-// w = alpha T depends only on what lies in front, so both kernels take the same front-to-back walk.
+// The geometry is CONSTANT in this file's kernels: alpha and T come from the saved records, and neither kernel sends a gradient to means,
+// scales, rotations or opacities (that gradient is render_aux_bwd.hip's, a back-to-front replay).  That is also why the adjoint needs no
+// back-to-front replay: w = alpha T depends only on what lies in front, so both kernels take the same front-to-back walk.
 //
 // Decomposition of render_common.h: one 256-lane workgroup per 16x16 tile, one wave64 per 8x8 quadrant, the list staged through LDS
 // in batches of 256, every wave culling a batch against its quadrant with a ballot.  A pixel takes part in list position k iff
@@ -362,6 +362,14 @@ int launch_render_aux_adjoint(int P, int W, int H, int C, const float *dL_dout, 
     KERNEL_CHECK(s, debug, "render_aux_adjoint");
     DAS3R_LAUNCH(aux_gather_kernel, dim3(div_up((int64_t)P * C, 256)), dim3(256), 0, s, P, C, (const uint32_t *)(geom + L.pub.tiles_touched),
                  (const uint32_t *)(geom + L.g_off_by_gid), partial, dL_dfeat, accumulate, (uint32_t)L.capacity);
+    KERNEL_CHECK(s, debug, "aux_gather");
+    return DAS3R_OK;
+}
+
+// the gather alone, for rows another kernel left (render_aux_bwd.hip: the geometry backward writes them on its own walk)
+int launch_aux_gather(int P, int C, const float *partial, float *dL_dfeat, const char *geom, const Layout &L, bool debug, hipStream_t s) {
+    DAS3R_LAUNCH(aux_gather_kernel, dim3(div_up((int64_t)P * C, 256)), dim3(256), 0, s, P, C, (const uint32_t *)(geom + L.pub.tiles_touched),
+                 (const uint32_t *)(geom + L.g_off_by_gid), partial, dL_dfeat, 0, (uint32_t)L.capacity);
     KERNEL_CHECK(s, debug, "aux_gather");
     return DAS3R_OK;
 }

@@ -442,7 +442,8 @@ def _aux_adjoint(state, grad, out, accumulate):
 
 
 class _CompositeFeatures(torch.autograd.Function):
-    """composite_features with its adjoint: the gradient goes to `features` alone (the geometry is constant in an aux channel)."""
+    """composite_features with its adjoint: the gradient goes to `features` alone (the geometry is held constant; _AuxWithGeometry is the
+    form that differentiates it)."""
     @staticmethod
     def forward(ctx, features, state):
         ctx.state = state
@@ -461,12 +462,19 @@ def _composite(state, features):
                       for c0 in range(0, n, _lib.AUX_MAX_CHANNELS)], 0)
 
 
-def composite_features(state, features):
+def composite_features(state, features, geometry=None):
     """features [P, C] fp32 (one row per Gaussian of the forward that left `state`) -> [C, H, W]: per pixel sum_k features[g_k] alpha_k T_k
     over the splats the pixel's colour was blended from — same order, same alpha, same stop; no background term, an empty pixel is 0.
-    Nothing of the forward is repeated (no preprocess, emission or sort).  Differentiable with respect to `features` ONLY: alpha and T
-    are the forward's and constant here — no gradient reaches means, scales, rotations or opacities through an aux channel.  Tensors wider
-    than 8 channels take one library call per 8."""
+    Nothing of the forward is repeated (no preprocess, emission or sort).  Tensors wider than 8 channels take one library call per 8.
+    geometry=None: differentiable with respect to `features` ONLY — alpha and T are the forward's and constant, no gradient reaches
+    means, scales, rotations or opacities.  geometry=AuxGeometry(settings, the forward's input tensors): the image is differentiable with
+    respect to those tensors as well (das3r_raster_aux_backward: one compositing kernel over the saved lists and the per-Gaussian backward;
+    every discrete decision of the forward held fixed), and dL/dmean2D arrives in geometry.means2D.grad.  For a gradient of the COVERAGE use
+    alpha_of(state, geometry=) / return_alpha, not a column of ones: the blend of ones differentiates to the same value through a
+    cancellation that fp32 loses on pixels with hundreds of faint layers.  One workgroup per tile: on few tiles with ~10 k-entry lists it
+    is slower than it could be (docs/ledger.md (ck))."""
+    if geometry is not None:
+        return _aux_with_geometry(state, features, geometry, False)[0]
     _check_features(state, features)
     if features.requires_grad and torch.is_grad_enabled():
         return _CompositeFeatures.apply(features, state)
@@ -506,10 +514,13 @@ def feature_adjoint(state, grad_image, out=None, accumulate=False):
     return out
 
 
-def alpha_of(state):
+def alpha_of(state, geometry=None):
     """-> [1, H, W] = 1 - final_T: the coverage of the forward that left `state`, read out of its saved image buffer (the transmittance
     every forward stores for its backward pass; include/das3r_raster.h das3r_raster_get_layout).  Exactly 0 where nothing was blended.
-    A view of what is there: no kernel of the library is launched."""
+    A view of what is there: no kernel of the library is launched.  geometry=AuxGeometry(...): the same image, differentiable with respect
+    to the forward's geometry inputs (composite_features' docstring)."""
+    if geometry is not None:
+        return _aux_with_geometry(state, None, geometry, True)[1]
     _check_state(state)
     _needs_device(state)
     npix = state.H * state.W
@@ -518,6 +529,149 @@ def alpha_of(state):
     L = _lib.layout(state.P, int(state.capacity) if int(state.capacity) > 0 else state.num_rendered, state.W, state.H)
     T = state.img[L["final_T"]:L["final_T"] + 4 * npix].view(torch.float32).reshape(1, state.H, state.W)
     return 1.0 - T
+
+
+class AuxGeometry:
+    """The settings and input tensors of a forward, as `composite_features(state, features, geometry=)` / `alpha_of(state, geometry=)` take
+    them to send an aux image's or the coverage image's gradient to the geometry: the GaussianRasterizationSettings the forward ran with and
+    the tensors it was given (means2D: the dummy leaf whose .grad receives dL/dmean2D; shs / colors_precomp are not differentiated here — the
+    per-Gaussian backward reads the forward's inputs — exactly one of them, and scales + rotations or cov3D_precomp, as for the forward)."""
+    __slots__ = ("raster_settings", "means3D", "means2D", "opacities", "shs", "colors_precomp", "scales", "rotations", "cov3D_precomp")
+
+    def __init__(self, raster_settings, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
+                 cov3D_precomp=None):
+        self.raster_settings = raster_settings
+        self.means3D, self.means2D, self.opacities = means3D, means2D, opacities
+        self.shs, self.colors_precomp, self.scales, self.rotations, self.cov3D_precomp = shs, colors_precomp, scales, rotations, cov3D_precomp
+
+
+def _given(t):
+    return t is not None and t.numel() > 0
+
+
+def _check_geometry(state, geometry):
+    """What the aux backward cannot take is refused here, before the library is reached."""
+    _check_state(state)
+    if not isinstance(geometry, AuxGeometry):
+        raise TypeError(f"geometry must be a das3r_amd.rasterizer.AuxGeometry, got {type(geometry).__name__}")
+    _needs_device(state)
+    rs = geometry.raster_settings
+    if (int(rs.image_width), int(rs.image_height)) != (state.W, state.H):
+        raise ValueError(f"geometry.raster_settings is {int(rs.image_width)} x {int(rs.image_height)}, the forward rendered {state.W} x {state.H}")
+    for name in ("means3D", "means2D", "opacities"):
+        t = getattr(geometry, name)
+        if not torch.is_tensor(t) or t.dim() != 2 or t.shape[0] != state.P:
+            raise ValueError(f"geometry.{name} must be the forward's own tensor ({state.P} rows)")
+        if t.device != state.device:
+            raise RuntimeError(f"geometry.{name} is on {t.device}, the forward ran on {state.device}")
+    if _given(geometry.shs) == _given(geometry.colors_precomp) and state.P > 0:
+        raise ValueError("geometry needs exactly one of shs / colors_precomp (the forward's own)")
+    if state.P > 0 and (_given(geometry.scales) and _given(geometry.rotations)) == _given(geometry.cov3D_precomp):
+        raise ValueError("geometry needs exactly one of the scales + rotations pair / cov3D_precomp (the forward's own)")
+    for name in ("shs", "colors_precomp", "scales", "rotations", "cov3D_precomp"):
+        t = getattr(geometry, name)
+        if _given(t) and t.shape[0] != state.P:
+            raise ValueError(f"geometry.{name} has {t.shape[0]} rows, the forward rasterised {state.P} Gaussians")
+
+
+def _aux_backward_impl(state, rs, features, grad_image, grad_alpha, want_features, means3D, sh, colors_precomp, opacities, scales, rotations,
+                       cov3Ds_precomp, _scratch_misalign=0, _fill=None):
+    """One das3r_raster_aux_backward call: the backward of <grad_image, composite_features(features)> + <grad_alpha, alpha_of> for the forward
+    that left `state` -> (g_means2D, g_opac, g_means3D, g_cov, g_scales, g_rot, g_features or None).  features [P, C <= 8] / grad_image
+    [C, H, W] or both None (coverage alone); grad_alpha [1, H, W] or None.  (_fill: tests fill the scratch and every output with it first.)"""
+    lib = _lib.load()
+    device, P = state.device, state.P
+    M = sh.shape[1] if sh.numel() else 0
+    C_ = 0 if features is None else int(features.shape[1])
+    z = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=device) if _fill is None else torch.full(shape, float(_fill), dtype=torch.float32, device=device)
+    has_sh, has_cov = sh.numel() > 0, cov3Ds_precomp.numel() > 0
+    g_means2D, g_opac, g_means3D = z(P, 3), z(P, 1), z(P, 3)
+    g_col = z(P, M, 3) if has_sh else z(P, 3)   # (identically zero for this loss; the per-Gaussian backward writes it all the same)
+    g_scales, g_rot = (None, None) if has_cov else (z(P, 3), z(P, 4))
+    g_cov = z(P, 6) if has_cov else None
+    g_feat = z(P, C_) if (want_features and C_ > 0) else None
+    if P == 0:
+        return g_means2D, g_opac, g_means3D, g_cov, g_scales, g_rot, g_feat
+    nbytes = int(lib.das3r_raster_aux_backward_scratch_bytes(max(int(state.capacity), 1), C_))
+    scratch = torch.empty(nbytes + int(_scratch_misalign), dtype=torch.uint8, device=device)   # rows written before they are read
+    if _fill is not None:
+        scratch[int(_scratch_misalign):][:nbytes // 4 * 4].view(torch.float32).fill_(_fill)
+    keep = []
+    a = _fill_args(rs, P, M, device, keep)
+    i = _fill_in(means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp)
+    _, saved = state._c_args()
+    g = _lib.RasterGrads()
+    g.dL_dmeans2D, g.dL_dopacities, g.dL_dmeans3D = g_means2D.data_ptr(), g_opac.data_ptr(), g_means3D.data_ptr()
+    g.dL_dshs, g.dL_dcolors_precomp = (g_col.data_ptr(), None) if has_sh else (None, g_col.data_ptr())
+    g.dL_dscales, g.dL_drotations, g.dL_dcov3D = _ptr(g_scales), _ptr(g_rot), _ptr(g_cov)
+    g.scratch = scratch.data_ptr() + int(_scratch_misalign)
+    with _on_device(device):
+        rc = lib.das3r_raster_aux_backward(C.byref(a), C.byref(i), C.byref(saved), C_, _ptr(features), _ptr(grad_image), _ptr(grad_alpha),
+                                           _ptr(g_feat), C.byref(g), _stream(device))
+    _lib.check(rc, "das3r_raster_aux_backward")
+    return g_means2D, g_opac, g_means3D, g_cov, g_scales, g_rot, g_feat
+
+
+class _AuxWithGeometry(torch.autograd.Function):
+    """(feature image or None, alpha or None) of a forward's saved lists, differentiable with respect to `features` AND the forward's geometry
+    inputs: the backward is ONE das3r_raster_aux_backward call for both upstream gradients (one per 8 channels of a wider tensor), and returns
+    dL/dmean2D for the dummy means2D leaf — autograd adds it to the colour loss's there."""
+    @staticmethod
+    def forward(ctx, features, means3D, means2D, opacities, scales, rotations, cov3Ds_precomp, sh, colors_precomp, raster_settings, state,
+                want_alpha):
+        device = state.device
+        tensors = [_prep(t, device, n) for t, n in ((means3D, "means3D"), (opacities, "opacities"), (scales, "scales"), (rotations, "rotations"),
+                                                    (cov3Ds_precomp, "cov3D_precomp"), (sh, "shs"), (colors_precomp, "colors_precomp"))]
+        feat = None if features is None else _prep(features.detach(), device, "features")
+        ctx.state, ctx.raster_settings, ctx.has_features = state, raster_settings, feat is not None
+        ctx.save_for_backward(*tensors, *(() if feat is None else (feat,)))
+        ctx.set_materialize_grads(False)
+        image = None if feat is None else _composite(state, feat)
+        alpha = alpha_of(state) if want_alpha else None
+        return image, alpha
+
+    @staticmethod
+    def backward(ctx, grad_image, grad_alpha):
+        none = (None,) * 12
+        if grad_image is None and grad_alpha is None:
+            return none
+        saved = ctx.saved_tensors
+        means3D, opacities, scales, rotations, cov3Ds_precomp, sh, colors_precomp = saved[:7]
+        feat = saved[7] if ctx.has_features else None
+        state = ctx.state
+        dense = lambda t: None if t is None else (t if t.dtype == torch.float32 else t.float()).contiguous()
+        grad_image, grad_alpha = dense(grad_image), dense(grad_alpha)
+        if grad_image is None:
+            feat = None
+        want_feat = feat is not None and ctx.needs_input_grad[0]
+        inputs = (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
+        n = 0 if feat is None else feat.shape[1]
+        if n <= _lib.AUX_MAX_CHANNELS:
+            out = _aux_backward_impl(state, ctx.raster_settings, feat, grad_image, grad_alpha, want_feat, *inputs)
+        else:   # wider tensors: a call per 8 channels, the coverage term with the first; every gradient is linear in the loss terms
+            out = None
+            for c0 in range(0, n, _lib.AUX_MAX_CHANNELS):
+                part = _aux_backward_impl(state, ctx.raster_settings, feat[:, c0:c0 + _lib.AUX_MAX_CHANNELS].contiguous(),
+                                          grad_image[c0:c0 + _lib.AUX_MAX_CHANNELS], grad_alpha if c0 == 0 else None, want_feat, *inputs)
+                out = part if out is None else tuple(None if x is None else (torch.cat((x, y), 1) if k == 6 else x + y)
+                                                     for k, (x, y) in enumerate(zip(out, part)))
+        g_means2D, g_opac, g_means3D, g_cov, g_scales, g_rot, g_feat = out
+        return (g_feat, g_means3D, g_means2D, g_opac, g_scales if scales.numel() else None, g_rot if rotations.numel() else None,
+                g_cov if cov3Ds_precomp.numel() else None, None, None, None, None, None)
+
+
+def _aux_with_geometry(state, features, geometry, want_alpha):
+    """-> (feature image or None, alpha or None) through _AuxWithGeometry; the checks of composite_features / _check_geometry first."""
+    _check_geometry(state, geometry)
+    if features is not None:
+        _check_features(state, features)
+    elif not want_alpha:
+        raise ValueError("nothing to render: neither features nor the coverage image was asked for")
+    e = _empty(state.device)
+    opt = lambda t: e if t is None else t
+    return _AuxWithGeometry.apply(features, geometry.means3D, geometry.means2D, geometry.opacities, opt(geometry.scales), opt(geometry.rotations),
+                                  opt(geometry.cov3D_precomp), opt(geometry.shs), opt(geometry.colors_precomp), geometry.raster_settings, state,
+                                  bool(want_alpha))
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, antialiasing=False,
@@ -667,15 +821,16 @@ class GaussianRasterizer(nn.Module):
         self.keep_state = bool(keep_state)
         self.state = None
 
-    def __call__(self, *args, log_focal=None, **kwargs):
-        """The module call takes one keyword more than forward(): log_focal (forward's docstring).  None: nn.Module's call, as it was."""
-        if log_focal is None:
+    def __call__(self, *args, log_focal=None, aux_geometry_grad=False, **kwargs):
+        """The module call takes two keywords more than forward(): log_focal and aux_geometry_grad (forward's docstring).  None / False:
+        nn.Module's call, as it was."""
+        if log_focal is None and not aux_geometry_grad:
             return super().__call__(*args, **kwargs)
-        _last.log_focal = log_focal
+        _last.log_focal, _last.aux_geometry_grad = log_focal, bool(aux_geometry_grad)
         try:
             return super().__call__(*args, **kwargs)
         finally:
-            _last.log_focal = None
+            _last.log_focal, _last.aux_geometry_grad = None, False
 
     def markVisible(self, positions):
         with torch.no_grad():
@@ -704,16 +859,26 @@ class GaussianRasterizer(nn.Module):
         sqrt(max(det(Sigma2D) / det(Sigma2D + 0.3 I), 2.5e-5)), and the backward differentiates that factor too.  Radii are unchanged.
         features ([P, C] fp32) / return_alpha: the extra results come after the others — (color, radii[, invdepth][, feature_image]
         [, alpha]) — feature_image [C, H, W] = composite_features over this forward's lists (differentiable with respect to `features`
-        only: the geometry is constant in an aux channel), alpha [1, H, W] = alpha_of.  The colour, the radii and every gradient of a
+        only, unless aux_geometry_grad — below), alpha [1, H, W] = alpha_of.  The colour, the radii and every gradient of a
         colour loss are the same bit for bit; with both at their defaults the call is the one it was.
         log_focal ([2] fp32 tensor; a keyword of the module CALL — rasterizer(..., log_focal=t), see __call__ — so that this method keeps the
         parameters it had): log-focal offsets (s_x, s_y) of the camera, e.g. (-log tan(FoVx / 2), -log tan(FoVy / 2)).  Like the
         dummy means2D its VALUE is not read — raster_settings (tanfov, projmatrix) must have been built from the same field of view.  When
         it requires grad the backward pass returns dL/ds for it (das3r_raster_backward_focal: the rendering with tanfov e^(-s) and the
         clip-x / clip-y columns of projmatrix scaled by e^(s), every discrete decision held fixed), with and without return_invdepth /
-        antialiasing; every other gradient is the same bit for bit.  None: the functions and library calls are the ones they were."""
+        antialiasing; every other gradient is the same bit for bit.  None: the functions and library calls are the ones they were.
+        aux_geometry_grad (bool; like log_focal a keyword of the module CALL — rasterizer(..., features=f, aux_geometry_grad=True)): False,
+        the default: the functions and library calls are the ones they were, a loss on feature_image reaches `features` alone and alpha
+        carries no gradient.  True (needs features and / or return_alpha): feature_image and alpha are differentiable with respect to
+        means3D, opacities, scales, rotations / cov3D_precomp as well, and their dL/dmean2D is added to means2D.grad beside the colour
+        loss's — one das3r_raster_aux_backward call for both images (a compositing kernel over this forward's saved lists + the per-Gaussian
+        backward; no second forward).  The colour, radii and colour-loss gradients are the same bit for bit.  For a coverage / mask loss ask
+        for return_alpha; a column of ones in `features` has the same derivative on paper and a poorly conditioned one in fp32."""
         raster_settings = self.raster_settings
         log_focal, _last.log_focal = getattr(_last, "log_focal", None), None   # (handed over by __call__; consumed here)
+        aux_geometry_grad, _last.aux_geometry_grad = getattr(_last, "aux_geometry_grad", False), False
+        if aux_geometry_grad and features is None and not return_alpha:
+            raise ValueError("aux_geometry_grad=True needs features= and / or return_alpha=True: there is no aux image to differentiate")
         want_state = features is not None or return_alpha or self.keep_state
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
@@ -736,13 +901,13 @@ class GaussianRasterizer(nn.Module):
             _last.want_state, _last.state = True, None
         try:
             return self._forward_checked(means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, return_invdepth,
-                                         antialiasing, features, return_alpha, want_state, log_focal)
+                                         antialiasing, features, return_alpha, want_state, log_focal, aux_geometry_grad)
         finally:
             if want_state:
                 _last.want_state, _last.state = False, None
 
     def _forward_checked(self, means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, return_invdepth, antialiasing,
-                         features, return_alpha, want_state, log_focal=None):
+                         features, return_alpha, want_state, log_focal=None, aux_geometry_grad=False):
         raster_settings = self.raster_settings
         if log_focal is not None and return_invdepth:
             color, radii, invdepth = _apply(_RasterizeGaussiansFocal, _check_log_focal(log_focal, means3D.device), True, means3D, means2D, shs,
@@ -761,6 +926,10 @@ class GaussianRasterizer(nn.Module):
         out = (color, radii, invdepth) if return_invdepth else (color, radii)
         if want_state:
             state = self.state = _last.state
+            if aux_geometry_grad:
+                geometry = AuxGeometry(raster_settings, means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp)
+                fimg, alpha = _aux_with_geometry(state, features, geometry, return_alpha)
+                return out + (() if features is None else (fimg,)) + ((alpha,) if return_alpha else ())
             if features is not None:
                 out = out + (composite_features(state, features),)
             if return_alpha:

@@ -179,7 +179,7 @@ def rasterizer_inputs(cam, pc, pipe, bg_color, scaling_modifier=1.0, override_co
     return settings, kw
 
 
-def _mode_kw(pipe, return_invdepth, features=None, return_alpha=False):
+def _mode_kw(pipe, return_invdepth, features=None, return_alpha=False, aux_geometry_grad=False):
     """GaussianRasterizer.forward's keywords beyond upstream's eight tensors: only those that are on."""
     kw = {"return_invdepth": True} if return_invdepth else {}
     if bool(getattr(pipe, "antialiasing", False)):
@@ -188,12 +188,14 @@ def _mode_kw(pipe, return_invdepth, features=None, return_alpha=False):
         kw["features"] = features
     if return_alpha:
         kw["return_alpha"] = True
+    if aux_geometry_grad:
+        kw["aux_geometry_grad"] = True
     return kw
 
 
 def das3r_render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, camera_pose=None,
                  filtering=None, use_conf=True, fused=False, variant="render", return_invdepth=False, features=None, return_alpha=False,
-                 return_state=False):
+                 return_state=False, aux_geometry_grad=False):
     """viewpoint_camera: .FoVx .FoVy .image_height .image_width .projection_matrix (4x4, already transposed) [.camera_center for
     pipe.convert_SHs_python]; pc: splat model (das3r_amd.model.SplatModel or anything with the same attributes); pipe: .debug
     .compute_cov3D_python .convert_SHs_python; camera_pose: (7,) tensor (qw,qx,qy,qz,tx,ty,tz), may require grad.
@@ -201,7 +203,10 @@ def das3r_render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, ove
     pipe.antialiasing (where upstream's newer renderer reads it; absent = False): the rasterizer's antialiasing mode.
     features ([P, C] fp32, one row per rasterised Gaussian — after `filtering`): render_pkg["features"] = the [C, H, W] image of those
     channels blended over this render's own lists (rasterizer.composite_features: no second forward; differentiable with respect to
-    `features` only, the geometry is constant in an aux channel).  return_alpha: render_pkg["alpha"] = [1, H, W] coverage, 1 - final T.
+    `features` only unless aux_geometry_grad).  return_alpha: render_pkg["alpha"] = [1, H, W] coverage, 1 - final T.
+    aux_geometry_grad: render_pkg["features"] / ["alpha"] also send their gradients to the geometry — means, scales, rotations, opacities
+    and, through them, the pose and the confidences; render_pkg["viewspace_points"].grad carries their dL/dmean2D beside the colour loss's
+    (GaussianRasterizer.forward's docstring; a coverage / mask loss belongs on "alpha", not on a ones column of `features`).
     return_state: render_pkg["raster_state"] = the forward's RasterState, for further composite_features / feature_adjoint calls.
     With OptimParams.fov_lr > 0 (pc.fov_lr) the "render" variant takes the field of view and the projection from pc.FoVx / pc.FoVy instead
     of the camera's — training, held-out passes and reports alike — and a backward pass leaves dL/dFoV on them (one host read-back of the
@@ -209,7 +214,7 @@ def das3r_render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, ove
     settings, kw = rasterizer_inputs(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, camera_pose, filtering,
                                      use_conf, fused, variant)
     rasterizer = GaussianRasterizer(raster_settings=settings, keep_state=True) if return_state else GaussianRasterizer(raster_settings=settings)
-    out = rasterizer(**kw, **_mode_kw(pipe, return_invdepth, features, return_alpha))   # (upstream's call when all are off)
+    out = rasterizer(**kw, **_mode_kw(pipe, return_invdepth, features, return_alpha, aux_geometry_grad))   # (upstream's call when all are off)
     image, radii = out[0], out[1]
     if variant == "confidence":
         return image   # (render_confidence returns the image alone: gaussian_renderer/__init__.py:510)

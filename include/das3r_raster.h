@@ -476,8 +476,8 @@ int das3r_thin_voxels(int32_t P, const float *xyz, const float *score /* or NULL
  * or without out_invdepth, antialiased or not (the factor is part of the saved opacity), an evaluation forward (flags bit 3), every
  * binning path and forward kernel — any number of times while the caller keeps the three buffers, before or after
  * das3r_raster_backward / _depth (neither call writes what the other reads).  No preprocess, emission or sort is repeated.
- * THE GEOMETRY IS CONSTANT in these calls: alpha and T are the forward's, and no gradient reaches means, scales, rotations or opacities
- * through an aux channel — the defined semantics, not an omission.
+ * THE GEOMETRY IS CONSTANT in these two calls: alpha and T are the forward's, and neither sends a gradient to means, scales, rotations or
+ * opacities.  The gradients of an aux image and of the coverage image with respect to the geometry are das3r_raster_aux_backward's (below).
  * args supplies P, image_width, image_height and debug only.  1 <= C <= DAS3R_AUX_MAX_CHANNELS per call (wider tensors: several calls).
  * scratch: das3r_raster_aux_scratch_bytes(saved->capacity, C) bytes (one row of C sums per list entry; need not be zeroed).  dL_dfeat is
  * fully written (zeros for a Gaussian that was not rendered) unless accumulate.  No floating-point atomics: bit-identical from run to run.
@@ -489,6 +489,35 @@ int das3r_raster_aux_forward(const das3r_raster_args *args, const das3r_raster_s
 size_t das3r_raster_aux_scratch_bytes(int64_t capacity, int32_t C);
 int das3r_raster_aux_adjoint(const das3r_raster_args *args, const das3r_raster_saved *saved, int32_t C, const float *dL_dout /* [C,H,W] */,
                              float *dL_dfeat /* [P,C] */, int32_t accumulate, float *scratch, das3r_stream_t stream);
+
+/* ---- aux channels and coverage: gradients to the geometry (opt-in) ---------------------------------------------------------------
+ * Additive symbols under ABI 16.  das3r_raster_aux_backward is the whole backward pass of
+ *     L = <dL_dout, das3r_raster_aux_forward's image of `features`> + <dL_dalpha, 1 - final_T>            (either term may be absent)
+ * for the forward that left `saved`, with respect to the forward's geometry inputs — and, with dL_dfeatures, to `features` as well (the sums
+ * of das3r_raster_aux_adjoint, from the same walk).  Launches: ONE compositing kernel (render_aux_backward_kernel: every pixel replayed back to
+ * front over the saved lists from T = final_T, stop n_contrib; no second forward, no preprocess, emission or sort), the gather for
+ * dL_dfeatures if asked, and the per-Gaussian backward das3r_raster_backward ends with — the antialiasing factor of an antialiased forward
+ * (flags bit 4) is differentiated exactly as for a colour loss.  Every discrete decision of the forward is held fixed: cull, radius, tile
+ * rectangle, lists, the 1/255 and T < 1e-4 cut-offs, n_contrib.
+ * The coverage term is differentiated in the direct form dL/dalpha_k += dL_dalpha T_final / (1 - alpha_k).  Ask for it with dL_dalpha; do NOT
+ * blend a column of ones instead: the same value then comes out of T_k - R / (1 - alpha_k), which cancels in fp32 (measured on pixels
+ * with hundreds of faint layers: 1.3e-4 .. 5.4e-4 of the largest gradient against 3e-6 for the direct form).
+ * args / in: the ones the forward was given (the per-Gaussian backward reads the inputs), as for das3r_raster_backward.  0 <= C <=
+ * DAS3R_AUX_MAX_CHANNELS; C == 0 is the coverage term alone.  features [P, C] and dL_dout [C, H, W] are required iff C > 0; dL_dalpha [H, W]
+ * or NULL; dL_dfeatures [P, C] or NULL (fully written; zeros for a Gaussian that was not rendered).
+ * grads: every buffer das3r_raster_backward would ask for, fully written; the colour gradient of this loss is identically zero, and
+ * dL_dshs / dL_dcolors_precomp (whichever the forward's input calls for — still required) is written as zeros.  grads->scratch:
+ * das3r_raster_aux_backward_scratch_bytes(saved->capacity, C) bytes — the nine-float rows, then C floats per instance — 4-byte aligned, need
+ * not be initialised.  No floating-point atomics: bit-identical from run to run.  P == 0 or nothing rendered: every output is zeros.
+ * DAS3R_ERR_INVALID_ARG with a das3r_last_error() message, before anything is launched: grads->chain != NULL (the chained backward is the
+ * colour loss's), C outside 0 .. 8, C == 0 with NULL dL_dalpha (or with dL_dfeatures), a NULL among the pointers the chosen C needs, NULL
+ * grads->scratch, and whatever das3r_raster_backward refuses.  The forward's binning self-check is examined first (das3r_raster_check).
+ * One workgroup per tile: few tiles with very long lists (~10 k entries) leave most of the chip idle — see docs/ledger.md (ck). */
+size_t das3r_raster_aux_backward_scratch_bytes(int64_t capacity, int32_t C);
+int das3r_raster_aux_backward(const das3r_raster_args *args, const das3r_raster_in *in, const das3r_raster_saved *saved, int32_t C,
+                              const float *features /* [P,C]; NULL iff C == 0 */, const float *dL_dout /* [C,H,W]; NULL iff C == 0 */,
+                              const float *dL_dalpha /* [H,W] or NULL */, float *dL_dfeatures /* [P,C] or NULL */,
+                              const das3r_raster_grads *grads, das3r_stream_t stream);
 
 /* ---- introspection (used by the parity tests and the roofline accounting) ---- */
 

@@ -99,7 +99,7 @@ def _check(name, color, g, ref_color, ref_g, tol=None, scale_modifier=1.0):
 # ("deep", ~4000 faint layers per tile, is left out: with the factor one of its pixels meets T < 1e-4 one splat later in fp32 than in fp64 —
 #  a threshold flip of 3e-3 of the gradient maxima on the splats of that pixel, everything else within the bars)
 @pytest.mark.parametrize("name", ["aa_tiny", "basic_deg3", "long_lists", "ragged_image", "culled", "deg0", "colors_precomp", "cov3D_precomp",
-                                  "scale_modifier", "world_camera"])
+                                  "scale_modifier", "world_camera"] + util.CAMERA_VARIANTS)
 def test_antialiased_forward_and_backward_against_the_dense_oracle(name):
     sc, mode = _scene(name)
     dev = _dev()
@@ -148,21 +148,22 @@ def test_antialiasing_through_every_compositing_kernel(env, monkeypatch):
     _check(str(env), color, g, ref_color, ref_g, tol=util.tolerances_for(env.get("DAS3R_RENDER_BWD"))["tol"])
 
 
-@pytest.mark.parametrize("bwd", ["dpp", "blk", "fine"])
-def test_antialiased_backward_depth_against_the_dense_oracle(bwd, monkeypatch):
+@pytest.mark.parametrize("bwd,name", [pytest.param(b, n, id=b if n == "aa_tiny" else f"{b}-{n}") for n in ("aa_tiny", "portrait_world")
+                                      for b in ("dpp", "blk", "fine")])
+def test_antialiased_backward_depth_against_the_dense_oracle(bwd, name, monkeypatch):
     """das3r_raster_backward_depth with bit 4: the factor's derivative is applied once, to the opacity sums of both passes."""
     monkeypatch.setenv("DAS3R_RENDER_BWD", bwd)
     if bwd == "fine":
         monkeypatch.setenv("DAS3R_RENDER", "fine")
     if bwd != "dpp":
         monkeypatch.setenv("DAS3R_BWD_BUCKETS", "4")
-    sc, mode = _scene("aa_tiny")
+    sc, mode = _scene(name)
     dev = _dev()
     gD = torch.randn(sc.H, sc.W, generator=torch.Generator().manual_seed(5)) * 0.5
     _, ref_g, _ = _oracle(sc, mode, dev, gD)
     _, _, g = _hip(sc, mode, dev, True, gD)
     for k in ref_g:
-        util.assert_grad_close(g[k].double().cpu().numpy(), ref_g[k].cpu().numpy(), f"aa_tiny {bwd} depth dL/d{k}")
+        util.assert_grad_close(g[k].double().cpu().numpy(), ref_g[k].cpu().numpy(), f"{name} {bwd} depth dL/d{k}")
 
 
 def _direct(sc, mode, dev, invdepth, flags_mask=~0):

@@ -17,8 +17,8 @@ from tests import util
 
 pytestmark = pytest.mark.gpu
 
-FWD_VARIANTS = ["basic_deg3", "ragged_image", "long_lists", "deep", "culled", "depth_ties", "single"]
-ADJ_VARIANTS = ["basic_deg3", "deep", "culled", "long_lists"]
+FWD_VARIANTS = ["basic_deg3", "ragged_image", "long_lists", "deep", "culled", "depth_ties", "single"] + util.CAMERA_VARIANTS
+ADJ_VARIANTS = ["basic_deg3", "deep", "culled", "long_lists", "frustum_edge"]
 PATHS = [("quad", "radix"), ("rows", "local"), ("rows", "seg"), ("lanes", "radix"), ("fine", "radix")]
 KERNELS = {"quad": "render_forward_kernel", "rows": "render_forward_rows_kernel", "lanes": "render_forward_lanes_kernel",
            "fine": "render_forward_regions_kernel"}

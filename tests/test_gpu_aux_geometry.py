@@ -14,7 +14,7 @@ from tests import util
 
 pytestmark = pytest.mark.gpu
 
-VARIANTS = ["basic_deg3", "ragged_image", "long_lists", "deep", "culled", "depth_ties", "cov3D_precomp", "single"]
+VARIANTS = ["basic_deg3", "ragged_image", "long_lists", "deep", "culled", "depth_ties", "cov3D_precomp", "single"] + util.CAMERA_VARIANTS
 PATHS = [("quad", "radix"), ("rows", "local"), ("rows", "seg"), ("lanes", "radix"), ("fine", "radix")]   # tests/test_gpu_aux.py's
 
 

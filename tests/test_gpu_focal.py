@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 
 PIPE = SimpleNamespace(debug=False, compute_cov3D_python=False, convert_SHs_python=False)
 VARIANTS = ["basic_deg3", "deg0", "ragged_image", "colors_precomp", "cov3D_precomp", "scale_modifier", "long_lists", "deep", "world_camera",
-            "culled", "depth_ties", "single"]
+            "culled", "depth_ties", "single"] + util.CAMERA_VARIANTS
 GRAD_NAMES = ["means2D", "colors", "opacities", "means3D", "cov3D", "shs", "scales", "rotations"]
 
 
@@ -137,7 +137,9 @@ def test_per_splat_against_the_oracles_per_splat_gradient(name):
 @pytest.mark.parametrize("name,depth,aa,use_pre", [("basic_deg3", True, False, False), ("long_lists", True, False, False),
                                                    ("aa_tiny", False, True, False), ("basic_deg3", False, True, False),
                                                    ("cov3D_precomp", False, True, False), ("aa_tiny", True, True, False),
-                                                   ("basic_deg3", False, False, True), ("aa_tiny", True, True, True)])
+                                                   ("basic_deg3", False, False, True), ("aa_tiny", True, True, True),
+                                                   ("frustum_edge", True, True, False), ("aniso_focal", False, False, True),
+                                                   ("portrait_world", True, False, False)])
 def test_the_extra_modes_against_the_oracle(name, depth, aa, use_pre):
     """With dL_dinvdepth (the oracle image tests/test_gpu_invdepth.py uses), with antialiasing (the reference factor of
     tests/test_gpu_antialiasing.py), with in->pre (identity pose: the oracle's scene up to the rounding of log / exp and logit / sigmoid),

@@ -47,7 +47,7 @@ def _oracle_invdepth(kw, skw):
     return color[0].cpu()
 
 
-@pytest.mark.parametrize("name", ["basic_deg3", "long_lists", "deep", "ragged_image", "culled"])
+@pytest.mark.parametrize("name", ["basic_deg3", "long_lists", "deep", "ragged_image", "culled"] + util.CAMERA_VARIANTS)
 @pytest.mark.parametrize("kind,binning", [("quad", "radix"), ("rows", "radix"), ("lanes", "radix"), ("fine", "radix"),
                                           ("quad", "local"), ("rows", "local"), ("rows", "seg")])
 def test_invdepth_every_forward_kernel_against_the_dense_oracle(name, kind, binning, monkeypatch):
@@ -116,7 +116,7 @@ def _gD(sc, seed=5):
     return torch.randn(sc.H, sc.W, generator=torch.Generator().manual_seed(seed)) * 0.5
 
 
-@pytest.mark.parametrize("name,bwd", [(n, b) for n in ("basic_deg3", "deep", "culled") for b in ("dpp", "blk", "fine")] + [("long_lists", "dpp")])
+@pytest.mark.parametrize("name,bwd", [(n, b) for n in ("basic_deg3", "deep", "culled", "frustum_edge", "portrait_world") for b in ("dpp", "blk", "fine")] + [("long_lists", "dpp")])
 def test_invdepth_gradients_against_the_dense_oracle(name, bwd, monkeypatch):
     """L = <gC, color> + <gD, invdepth> through every compositing backward the library picks on its own (forced), against float64 autograd.
     (long_lists on the bucket-parallel blk / fine walks: test_invdepth_gradients_on_long_lists_match_the_colour_path.)"""

@@ -41,7 +41,13 @@ def _run_hip(sc, mode, backward=True):
     return color.detach(), radii, grads, color.grad_fn
 
 
-@pytest.mark.parametrize("name", util.VARIANTS)
+def _assert_rows_close(t, ref, rows, what):
+    """assert_grad_close on a subset of a gradient's rows: the scale is then those rows' own maximum."""
+    assert rows.any(), what
+    util.assert_grad_close(t[rows], ref[rows], what)
+
+
+@pytest.mark.parametrize("name", util.VARIANTS + util.CAMERA_VARIANTS)
 def test_forward_backward_vs_oracle(name):
     sc, mode = util.scene_variant(name)
     ref_color, ref_radii, ref_g, S = util.run_oracle(sc, mode)
@@ -57,6 +63,12 @@ def test_forward_backward_vs_oracle(name):
         util.assert_grad_elementwise(t.cpu().numpy(), ref_g[gmap[k]], f"{name} dL/d{k}")
     # viewspace gradient convention: z component stays zero
     assert float(g["means2D"][:, 2].abs().max()) == 0.0
+    if name == "frustum_edge":   # the EWA clamp branch held to the bar on its own, whatever its share of the tensor — and so the rest
+        clamped = util.frustum_clamp_flags(sc).any(1) & (ref_radii > 0)
+        for k in ("means3D", "scales", "rotations", "means2D"):
+            _assert_rows_close(g[k].cpu().numpy(), ref_g[k], clamped, f"{name} dL/d{k}, rendered splats past the frustum clamp")
+            _assert_rows_close(g[k].cpu().numpy(), ref_g[k], ~clamped, f"{name} dL/d{k}, every other splat")
+
 
 @pytest.mark.parametrize("degree", [0, 1, 2])
 def test_compact_sh_layouts_and_ragged_waves_vs_oracle(degree):
@@ -80,7 +92,7 @@ def test_compact_sh_layouts_and_ragged_waves_vs_oracle(degree):
 
 
 @pytest.mark.parametrize("binning_path", ["radix", "local", "seg", "seg3"])
-@pytest.mark.parametrize("name", ["basic_deg3", "ragged_image", "long_lists", "deep", "culled", "depth_ties", "world_camera"])
+@pytest.mark.parametrize("name", ["basic_deg3", "ragged_image", "long_lists", "deep", "culled", "depth_ties", "world_camera"] + util.CAMERA_VARIANTS)
 def test_binning_bit_exact(name, binning_path, monkeypatch):
     """Per-Gaussian geometry, depth order, per-tile splat lists and tile ranges are integer / exactly-rounded fp32 work:
     they must equal the oracle's bit for bit (binning over upstream's 3-sigma square: DAS3R_RECT=upstream; the default
@@ -315,7 +327,7 @@ def test_repeated_forwards_agree_and_count_is_exact():
         util.assert_grad_close(a.cpu().numpy(), b.cpu().numpy(), "repeated forward", tol=1e-5)
 
 
-@pytest.mark.parametrize("name", ["basic_deg3", "long_lists", "deep", "culled"])
+@pytest.mark.parametrize("name", ["basic_deg3", "long_lists", "deep", "culled"] + util.CAMERA_VARIANTS)
 def test_tight_rect_is_exact(name, monkeypatch):
     """Binning over the opacity-aware clipped rectangle only drops (tile, splat) instances whose alpha is < 1/255 on every
     pixel of the tile: the image must be bit-identical to binning over upstream's square, gradients equal up to the order of
@@ -336,7 +348,7 @@ def test_tight_rect_is_exact(name, monkeypatch):
 
 
 @pytest.mark.parametrize("binning", ["radix", "seg"])
-@pytest.mark.parametrize("name", ["basic_deg3", "long_lists", "deep", "culled", "ragged_image", "depth_ties"])
+@pytest.mark.parametrize("name", ["basic_deg3", "long_lists", "deep", "culled", "ragged_image", "depth_ties"] + util.CAMERA_VARIANTS)
 def test_forward_kernels_agree_bit_for_bit(name, binning, monkeypatch):
     """The forward compositing kernels — sub-list per 8x8 quadrant, per 4x4 block (render_rows.hip), four lanes per pixel
     (render_lanes.hip) — visit every pixel's splats in the same order with the same arithmetic for alpha and T: radii, final_T and
@@ -383,7 +395,7 @@ def test_forward_kernels_agree_bit_for_bit(name, binning, monkeypatch):
 
 
 @pytest.mark.parametrize("binning", ["radix", "seg"])
-@pytest.mark.parametrize("name", ["basic_deg3", "long_lists", "deep", "culled", "ragged_image", "depth_ties", "deg0"])
+@pytest.mark.parametrize("name", ["basic_deg3", "long_lists", "deep", "culled", "ragged_image", "depth_ties", "deg0"] + util.CAMERA_VARIANTS)
 @pytest.mark.parametrize("kernel", ["slices", "fine"])
 def test_sliced_forward_against_the_four_lanes_kernel_and_the_oracle(name, binning, kernel, monkeypatch):
     """render_slices.hip (round 6): a block's list of a batch cut into chunks that any wave walks from T = 1, the block's owner composing
@@ -524,7 +536,7 @@ def _built_kinds(kinds):
 
 
 
-@pytest.mark.parametrize("name", ["basic_deg3", "long_lists", "deep", "culled", "ragged_image", "deg1", "single"])
+@pytest.mark.parametrize("name", ["basic_deg3", "long_lists", "deep", "culled", "ragged_image", "deg1", "single"] + util.CAMERA_VARIANTS)
 def test_backward_kernels_agree(name, monkeypatch):
     """The backward compositing kernels against each other: pixel per lane with the cross-lane DPP reduction of the nine per-pair
     sums (render_bwd.hip), the same with the moments reduced on the matrix cores through an LDS slab (render_bwd_mfma.hip), and
@@ -546,7 +558,7 @@ def test_backward_kernels_agree(name, monkeypatch):
 
 
 @pytest.mark.parametrize("kind", ["dpp", "mfma", "scan64", "scan128", "scan256", "scana256", "stream", "blk64", "blk128", "blk256", "fine64", "fine128", "fine160", "fine192", "fine256", "fine128q", "fine128s"])
-@pytest.mark.parametrize("name", ["basic_deg3", "long_lists", "deep", "ragged_image", "culled"])
+@pytest.mark.parametrize("name", ["basic_deg3", "long_lists", "deep", "ragged_image", "culled", "frustum_edge", "portrait_world"])
 def test_every_backward_kernel_vs_oracle(name, kind, monkeypatch):
     """Each backward compositing kernel on its own against the CPU oracle (the default one is covered on all variants above)."""
     if not _built_kinds((kind,)):
@@ -564,11 +576,11 @@ def test_every_backward_kernel_vs_oracle(name, kind, monkeypatch):
 
 @pytest.mark.parametrize("kind", ["scan128", "scan256", "blk128", "blk256", "fine128", "fine192"])
 @pytest.mark.parametrize("slices", [2, 5])
-@pytest.mark.parametrize("name", ["deep", "long_lists", "basic_deg3"])
+@pytest.mark.parametrize("name", ["deep", "long_lists", "basic_deg3", "frustum_edge"])
 def test_bucket_parallel_backward(name, kind, slices, monkeypatch):
     """Long tile lists replayed bucket by bucket in parallel workgroups, each from the pixel states the forward checkpointed at
     the bucket boundaries (common.h BUCKET = 1024 list positions; "deep" has ~4000 entries per tile, "long_lists" ~1500 and
-    saturating pixels, "basic_deg3" none that long: every tile is its own last bucket) — against the oracle and against the
+    saturating pixels, "basic_deg3" and "frustum_edge" none that long: every tile is its own last bucket) — against the oracle and against the
     sequential replay."""
     sc, mode = util.scene_variant(name)
     _, _, ref_g, S = util.run_oracle(sc, mode)
@@ -577,7 +589,7 @@ def test_bucket_parallel_backward(name, kind, slices, monkeypatch):
     _, _, g_seq, fn = _run_hip(sc, mode)
     monkeypatch.setenv("DAS3R_BWD_BUCKETS", str(slices))
     _, _, g, _ = _run_hip(sc, mode)
-    if name != "basic_deg3":
+    if name not in ("basic_deg3", "frustum_edge"):
         tiles = ((sc.W + 15) // 16) * ((sc.H + 15) // 16)
         assert fn.num_rendered > 1024 * tiles, "the scene is meant to have lists of several buckets"
     gmap = {"means3D": "means3D", "opacities": "opacities", "shs": "shs", "scales": "scales", "rotations": "rotations", "means2D": "means2D"}
@@ -722,7 +734,7 @@ def test_segmented_binning_is_chosen_for_long_lists_and_backs_off(monkeypatch):
 
 
 @pytest.mark.parametrize("render", ["quad", "rows"])
-@pytest.mark.parametrize("name", ["basic_deg3", "long_lists", "deep", "depth_ties", "ragged_image"])
+@pytest.mark.parametrize("name", ["basic_deg3", "long_lists", "deep", "depth_ties", "ragged_image"] + util.CAMERA_VARIANTS)
 def test_depth_orders_agree(name, render, monkeypatch):
     """Global depth sort vs the local depth order (tile lists sorted by the compositing kernel, forward.hip): the lists are
     identical, so image, radii and num_rendered must be too, and the gradients up to the order of the per-wave LDS adds

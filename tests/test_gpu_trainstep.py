@@ -23,14 +23,16 @@ PIPE = SimpleNamespace(debug=False, compute_cov3D_python=False, convert_SHs_pyth
 SCHEDULE_SIGMA_TRAIN_DB, SCHEDULE_SIGMA_HELDOUT_DB = 0.124, 0.101
 
 
-def _pair(frames, W, H, seed, heldout, iterations, fused=False, generic=False, mask_some=False):
+def _pair(frames, W, H, seed, heldout, iterations, fused=False, generic=False, mask_some=False, focal_y_scale=1.0):
     """-> (HIP model, train cams, test cams, dense trainer) initialised from the same sequence.  generic: leave DAS3R's initial
     state (every Gaussian isotropic with an identity quaternion, where dL/d(rotation) is rounding noise around an exact zero that
-    Adam's sign-like first steps amplify) for anisotropic scales and random rotations."""
+    Adam's sign-like first steps amplify) for anisotropic scales and random rotations.  focal_y_scale: every frame's focal_y is that
+    multiple of its focal_x (the ground-truth images stay those of the square-pixel camera: a step's parity does not need them to fit)."""
     from das3r_amd.model import OptimParams
     from das3r_amd.train import build_from_sequence, synthetic_sequence
     from oracle.dense_trainer import DenseTrainer
     seq = synthetic_sequence(frames=frames, W=W, H=H, focal=0.9 * W, n_splats=1500, seed=seed)
+    seq["K"][:, 1, 1] *= focal_y_scale
     if mask_some:   # pixels below the confidence threshold make no Gaussian: the model's mask index is then not the identity (fast_step: mask_ptr)
         seq["confs"][:, ::3, 1::5] = -1.0
     if heldout:
@@ -54,12 +56,14 @@ NAMES = {"xyz": "_xyz", "f_dc": "_features_dc", "f_rest": "_features_rest", "opa
          "rotation": "_rotation", "conf_static": "_conf_static", "Q": "Q", "T": "T"}
 
 
-def test_one_step_loss_and_gradients_match_the_float64_restatement():
+@pytest.mark.parametrize("focal_y_scale", [1.0, 0.75])
+def test_one_step_loss_and_gradients_match_the_float64_restatement(focal_y_scale):
     """Loss, frame PSNR and EVERY gradient of one iteration (render -> masked L1 + SSIM -> backward) against the float64 dense
     restatement.  fp32 tolerance: 2e-3 of the tensor's largest gradient, and element-wise 1e-2 |ref| + 1e-4 max|ref|."""
     from das3r_amd.losses import l1_loss, psnr, ssim
     from das3r_amd.render import das3r_render
-    model, cams, _, opt, dense = _pair(frames=3, W=32, H=24, seed=3, heldout=False, iterations=100, generic=True)
+    model, cams, _, opt, dense = _pair(frames=3, W=32, H=24, seed=3, heldout=False, iterations=100, generic=True, focal_y_scale=focal_y_scale)
+    assert math.tan(0.5 * cams[0].FoVy) * 32 == pytest.approx(math.tan(0.5 * cams[0].FoVx) * 24 / focal_y_scale, rel=1e-6)
     bg = torch.zeros(3, device="cuda")
     uid = 1
     pkg = das3r_render(cams[uid], model, PIPE, bg, camera_pose=model.get_RT(uid))
@@ -150,8 +154,9 @@ def test_active_sh_prefix_steps_like_the_full_tensor(degree):
         assert float(far.double().mean()) <= 1e-3, (k, float(far.double().mean()))
 
 
-@pytest.mark.parametrize("degree", [0, 1, 3])
-def test_direct_fused_step_matches_the_autograd_fused_step(degree):
+@pytest.mark.parametrize("degree,focal_y_scale", [pytest.param(0, 1.0, id="0"), pytest.param(1, 1.0, id="1"), pytest.param(3, 1.0, id="3"),
+                                                  pytest.param(1, 0.75, id="1-focal_y_0.75")])
+def test_direct_fused_step_matches_the_autograd_fused_step(degree, focal_y_scale):
     """Round 4: the fused iteration as a straight sequence of C-ABI calls (das3r_amd/fast_step.py: no autograd, cached settings, pose
     rows in and out, loss / PSNR / gate on the device) against round 3's form of it (the same kernels under torch.autograd and the
     reference's Python; model.fast_step = False): four steps over three cameras — losses, frame PSNR, every parameter, the pose
@@ -160,7 +165,8 @@ def test_direct_fused_step_matches_the_autograd_fused_step(degree):
     from das3r_amd.train import train_step
     out = []
     for direct in (True, False, "grads"):   # ("grads": the direct form with the pre-transform's backward and Adam as two kernels — model.fuse_geometry_adam = False)
-        model, cams, _, opt, _dense = _pair(frames=3, W=32, H=24, seed=9, heldout=False, iterations=100, fused=True, generic=True)
+        model, cams, _, opt, _dense = _pair(frames=3, W=32, H=24, seed=9, heldout=False, iterations=100, fused=True, generic=True,
+                                            focal_y_scale=focal_y_scale)
         model.fast_step = bool(direct)
         model.fuse_geometry_adam = direct is True
         assert fast_step.available(model, PIPE) == bool(direct)

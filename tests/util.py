@@ -45,6 +45,53 @@ def look_at_view(eye, target, up=(0.0, 1.0, 0.0)):
     return torch.tensor(M, dtype=torch.float32)
 
 
+ROLLED_EYE = (0.7, -0.4, -1.5)
+
+
+def rolled_view():
+    """world_camera's eye and target with an up vector off the y axis: the view rotation has roll, so x and y mix in T = J R."""
+    return look_at_view(ROLLED_EYE, (0.2, 0.1, 5.0), up=(0.35, 1.0, 0.1))
+
+
+def general_camera_scene(P, W, H, fx, fy, sh_degree, seed, view_col=None, eye=(0., 0., 0.), s_px=(0.5, 4.0), bg=(0.2, 0.1, 0.3)):
+    """make_scene's splats under a camera whose two focal lengths differ (and, with view_col, whose view matrix is not the identity): every
+    splat keeps its normalised image position (u, v) and its depth, the frustum is the new one."""
+    sc = make_scene(P=P, W=W, H=H, focal=math.sqrt(fx * fy), sh_degree=sh_degree, seed=seed, s_px=s_px, bg=bg)
+    tx, ty = W / (2.0 * fx), H / (2.0 * fy)
+    m = sc.means3D.clone()                       # camera frame: keep (u, v, z), re-aim at the new frustum
+    m[:, 0] *= tx / sc.tanfovx
+    m[:, 1] *= ty / sc.tanfovy
+    Pm = projection_matrix(0.01, 100.0, 2 * math.atan(tx), 2 * math.atan(ty))
+    if view_col is None:
+        view, proj, campos = torch.eye(4), Pm.t().contiguous(), torch.zeros(3)
+    else:                                        # world = R^T (cam - t)
+        R, t = view_col[:3, :3], view_col[:3, 3]
+        m = (m - t) @ R
+        view, proj, campos = view_col.t().contiguous(), (view_col.t() @ Pm.t()).contiguous(), torch.tensor(eye, dtype=torch.float32)
+    return Scene(**{**sc.__dict__, "tanfovx": tx, "tanfovy": ty, "viewmatrix": view, "projmatrix": proj, "campos": campos, "means3D": m.contiguous()})
+
+
+def push_past_the_frustum_clamp(sc, n):
+    """Identity-view scene, in place: splats 0 .. n-1 go 1.35 .. 2.2 tanfovx off the axis in x, splats n .. 2n-1 the same in y — past the
+    1.3 tanfov clamp of the EWA Jacobian — and grow eightfold, so that their footprints still reach the image."""
+    g = torch.Generator().manual_seed(9)
+    for axis, tanfov in ((0, sc.tanfovx), (1, sc.tanfovy)):
+        sl = slice(axis * n, (axis + 1) * n)
+        u = torch.rand(n, generator=g) * 0.85 + 1.35
+        sign = torch.where(torch.rand(n, generator=g) < 0.5, -1.0, 1.0)
+        sc.means3D[sl, axis] = sc.means3D[sl, 2] * tanfov * u * sign
+        sc.scales[sl] *= 8
+    return sc
+
+
+def frustum_clamp_flags(sc):
+    """[P, 2] bool, float64 from the inputs: |t.x / t.z| > 1.3 tanfovx, |t.y / t.z| > 1.3 tanfovy (the EWA clamp: splat_math.h ewa_T)."""
+    m = sc.means3D.double()
+    t = torch.cat([m, torch.ones(sc.P, 1, dtype=torch.float64)], 1) @ sc.viewmatrix.double()[:, :3]
+    lim = torch.tensor([1.3 * sc.tanfovx, 1.3 * sc.tanfovy], dtype=torch.float64)
+    return ((t[:, :2] / t[:, 2:3]).abs() > lim).numpy()
+
+
 def scene_variant(name):
     """Returns (Scene, mode dict).  mode: colors_precomp / cov3D_precomp flags, scale_modifier."""
     mode = dict(colors_precomp=False, cov3D_precomp=False, scale_modifier=1.0)
@@ -92,6 +139,12 @@ def scene_variant(name):
     elif name == "single":
         sc = make_scene(P=1, W=48, H=32, focal=40.0, sh_degree=3, seed=33, s_px=(4.0, 4.0))
         sc.means3D[0] = torch.tensor([0.05, -0.02, 2.0])
+    elif name == "aniso_focal":    # focal_x / focal_y = 1.43: every other scene above has the two equal
+        sc = general_camera_scene(1500, 112, 72, 100.0, 70.0, 2, 61)
+    elif name == "frustum_edge":   # the same camera; 150 + 150 splats past the EWA clamp in x / in y whose footprints reach the image
+        sc = push_past_the_frustum_clamp(general_camera_scene(1500, 112, 72, 100.0, 70.0, 2, 61), 150)
+    elif name == "portrait_world":  # H > W, both ragged (5 x 8 tiles), focal_x < focal_y, a view rotation with roll, degree 3
+        sc = general_camera_scene(1500, 72, 123, 60.0, 95.0, 3, 62, view_col=rolled_view(), eye=ROLLED_EYE)
     else:
         raise KeyError(name)
     return sc, mode
@@ -99,6 +152,7 @@ def scene_variant(name):
 
 VARIANTS = ["basic_deg3", "deg0", "deg1", "deg2", "ragged_image", "colors_precomp", "cov3D_precomp", "scale_modifier",
             "long_lists", "deep", "world_camera", "culled", "depth_ties", "single"]
+CAMERA_VARIANTS = ["aniso_focal", "frustum_edge", "portrait_world"]   # general cameras: tests/test_oracle.py says what each must exercise
 
 
 def cov3d_of(sc, scale_modifier=1.0):

@@ -106,6 +106,18 @@ class FwdChoice(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("kernel", "quad_lanes", "row_private", "tile_lpt")]
 
 
+class PreprocessBackwardInputs(C.Structure):
+    """include/das3r_raster.h das3r_preprocess_backward_inputs (csrc/preprocess_choice.h PreprocessBackwardInputs)."""
+    _fields_ = [(n, C.c_int32) for n in ("has_sh", "has_cov", "M", "sh_degree", "shs_aligned16", "dL_dshs_aligned16", "no_sh_stage", "jac_saved",
+                                         "chained", "quad_rows", "depth", "aa")]
+
+
+class PreprocessForm(C.Structure):
+    """include/das3r_raster.h das3r_preprocess_form: preprocess_backward_kernel's nine template arguments + base_index, sh_rows_staged."""
+    _fields_ = [(n, C.c_int32) for n in ("has_sh", "has_cov", "stage_in", "stage_out", "deg0", "chain", "depth", "jac", "aa", "base_index",
+                                         "sh_rows_staged")]
+
+
 PRUNE_GROUP_ROWS = 1024   # DAS3R_PRUNE_GROUP_ROWS
 
 
@@ -137,7 +149,7 @@ EXPORTS = ("das3r_raster_forward", "das3r_raster_backward", "das3r_raster_backwa
            "das3r_debug_path_policy_fresh", "das3r_debug_path_policy_plan", "das3r_debug_path_policy_count", "das3r_debug_path_policy_skew",
            "das3r_debug_path_policy_hint", "das3r_debug_path_policy_forget", "das3r_debug_path_policy_resume", "das3r_debug_seg_dbits",
            "das3r_debug_parse_switches", "das3r_debug_choose_backward", "das3r_debug_choose_forward", "das3r_debug_has_invdepth_form",
-           "das3r_debug_kernel_name")
+           "das3r_debug_kernel_name", "das3r_debug_choose_preprocess_backward", "das3r_debug_preprocess_backward_name")
 
 _lib = None
 
@@ -284,6 +296,10 @@ def load():
     L.das3r_debug_has_invdepth_form.argtypes = [C.c_int32, C.c_int32]
     L.das3r_debug_kernel_name.restype = C.c_char_p
     L.das3r_debug_kernel_name.argtypes = [C.c_int32, C.c_int32]
+    L.das3r_debug_choose_preprocess_backward.restype = C.c_int   # the per-Gaussian backward's form (additive under ABI 16; host-only)
+    L.das3r_debug_choose_preprocess_backward.argtypes = [C.POINTER(PreprocessBackwardInputs), C.POINTER(PreprocessForm)]
+    L.das3r_debug_preprocess_backward_name.restype = C.c_char_p
+    L.das3r_debug_preprocess_backward_name.argtypes = [C.POINTER(PreprocessForm)]
     L.das3r_raster_get_layout.restype = C.c_int
     L.das3r_raster_get_layout.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(RasterLayout)]
     _lib = L

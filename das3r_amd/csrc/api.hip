@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "host_state.h"
+#include "preprocess_choice.h"
 #include <algorithm>
 
 namespace das3r {
@@ -297,6 +298,20 @@ extern "C" int das3r_debug_has_invdepth_form(int32_t backward, int32_t kernel) {
 extern "C" const char *das3r_debug_kernel_name(int32_t backward, int32_t kernel) {
     return backward ? bwd_kernel_name((BwdKernel)kernel) : fwd_kernel_name((FwdKernel)kernel);
 }
+
+// The functions of preprocess_choice.h on a caller's own values: which form of preprocess_backward_kernel a backward launches, and its raw name
+static PreprocessForm form_from(const das3r_preprocess_form *f) {
+    return PreprocessForm{f->has_sh != 0, f->has_cov != 0, f->stage_in != 0, f->stage_out != 0, f->deg0 != 0, f->chain != 0, f->depth != 0, f->jac != 0, f->aa != 0};
+}
+extern "C" int das3r_debug_choose_preprocess_backward(const das3r_preprocess_backward_inputs *in, das3r_preprocess_form *out) {
+    const PreprocessBackwardInputs ci = {in->has_sh != 0, in->has_cov != 0, in->M, in->sh_degree, in->shs_aligned16 != 0, in->dL_dshs_aligned16 != 0,
+                                         in->no_sh_stage != 0, in->jac_saved != 0, in->chained != 0, in->quad_rows != 0, in->depth != 0, in->aa != 0};
+    const PreprocessForm f = choose_preprocess_backward(ci);
+    *out = das3r_preprocess_form{f.has_sh, f.has_cov, f.stage_in, f.stage_out, f.deg0, f.chain, f.depth, f.jac, f.aa, preprocess_backward_base_index(f),
+                                 sh_rows_staged(ci.has_sh, ci.M, ci.sh_degree, ci.shs_aligned16, ci.no_sh_stage)};
+    return chain_refusal(ci);
+}
+extern "C" const char *das3r_debug_preprocess_backward_name(const das3r_preprocess_form *form) { return preprocess_backward_name(form_from(form)); }
 
 extern "C" int das3r_raster_get_layout(int32_t P, int64_t num_rendered, int32_t W, int32_t H, das3r_raster_layout *out) {
     if (!out || P < 0 || num_rendered < 0 || W <= 0 || H <= 0) { set_error("das3r_raster_get_layout: invalid argument"); return DAS3R_ERR_INVALID_ARG; }

@@ -338,6 +338,11 @@ int launch_depth_fold(int P, const char *geom, const Layout &L, float *partial, 
 size_t focal_workspace_bytes(int P);
 int launch_focal_grad(const das3r_raster_args *a, const das3r_raster_in *in, const char *geom, const Layout &L, const float *partial, bool quad_rows,
                       bool aa /*ANTIALIAS_FLAG*/, float *sums /*[2]*/, float *per_splat /*[P,2] or null*/, float *workspace, hipStream_t s);
+// the existence bytes [I][4] behind the quadrant rows [I][4][12] of `partial` (render_bwd_stream.hip lays them out); null: one row per instance
+static inline const uint8_t *quad_rows_exist(const float *partial, const Layout &L, bool quad_rows) {
+    const size_t cap_rows = L.capacity > 0 ? (size_t)L.capacity : 1;
+    return quad_rows ? reinterpret_cast<const uint8_t *>(partial) + align_up(cap_rows * 4 * 12 * sizeof(float)) : nullptr;
+}
 // partial: [num_rendered, 9] per-instance sums written by the render backward, gathered by the preprocess backward
 // *quad_rows (out): false = partial[I][9], one row per instance; true = the stream kernel's rows[I][4][12] + existence bytes
 int launch_render_backward(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,

@@ -7,7 +7,8 @@
 // (u - (W - 1) / 2) e^(s_x), its undilated covariance as a0 e^(2 s_x), b e^(s_x + s_y), c0 e^(2 s_y); the SH view direction and 1/z do not move.
 // So, per rendered splat, from the row sums the compositing backward left (partial[], the rows off_by_gid[i] .. + tiles_touched[i]):
 //   c_x = dL/du (u - (W - 1) / 2) + 2 a0 dL/da + b dL/db        c_y = dL/dv (v - (H - 1) / 2) + 2 c0 dL/dc + b dL/db
-// with dL/d(a, b, c) exactly preprocess_backward_kernel's (the antialiasing factor's term included), and dL/ds = sum_i c(i).
+// with dL/d(a, b, c) preprocess_backward_kernel's — the same function, splat_math.h conic_grad_to_cov2d, the antialiasing factor's term
+// included — and dL/ds = sum_i c(i).
 // No float atomics: a workgroup adds its 256 lanes in a fixed tree and stores one row; focal_finish_kernel adds the rows in a fixed order.
 // Nothing needs pre-zeroing: every word of per_splat, of the workspace rows and of sums is written.
 #include <algorithm>
@@ -46,49 +47,15 @@ __global__ void __launch_bounds__(256) focal_grad_kernel(
     if (n > 0u) {
         // the splat's row sums, columns 3 .. 8 (dL/dmean2D x, y; dL/dconic A, B, C; dL/dopacity), in preprocess_backward_kernel's order
         float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        const uint32_t e0 = off_by_gid[i];
-        if (row_exists) {   // (uniform) up to four 48-byte rows per instance, one per quadrant of the tile that met the splat
-            for (uint32_t k = 0; k < n; k++) {
-                const uint8_t *have = row_exists + (size_t)(e0 + k) * 4;
-#pragma unroll
-                for (int w = 0; w < 4; w++) {
-                    if (have[w]) {
-                        const float *row = partial + ((size_t)(e0 + k) * 4 + w) * 12;
-#pragma unroll
-                        for (int q = 0; q < 6; q++) acc[q] += row[3 + q];
-                    }
-                }
-            }
-        } else {
-            for (uint32_t k = 0; k < n; k++) {
-                const float *row = partial + (size_t)(e0 + k) * 9;
-#pragma unroll
-                for (int q = 0; q < 6; q++) acc[q] += row[3 + q];
-            }
-        }
+        sum_instance_rows<3, 6, true>(partial, row_exists, off_by_gid[i], n, acc);
         // the forward's inputs again (pretransform_math.h: the same bits), its T and its undilated covariance
-        float3 mean;
+        float3 mean, sc;
+        float4 q;
         float c3[6];
-        float op_in = 0.f;
-        if (!HAS_COV && pre.xyz != nullptr) {   // (uniform)
-            PoseRegs pose;
-            load_pose(pre.Rm, pre.tv, pre.Lq, pose);
-            mean = pre_mean(pose, pre.xyz[3 * i], pre.xyz[3 * i + 1], pre.xyz[3 * i + 2]);
-            const float4 q = pre_rot(pose, reinterpret_cast<const float4 *>(pre.rot)[i]);
-            const float3 sc = make_float3(pre_scale(pre.scaling[3 * i]), pre_scale(pre.scaling[3 * i + 1]), pre_scale(pre.scaling[3 * i + 2]));
-            cov3d_from_scale_rot(sc, scale_modifier, q, c3);
-            if constexpr (AA) op_in = pre_opacity(pre.opacity_raw[i], pre.conf_flat[pre.mask_index ? pre.mask_index[i] : (int64_t)i]);
-        } else {
-            mean = make_float3(means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]);
-            if constexpr (HAS_COV) {
-#pragma unroll
-                for (int j = 0; j < 6; j++) c3[j] = cov3D_precomp[6 * (size_t)i + j];
-            } else {
-                const float3 sc = make_float3(scales[3 * i], scales[3 * i + 1], scales[3 * i + 2]);
-                cov3d_from_scale_rot(sc, scale_modifier, reinterpret_cast<const float4 *>(rotations)[i], c3);
-            }
-            if constexpr (AA) op_in = opacities[i];
-        }
+        RawGeometry raw;
+        float op_in = 0.f;   // (AA only)
+        load_forward_inputs<HAS_COV, AA>(pre, false, means3D, scales, rotations, opacities, cov3D_precomp, i, mean, sc, q, c3, op_in, raw);
+        if constexpr (!HAS_COV) cov3d_from_scale_rot(sc, scale_modifier, q, c3);
         float V[16];
 #pragma unroll
         for (int j = 0; j < 16; j++) V[j] = viewmatrix[j];
@@ -99,7 +66,7 @@ __global__ void __launch_bounds__(256) focal_grad_kernel(
         ewa_T(xform43(mean, V), V, focal_x, focal_y, tanfovx, tanfovy, T, t, clampx, clampy);
         float a0, b, c0;
         cov2d_undilated(T, c3, a0, b, c0);
-        // ---- conic sums -> dL/d(a, b, c): preprocess_backward_kernel's expressions
+        // ---- conic sums -> dL/d(a, b, c): preprocess_backward_kernel's, by the functions it calls (splat_math.h)
         const float ca = a0 + 0.3f, cc = c0 + 0.3f;
         const float gA = acc[2], gB = acc[3], gC = acc[4];
         const float denom = ca * cc - b * b;
@@ -107,21 +74,11 @@ __global__ void __launch_bounds__(256) focal_grad_kernel(
         if constexpr (AA) {
             aa_r = aa_rho(a0, b, c0, denom);
             const float f = aa_factor(aa_r);
-            if (aa_r > AA_RHO_MIN) aa_drho = acc[5] * op_in / (2.f * f);
+            aa_drho = aa_opacity_grad_to_rho(aa_r, f, acc[5], op_in);
         }
         float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
         const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
-        if (denom2inv != 0.f) {
-            dL_da = denom2inv * (-cc * cc * gA + 2 * b * cc * gB + (denom - ca * cc) * gC);
-            dL_dc = denom2inv * (-ca * ca * gC + 2 * ca * b * gB + (denom - ca * cc) * gA);
-            dL_db = denom2inv * 2 * (b * cc * gA - (denom + 2 * b * b) * gB + ca * b * gC);
-            if constexpr (AA) {
-                const float k = aa_drho / denom;
-                dL_da += k * (c0 - aa_r * cc);
-                dL_dc += k * (a0 - aa_r * ca);
-                dL_db += k * (-2.f * b * (1.f - aa_r));
-            }
-        }
+        if (denom2inv != 0.f) conic_grad_to_cov2d<AA>(gA, gB, gC, ca, b, cc, a0, c0, denom, denom2inv, aa_r, aa_drho, dL_da, dL_db, dL_dc);
         // the row sums hold dL/d(ndc) = dL/d(pixel) W / 2 (the compositing backward's ddelx_dx): dL/du (u - (W - 1) / 2) = acc (that / (W / 2))
         const float4 rec = xyh[(size_t)i * SPLAT_REC];
         const float nx = (rec.x - 0.5f * (float)(W - 1)) / (0.5f * (float)W), ny = (rec.y - 0.5f * (float)(H - 1)) / (0.5f * (float)H);
@@ -158,8 +115,7 @@ int launch_focal_grad(const das3r_raster_args *a, const das3r_raster_in *in, con
                       bool aa, float *sums, float *per_splat, float *workspace, hipStream_t s) {
     const int P = a->P;
     const int blocks = div_up(P, 256);
-    const size_t cap_rows = L.capacity > 0 ? (size_t)L.capacity : 1;
-    const uint8_t *exists = quad_rows ? reinterpret_cast<const uint8_t *>(partial) + align_up(cap_rows * 4 * 12 * sizeof(float)) : nullptr;
+    const uint8_t *exists = quad_rows_exist(partial, L, quad_rows);
     const PreXform pre = pre_xform(in);
 #define ARGS                                                                                                                              \
     P, in->means3D, in->scales, a->scale_modifier, in->rotations, in->cov3D_precomp, in->opacities, pre, a->viewmatrix, a->image_width,   \

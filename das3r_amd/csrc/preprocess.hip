@@ -13,6 +13,7 @@
 #include "segkey.h"
 #include "splat_math.h"
 #include "pretransform_math.h"
+#include "preprocess_choice.h"
 
 namespace das3r {
 
@@ -60,29 +61,8 @@ __global__ void __launch_bounds__(256) preprocess_kernel(PRE_PARAMS) {
     float op;
     float4 q_in = make_float4(0.f, 0.f, 0.f, 0.f);
     float c3_in[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (!HAS_COV && pre.xyz != nullptr) {   // (uniform) the pose pre-transform on the way in: pretransform_math.h, the bits of pretransform_forward_kernel
-        PoseRegs pose;
-        load_pose(pre.Rm, pre.tv, pre.Lq, pose);
-        const float rx = pre.xyz[3 * idx], ry = pre.xyz[3 * idx + 1], rz = pre.xyz[3 * idx + 2];
-        const float4 rq = reinterpret_cast<const float4 *>(pre.rot)[idx];
-        const float r0 = pre.scaling[3 * idx], r1 = pre.scaling[3 * idx + 1], r2 = pre.scaling[3 * idx + 2];
-        const float ro = pre.opacity_raw[idx];
-        const float rc = pre.conf_flat[pre.mask_index ? pre.mask_index[idx] : (int64_t)idx];
-        p = pre_mean(pose, rx, ry, rz);
-        q_in = pre_rot(pose, rq);
-        s_in = make_float3(pre_scale(r0), pre_scale(r1), pre_scale(r2));
-        op = pre_opacity(ro, rc);
-    } else {
-        p = make_float3(means3D[3 * idx], means3D[3 * idx + 1], means3D[3 * idx + 2]);
-        op = opacities[idx];
-        if (HAS_COV) {
-#pragma unroll
-            for (int i = 0; i < 6; i++) c3_in[i] = cov3D_precomp[6 * idx + i];
-        } else {
-            s_in = make_float3(scales[3 * idx], scales[3 * idx + 1], scales[3 * idx + 2]);
-            q_in = reinterpret_cast<const float4 *>(rotations)[idx];
-        }
-    }
+    RawGeometry raw;   // (the backward's business)
+    load_forward_inputs<HAS_COV, true>(pre, false, means3D, scales, rotations, opacities, cov3D_precomp, idx, p, s_in, q_in, c3_in, op, raw);   // pretransform_math.h
     __shared__ uint32_t s_tiles;   // this workgroup's sum of tiles_touched (num_rendered is their grand total)
     if (threadIdx.x == 0) s_tiles = 0;
     if (!STAGE) __syncthreads();
@@ -530,7 +510,7 @@ int launch_preprocess(const das3r_raster_args *a, const das3r_raster_in *in, int
         (float4 *)(geom + L.pub.conic_opacity), (float4 *)(geom + L.pub.rgbd), (uint8_t *)(geom + L.pub.clamped),         \
         (uint32_t *)(geom + L.pub.tiles_touched), (uint32_t *)(geom + L.g_rect), (use_tight_rect() ? 1 : 0) | (a->prefiltered ? 2 : 0), (uint32_t *)(geom + L.g_ghist), (uint32_t)(L.g_ctrl_bytes / 4),                 \
         (uint32_t *)(img + L.pub.ranges), (uint32_t)(2 * L.ntiles), (uint32_t *)binning_ctrl, (uint32_t)(binning_ctrl_bytes / 4), arrive, host_out, tag, em, dhist, dhist_mask, dhist_next, pre, shjac
-    const bool stage = has_sh && a->M == 16 && a->sh_degree >= 2 && ((uintptr_t)in->shs & 15) == 0 && !switches().no_sh_stage;
+    const bool stage = sh_rows_staged(has_sh, a->M, a->sh_degree, ((uintptr_t)in->shs & 15) == 0, switches().no_sh_stage);
     if (side != nullptr) {   // the split form (forward.hip split_colour_rule: SH given, no fused emission, a binning path that keeps the depth keys)
         if (!has_sh || emit != nullptr) { set_error("launch_preprocess: the split form needs SH rows and a binning chain of its own"); return DAS3R_ERR_INVALID_ARG; }
         if (has_cov) {
@@ -572,7 +552,7 @@ int launch_sh_colour(const das3r_raster_args *a, const das3r_raster_in *in, char
     const int P = a->P;
     const PreXform pre = pre_xform(in);
     float *const shjac = L.g_shjac ? (float *)(geom + L.g_shjac) : nullptr;
-    const bool stage = a->M == 16 && a->sh_degree >= 2 && ((uintptr_t)in->shs & 15) == 0 && !switches().no_sh_stage;
+    const bool stage = sh_rows_staged(true, a->M, a->sh_degree, ((uintptr_t)in->shs & 15) == 0, switches().no_sh_stage);   // (the split form: SH rows given)
     HIP_TRY(hipStreamWaitEvent(side->stream, side->fork, 0));
     const int slices = div_up(P, COLOUR_T);
     const dim3 cgrid(slices < side->colour_blocks ? slices : side->colour_blocks), cblock(COLOUR_T);

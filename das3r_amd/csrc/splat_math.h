@@ -95,6 +95,70 @@ __device__ __forceinline__ void cov2d_from_T(const float T[2][3], const float *c
 constexpr float AA_RHO_MIN = 2.5e-5f;
 __device__ __forceinline__ float aa_rho(const float a0, const float b, const float c0, const float det) { return (a0 * c0 - b * b) / det; }
 __device__ __forceinline__ float aa_factor(const float rho) { return sqrtf(fmaxf(rho, AA_RHO_MIN)); }
+// ... backward: g_op = dL/d(o f) summed over the compositing passes, op_in = o, the forward's opacity before the factor.  dL/do = g_op f is the
+// caller's; dL/df = g_op o reaches the 2D covariance through rho = f^2 — unless f sat at its clamp: dL/drho = g_op o / (2 f)
+__device__ __forceinline__ float aa_opacity_grad_to_rho(const float rho, const float f, const float g_op, const float op_in) {
+    float aa_drho = 0.f;
+    if (rho > AA_RHO_MIN) aa_drho = g_op * op_in / (2.f * f);
+    return aa_drho;
+}
+
+// Backward of conic = inverse of the dilated 2D covariance (a, b, c) = (ca, cb, cc): the conic sums (gA, gB, gC) -> dL/d(a, b, c), with
+// denom = ca cc - cb^2 and denom2inv = 1 / (denom^2 + 1e-7) [upstream computeCov2DCUDA].  The caller holds all of them and calls this under
+// `denom2inv != 0` (the per-Gaussian backward computes dL/dcov3D under the same test).  AA: + dL/drho drho/d(a, b, c), rho = aa_r of the
+// undilated entries (ca0, cb, cc0); drho/da = (c0 det - det0 c) / det^2 = (c0 - rho c) / det, and so on.
+// ONE definition for preprocess_backward_kernel and focal_grad_kernel: the focal gradient is defined as using the backward's dL/d(a, b, c).
+template <bool AA>
+__device__ __forceinline__ void conic_grad_to_cov2d(const float gA, const float gB, const float gC, const float ca, const float cb, const float cc,
+                                                    const float ca0, const float cc0, const float denom, const float denom2inv, const float aa_r,
+                                                    const float aa_drho, float &dL_da, float &dL_db, float &dL_dc) {
+    dL_da = denom2inv * (-cc * cc * gA + 2 * cb * cc * gB + (denom - ca * cc) * gC);
+    dL_dc = denom2inv * (-ca * ca * gC + 2 * ca * cb * gB + (denom - ca * cc) * gA);
+    dL_db = denom2inv * 2 * (cb * cc * gA - (denom + 2 * cb * cb) * gB + ca * cb * gC);
+    if constexpr (AA) {
+        const float k = aa_drho / denom;
+        dL_da += k * (cc0 - aa_r * cc);
+        dL_dc += k * (ca0 - aa_r * ca);
+        dL_db += k * (-2.f * cb * (1.f - aa_r));
+    }
+}
+
+// A splat's sums over its per-instance rows, columns Q0 .. Q0 + NQ - 1 of the nine the compositing backward left (colour 0 - 2, mean2D 3 - 4,
+// conic 5 - 7, opacity 8): the rows e0 .. e0 + n - 1 of partial[I][9], indexed by emission slot (contiguous per splat), in slot order.
+// QUADS && row_exists != null (uniform; render_bwd_stream.hip, experiments build): up to four 48-byte rows per instance, partial[I][4][12], one
+// per quadrant of the tile that met the splat, row_exists[I][4] saying which — instance by instance, quadrant by quadrant.
+template <int Q0, int NQ, bool QUADS>
+__device__ __forceinline__ void sum_instance_rows(const float *partial, const uint8_t *row_exists, const uint32_t e0,
+                                                  const uint32_t n, float (&acc)[NQ]) {
+    if (QUADS && row_exists) {
+        for (uint32_t k = 0; k < n; k++) {
+            const uint32_t have = *reinterpret_cast<const uint32_t *>(row_exists + (size_t)(e0 + k) * 4);
+#pragma unroll
+            for (int w = 0; w < 4; w++) {
+                if ((have >> (8 * w)) & 0xffu) {   // the row's columns as the float4 words that hold them (rows are 48 bytes) and column 8 alone
+                    const float4 *row = reinterpret_cast<const float4 *>(partial + ((size_t)(e0 + k) * 4 + w) * 12);
+                    float v[9];
+#pragma unroll
+                    for (int b = 0; b < 2; b++) {
+                        if (Q0 < 4 * b + 4 && Q0 + NQ > 4 * b) {
+                            const float4 r = row[b];
+                            v[4 * b] = r.x; v[4 * b + 1] = r.y; v[4 * b + 2] = r.z; v[4 * b + 3] = r.w;
+                        }
+                    }
+                    if (Q0 + NQ > 8) v[8] = reinterpret_cast<const float *>(row)[8];
+#pragma unroll
+                    for (int q = 0; q < NQ; q++) acc[q] += v[Q0 + q];
+                }
+            }
+        }
+    } else {
+        for (uint32_t k = 0; k < n; k++) {
+            const float *row = partial + (size_t)(e0 + k) * 9;
+#pragma unroll
+            for (int q = 0; q < NQ; q++) acc[q] += row[Q0 + q];
+        }
+    }
+}
 
 // tile rectangle touched by a 2D splat of integer radius r (C truncation toward zero, clamped to the grid)
 __device__ __forceinline__ void tile_rect(const float px, const float py, const int r, const int tiles_x, const int tiles_y,
@@ -179,6 +243,33 @@ __device__ __forceinline__ float3 sh_eval(const int deg, const float sh[48], con
         out[c] = r + 0.5f;
     }
     return make_float3(out[0], out[1], out[2]);
+}
+
+// basis functions of the real SH up to degree 3 evaluated at unit direction (x,y,z): rgb_c = sum_k b[k] * sh[k][c]
+__device__ __forceinline__ void sh_basis(const int D, const float x, const float y, const float z, float b[16]) {
+    b[0] = SH_C0;
+    if (D > 0) {
+        b[1] = -SH_C1 * y;
+        b[2] = SH_C1 * z;
+        b[3] = -SH_C1 * x;
+        if (D > 1) {
+            const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+            b[4] = SH_C2_0 * xy;
+            b[5] = SH_C2_1 * yz;
+            b[6] = SH_C2_2 * (2.f * zz - xx - yy);
+            b[7] = SH_C2_3 * xz;
+            b[8] = SH_C2_4 * (xx - yy);
+            if (D > 2) {
+                b[9] = SH_C3_0 * y * (3.f * xx - yy);
+                b[10] = SH_C3_1 * xy * z;
+                b[11] = SH_C3_2 * y * (4.f * zz - xx - yy);
+                b[12] = SH_C3_3 * z * (2.f * zz - 3.f * xx - 3.f * yy);
+                b[13] = SH_C3_4 * x * (4.f * zz - xx - yy);
+                b[14] = SH_C3_5 * z * (xx - yy);
+                b[15] = SH_C3_6 * x * (xx - 3.f * yy);
+            }
+        }
+    }
 }
 
 // d(rgb_c)/d(dir) for one channel; sh = that channel's coefficients accessed as SHC(k).  Needs D and the unit direction x, y, z with

@@ -687,6 +687,28 @@ void das3r_debug_choose_forward(const das3r_switches *sw, int32_t ntiles, int64_
 int das3r_debug_has_invdepth_form(int32_t backward, int32_t kernel);      /* can the (backward != 0: backward) kernel kind run with an inverse-depth map */
 const char *das3r_debug_kernel_name(int32_t backward, int32_t kernel);    /* the kind's name in DAS3R_RENDER / DAS3R_RENDER_BWD and in error messages */
 
+/* ---- the form of the per-Gaussian backward kernel on a caller's own values (test aid) -----------------------------------------------
+ * Additive symbols under ABI 16.  Which of its instantiations preprocess_backward_kernel is launched as is host arithmetic
+ * (csrc/preprocess_choice.h); these calls run exactly those functions.  Host-only: no device needed, no HIP call.  Flags are 0 / 1. */
+typedef struct {
+    int32_t has_sh, has_cov;                        /* SH rows / cov3D given */
+    int32_t M, sh_degree;
+    int32_t shs_aligned16, dL_dshs_aligned16;       /* 16-byte alignment of in->shs and of grads->dL_dshs */
+    int32_t no_sh_stage;                            /* das3r_switches.no_sh_stage */
+    int32_t jac_saved;                              /* das3r_raster_saved.flags bit 2: the forward left the colour's Jacobian planes */
+    int32_t chained, quad_rows;                     /* grads->chain given; quadrant rows from the compositing backward (experiments build) */
+    int32_t depth, aa;                              /* das3r_raster_backward_depth; das3r_raster_saved.flags bit 4 */
+} das3r_preprocess_backward_inputs;
+typedef struct {
+    int32_t has_sh, has_cov, stage_in, stage_out, deg0, chain, depth, jac, aa;   /* the kernel's template arguments, in their order */
+    int32_t base_index;                             /* out: position of the base form in the list of instantiated ones (-1: not instantiated) */
+    int32_t sh_rows_staged;                         /* out: the forward's rule on the same inputs (its SH rows come in through LDS) */
+} das3r_preprocess_form;
+/* returns why a chained call is refused: 0 not refused (or not chained), 1 no SH rows, 2 cov3D given, 3 a staged SH layout, 4 quadrant rows */
+int das3r_debug_choose_preprocess_backward(const das3r_preprocess_backward_inputs *in, das3r_preprocess_form *out);
+/* the raw name das3r_profile_report lists a launch of the form under (reads the nine flags); null: not instantiated */
+const char *das3r_debug_preprocess_backward_name(const das3r_preprocess_form *form);
+
 int das3r_abi_version(void);
 const char *das3r_last_error(void);
 

@@ -327,6 +327,77 @@ def test_backward_chained_through_the_pretransform_matches_the_two_calls(degree,
         assert float(far.double().mean()) <= 1e-3, (k, float(far.double().mean()))
 
 
+@pytest.mark.parametrize("W,H", [(160, 104), (320, 208)], ids=["260-workgroups", "1040-workgroups"])
+def test_backward_chained_through_the_pretransform_matches_the_two_calls_past_256_and_1024_rows(W, H, monkeypatch):
+    """The one-step half of the test above where the chained form's fixed-order row combine (csrc/pretransform_chain.h pose_sums_finish, called
+    with an uncapped grid) has more than 256 rows — 4 x 160 x 104 = 66 560 Gaussians, a thread's second row — and more than 1024 — 4 x 320 x
+    208 = 266 240, the second outer iteration.  Degree 0, unmasked: equal losses, the four tensors, their moments, the confidence map and the
+    SH coefficients bit for bit, Q and T within 1e-6.  And the pose gradients themselves, read from the step's dense rows before anything
+    else is written there: the two forms differ by no more than the sum of their depth-and-magnitude budgets (tests/pose_reference.py: the
+    28 sums' budgets of either grid carried through the pose chain, plus the chain kernel's own roundings on either side), the magnitudes
+    taken from the camera-frame gradients of the two-call run."""
+    from das3r_amd import _lib, fast_step
+    from das3r_amd.train import train_step
+    from tests import pose_reference as PR
+    bg = torch.zeros(3, device="cuda")
+    P = 4 * W * H
+    assert PR.grid_of(P) == {66560: 260, 266240: 1040}[P]
+    seen = {}
+    inner = fast_step._backward_impl
+
+    def recording(*args, **kw):
+        out = inner(*args, **kw)
+        seen["g_means3D"], seen["g_rot"] = out[3], out[7]
+        return out
+
+    monkeypatch.setattr(fast_step, "_backward_impl", recording)
+
+    def run(chained):
+        model, cams, _, opt, _dense = _pair(frames=4, W=W, H=H, seed=23, heldout=False, iterations=4000, fused=True, generic=True)
+        assert model._xyz.shape[0] == P
+        model.fast_step = True
+        model.fuse_backward_chain = chained
+        st = fast_step._state(model)
+        assert st.mask_is_everything and fast_step.available(model, PIPE)
+        uid = cams[0].uid
+        before = dict(xyz=model._xyz.detach().clone(), rot=model._rotation.detach().clone(), q=model.Q[uid].detach().clone())
+        _lib.profile_report()
+        _lib.profile_enable(True)
+        try:
+            rec = tuple(float(v) for v in train_step(model, cams[0], opt, 100, PIPE, bg, fused=True)[:2])
+            torch.cuda.synchronize()
+        finally:
+            _lib.profile_enable(False)
+        kernels = _lib.profile_report()
+        pose_grad = (st.Qg[uid].detach().clone().cpu(), st.Tg[uid].detach().clone().cpu())
+        moments = {k: model.optimizer.state[getattr(model, a)]["exp_avg"].clone() for k, a in NAMES.items() if k in ("xyz", "rotation", "scaling", "opacity")}
+        return rec, {k: getattr(model, a).detach().clone() for k, a in NAMES.items()}, moments, kernels, pose_grad, before
+
+    ra, pa, ma, ka, (gqa, gta), _ = run(True)
+    rb, pb, mb, kb, (gqb, gtb), before = run(False)
+    cam_frame = {k: v.detach().clone() for k, v in seen.items()}   # (of the run just made: the two-call form)
+    assert not any(k.startswith("pretransform_backward_kernel") for k in ka) and any(k.startswith("pretransform_backward_kernel") for k in kb), (list(ka), list(kb))
+    assert ra == rb
+    for k in pa:
+        if k in ("Q", "T"):
+            assert float((pa[k] - pb[k]).abs().max()) <= 1e-6 * float(pb[k].abs().max()), k
+        else:
+            assert torch.equal(pa[k], pb[k]), k
+    for k in ma:
+        assert torch.equal(ma[k], mb[k]), k
+    # the pose gradient: |chained - two calls| <= budget(chained grid) + budget(the Adam form's grid), through the chain rule of the pose
+    assert tuple(cam_frame["g_means3D"].shape) == (P, 3) and tuple(cam_frame["g_rot"].shape) == (P, 4)
+    m = PR.matrices64(before["q"], torch.zeros(3))[0]
+    ref, mag, _ = PR.backward64(before["xyz"], before["rot"], None, None, None, None, m["R"], m["Lq"], cam_frame["g_means3D"], cam_frame["g_rot"], None, None)
+    tol28 = (PR.sums_depth(P) + PR.sums_depth(P, PR.CAP_ADAM)) * PR.U * mag["sums"]
+    own = PR.pose_chain64(before["q"], ref["sums"])[2]
+    both = PR.pose_chain64(before["q"], ref["sums"], g28_tol=tol28)[2]
+    assert float(gqb.abs().max()) > 0 and float(gtb.abs().max()) > 0
+    for name, a, b in (("g_q", gqa, gqb), ("g_t", gta, gtb)):
+        ratio = PR.assert_within(a, b.double(), own[name] + both[name], PR.K, f"chained against two calls, {P} Gaussians, {name}")
+        print(f"[chained against two calls, {P} Gaussians] {name}: worst ratio to the budget {ratio:.3f}; |difference| {float((a - b).abs().max()):.3e} of {float(b.abs().max()):.3e}")
+
+
 def test_packed_sh_tensor_is_kept_current_by_the_optimizer_and_rebuilt_when_it_cannot_be_vouched_for():
     """Round 6: above degree 0 the direct iteration used to concatenate f_dc and the active prefix of f_rest before every render (0.16 ms at
     2.13 M Gaussians) and to split dL/dshs into two copies behind it.  Now the packed [P, K, 3] tensor is built once and FusedAdam writes the

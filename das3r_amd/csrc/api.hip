@@ -238,14 +238,14 @@ struct PolicyOnState {
     }
 };
 ForwardPlan plan_of(const das3r_path_policy_plan *p) {
-    return ForwardPlan{p->local != 0, p->seg != 0, p->seg_bits, p->seg_passes, p->speculate != 0, p->cap, p->decide_fine != 0, p->gen};
+    return ForwardPlan{p->local != 0, p->seg != 0, p->seg == 2, p->seg_bits, p->seg_passes, p->speculate != 0, p->cap, p->decide_fine != 0, p->gen};
 }
 }  // namespace
 extern "C" void das3r_debug_path_policy_fresh(das3r_path_policy_state *state, uint32_t gen) { policy_state_to(Verdict::fresh(gen), Resume(), state); }
 extern "C" void das3r_debug_path_policy_plan(das3r_path_policy_state *state, const das3r_path_policy_inputs *in, das3r_path_policy_plan *out) {
     PolicyOnState on(state);
     const ForwardPlan p = plan_forward(on.v, on.inputs(in));
-    *out = das3r_path_policy_plan{p.local, p.seg, p.seg_bits, p.seg_passes, p.speculate, p.decide_fine, p.gen, p.cap};
+    *out = das3r_path_policy_plan{p.local, p.bucket_local ? 2 : (p.seg ? 1 : 0), p.seg_bits, p.seg_passes, p.speculate, p.decide_fine, p.gen, p.cap};
 }
 extern "C" int das3r_debug_path_policy_count(das3r_path_policy_state *state, const das3r_path_policy_inputs *in, const das3r_path_policy_plan *plan, int64_t I) {
     PolicyOnState on(state);

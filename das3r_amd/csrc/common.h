@@ -217,6 +217,9 @@ struct LocalBin {
     // shapes whose tile lists are skewed (path_policy.h Verdict::fine, decided from the tile ranges themselves: launch_list_skew, learn_skew)
     bool prefer_regions;
     const uint32_t *tile_order;         // with prefer_regions: the tiles, longest list first (tile_lpt_kernel); null: the locality order
+    // segmented emission, local finish (path_policy.h bucket_local_rule): the lists arrive ordered by depth bucket, in index order inside a
+    // bucket, and `keys` holds their partition keys (tile << (dbits + fbits) | bucket << fbits | fraction: segkey.h).  dbits == 0: index order.
+    int dbits, fbits;
 };
 void compute_layout(int P, int64_t I, int W, int H, Layout *L, bool shjac = false);
 
@@ -320,7 +323,8 @@ bool use_tight_rect();  // DAS3R_RECT=upstream bins over upstream's 3-sigma squa
 int launch_binning(int P, int64_t I, int W, int H, const int32_t *radii, char *geom, char *binning, char *img, const Layout &L,
                    bool fused_scan, uint32_t *host_late, uint32_t tag, bool debug, hipStream_t s, uint32_t **dead_keys = nullptr,
                    uint32_t *emit_slot = nullptr /*fused emission: {err, pad, ghist} ring slot, re-armed by the last kernel*/,
-                   uint32_t *seg_host_flag = nullptr, uint32_t seg_flag_value = 0 /*segmented path (L.dbits > 0): mailbox word for a segment too long for LDS*/);
+                   uint32_t *seg_host_flag = nullptr, uint32_t seg_flag_value = 0 /*segmented path (L.dbits > 0): mailbox word for a segment too long for LDS*/,
+                   bool local_finish = false /*L.dbits > 0: no segment sort — tile ranges from the bucketed keys, the compositing kernel finishes the lists*/);
 // segsort.hip: exact (depth bits, index) order inside every (tile, depth bucket) segment of the partitioned list, in place
 int launch_segment_sort(int64_t cap, const uint32_t *n_ptr, const uint32_t *keys_final, int fbits, uint32_t *point_list, uint32_t *slot_list,
                         const uint32_t *depth_key, uint32_t last_g, uint32_t *scratch_keys, uint32_t *host_flag, uint32_t flag_value, bool debug,

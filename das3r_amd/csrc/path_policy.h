@@ -1,5 +1,5 @@
 // path_policy.h — what a forward LEARNS about a shape (P, W, H) and what the next forward of the shape does with it: which binning path it
-// takes (local order, segmented with N partition passes, global radix sort), when a shape backs off to the global sort and for how
+// takes (local order, segmented with N partition passes, segmented emission with the local finish, global radix sort), when a shape backs off to the global sort and for how
 // long, whether it speculates on its capacity, and which compositing kernels its tile lists call for.  Pure host arithmetic on a
 // caller-owned Verdict: no HIP, no switches(), no error reporting — forward.hip (das3r_raster_forward) reads the mailbox words and the
 // switches, calls in here at the places named below, and launches what the plan says.  Compiles with a plain C++17 compiler
@@ -13,6 +13,9 @@ namespace das3r {
 
 constexpr int64_t LOCAL_AVG = 384;            // mean list length up to which the local order wins (measured: 1 M splats at 1080p, mean 320: -4 %)
 constexpr int64_t SEG_AVG = 384;              // mean entries per segment up to which the segmented path is taken
+constexpr int64_t BUCKET_LOCAL_AVG = 256;     // mean list length ABOVE which (up to LOCAL_AVG) the local order takes its lists pre-ordered by depth bucket (bucket_local_rule)
+constexpr int BUCKET_LOCAL_TILES = 1024;      // ... on images of more tiles than this (the lanes / regions shapes keep their paths)
+constexpr int BUCKET_LOCAL_DBITS = 2;         // ... when the tile partition's passes have at least this many free key bits
 constexpr uint32_t CROWDED16 = 23u * 16u;     // of 64 consecutive list entries, those in the tile's fullest quadrant, x 16, from which a shape is "crowded" (learn_skew)
 constexpr uint32_t FINE_PERIOD = 512;         // forwards of a shape between two looks at its tile lists (a power of two: plan_forward)
 constexpr int BACKOFF_MIN = 64, BACKOFF_MAX = 4096;   // forwards on the global sort after a failure: doubled from MIN while failures come soon, up to MAX
@@ -24,6 +27,21 @@ static inline int seg_dbits(int tbits, int passes) { return 8 * (passes < 3 ? pa
 
 // Every decision of plan_forward starts a new GENERATION of the shape (below); 0 names nobody, so the counter skips it when it wraps.
 static inline uint32_t next_gen(uint32_t gen) { return gen + 1u ? gen + 1u : 1u; }
+
+// The fourth binning plan: segmented emission, local finish.  The instances are emitted and partitioned as on the segmented path
+// (key = tile << (dbits + fbits) | depth bucket << fbits | fraction: segkey.h, in the passes the tile ids need anyway), but no
+// segment_sort_kernel follows: the lists reach the compositing kernel ordered by depth bucket, and its prologue finishes a list of 257 - 512
+// entries by ranking every entry inside its (tile, bucket) segment on the fraction bits of the key words (render_common.h
+// local_order_tile) instead of gathering depths and running a sort network.  Every other list length takes the local order's branches,
+// which are exact whatever the arrival order.  From the call's shape alone: onesweep binning, free key bits, more than 1024 tiles, and the
+// learnt mean list in (BUCKET_LOCAL_AVG, LOCAL_AVG] — at or below 256 the rank sort fused with the staging takes nearly every list, and it
+// neither needs nor uses the arrival order (the bucket map of the emission would buy nothing).  forced: DAS3R_BINNING=bucket (4) wherever
+// the key bits are there.
+static inline bool bucket_local_rule(int forced, bool onesweep, int tbits, int tile_passes, int ntiles, int64_t last_I, int radix_left) {
+    if (!onesweep || seg_dbits(tbits, tile_passes) < BUCKET_LOCAL_DBITS) return false;
+    if (forced == 4) return true;
+    return forced == 0 && radix_left == 0 && ntiles > BUCKET_LOCAL_TILES && last_I > BUCKET_LOCAL_AVG * ntiles && last_I <= LOCAL_AVG * ntiles;
+}
 
 // What the last forward of the current shape (P, W, H) taught us.
 struct Verdict {
@@ -58,7 +76,7 @@ struct PolicyInputs {
     int ntiles, tbits, tile_passes;   // Layout
     uint32_t too_long;     // mailbox word: != 0: a forward of the shape with that generation number met a list too long for LDS
     uint32_t want_bits;    // mailbox word: != 0: the segmented path of that generation sorted a segment long enough to want more bucket bits
-    int forced;            // Switches::binning (DAS3R_BINNING=local | radix | seg | seg3: 1 | -1 | 2 | 3): force one (diagnostics, tests); 0: by shape
+    int forced;            // Switches::binning (DAS3R_BINNING=local | radix | seg | seg3 | bucket: 1 | -1 | 2 | 3 | 4): force one (diagnostics, tests); 0: by shape
     bool onesweep;         // use_onesweep(): false only with the classic radix passes of an experiments build, which have no fast path
     int64_t capacity_hint; // das3r_raster_args: -1 = the caller wants the exact size
     bool capacity_exact;   // Switches::capacity_exact (DAS3R_CAPACITY=exact)
@@ -67,6 +85,7 @@ struct PolicyInputs {
 
 struct ForwardPlan {
     bool local, seg;            // local order / segmented path; neither: the global depth sort
+    bool bucket_local;          // (with seg) segmented emission and passes, no segment sort: the compositing kernel finishes the lists (bucket_local_rule)
     int seg_bits, seg_passes;   // depth-bucket bits and partition passes the segmented path would take (applied to the layout when seg)
     bool speculate;             // enqueue the whole forward for `cap` instances before its own count is known
     int64_t cap;                // (with speculate)
@@ -122,7 +141,9 @@ static inline ForwardPlan plan_forward(Verdict &v, const PolicyInputs &in) {
         v.gen = next_gen(v.gen);
     }
     const int forced = in.forced;
-    p.local = in.onesweep && (forced == 1 || (forced == 0 && v.radix_left == 0 && v.last_I <= LOCAL_AVG * in.ntiles));
+    p.bucket_local = bucket_local_rule(forced, in.onesweep, in.tbits, in.tile_passes, in.ntiles, v.last_I, v.radix_left);
+    // (DAS3R_BINNING=bucket where the key has no room for buckets: the local order)
+    p.local = !p.bucket_local && in.onesweep && (forced == 1 || forced == 4 || (forced == 0 && v.radix_left == 0 && v.last_I <= LOCAL_AVG * in.ntiles));
     // Long lists (round 4): the segmented path — no global depth sort; the tile partition's passes carry a depth bucket in the key bits
     // the tile ids leave free, and every (tile, bucket) segment is sorted inside LDS (segkey.h, segsort.hip).  Needs free key bits
     // and segments that stay short on average; a segment that did not fit in LDS sends the shape back to the global sort for a
@@ -132,11 +153,11 @@ static inline ForwardPlan plan_forward(Verdict &v, const PolicyInputs &in) {
     // segment says so (want_bits), and the shape takes ONE MORE partition pass from then on: eight more bucket bits — a band
     // that held 3 % of the scene's instances in 4 of 128 buckets is cut into a thousand (r4, coherent-depth 5 M-splat scene:
     // segment sort 1.08 ms with two passes, see DESIGN.md with three).
-    p.seg_passes = in.tile_passes + ((forced == 3 || (forced == 0 && v.seg_extra)) ? 1 : 0);
+    p.seg_passes = in.tile_passes + ((!p.bucket_local && (forced == 3 || (forced == 0 && v.seg_extra))) ? 1 : 0);
     p.seg_bits = (in.onesweep && p.seg_passes <= 3) ? seg_dbits(in.tbits, p.seg_passes) : 0;
-    p.seg = !p.local && p.seg_bits > 0 && (forced >= 2 || (forced == 0 && v.radix_left == 0 && v.last_I >= 0 &&
-                                                            (v.last_I >> std::min(p.seg_bits, 20)) <= SEG_AVG * in.ntiles));
-    v.last_seg = p.seg;
+    p.seg = p.bucket_local || (!p.local && p.seg_bits > 0 && (forced == 2 || forced == 3 || (forced == 0 && v.radix_left == 0 && v.last_I >= 0 &&
+                                                                                              (v.last_I >> std::min(p.seg_bits, 20)) <= SEG_AVG * in.ntiles)));
+    v.last_seg = p.seg && !p.bucket_local;   // (a list that outgrows LDS under the bucket-ordered local finish backs off as the local order does: no extra pass)
     if (p.local || p.seg) v.clean++;   // (a failure of this forward is reported to the next one: reset there)
     if (forced == 0 && v.radix_left > 0) v.radix_left--;
     // Local order or segments + a previous forward of the same shape: nothing else could be enqueued while the count is on its way, so

@@ -373,6 +373,11 @@ __device__ __forceinline__ void wave_bitonic_sort(double *key, const int lane) {
 //              borrow the staging area.
 //   longer     the same network over global memory (slow; the host is told and goes back to the global sort for the next
 //              forwards); s_gid is not filled.
+// rank += [kj < ki]: the borrow of kj - ki, added with carry — two full-rate instructions (segsort.hip count_below)
+__device__ __forceinline__ void rank_below(uint32_t &rank, const uint32_t kj, const uint32_t ki) {
+    uint32_t tmp;
+    asm("v_sub_co_u32 %1, vcc, %2, %3\n\tv_addc_co_u32 %0, vcc, 0, %0, vcc" : "+v"(rank), "=&v"(tmp) : "v"(kj), "v"(ki) : "vcc");
+}
 struct NoMark {
     __device__ __forceinline__ void operator()(int) const {}
 };
@@ -418,6 +423,105 @@ __device__ __forceinline__ bool local_order_tile(const LocalBin &lb, const uint2
             stage[tid] = null_splat();   // entries n .. 255: initialised (see null_splat)
         }
         return true;   // the compositing loop's barrier publishes the batch
+    }
+    if (lb.dbits > 0 && n <= 2 * TILE_PIX) {   // (uniform) 257 .. 512 entries that arrive ordered by depth bucket (path_policy.h bucket_local_rule)
+        // The key word of an entry is tile | bucket | fraction (segkey.h), bucket and fraction being the top bits of ONE monotone map of the
+        // depth bits: (bucket, fraction, position) orders the list exactly wherever no two entries of a (tile, bucket) segment share a
+        // fraction — equal depths share both and arrive in index order, the partition passes being stable.  So: three coalesced streams, no
+        // depth gather; an entry's rank is the number of (bucket | fraction) << 9 | position words below its own, and only the words of its
+        // own segment need counting (everything in front of the segment is below, everything behind it above).  The segment bounds come from
+        // the places where the bucket changes.  The segment is read eight words at a time from its start rounded down to four (the words in
+        // front of it count as they must) to past its end (behind it: words that are below nobody of the segment).  Only the entries of a TIE
+        // GROUP — neighbours by rank with the same bucket and fraction, about one tile in ten has one — fetch their depth bits and are ranked
+        // again inside the group by (depth bits, position), as segsort.hip does it.
+        uint32_t *s_word = reinterpret_cast<uint32_t *>(stage), *s_byrank = s_word + 2 * TILE_PIX + 8, *s_depth = s_byrank + 2 * TILE_PIX + 8;
+        uint32_t *s_lo = s_depth + 2 * TILE_PIX, *s_hi = s_lo + 128;
+        const uint32_t *kk = lb.keys + range.x;
+        const int wsh = lb.fbits + 9;                                  // a word's bucket sits above fraction and position
+        const uint32_t kmask = (1u << (lb.dbits + lb.fbits)) - 1u;     // (dbits <= 7, fbits <= 16: the word fits 32 bits)
+        uint32_t g[2], slot[2], w[2], rank[2];
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            const int i = u * TILE_PIX + tid;
+            g[u] = slot[u] = 0u;
+            rank[u] = 0xFFFFFFFFu;   // (no entry)
+            w[u] = 0xFFFFFFFFu;
+            if (i < n) {
+                g[u] = min(pl[i], lb.last_g);
+                slot[u] = sl[i];
+                w[u] = ((kk[i] & kmask) << 9) | (uint32_t)i;
+            }
+            s_word[i] = w[u];
+        }
+        if (tid < 8) s_word[2 * TILE_PIX + tid] = 0xFFFFFFFFu;
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            const int i = u * TILE_PIX + tid;
+            if (i < n) {
+                const uint32_t b = w[u] >> wsh, before = i ? s_word[i - 1] >> wsh : 0xFFFFFFFFu;
+                if (before != b) {
+                    s_lo[b] = (uint32_t)i;
+                    if (i) s_hi[before] = (uint32_t)i;
+                }
+                if (i == n - 1) s_hi[b] = (uint32_t)n;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            const int i = u * TILE_PIX + tid;
+            if (i < n) {
+                const uint32_t b = w[u] >> wsh, lo = min(s_lo[b], (uint32_t)n) & ~3u, hi = min(s_hi[b], (uint32_t)n);
+                uint32_t r = lo;
+                for (uint32_t j = lo; j < hi; j += 8u) {
+                    const uint4 o = *reinterpret_cast<const uint4 *>(s_word + j), q = *reinterpret_cast<const uint4 *>(s_word + j + 4u);
+                    rank_below(r, o.x, w[u]);
+                    rank_below(r, o.y, w[u]);
+                    rank_below(r, o.z, w[u]);
+                    rank_below(r, o.w, w[u]);
+                    rank_below(r, q.x, w[u]);
+                    rank_below(r, q.y, w[u]);
+                    rank_below(r, q.z, w[u]);
+                    rank_below(r, q.w, w[u]);
+                }
+                rank[u] = min(r, (uint32_t)(n - 1));   // (a permutation of 0 .. n - 1 whenever the keys are what the passes leave; in bounds whatever they are)
+                s_byrank[rank[u]] = w[u];
+            }
+        }
+        __syncthreads();
+        bool tied[2];
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            const uint32_t r = rank[u], f = w[u] >> 9;   // bucket | fraction
+            tied[u] = r != 0xFFFFFFFFu && ((r > 0u && (s_byrank[r - 1u] >> 9) == f) || (r + 1u < (uint32_t)n && (s_byrank[r + 1u] >> 9) == f));
+            if (tied[u]) s_depth[r] = __float_as_uint(rgbd[(size_t)g[u] * SPLAT_REC].w);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < 2; u++)
+            if (tied[u]) {   // the group [a, b) of ranks around mine, in (depth bits, position) order
+                const uint32_t r = rank[u], f = w[u] >> 9, mine = s_depth[r], at = w[u] & 0x1FFu;
+                uint32_t a = r, b = r + 1u, below = 0u;
+                while (a > 0u && (s_byrank[a - 1u] >> 9) == f) a--;
+                while (b < (uint32_t)n && (s_byrank[b] >> 9) == f) b++;
+                for (uint32_t k = a; k < b; k++) {
+                    const uint32_t dk = s_depth[k], pk = s_byrank[k] & 0x1FFu;
+                    below += (dk < mine || (dk == mine && pk < at)) ? 1u : 0u;
+                }
+                rank[u] = a + below;
+            }
+#pragma unroll
+        for (int u = 0; u < 2; u++)
+            if (rank[u] != 0xFFFFFFFFu) s_gid[rank[u]] = g[u];
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < 2; u++)   // (behind the barrier: nobody waits for these stores to be acknowledged)
+            if (rank[u] != 0xFFFFFFFFu) {
+                pl[rank[u]] = g[u];
+                sl[rank[u]] = slot[u];
+            }
+        return false;
     }
     if (n <= LOCAL_MAX) {
         unsigned long long *s_key = reinterpret_cast<unsigned long long *>(stage);

@@ -317,7 +317,7 @@ int launch_binning_scan_emit(int P, int64_t I, const int32_t *radii, char *geom,
 // I = capacity of the binning buffer; the true instance count is read by the kernels from geom + L.g_count
 int launch_binning(int P, int64_t I, int W, int H, const int32_t *radii, char *geom, char *binning, char *img, const Layout &L,
                    bool fused_scan, uint32_t *host_late, uint32_t tag, bool debug, hipStream_t s, uint32_t **dead_keys, uint32_t *emit_slot,
-                   uint32_t *seg_host_flag, uint32_t seg_flag_value) {
+                   uint32_t *seg_host_flag, uint32_t seg_flag_value, bool local_finish) {
     const uint32_t *n_ptr = (const uint32_t *)(geom + L.g_count);
     (void)W; (void)H;
     uint2 *ranges = (uint2 *)(img + L.pub.ranges);  // zeroed by preprocess_kernel
@@ -345,7 +345,8 @@ int launch_binning(int P, int64_t I, int W, int H, const int32_t *radii, char *g
         int rc1 = launch_onesweep_partition(I, geom, binning, L, &kfinal, debug, s, emit_slot ? emit_slot + 64 : nullptr, emit_slot);
         if (rc1) return rc1;
         if (dead_keys) *dead_keys = kfinal;   // the tile keys are dead once tile_ranges_kernel has run
-        if (L.dbits > 0) {   // segmented path: exact depth order inside every (tile, bucket) segment, in place (segsort.hip)
+        // (local_finish: no segment sort — the tile ranges below come from the bucketed keys, which stay in kfinal for the compositing kernel)
+        if (L.dbits > 0 && !local_finish) {   // segmented path: exact depth order inside every (tile, bucket) segment, in place (segsort.hip)
             uint32_t *other = kfinal == keyA ? keyB : keyA;   // the previous pass's keys: dead, scratch for a segment too long for LDS
             // (round 6: it also writes the tile ranges and hands over the self-check word — no tile_ranges launch behind it; the segmented path
             //  never runs with the fused emission, whose ring slot that kernel re-arms)

@@ -633,13 +633,14 @@ typedef struct {
 typedef struct {
     int32_t P, W, H, ntiles, tbits, tile_passes;   /* tbits: bits of a tile id; tile_passes = (tbits + 7) / 8 */
     uint32_t too_long, want_bits;                  /* the two mailbox words as read before the forward (0: not raised) */
-    int32_t forced;                                /* DAS3R_BINNING: 0 unset, 1 local, -1 radix, 2 seg, 3 seg3 */
+    int32_t forced;                                /* DAS3R_BINNING: 0 unset, 1 local, -1 radix, 2 seg, 3 seg3, 4 bucket */
     int32_t onesweep;                              /* 1 except with DAS3R_SORT=classic of an experiments build */
     int64_t capacity_hint;                         /* das3r_raster_args.capacity_hint */
     int32_t capacity_exact;                        /* DAS3R_CAPACITY=exact */
 } das3r_path_policy_inputs;
 typedef struct {
-    int32_t local, seg, seg_bits, seg_passes;      /* local order / segmented path (neither: global sort); bucket bits and passes of the latter */
+    int32_t local, seg, seg_bits, seg_passes;      /* local order / segmented path (neither: global sort); bucket bits and passes of the latter;
+                                                      seg == 2: segmented emission and passes, the lists finished by the compositing kernel */
     int32_t speculate, decide_fine;
     uint32_t gen;
     int64_t cap;                                   /* with speculate */

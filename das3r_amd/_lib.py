@@ -186,6 +186,8 @@ def load():
     L.das3r_raster_backward_scratch_bytes.argtypes = [C.c_int64]
     L.das3r_raster_check.restype = C.c_int
     L.das3r_raster_check.argtypes = [C.POINTER(RasterSaved), C.c_void_p]
+    L.das3r_raster_count_live_pairs.restype = C.c_int   # measurement aid (ABI 12)
+    L.das3r_raster_count_live_pairs.argtypes = [C.POINTER(RasterArgs), C.POINTER(RasterSaved), C.POINTER(C.c_uint64), C.c_void_p]
     L.das3r_mark_visible.restype = C.c_int
     L.das3r_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.das3r_knn3_workspace_bytes.restype = C.c_size_t

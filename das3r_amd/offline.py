@@ -137,7 +137,7 @@ def render_view_fused(model, view, pose7, background, pipe=PIPE, invdepth=False,
     (rasterizer.composite_features) and the [1, H, W] coverage (rasterizer.alpha_of); return_state: last, the forward's RasterState."""
     import ctypes as C
     from . import _lib
-    from .rasterizer import RasterState, _forward_full, _on_device, _stream, alpha_of, check_forward, composite_features
+    from .rasterizer import _forward, _on_device, _stream, alpha_of, composite_features
     from .render import _settings
     st = model.__dict__.get("_das3r_eval")
     if st is None:
@@ -156,18 +156,16 @@ def render_view_fused(model, view, pose7, background, pipe=PIPE, invdepth=False,
     pre.conf_flat, pre.mask_index = conf.data_ptr(), None
     pre.R, pre.t, pre.Lq = st.mats.data_ptr(), st.mats.data_ptr() + 36, st.mats.data_ptr() + 48
     rs = _settings(view, model, pipe, background, 1.0, dev)
-    res = _forward_full(rs, xyz, st.packed_sh(model), st.e, op, sc, rot, st.e, pre=pre, invdepth=invdepth, no_backward=True,
-                        antialiasing=bool(getattr(pipe, "antialiasing", False)))
-    check_forward(res[6], dev)   # (no backward pass will examine this forward's binning self-check)
-    out = (res[1], res[2], res[7]) if invdepth else (res[1], res[2])
-    if features is not None or alpha or return_state:
-        state = RasterState.of(res, rs)
-        if features is not None:
-            out = out + (composite_features(state, features),)
-        if alpha:
-            out = out + (alpha_of(state),)
-        if return_state:
-            out = out + (state,)
+    state, image, radii, inv = _forward(rs, xyz, st.packed_sh(model), st.e, op, sc, rot, st.e, pre=pre, invdepth=invdepth, no_backward=True,
+                                        antialiasing=bool(getattr(pipe, "antialiasing", False)))
+    state.check()   # (no backward pass will examine this forward's binning self-check)
+    out = (image, radii, inv) if invdepth else (image, radii)
+    if features is not None:
+        out = out + (composite_features(state, features),)
+    if alpha:
+        out = out + (alpha_of(state),)
+    if return_state:
+        out = out + (state,)
     return out
 
 

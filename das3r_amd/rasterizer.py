@@ -5,6 +5,11 @@ Same names, argument meaning, return values and error behaviour as the module DA
 /root/reference/gaussian_renderer/__init__.py:14-17 and calls at :62-80,131-140
 (upstream:diff_gaussian_rasterization/__init__.py): `GaussianRasterizationSettings` (12-field NamedTuple),
 `GaussianRasterizer(nn.Module)` with `forward(...) -> (color[3,H,W], radii[P])` and `markVisible`.
+
+How a call is wired: `_forward` returns a `RasterState` (the record of a finished forward) beside the images, `_backward` and the aux-channel
+calls take it; `RasterState` alone fills the library's das3r_raster_saved.  `_RasterizeGaussians` is the one rasterising autograd function,
+its per-call options an `_Options` argument.  `_forward_full` / `_backward_impl` / `check_forward` / `count_live_pairs` are the same calls
+on plain tuples, for bench.py, the tools and the tests.
 """
 import ctypes as C
 import threading
@@ -50,6 +55,11 @@ def _empty(device):
     return t
 
 
+def _or_empty(device, *tensors):
+    e = _empty(device)
+    return tuple(e if t is None else t for t in tensors)
+
+
 def _prep(t, device, name):
     """contiguous fp32 tensor on `device` (empty tensors mean 'not provided', as upstream)."""
     if t is None:
@@ -71,6 +81,57 @@ def _small(t, device, n, name):
     if t.numel() != n:
         raise ValueError(f"{name} must have {n} elements")
     return t
+
+
+def _dense(grad):
+    """An upstream gradient as the library reads it: fp32, contiguous (None stays None)."""
+    if grad is None:
+        return None
+    grad = grad.contiguous()
+    return grad if grad.dtype == torch.float32 else grad.float()
+
+
+def _chunks(n):
+    """[(first channel, channels)] of the library calls that n aux channels take: DAS3R_AUX_MAX_CHANNELS at a time, one call for none."""
+    return [(c0, min(_lib.AUX_MAX_CHANNELS, n - c0)) for c0 in range(0, max(n, 1), _lib.AUX_MAX_CHANNELS)]
+
+
+def _scratch(nbytes, device, misalign=0, fill=None):
+    """-> (tensor to keep alive, address for the library) of a scratch buffer the library writes before it reads.  Tests hand it one that
+    is only 4-byte aligned (a C caller may) and fill it first."""
+    nbytes, misalign = int(nbytes), int(misalign)
+    t = torch.empty(nbytes + misalign, dtype=torch.uint8, device=device)
+    if fill is not None:
+        t[misalign:][:nbytes // 4 * 4].view(torch.float32).fill_(fill)
+    return t, t.data_ptr() + misalign
+
+
+def _new(device, fill=None):
+    """-> z(*shape): an fp32 tensor on `device` that the library writes in full (fill: tests fill it first all the same)"""
+    if fill is None:
+        return lambda *shape: torch.empty(*shape, dtype=torch.float32, device=device)
+    return lambda *shape: torch.full(shape, float(fill), dtype=torch.float32, device=device)
+
+
+def _grad_set(device, P, M, has_sh, has_cov, chain=None, fill=None):
+    """-> ((g_means2D, g_colors, g_opac, g_means3D, g_cov, g_sh, g_scales, g_rot), das3r_raster_grads pointing at them): only the gradients
+    the call's inputs have, the others None / NULL.  chain (a _lib.Chain the caller keeps alive): the library goes on through the pose
+    pre-transform and the Adam step itself — dL/d(camera-frame means, opacities, scales, rotations) are not produced.  Every tensor is
+    written in full by the library (fill: tests fill them first all the same)."""
+    z = _new(device, fill)
+    g_means2D = z(P, 3)
+    g_opac, g_means3D = (None, None) if chain is not None else (z(P, 1), z(P, 3))
+    g_sh = z(P, M, 3) if has_sh else None
+    g_colors = None if has_sh else z(P, 3)
+    g_scales, g_rot = (None, None) if (has_cov or chain is not None) else (z(P, 3), z(P, 4))
+    g_cov = z(P, 6) if has_cov else None
+    g = _lib.RasterGrads()
+    g.dL_dmeans2D, g.dL_dopacities, g.dL_dmeans3D = g_means2D.data_ptr(), _ptr(g_opac), _ptr(g_means3D)
+    g.dL_dshs, g.dL_dcolors_precomp = _ptr(g_sh), _ptr(g_colors)
+    g.dL_dscales, g.dL_drotations, g.dL_dcov3D = _ptr(g_scales), _ptr(g_rot), _ptr(g_cov)
+    if chain is not None:
+        g.chain = C.pointer(chain)
+    return (g_means2D, g_colors, g_opac, g_means3D, g_cov, g_sh, g_scales, g_rot), g
 
 
 class _Alloc:
@@ -170,190 +231,11 @@ class _Capacity(int):
     flags = 0   # das3r_raster_saved.flags of the forward (which compositing kernels its lists call for)
 
 
-def check_forward(capacity, device):
-    """Wait for the binning self-check of the forward that returned `capacity` (the 7th element of `_forward_full`'s result) and
-    raise RuntimeError if that forward's image is invalid — for callers that render without a backward pass (evaluation);
-    the backward pass does this itself before it launches anything (include/das3r_raster.h: das3r_raster_check)."""
-    if not getattr(capacity, "check_tag", 0):
-        return
-    saved = _lib.RasterSaved()
-    saved.check_word, saved.check_tag = capacity.check_word, capacity.check_tag
-    with _on_device(device):
-        rc = _lib.load().das3r_raster_check(C.byref(saved), _stream(device))
-    _lib.check(rc, "das3r_raster_check")
-
-
-def _forward_impl(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp):
-    """-> (num_rendered, color, radii, geom, binning, img), the binning buffer laid out for exactly num_rendered instances
-    (inspection helper of the tests and tools: `_lib.layout(P, num_rendered, W, H)` then describes the buffers)."""
-    return _forward_full(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, exact=True)[:6]
-
-
-def _forward_full(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, exact=False, pre=None, invdepth=False,
-                  no_backward=False, antialiasing=False):
-    """-> (num_rendered, color, radii, geom, binning, img, capacity); capacity >= num_rendered is what the binning buffer
-    was laid out for (`_lib.layout(P, capacity, W, H)`), == num_rendered when `exact`.  invdepth: the inverse-depth image [1, H, W]
-    (ABI 16, das3r_raster_out.out_invdepth) is appended to the tuple.  no_backward: no backward pass will follow (evaluation) — the
-    library leaves out what only the backward reads (das3r_raster_saved.flags bit 3 on the way in).  antialiasing: upstream's 2D mip filter
-    (flags bit 4 on the way in; the capacity's `flags` carry it back to `_backward_impl`, which then differentiates it)."""
-    lib = _lib.load()
-    device = means3D.device
-    if device.type != "cuda":
-        raise RuntimeError("das3r_amd rasterizer: tensors must live on a HIP device (torch device 'cuda'); "
-                           "there is no CPU path")
-    if means3D.dim() != 2 or means3D.shape[1] != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    P = means3D.shape[0]
-    H, W = int(rs.image_height), int(rs.image_width)
-    M = 0
-    if sh.numel():
-        if sh.dim() != 3 or sh.shape[0] != P or sh.shape[2] != 3:
-            raise RuntimeError("shs must have dimensions (num_points, M, 3)")
-        M = sh.shape[1]
-    if P == 0:   # upstream: zero image, background not applied, empty radii
-        e = torch.empty(0, dtype=torch.uint8, device=device)
-        out = (0, torch.zeros(3, H, W, dtype=torch.float32, device=device), torch.zeros(0, dtype=torch.int32, device=device),
-               e, e, e, 0)
-        return out + (torch.zeros(1, H, W, dtype=torch.float32, device=device),) if invdepth else out
-    # every pixel and every radii entry is written by the kernels: no memset needed
-    color = torch.empty(3, H, W, dtype=torch.float32, device=device)
-    radii = torch.empty(P, dtype=torch.int32, device=device)
-    alloc = _Alloc.get(device)
-    keep = []
-    a = _fill_args(rs, P, M, device, keep)
-    a.capacity_hint = -1 if exact else 0   # 0: the library may lay the binning buffer out with headroom (include/das3r_raster.h)
-    i = _fill_in(means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp, pre)
-    o = _lib.RasterOut()
-    o.out_color, o.radii = color.data_ptr(), radii.data_ptr()
-    inv = torch.empty(1, H, W, dtype=torch.float32, device=device) if invdepth else None
-    o.out_invdepth = _ptr(inv)
-    saved = _lib.RasterSaved()
-    saved.flags = (_lib.NO_BACKWARD_IN_FLAG if no_backward else 0) | (_lib.ANTIALIAS_FLAG if antialiasing else 0)
-    with _on_device(device):
-        rc = lib.das3r_raster_forward(C.byref(a), C.byref(i), C.byref(o), alloc.fns["geom"], alloc.fns["binning"],
-                                      alloc.fns["img"], None, C.byref(saved), _stream(device))
-    _lib.check(rc, "das3r_raster_forward")
-    empty = torch.empty(0, dtype=torch.uint8, device=device)
-    bufs = alloc.take()
-    cap = _Capacity(saved.capacity)
-    cap.check_word, cap.check_tag, cap.flags = saved.check_word, int(saved.check_tag), int(saved.flags)
-    out = (int(rc), color, radii, bufs.get("geom", empty), bufs.get("binning", empty), bufs.get("img", empty), cap)
-    return out + (inv,) if invdepth else out
-
-
-def _backward_impl(rs, num_rendered, grad_out_color, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                   geom, binning, img, capacity=None, _scratch_misalign=0, pre=None, chain=None, grad_invdepth=None, focal=False,
-                   focal_per_splat=False, _fill=None):
-    """grad_invdepth ([1, H, W] or None): also the backward of the forward's inverse-depth image (ABI 16, das3r_raster_backward_depth; the
-    forward must have been made with invdepth=True).  grad_out_color may then be None (zero).
-    focal: the same backward through das3r_raster_backward_focal — the result gains (sums [2], per_splat [P, 2] or None): dL/d(log-focal
-    offsets) of the same loss and, with focal_per_splat, every splat's share of it (include/das3r_raster.h).
-    (_fill: tests fill everything the library is said to write without reading — the scratch, and with focal sums, per_splat and the
-    workspace — with this value before the call.)"""
-    ticket = capacity
-    capacity = int(num_rendered) if capacity is None else int(capacity)
-    lib = _lib.load()
-    device = means3D.device
-    P = means3D.shape[0]
-    M = sh.shape[1] if sh.numel() else 0
-    z = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=device)  # fully written by the library
-    has_sh, has_cov = sh.numel() > 0, cov3Ds_precomp.numel() > 0
-    # chain (a _lib.Chain the caller keeps alive, with `pre`): the library goes on through the pose pre-transform and the Adam step of the four
-    # geometry tensors itself — dL/d(camera-frame means, opacities, scales, rotations) are not produced (returned as None)
-    g_means2D = z(P, 3)
-    g_opac, g_means3D = (None, None) if chain is not None else (z(P, 1), z(P, 3))
-    # only the gradients this call's inputs have (the others are returned as None by the autograd function)
-    g_sh = z(P, M, 3) if has_sh else None
-    g_colors = None if has_sh else z(P, 3)
-    g_scales, g_rot = (None, None) if (has_cov or chain is not None) else (z(P, 3), z(P, 4))
-    g_cov = z(P, 6) if has_cov else None
-    if P == 0:
-        out = (g_means2D, g_colors, g_opac, g_means3D, g_cov, g_sh, g_scales, g_rot)
-        return out + (torch.zeros(2, dtype=torch.float32, device=device), z(0, 2) if focal_per_splat else None) if focal else out
-    # per-instance partial sums, written by the render backward and added per Gaussian (no atomics, no memset by the caller)
-    # (_scratch_misalign: tests hand the library a scratch buffer that is only 4-byte aligned — a C caller may)
-    depth = grad_invdepth is not None
-    nbytes = (lib.das3r_raster_backward_depth_scratch_bytes if depth else lib.das3r_raster_backward_scratch_bytes)(max(capacity, 1))
-    scratch = torch.empty(int(nbytes) + int(_scratch_misalign), dtype=torch.uint8, device=device)
-    keep = []
-    a = _fill_args(rs, P, M, device, keep)
-    i = _fill_in(means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp, pre)
-    saved = _lib.RasterSaved()
-    saved.geom, saved.binning, saved.img = _ptr(geom), _ptr(binning), _ptr(img)
-    saved.num_rendered = int(num_rendered)
-    saved.capacity = capacity
-    if getattr(ticket, "check_tag", 0):   # the forward's binning self-check is examined before the backward launches anything
-        saved.check_word, saved.check_tag = ticket.check_word, ticket.check_tag
-    saved.flags = int(getattr(ticket, "flags", 0))
-    g = _lib.RasterGrads()
-    g.dL_dmeans2D, g.dL_dopacities, g.dL_dmeans3D = g_means2D.data_ptr(), _ptr(g_opac), _ptr(g_means3D)
-    if chain is not None:
-        g.chain = C.pointer(chain)
-    g.dL_dshs = _ptr(g_sh)
-    g.dL_dcolors_precomp = _ptr(g_colors)
-    g.dL_dscales, g.dL_drotations = _ptr(g_scales), _ptr(g_rot)
-    g.dL_dcov3D = _ptr(g_cov)
-    g.scratch = scratch.data_ptr() + int(_scratch_misalign)
-    H, W = int(rs.image_height), int(rs.image_width)
-    dL = grad_out_color.contiguous() if grad_out_color is not None else torch.zeros(3, H, W, dtype=torch.float32, device=device)
-    if dL.dtype != torch.float32:
-        dL = dL.float()
-    dD = None
-    if depth:
-        dD = grad_invdepth.contiguous()
-        if dD.dtype != torch.float32:
-            dD = dD.float()
-    if _fill is not None:
-        scratch[int(_scratch_misalign):][:int(nbytes) // 4 * 4].view(torch.float32).fill_(_fill)
-    if focal:   # (sums, per_splat and the workspace are written in full by the library)
-        sums, per = z(2), (z(P, 2) if focal_per_splat else None)
-        work = torch.empty(int(lib.das3r_raster_focal_workspace_bytes(P)), dtype=torch.uint8, device=device)
-        if _fill is not None:
-            for t in (sums, per, work.view(torch.float32)):
-                if t is not None:
-                    t.fill_(_fill)
-        with _on_device(device):
-            rc = lib.das3r_raster_backward_focal(C.byref(a), C.byref(i), C.byref(saved), C.c_void_p(dL.data_ptr()), _ptr(dD), C.byref(g),
-                                                 C.c_void_p(sums.data_ptr()), _ptr(per), C.c_void_p(work.data_ptr()), _stream(device))
-        _lib.check(rc, "das3r_raster_backward_focal")
-        return g_means2D, g_colors, g_opac, g_means3D, g_cov, g_sh, g_scales, g_rot, sums, per
-    if depth:
-        with _on_device(device):
-            rc = lib.das3r_raster_backward_depth(C.byref(a), C.byref(i), C.byref(saved), C.c_void_p(dL.data_ptr()), C.c_void_p(dD.data_ptr()),
-                                                 C.byref(g), _stream(device))
-        _lib.check(rc, "das3r_raster_backward_depth")
-        return g_means2D, g_colors, g_opac, g_means3D, g_cov, g_sh, g_scales, g_rot
-    with _on_device(device):
-        rc = lib.das3r_raster_backward(C.byref(a), C.byref(i), C.byref(saved), C.c_void_p(dL.data_ptr()), C.byref(g),
-                                       _stream(device))
-    _lib.check(rc, "das3r_raster_backward")
-    return g_means2D, g_colors, g_opac, g_means3D, g_cov, g_sh, g_scales, g_rot
-
-
-def count_live_pairs(rs, P, M, num_rendered, geom, binning, img, capacity):
-    """Measurement aid (include/das3r_raster.h das3r_raster_count_live_pairs): -> (live pairs, (pixel, list position) pairs below the
-    pixels' last contributors) of the forward that produced these buffers (`_forward_full`'s results)."""
-    lib = _lib.load()
-    device = geom.device
-    keep = []
-    a = _fill_args(rs, P, M, device, keep)
-    saved = _lib.RasterSaved()
-    saved.geom, saved.binning, saved.img = _ptr(geom), _ptr(binning), _ptr(img)
-    saved.num_rendered, saved.capacity = int(num_rendered), int(capacity)
-    out = (C.c_uint64 * 2)()
-    lib.das3r_raster_count_live_pairs.restype = C.c_int
-    lib.das3r_raster_count_live_pairs.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]
-    with _on_device(device):
-        rc = lib.das3r_raster_count_live_pairs(C.byref(a), C.byref(saved), out, _stream(device))
-    _lib.check(rc, "das3r_raster_count_live_pairs")
-    return int(out[0]), int(out[1])
-
-
 class RasterState:
-    """What a forward leaves behind, as the aux-channel calls take it (include/das3r_raster.h das3r_raster_aux_forward / _adjoint): the three
-    saved buffers, num_rendered and the capacity (which also carries the forward's self-check ticket and flags), P, W, H and the device.
-    Valid as long as it is kept, for any number of `composite_features` / `feature_adjoint` / `alpha_of` calls, before or after the
-    forward's own backward pass.  `RasterState.of(res, rs)` wraps a `_forward_full` result."""
+    """The record of a finished forward, as the backward pass and the aux-channel calls take it (include/das3r_raster.h das3r_raster_saved):
+    the three saved buffers, num_rendered and the capacity (a `_Capacity` also carries the forward's self-check ticket and flags; a plain int
+    means none), P, W, H and the device.  Valid as long as it is kept, for any number of `composite_features` / `feature_adjoint` /
+    `alpha_of` calls, before or after the forward's own backward pass.  `RasterState.of(res, rs)` wraps a `_forward_full` result."""
     __slots__ = ("geom", "binning", "img", "num_rendered", "capacity", "P", "W", "H", "device")
 
     def __init__(self, geom, binning, img, num_rendered, capacity, P, W, H, device):
@@ -370,16 +252,181 @@ class RasterState:
     def flags(self):
         return int(getattr(self.capacity, "flags", 0))
 
+    def saved(self, buffers=True):
+        """The das3r_raster_saved of this forward: the one place that fills it.  The self-check ticket goes in when the capacity carries
+        one (the library examines it before it launches anything); buffers=False: the ticket alone, all das3r_raster_check reads."""
+        s = _lib.RasterSaved()
+        if getattr(self.capacity, "check_tag", 0):
+            s.check_word, s.check_tag = self.capacity.check_word, self.capacity.check_tag
+        if buffers:
+            s.geom, s.binning, s.img = _ptr(self.geom), _ptr(self.binning), _ptr(self.img)
+            s.num_rendered, s.capacity, s.flags = self.num_rendered, int(self.capacity), self.flags
+        return s
+
     def _c_args(self):
+        """(the minimal das3r_raster_args — P and the image extents — and the saved struct) of the aux-channel calls"""
         a = _lib.RasterArgs()
         a.P, a.image_width, a.image_height = self.P, self.W, self.H
-        saved = _lib.RasterSaved()
-        saved.geom, saved.binning, saved.img = _ptr(self.geom), _ptr(self.binning), _ptr(self.img)
-        saved.num_rendered, saved.capacity = self.num_rendered, int(self.capacity)
-        if getattr(self.capacity, "check_tag", 0):
-            saved.check_word, saved.check_tag = self.capacity.check_word, self.capacity.check_tag
-        saved.flags = self.flags
-        return a, saved
+        return a, self.saved()
+
+    def check(self):
+        """Wait for this forward's binning self-check and raise RuntimeError if its image is invalid — for callers that render without a
+        backward pass (evaluation); the backward pass does this itself before it launches anything (include/das3r_raster.h:
+        das3r_raster_check)."""
+        if not getattr(self.capacity, "check_tag", 0):
+            return
+        with _on_device(self.device):
+            rc = _lib.load().das3r_raster_check(C.byref(self.saved(buffers=False)), _stream(self.device))
+        _lib.check(rc, "das3r_raster_check")
+
+
+def _forward(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, exact=False, pre=None, invdepth=False,
+             no_backward=False, antialiasing=False):
+    """-> (state, color, radii, inverse-depth image or None); the keywords are `_forward_full`'s."""
+    lib = _lib.load()
+    device = means3D.device
+    if device.type != "cuda":
+        raise RuntimeError("das3r_amd rasterizer: tensors must live on a HIP device (torch device 'cuda'); "
+                           "there is no CPU path")
+    if means3D.dim() != 2 or means3D.shape[1] != 3:
+        raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    P = means3D.shape[0]
+    H, W = int(rs.image_height), int(rs.image_width)
+    M = 0
+    if sh.numel():
+        if sh.dim() != 3 or sh.shape[0] != P or sh.shape[2] != 3:
+            raise RuntimeError("shs must have dimensions (num_points, M, 3)")
+        M = sh.shape[1]
+    if P == 0:   # upstream: zero image, background not applied, empty radii
+        e = torch.empty(0, dtype=torch.uint8, device=device)
+        return (RasterState(e, e, e, 0, 0, 0, W, H, device), torch.zeros(3, H, W, dtype=torch.float32, device=device),
+                torch.zeros(0, dtype=torch.int32, device=device), torch.zeros(1, H, W, dtype=torch.float32, device=device) if invdepth else None)
+    # every pixel and every radii entry is written by the kernels: no memset needed
+    color = torch.empty(3, H, W, dtype=torch.float32, device=device)
+    radii = torch.empty(P, dtype=torch.int32, device=device)
+    alloc = _Alloc.get(device)
+    keep = []
+    a = _fill_args(rs, P, M, device, keep)
+    a.capacity_hint = -1 if exact else 0   # 0: the library may lay the binning buffer out with headroom (include/das3r_raster.h)
+    i = _fill_in(means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp, pre)
+    o = _lib.RasterOut()
+    o.out_color, o.radii = color.data_ptr(), radii.data_ptr()
+    inv = torch.empty(1, H, W, dtype=torch.float32, device=device) if invdepth else None
+    o.out_invdepth = _ptr(inv)
+    saved = _lib.RasterSaved()   # (the forward's own in / out struct: only the flags go in)
+    saved.flags = (_lib.NO_BACKWARD_IN_FLAG if no_backward else 0) | (_lib.ANTIALIAS_FLAG if antialiasing else 0)
+    with _on_device(device):
+        rc = lib.das3r_raster_forward(C.byref(a), C.byref(i), C.byref(o), alloc.fns["geom"], alloc.fns["binning"],
+                                      alloc.fns["img"], None, C.byref(saved), _stream(device))
+    _lib.check(rc, "das3r_raster_forward")
+    empty = torch.empty(0, dtype=torch.uint8, device=device)
+    bufs = alloc.take()
+    cap = _Capacity(saved.capacity)
+    cap.check_word, cap.check_tag, cap.flags = saved.check_word, int(saved.check_tag), int(saved.flags)
+    return RasterState(bufs.get("geom", empty), bufs.get("binning", empty), bufs.get("img", empty), rc, cap, P, W, H, device), color, radii, inv
+
+
+def _backward(state, rs, grad_out_color, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, _scratch_misalign=0,
+              pre=None, chain=None, grad_invdepth=None, focal=False, focal_per_splat=False, _fill=None):
+    """The backward of the forward that left `state`; arguments and result as `_backward_impl`'s.  One library call: das3r_raster_backward,
+    _backward_depth when an inverse-depth gradient arrives, _backward_focal when the focal sums are wanted."""
+    lib = _lib.load()
+    device, P = means3D.device, means3D.shape[0]
+    M = sh.shape[1] if sh.numel() else 0
+    grads, g = _grad_set(device, P, M, sh.numel() > 0, cov3Ds_precomp.numel() > 0, chain)
+    z = _new(device)
+    if P == 0:
+        return grads + (torch.zeros(2, dtype=torch.float32, device=device), z(0, 2) if focal_per_splat else None) if focal else grads
+    # per-instance partial sums, written by the render backward and added per Gaussian (no atomics, no memset by the caller)
+    depth = grad_invdepth is not None
+    nbytes = (lib.das3r_raster_backward_depth_scratch_bytes if depth else lib.das3r_raster_backward_scratch_bytes)(max(int(state.capacity), 1))
+    scratch, g.scratch = _scratch(nbytes, device, _scratch_misalign, _fill)
+    keep = []
+    a = _fill_args(rs, P, M, device, keep)
+    i = _fill_in(means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp, pre)
+    saved = state.saved()
+    dL = _dense(grad_out_color) if grad_out_color is not None else torch.zeros(3, state.H, state.W, dtype=torch.float32, device=device)
+    dD = _dense(grad_invdepth)
+    # the entry and what it takes besides (args, in, saved, dL_dpix, ..., grads, ..., stream)
+    name, before, after, more = "das3r_raster_backward", (), (), ()
+    if depth:
+        name, before = "das3r_raster_backward_depth", (_ptr(dD),)
+    if focal:   # (sums, per_splat and the workspace are written in full by the library; tests fill them first)
+        sums, per = z(2), (z(P, 2) if focal_per_splat else None)
+        work = torch.empty(int(lib.das3r_raster_focal_workspace_bytes(P)), dtype=torch.uint8, device=device)
+        if _fill is not None:
+            for t in (sums, per, work.view(torch.float32)):
+                if t is not None:
+                    t.fill_(_fill)
+        name, before, after, more = "das3r_raster_backward_focal", (_ptr(dD),), (C.c_void_p(sums.data_ptr()), _ptr(per), C.c_void_p(work.data_ptr())), (sums, per)
+    with _on_device(device):
+        rc = getattr(lib, name)(C.byref(a), C.byref(i), C.byref(saved), C.c_void_p(dL.data_ptr()), *before, C.byref(g), *after, _stream(device))
+    _lib.check(rc, name)
+    return grads + more
+
+
+# ---- the same calls on plain tuples: what bench.py, the tools and most tests use
+
+
+def check_forward(capacity, device):
+    """Wait for the binning self-check of the forward that returned `capacity` (the 7th element of `_forward_full`'s result) and
+    raise RuntimeError if that forward's image is invalid (RasterState.check)."""
+    RasterState(None, None, None, 0, capacity, 0, 0, 0, device).check()
+
+
+def _forward_impl(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp):
+    """-> (num_rendered, color, radii, geom, binning, img), the binning buffer laid out for exactly num_rendered instances
+    (inspection helper of the tests and tools: `_lib.layout(P, num_rendered, W, H)` then describes the buffers)."""
+    return _forward_full(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, exact=True)[:6]
+
+
+def _forward_full(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, exact=False, pre=None, invdepth=False,
+                  no_backward=False, antialiasing=False):
+    """-> (num_rendered, color, radii, geom, binning, img, capacity); capacity >= num_rendered is what the binning buffer
+    was laid out for (`_lib.layout(P, capacity, W, H)`), == num_rendered when `exact`.  invdepth: the inverse-depth image [1, H, W]
+    (ABI 16, das3r_raster_out.out_invdepth) is appended to the tuple.  no_backward: no backward pass will follow (evaluation) — the
+    library leaves out what only the backward reads (das3r_raster_saved.flags bit 3 on the way in).  antialiasing: upstream's 2D mip filter
+    (flags bit 4 on the way in; the capacity's `flags` carry it back to `_backward_impl`, which then differentiates it)."""
+    st, color, radii, inv = _forward(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, exact=exact, pre=pre,
+                                     invdepth=invdepth, no_backward=no_backward, antialiasing=antialiasing)
+    out = (st.num_rendered, color, radii, st.geom, st.binning, st.img, st.capacity)
+    return out + (inv,) if invdepth else out
+
+
+def _backward_impl(rs, num_rendered, grad_out_color, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                   geom, binning, img, capacity=None, _scratch_misalign=0, pre=None, chain=None, grad_invdepth=None, focal=False,
+                   focal_per_splat=False, _fill=None):
+    """-> (g_means2D, g_colors, g_opac, g_means3D, g_cov, g_sh, g_scales, g_rot), None for what the inputs do not have.
+    capacity: the forward's (None: num_rendered, no self-check ticket, flags 0).
+    grad_invdepth ([1, H, W] or None): also the backward of the forward's inverse-depth image (ABI 16, das3r_raster_backward_depth; the
+    forward must have been made with invdepth=True).  grad_out_color may then be None (zero).
+    focal: the same backward through das3r_raster_backward_focal — the result gains (sums [2], per_splat [P, 2] or None): dL/d(log-focal
+    offsets) of the same loss and, with focal_per_splat, every splat's share of it (include/das3r_raster.h).
+    chain (a _lib.Chain the caller keeps alive, with `pre`): see `_grad_set`.
+    (_scratch_misalign, _fill: tests hand the library a scratch buffer that is only 4-byte aligned, and fill everything it is said to
+    write without reading — the scratch, and with focal sums, per_splat and the workspace — with this value before the call.)"""
+    state = RasterState(geom, binning, img, num_rendered, int(num_rendered) if capacity is None else capacity, means3D.shape[0],
+                        rs.image_width, rs.image_height, means3D.device)
+    return _backward(state, rs, grad_out_color, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                     _scratch_misalign=_scratch_misalign, pre=pre, chain=chain, grad_invdepth=grad_invdepth, focal=focal,
+                     focal_per_splat=focal_per_splat, _fill=_fill)
+
+
+def count_live_pairs(rs, P, M, num_rendered, geom, binning, img, capacity):
+    """Measurement aid (include/das3r_raster.h das3r_raster_count_live_pairs): -> (live pairs, (pixel, list position) pairs below the
+    pixels' last contributors) of the forward that produced these buffers (`_forward_full`'s results)."""
+    device = geom.device
+    keep = []
+    a = _fill_args(rs, P, M, device, keep)
+    saved = RasterState(geom, binning, img, num_rendered, int(capacity), P, rs.image_width, rs.image_height, device).saved()   # (no ticket)
+    out = (C.c_uint64 * 2)()
+    with _on_device(device):
+        rc = _lib.load().das3r_raster_count_live_pairs(C.byref(a), C.byref(saved), out, _stream(device))
+    _lib.check(rc, "das3r_raster_count_live_pairs")
+    return int(out[0]), int(out[1])
+
+
+# ---- aux channels over a forward's lists
 
 
 def _check_state(state):
@@ -455,11 +502,8 @@ class _CompositeFeatures(torch.autograd.Function):
 
 
 def _composite(state, features):
-    n = features.shape[1]
-    if n <= _lib.AUX_MAX_CHANNELS:
-        return _aux_forward(state, features)
-    return torch.cat([_aux_forward(state, features[:, c0:c0 + _lib.AUX_MAX_CHANNELS].contiguous())
-                      for c0 in range(0, n, _lib.AUX_MAX_CHANNELS)], 0)
+    parts = [_aux_forward(state, features[:, c0:c0 + n].contiguous()) for c0, n in _chunks(features.shape[1])]
+    return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
 
 
 def composite_features(state, features, geometry=None):
@@ -504,13 +548,12 @@ def feature_adjoint(state, grad_image, out=None, accumulate=False):
     grad_image = grad_image.detach().contiguous()
     if n <= _lib.AUX_MAX_CHANNELS:
         return _aux_adjoint(state, grad_image, out, accumulate)
-    for c0 in range(0, n, _lib.AUX_MAX_CHANNELS):
-        part = _aux_adjoint(state, grad_image[c0:c0 + _lib.AUX_MAX_CHANNELS],
-                            torch.empty(state.P, min(_lib.AUX_MAX_CHANNELS, n - c0), dtype=torch.float32, device=state.device), False)
+    for c0, c in _chunks(n):   # (a column block of `out` is not dense: each call writes a tensor of its own)
+        part = _aux_adjoint(state, grad_image[c0:c0 + c], torch.empty(state.P, c, dtype=torch.float32, device=state.device), False)
         if accumulate:
-            out[:, c0:c0 + part.shape[1]] += part
+            out[:, c0:c0 + c] += part
         else:
-            out[:, c0:c0 + part.shape[1]] = part
+            out[:, c0:c0 + c] = part
     return out
 
 
@@ -583,28 +626,20 @@ def _aux_backward_impl(state, rs, features, grad_image, grad_alpha, want_feature
     device, P = state.device, state.P
     M = sh.shape[1] if sh.numel() else 0
     C_ = 0 if features is None else int(features.shape[1])
-    z = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=device) if _fill is None else torch.full(shape, float(_fill), dtype=torch.float32, device=device)
-    has_sh, has_cov = sh.numel() > 0, cov3Ds_precomp.numel() > 0
-    g_means2D, g_opac, g_means3D = z(P, 3), z(P, 1), z(P, 3)
-    g_col = z(P, M, 3) if has_sh else z(P, 3)   # (identically zero for this loss; the per-Gaussian backward writes it all the same)
-    g_scales, g_rot = (None, None) if has_cov else (z(P, 3), z(P, 4))
-    g_cov = z(P, 6) if has_cov else None
-    g_feat = z(P, C_) if (want_features and C_ > 0) else None
+    # (the colour gradient is identically zero for this loss; the per-Gaussian backward writes it all the same)
+    (g_means2D, _g_colors, g_opac, g_means3D, g_cov, _g_sh, g_scales, g_rot), g = _grad_set(device, P, M, sh.numel() > 0, cov3Ds_precomp.numel() > 0,
+                                                                                           fill=_fill)
+    g_feat = None
+    if want_features and C_ > 0:
+        g_feat = _new(device, _fill)(P, C_)
     if P == 0:
         return g_means2D, g_opac, g_means3D, g_cov, g_scales, g_rot, g_feat
-    nbytes = int(lib.das3r_raster_aux_backward_scratch_bytes(max(int(state.capacity), 1), C_))
-    scratch = torch.empty(nbytes + int(_scratch_misalign), dtype=torch.uint8, device=device)   # rows written before they are read
-    if _fill is not None:
-        scratch[int(_scratch_misalign):][:nbytes // 4 * 4].view(torch.float32).fill_(_fill)
+    nbytes = lib.das3r_raster_aux_backward_scratch_bytes(max(int(state.capacity), 1), C_)
+    scratch, g.scratch = _scratch(nbytes, device, _scratch_misalign, _fill)   # rows written before they are read
     keep = []
     a = _fill_args(rs, P, M, device, keep)
     i = _fill_in(means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp)
-    _, saved = state._c_args()
-    g = _lib.RasterGrads()
-    g.dL_dmeans2D, g.dL_dopacities, g.dL_dmeans3D = g_means2D.data_ptr(), g_opac.data_ptr(), g_means3D.data_ptr()
-    g.dL_dshs, g.dL_dcolors_precomp = (g_col.data_ptr(), None) if has_sh else (None, g_col.data_ptr())
-    g.dL_dscales, g.dL_drotations, g.dL_dcov3D = _ptr(g_scales), _ptr(g_rot), _ptr(g_cov)
-    g.scratch = scratch.data_ptr() + int(_scratch_misalign)
+    saved = state.saved()
     with _on_device(device):
         rc = lib.das3r_raster_aux_backward(C.byref(a), C.byref(i), C.byref(saved), C_, _ptr(features), _ptr(grad_image), _ptr(grad_alpha),
                                            _ptr(g_feat), C.byref(g), _stream(device))
@@ -632,29 +667,21 @@ class _AuxWithGeometry(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_image, grad_alpha):
-        none = (None,) * 12
         if grad_image is None and grad_alpha is None:
-            return none
+            return (None,) * 12
         saved = ctx.saved_tensors
         means3D, opacities, scales, rotations, cov3Ds_precomp, sh, colors_precomp = saved[:7]
-        feat = saved[7] if ctx.has_features else None
-        state = ctx.state
-        dense = lambda t: None if t is None else (t if t.dtype == torch.float32 else t.float()).contiguous()
-        grad_image, grad_alpha = dense(grad_image), dense(grad_alpha)
-        if grad_image is None:
-            feat = None
+        grad_image, grad_alpha = _dense(grad_image), _dense(grad_alpha)
+        feat = saved[7] if ctx.has_features and grad_image is not None else None
         want_feat = feat is not None and ctx.needs_input_grad[0]
-        inputs = (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
-        n = 0 if feat is None else feat.shape[1]
-        if n <= _lib.AUX_MAX_CHANNELS:
-            out = _aux_backward_impl(state, ctx.raster_settings, feat, grad_image, grad_alpha, want_feat, *inputs)
-        else:   # wider tensors: a call per 8 channels, the coverage term with the first; every gradient is linear in the loss terms
-            out = None
-            for c0 in range(0, n, _lib.AUX_MAX_CHANNELS):
-                part = _aux_backward_impl(state, ctx.raster_settings, feat[:, c0:c0 + _lib.AUX_MAX_CHANNELS].contiguous(),
-                                          grad_image[c0:c0 + _lib.AUX_MAX_CHANNELS], grad_alpha if c0 == 0 else None, want_feat, *inputs)
-                out = part if out is None else tuple(None if x is None else (torch.cat((x, y), 1) if k == 6 else x + y)
-                                                     for k, (x, y) in enumerate(zip(out, part)))
+        out = None
+        # a call per 8 channels, the coverage term with the first; every gradient is linear in the loss terms
+        for c0, n in _chunks(0 if feat is None else feat.shape[1]):
+            part = _aux_backward_impl(ctx.state, ctx.raster_settings, None if feat is None else feat[:, c0:c0 + n].contiguous(),
+                                      None if feat is None else grad_image[c0:c0 + n], grad_alpha if c0 == 0 else None, want_feat,
+                                      means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
+            out = part if out is None else tuple(None if x is None else (torch.cat((x, y), 1) if k == 6 else x + y)
+                                                 for k, (x, y) in enumerate(zip(out, part)))
         g_means2D, g_opac, g_means3D, g_cov, g_scales, g_rot, g_feat = out
         return (g_feat, g_means3D, g_means2D, g_opac, g_scales if scales.numel() else None, g_rot if rotations.numel() else None,
                 g_cov if cov3Ds_precomp.numel() else None, None, None, None, None, None)
@@ -667,112 +694,24 @@ def _aux_with_geometry(state, features, geometry, want_alpha):
         _check_features(state, features)
     elif not want_alpha:
         raise ValueError("nothing to render: neither features nor the coverage image was asked for")
-    e = _empty(state.device)
-    opt = lambda t: e if t is None else t
-    return _AuxWithGeometry.apply(features, geometry.means3D, geometry.means2D, geometry.opacities, opt(geometry.scales), opt(geometry.rotations),
-                                  opt(geometry.cov3D_precomp), opt(geometry.shs), opt(geometry.colors_precomp), geometry.raster_settings, state,
-                                  bool(want_alpha))
+    return _AuxWithGeometry.apply(features, geometry.means3D, geometry.means2D, geometry.opacities,
+                                  *_or_empty(state.device, geometry.scales, geometry.rotations, geometry.cov3D_precomp, geometry.shs,
+                                             geometry.colors_precomp), geometry.raster_settings, state, bool(want_alpha))
 
 
-def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, antialiasing=False,
-                        log_focal=None):
-    """log_focal ([2] tensor or None): see GaussianRasterizer.forward's docstring."""
-    if log_focal is not None:
-        return _apply(_RasterizeGaussiansFocal, _check_log_focal(log_focal, means3D.device), False, means3D, means2D, sh, colors_precomp, opacities,
-                      scales, rotations, cov3Ds_precomp, raster_settings, antialiasing=antialiasing)
-    return _apply(_RasterizeGaussians, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                  antialiasing=antialiasing)
+# ---- the rasterising autograd function and the module
 
 
-_last = threading.local()
+class _Options:
+    """What one application of _RasterizeGaussians is asked for besides upstream's nine inputs — invdepth: the inverse-depth image as a third
+    output; antialiasing: upstream's 2D mip filter (the settings tuple keeps upstream's twelve fields); no_backward: no backward pass can
+    follow (evaluation); want_state: the caller keeps the forward's state beyond the call — and, written by the function's forward, `state`:
+    the RasterState it left."""
+    __slots__ = ("invdepth", "antialiasing", "no_backward", "want_state", "state")
 
-
-def _apply(fn, *args, antialiasing=False):
-    """fn.apply(*args), telling its forward whether a backward pass can follow: not under torch.no_grad, nor when no input takes a
-    gradient (inside the autograd function's forward grad mode is always off, and needs_input_grad ignores it) — and whether it is an
-    antialiased forward (the settings tuple keeps upstream's twelve fields)."""
-    _last.no_backward = not (torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in args))
-    _last.antialiasing = bool(antialiasing)
-    try:
-        return fn.apply(*args)
-    finally:
-        _last.no_backward = False
-        _last.antialiasing = False
-
-
-class _RasterizeGaussians(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
-        return _RasterizeGaussians._forward(ctx, False, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
-
-    @staticmethod
-    def _forward(ctx, invdepth, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
-        device = means3D.device
-        means3D = _prep(means3D, device, "means3D")
-        sh = _prep(sh, device, "shs")
-        colors_precomp = _prep(colors_precomp, device, "colors_precomp")
-        opacities = _prep(opacities, device, "opacities")
-        scales = _prep(scales, device, "scales")
-        rotations = _prep(rotations, device, "rotations")
-        cov3Ds_precomp = _prep(cov3Ds_precomp, device, "cov3D_precomp")
-        args = (raster_settings, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
-        no_backward = getattr(_last, "no_backward", False)
-        aa = getattr(_last, "antialiasing", False)   # (the backward learns it from the forward's flags: ctx.capacity)
-        if raster_settings.debug:
-            cpu_args = cpu_deep_copy_tuple(args)  # copy them before they can be corrupted
-            try:
-                res = _forward_full(*args, invdepth=invdepth, no_backward=no_backward, antialiasing=aa)
-            except Exception as ex:
-                torch.save(cpu_args, "snapshot_fw.dump")
-                print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
-                raise ex
-        else:
-            res = _forward_full(*args, invdepth=invdepth, no_backward=no_backward, antialiasing=aa)
-        num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer, capacity = res[:7]
-        ctx.raster_settings = raster_settings
-        ctx.num_rendered = num_rendered
-        ctx.capacity = capacity
-        _last.capacity = capacity   # GaussianRasterizer.forward: a render that no backward pass will follow checks itself
-        if getattr(_last, "want_state", False):   # (features= / return_alpha= / keep_state: the aux-channel calls work on this forward's lists)
-            _last.state = RasterState.of(res, raster_settings)
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, opacities, geomBuffer,
-                              binningBuffer, imgBuffer)
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)   # no zero-filled 'gradient' for radii on every backward (a fill kernel per step)
-        return (color, radii, res[7]) if invdepth else (color, radii)
-
-    @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii):
-        return _RasterizeGaussians._backward(ctx, grad_out_color, None)
-
-    @staticmethod
-    def _backward(ctx, grad_out_color, grad_invdepth, focal=False):
-        """focal: through das3r_raster_backward_focal; the tuple then ends with dL/d(log-focal offsets) [2] (or None)."""
-        rs = ctx.raster_settings
-        if grad_out_color is None and grad_invdepth is None:   # (grads are not materialised) nothing flows back
-            return (None,) * (10 if focal else 9)
-        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, opacities, geomBuffer, binningBuffer,
-         imgBuffer) = ctx.saved_tensors
-        args = (rs, ctx.num_rendered, grad_out_color, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                geomBuffer, binningBuffer, imgBuffer, ctx.capacity)
-        kw = {} if grad_invdepth is None else {"grad_invdepth": grad_invdepth}   # (None: today's das3r_raster_backward call)
-        if focal:
-            kw["focal"] = True
-        if rs.debug:
-            cpu_args = cpu_deep_copy_tuple(args)
-            try:
-                out = _backward_impl(*args, **kw)
-            except Exception as ex:
-                torch.save(cpu_args, "snapshot_bw.dump")
-                print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
-                raise ex
-        else:
-            out = _backward_impl(*args, **kw)
-        g_means2D, g_colors, g_opac, g_means3D, g_cov, g_sh, g_scales, g_rot = out[:8]
-        tail = (out[8],) if focal else ()
-        return (g_means3D, g_means2D, g_sh if sh.numel() else None, g_colors if colors_precomp.numel() else None, g_opac,
-                g_scales if scales.numel() else None, g_rot if rotations.numel() else None,
-                g_cov if cov3Ds_precomp.numel() else None, None) + tail
+    def __init__(self, invdepth=False, antialiasing=False, no_backward=False, want_state=False):
+        self.invdepth, self.antialiasing, self.no_backward, self.want_state = bool(invdepth), bool(antialiasing), bool(no_backward), bool(want_state)
+        self.state = None
 
 
 def _check_log_focal(log_focal, device):
@@ -783,34 +722,94 @@ def _check_log_focal(log_focal, device):
     return log_focal
 
 
-class _RasterizeGaussiansFocal(torch.autograd.Function):
-    """_RasterizeGaussians / _RasterizeGaussiansInvDepth with one more input, log_focal [2]: its value is not read (like the dummy means2D — the
-    caller built raster_settings from the same field of view); when it takes a gradient the backward is das3r_raster_backward_focal and
-    returns dL/d(log-focal offsets) for it, otherwise today's calls."""
+def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, antialiasing=False,
+                        log_focal=None, options=None):
+    """-> (color, radii), or (color, radii, invdepth) when options.invdepth.  log_focal ([2] tensor or None): see GaussianRasterizer.forward's
+    docstring.  options: an _Options with invdepth / want_state set; antialiasing and no_backward are set here, its `state` by the forward.
+    no_backward: under torch.no_grad, or when no input takes a gradient (inside the autograd function's forward grad mode is always off,
+    and needs_input_grad ignores it)."""
+    if options is None:
+        options = _Options()
+    if log_focal is not None:
+        _check_log_focal(log_focal, means3D.device)
+    options.antialiasing = bool(antialiasing)
+    options.no_backward = not (torch.is_grad_enabled() and any(
+        torch.is_tensor(t) and t.requires_grad for t in (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, log_focal)))
+    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, options,
+                                     log_focal)
+
+
+class _RasterizeGaussians(torch.autograd.Function):
+    """The rasterising function: upstream's nine inputs, then optionally an _Options (None: the defaults — upstream's own nine-argument
+    apply) and log_focal ([2] tensor or None: its value is not read, like the dummy means2D — the caller built raster_settings from the same
+    field of view; when it takes a gradient the backward is das3r_raster_backward_focal and returns dL/d(log-focal offsets) for it).
+    -> (color, radii) or, with options.invdepth, (color, radii, invdepth): a backward that receives no gradient for the inverse depth is the
+    das3r_raster_backward call, otherwise das3r_raster_backward_depth takes both."""
     @staticmethod
-    def forward(ctx, log_focal, invdepth, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
-        ctx.focal_shape = log_focal.shape
-        return _RasterizeGaussians._forward(ctx, bool(invdepth), means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, options=None,
+                log_focal=None):
+        if options is None:
+            options = _Options()
+        device = means3D.device
+        means3D = _prep(means3D, device, "means3D")
+        sh = _prep(sh, device, "shs")
+        colors_precomp = _prep(colors_precomp, device, "colors_precomp")
+        opacities = _prep(opacities, device, "opacities")
+        scales = _prep(scales, device, "scales")
+        rotations = _prep(rotations, device, "rotations")
+        cov3Ds_precomp = _prep(cov3Ds_precomp, device, "cov3D_precomp")
+        args = (raster_settings, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
+        cpu_args = cpu_deep_copy_tuple(args) if raster_settings.debug else None   # copy them before they can be corrupted
+        try:   # (the backward learns of the antialiasing from the forward's flags: the state's capacity)
+            state, color, radii, invdepth = _forward(*args, invdepth=options.invdepth, no_backward=options.no_backward,
+                                                     antialiasing=options.antialiasing)
+        except Exception:
+            if cpu_args is not None:
+                torch.save(cpu_args, "snapshot_fw.dump")
+                print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
+            raise
+        options.state = state   # (GaussianRasterizer.forward: a render that no backward pass will follow checks itself; the aux-channel calls)
+        ctx.raster_settings, ctx.num_rendered, ctx.capacity = raster_settings, state.num_rendered, state.capacity
+        ctx.focal_shape = None if log_focal is None else log_focal.shape
+        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, opacities, state.geom, state.binning,
+                              state.img)
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)   # no zero-filled 'gradient' for radii on every backward (a fill kernel per step)
+        return (color, radii, invdepth) if options.invdepth else (color, radii)
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, grad_invdepth=None):
-        if not ctx.needs_input_grad[0]:
-            return (None, None) + _RasterizeGaussians._backward(ctx, grad_out_color, grad_invdepth)
-        out = _RasterizeGaussians._backward(ctx, grad_out_color, grad_invdepth, focal=True)
-        g_focal = out[9]
-        return (None if g_focal is None else g_focal.reshape(ctx.focal_shape), None) + out[:9]
+        rs = ctx.raster_settings
+        n = len(ctx.needs_input_grad)   # (as many as the inputs actually given: 9, 10 or 11)
+        if grad_out_color is None and grad_invdepth is None:   # (grads are not materialised) nothing flows back
+            return (None,) * n
+        focal = n > 10 and ctx.needs_input_grad[10]
+        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, opacities, geomBuffer, binningBuffer,
+         imgBuffer) = ctx.saved_tensors
+        state = RasterState(geomBuffer, binningBuffer, imgBuffer, ctx.num_rendered, ctx.capacity, means3D.shape[0], rs.image_width,
+                            rs.image_height, means3D.device)
+        inputs = (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
+        cpu_args = None
+        if rs.debug:
+            cpu_args = cpu_deep_copy_tuple((rs, ctx.num_rendered, grad_out_color) + inputs + (geomBuffer, binningBuffer, imgBuffer, ctx.capacity))
+        try:
+            out = _backward(state, rs, grad_out_color, *inputs, grad_invdepth=grad_invdepth, focal=focal)
+        except Exception:
+            if cpu_args is not None:
+                torch.save(cpu_args, "snapshot_bw.dump")
+                print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+            raise
+        g_means2D, g_colors, g_opac, g_means3D, g_cov, g_sh, g_scales, g_rot = out[:8]
+        g_focal = out[8].reshape(ctx.focal_shape) if focal else None
+        return (g_means3D, g_means2D, g_sh if sh.numel() else None, g_colors if colors_precomp.numel() else None, g_opac,
+                g_scales if scales.numel() else None, g_rot if rotations.numel() else None,
+                g_cov if cov3Ds_precomp.numel() else None, None, None, g_focal)[:n]
 
 
-class _RasterizeGaussiansInvDepth(torch.autograd.Function):
-    """_RasterizeGaussians with the inverse-depth image as a third output (ABI 16), differentiable: a backward that receives no gradient for
-    it is today's das3r_raster_backward call; otherwise das3r_raster_backward_depth takes both."""
-    @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
-        return _RasterizeGaussians._forward(ctx, True, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
-
-    @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii, grad_invdepth):
-        return _RasterizeGaussians._backward(ctx, grad_out_color, grad_invdepth)
+# The one hand-over that upstream's fixed `forward` signature forces: GaussianRasterizer.__call__ passes its two extra keywords (log_focal,
+# aux_geometry_grad) to GaussianRasterizer.forward through this thread-local, and forward consumes them.  Nothing else in this module reads
+# or writes module-level per-call state: options travel as arguments (_Options), results as return values (RasterState).
+_last = threading.local()
 
 
 class GaussianRasterizer(nn.Module):
@@ -844,7 +843,7 @@ class GaussianRasterizer(nn.Module):
             if P:
                 vm = _small(rs.viewmatrix, device, 16, "viewmatrix")
                 pm = _small(rs.projmatrix, device, 16, "projmatrix")
-                with torch.cuda.device(device):
+                with _on_device(device):
                     rc = _lib.load().das3r_mark_visible(P, _ptr(pos), _ptr(vm), _ptr(pm), _ptr(present), _stream(device))
                 _lib.check(rc, "das3r_mark_visible")
             return present.bool()
@@ -866,9 +865,9 @@ class GaussianRasterizer(nn.Module):
         dummy means2D its VALUE is not read — raster_settings (tanfov, projmatrix) must have been built from the same field of view.  When
         it requires grad the backward pass returns dL/ds for it (das3r_raster_backward_focal: the rendering with tanfov e^(-s) and the
         clip-x / clip-y columns of projmatrix scaled by e^(s), every discrete decision held fixed), with and without return_invdepth /
-        antialiasing; every other gradient is the same bit for bit.  None: the functions and library calls are the ones they were.
+        antialiasing; every other gradient is the same bit for bit.  None: the library calls are the ones they were.
         aux_geometry_grad (bool; like log_focal a keyword of the module CALL — rasterizer(..., features=f, aux_geometry_grad=True)): False,
-        the default: the functions and library calls are the ones they were, a loss on feature_image reaches `features` alone and alpha
+        the default: the library calls are the ones they were, a loss on feature_image reaches `features` alone and alpha
         carries no gradient.  True (needs features and / or return_alpha): feature_image and alpha are differentiable with respect to
         means3D, opacities, scales, rotations / cov3D_precomp as well, and their dL/dmean2D is added to means2D.grad beside the colour
         loss's — one das3r_raster_aux_backward call for both images (a compositing kernel over this forward's saved lists + the per-Gaussian
@@ -879,53 +878,24 @@ class GaussianRasterizer(nn.Module):
         aux_geometry_grad, _last.aux_geometry_grad = getattr(_last, "aux_geometry_grad", False), False
         if aux_geometry_grad and features is None and not return_alpha:
             raise ValueError("aux_geometry_grad=True needs features= and / or return_alpha=True: there is no aux image to differentiate")
-        want_state = features is not None or return_alpha or self.keep_state
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
-        e = _empty(means3D.device)   # upstream: torch.Tensor([]) placeholders
-        if shs is None:
-            shs = e
-        if colors_precomp is None:
-            colors_precomp = e
-        if scales is None:
-            scales = e
-        if rotations is None:
-            rotations = e
-        if cov3D_precomp is None:
-            cov3D_precomp = e
-        _last.capacity = None
-        if want_state:
-            _last.want_state, _last.state = True, None
-        try:
-            return self._forward_checked(means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, return_invdepth,
-                                         antialiasing, features, return_alpha, want_state, log_focal, aux_geometry_grad)
-        finally:
-            if want_state:
-                _last.want_state, _last.state = False, None
-
-    def _forward_checked(self, means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, return_invdepth, antialiasing,
-                         features, return_alpha, want_state, log_focal=None, aux_geometry_grad=False):
-        raster_settings = self.raster_settings
-        if log_focal is not None and return_invdepth:
-            color, radii, invdepth = _apply(_RasterizeGaussiansFocal, _check_log_focal(log_focal, means3D.device), True, means3D, means2D, shs,
-                                            colors_precomp, opacities, scales, rotations, cov3D_precomp, raster_settings, antialiasing=antialiasing)
-        elif return_invdepth:
-            color, radii, invdepth = _apply(_RasterizeGaussiansInvDepth, means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                            cov3D_precomp, raster_settings, antialiasing=antialiasing)
-        else:
-            color, radii = rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                               raster_settings, antialiasing=antialiasing, **({} if log_focal is None else {"log_focal": log_focal}))
-        if not color.requires_grad and getattr(_last, "capacity", None) is not None:
+        # upstream: torch.Tensor([]) placeholders
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _or_empty(means3D.device, shs, colors_precomp, scales, rotations, cov3D_precomp)
+        want_state = features is not None or return_alpha or self.keep_state
+        options = _Options(invdepth=return_invdepth, want_state=want_state)
+        out = rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, raster_settings,
+                                  antialiasing=antialiasing, options=options, **({} if log_focal is None else {"log_focal": log_focal}))
+        state = options.state
+        if state is not None and not out[0].requires_grad:
             # evaluation (torch.no_grad, or no input that takes a gradient): no backward pass will examine this forward's binning
             # self-check, so it is examined here, before the image is used (include/das3r_raster.h: das3r_raster_check)
-            check_forward(_last.capacity, means3D.device)
-        _last.capacity = None
-        out = (color, radii, invdepth) if return_invdepth else (color, radii)
+            state.check()
         if want_state:
-            state = self.state = _last.state
+            self.state = state
             if aux_geometry_grad:
                 geometry = AuxGeometry(raster_settings, means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp)
                 fimg, alpha = _aux_with_geometry(state, features, geometry, return_alpha)

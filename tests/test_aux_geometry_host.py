@@ -127,8 +127,8 @@ def test_default_call_is_the_one_it_was(monkeypatch):
     from das3r_amd import GaussianRasterizer, rasterizer
     seen = {}
 
-    def fake(*a, antialiasing=False):
-        seen["want_state"] = getattr(rasterizer._last, "want_state", False)
+    def fake(*a, antialiasing=False, options=None):
+        seen["want_state"] = options.want_state
         seen["calls"] = seen.get("calls", 0) + 1
         return torch.zeros(3, 4, 4), torch.zeros(5, dtype=torch.int32)
 

@@ -144,8 +144,8 @@ def test_default_forward_returns_two_results_and_never_asks_for_the_state(monkey
     from das3r_amd import GaussianRasterizationSettings, GaussianRasterizer, rasterizer
     seen = {}
 
-    def fake(*a, antialiasing=False):
-        seen["want_state"] = getattr(rasterizer._last, "want_state", False)
+    def fake(*a, antialiasing=False, options=None):
+        seen["want_state"] = options.want_state
         seen["calls"] = seen.get("calls", 0) + 1
         return torch.zeros(3, 4, 4), torch.zeros(5, dtype=torch.int32)
 

@@ -596,6 +596,67 @@ extern "C" int das3r_raster_aux_backward(const das3r_raster_args *a, const das3r
     return launch_preprocess_backward(a, in, saved->geom, saved->binning, L, g, partial, s, false, nullptr, (saved->flags & ANTIALIAS_FLAG) != 0);
 }
 
+// ---- the ray-distortion regulariser over a forward's saved lists (render_distort.hip) ----
+// Additive under ABI 16; include/das3r_raster.h fixes the definition.  The forward call reads the saved state only, as das3r_raster_aux_forward
+// does; the backward call is das3r_raster_aux_backward's sequence with one more step: the compositing kernel leaves the per-instance dL/dm sums
+// in column 0 of the nine-float rows, the fold turns them into dz [P] behind the rows — caller scratch, not the binning buffer's depth part,
+// which a colour-only forward does not have — and the per-Gaussian backward takes dz as the depth pass's.
+extern "C" int das3r_raster_distortion_forward(const das3r_raster_args *a, const das3r_raster_saved *saved, float *out, float *totals,
+                                               das3r_stream_t stream) {
+    static const char who[] = "das3r_raster_distortion_forward";
+    hipStream_t s = (hipStream_t)stream;
+    if (!a || !saved) { set_error("%s: null args / saved state", who); return DAS3R_ERR_INVALID_ARG; }
+    if (a->P < 0 || a->image_width <= 0 || a->image_height <= 0) { set_error("%s: bad extents P=%d W=%d H=%d", who, a->P, a->image_width, a->image_height); return DAS3R_ERR_INVALID_ARG; }
+    if (!out) { set_error("%s: null image pointer", who); return DAS3R_ERR_INVALID_ARG; }
+    if (a->P > 0 && saved->num_rendered > 0 && (!saved->geom || !saved->binning || !saved->img)) { set_error("%s: saved buffers missing", who); return DAS3R_ERR_INVALID_ARG; }
+    const int P = a->P, W = a->image_width, H = a->image_height;
+    if (P == 0 || saved->num_rendered <= 0) {   // nothing was blended: no pair anywhere
+        HIP_TRY(hipMemsetAsync(out, 0, sizeof(float) * (size_t)W * (size_t)H, s));
+        if (totals) HIP_TRY(hipMemsetAsync(totals, 0, sizeof(float) * (size_t)W * (size_t)H, s));
+        return DAS3R_OK;
+    }
+    int rc = das3r_raster_check(saved, stream);   // a failed binning is an error, not a walk over bad lists
+    if (rc) return rc;
+    const Layout L = saved_layout(a, saved);
+    return launch_render_distortion_forward(P, W, H, out, totals, saved->geom, saved->binning, saved->img, L, a->debug != 0, s);
+}
+
+// the nine-float rows as das3r_raster_backward_scratch_bytes rounds them, then dz: one float per Gaussian
+extern "C" size_t das3r_raster_distortion_backward_scratch_bytes(int64_t capacity, int32_t P) {
+    const size_t c = capacity > 0 ? (size_t)capacity : 1, p = P > 0 ? (size_t)P : 0;
+    return align_up(c * 9 * sizeof(float) + 16) + p * sizeof(float) + 16;
+}
+
+extern "C" int das3r_raster_distortion_backward(const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_saved *saved,
+                                                const float *dL_ddist, const float *totals, const das3r_raster_grads *g, das3r_stream_t stream) {
+    static const char who[] = "das3r_raster_distortion_backward";
+    hipStream_t s = (hipStream_t)stream;
+    if (!a || !in || !saved || !g) { set_error("%s: null args / inputs / saved state / grads", who); return DAS3R_ERR_INVALID_ARG; }
+    if (!dL_ddist || !totals) { set_error("%s: null dL_ddist / totals plane (das3r_raster_distortion_forward writes it)", who); return DAS3R_ERR_INVALID_ARG; }
+    if (g->chain) { set_error("%s: grads->chain is not supported here (the chained backward belongs to the colour loss)", who); return DAS3R_ERR_INVALID_ARG; }
+    if (!g->scratch) { set_error("%s: null scratch (das3r_raster_distortion_backward_scratch_bytes)", who); return DAS3R_ERR_INVALID_ARG; }
+    int rc = validate(a, in);
+    if (rc) return rc;
+    const int P = a->P, W = a->image_width, H = a->image_height;
+    if (P == 0) return DAS3R_OK;   // no gradient has a row
+    if ((rc = backward_validate(who, in, saved, /*dL_dpix: not this entry's*/ dL_ddist, false, nullptr, g))) return rc;
+    if (saved->num_rendered > 0 && !saved->binning) { set_error("%s: binning buffer missing", who); return DAS3R_ERR_INVALID_ARG; }
+    // the forward's binning self-check first: nothing is launched on the strength of an invalid image / list
+    if ((rc = das3r_raster_check(saved, stream))) return rc;
+    const Layout L = saved_layout(a, saved, shjac_saved(a, in, saved));
+    float *partial = g->scratch;
+    const float *dz = nullptr;
+    if (saved->num_rendered > 0) {
+        const size_t c = L.capacity > 0 ? (size_t)L.capacity : 1;
+        float *dzw = (float *)((char *)g->scratch + align_up(c * 9 * sizeof(float) + 16));
+        if ((rc = launch_render_distortion_backward(P, W, H, dL_ddist, totals, partial, saved->geom, saved->binning, saved->img, L, a->debug != 0, s))) return rc;
+        if ((rc = launch_distortion_fold(P, saved->geom, L, partial, dzw, a->debug != 0, s))) return rc;
+        dz = dzw;
+    }
+    // (nothing rendered: tiles_touched is all zero, the kernel reads no row and writes the zeros; columns 0..2 are zero: so is dL/d(colour, SH))
+    return launch_preprocess_backward(a, in, saved->geom, saved->binning, L, g, partial, s, false, dz, (saved->flags & ANTIALIAS_FLAG) != 0);
+}
+
 extern "C" int das3r_has_experiments(void) {
 #ifdef DAS3R_EXPERIMENTS
     return 1;

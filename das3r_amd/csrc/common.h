@@ -361,6 +361,13 @@ int launch_aux_gather(int P, int C, const float *partial, float *dL_dfeat, const
 // render_aux_bwd.hip: the compositing backward of aux channels / coverage with respect to the geometry -> partial [capacity, 9] (+ partial_f [capacity, C] or null)
 int launch_render_aux_backward(int P, int W, int H, int C, const float *feat, const float *dL_dout, const float *dL_dalpha, float *partial,
                                float *partial_f, const char *geom, const char *binning, const char *img, const Layout &L, bool debug, hipStream_t s);
+// render_distort.hip: the ray-distortion term over the saved lists -> out [H,W] (+ totals [H,W] or null); its compositing backward ->
+// partial [capacity, 9] (column 0: the per-instance sum of dL/dm, columns 1..2 zero), then the fold of column 0 into dz [P] (column 0 zeroed)
+int launch_render_distortion_forward(int P, int W, int H, float *out, float *totals, const char *geom, const char *binning, const char *img,
+                                     const Layout &L, bool debug, hipStream_t s);
+int launch_render_distortion_backward(int P, int W, int H, const float *dL_ddist, const float *totals, float *partial, const char *geom,
+                                      const char *binning, const char *img, const Layout &L, bool debug, hipStream_t s);
+int launch_distortion_fold(int P, const char *geom, const Layout &L, float *partial, float *dz, bool debug, hipStream_t s);
 // pair_count.hip (measurement aid): out[0] += live pairs, out[1] += (pixel, list position) pairs below the pixel's n_contrib
 int launch_count_live_pairs(const das3r_raster_args *a, char *geom, char *binning, char *img, const Layout &L, unsigned long long *out, hipStream_t s);
 int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in *in, char *geom, char *binning, const Layout &L,

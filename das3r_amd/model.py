@@ -63,6 +63,11 @@ class OptimParams:   # /root/reference/arguments/__init__.py:73-90 (densificatio
     # trainable field of view (the reference builds the two optimizer groups and never feeds them: module docstring): the learning rate of
     # the fovX / fovY groups.  0: off — the groups stay inert at the reference's 1e-4, every render takes the camera's field of view.
     fov_lr: float = 0.0
+    # ray-distortion regulariser (Mip-NeRF 360 / 2DGS; not in the reference): loss += distortion_weight * mean over pixels of
+    # sum_{j<k} w_j w_k (1/z_j - 1/z_k) along the ray (rasterizer.distortion_of) — it pulls the near-copies of a surface that a ray crosses
+    # to one depth, and needs no target.  0: off — the step is the one it was, call for call.  > 0: the autograd forms of train_step only
+    # (the direct iteration of fast_step.py does not carry the term yet).
+    distortion_weight: float = 0.0
 
 
 def log_focal_of(fovx, fovy):

@@ -699,6 +699,96 @@ def _aux_with_geometry(state, features, geometry, want_alpha):
                                              geometry.colors_precomp), geometry.raster_settings, state, bool(want_alpha))
 
 
+# ---- the ray-distortion regulariser over a forward's lists
+
+
+def _distortion_forward(state, want_totals, _fill=None):
+    """One das3r_raster_distortion_forward call -> (D [1, H, W], the totals plane [H, W] its backward takes, or None)."""
+    _needs_device(state)
+    lib = _lib.load()
+    z = _new(state.device, _fill)   # both fully written by the call
+    out = z(1, state.H, state.W)
+    totals = z(state.H, state.W) if want_totals else None
+    a, saved = state._c_args()
+    with _on_device(state.device):
+        rc = lib.das3r_raster_distortion_forward(C.byref(a), C.byref(saved), C.c_void_p(out.data_ptr()),
+                                                 None if totals is None else C.c_void_p(totals.data_ptr()), _stream(state.device))
+    _lib.check(rc, "das3r_raster_distortion_forward")
+    return out, totals
+
+
+def _distortion_backward_impl(state, rs, grad, totals, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                              _scratch_misalign=0, _fill=None):
+    """One das3r_raster_distortion_backward call: the backward of <grad, distortion_of> for the forward that left `state` ->
+    (g_means2D, g_opac, g_means3D, g_cov, g_scales, g_rot).  grad [1, H, W], totals [H, W]: the forward call's.  (_fill: tests fill the scratch
+    and every output with it first.)"""
+    lib = _lib.load()
+    device, P = state.device, state.P
+    M = sh.shape[1] if sh.numel() else 0
+    # (the colour gradient is identically zero for this loss; the per-Gaussian backward writes it all the same)
+    (g_means2D, _g_colors, g_opac, g_means3D, g_cov, _g_sh, g_scales, g_rot), g = _grad_set(device, P, M, sh.numel() > 0, cov3Ds_precomp.numel() > 0,
+                                                                                           fill=_fill)
+    if P == 0:
+        return g_means2D, g_opac, g_means3D, g_cov, g_scales, g_rot
+    nbytes = lib.das3r_raster_distortion_backward_scratch_bytes(max(int(state.capacity), 1), P)
+    scratch, g.scratch = _scratch(nbytes, device, _scratch_misalign, _fill)   # rows and dz written before they are read
+    keep = []
+    a = _fill_args(rs, P, M, device, keep)
+    i = _fill_in(means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp)
+    saved = state.saved()
+    with _on_device(device):
+        rc = lib.das3r_raster_distortion_backward(C.byref(a), C.byref(i), C.byref(saved), C.c_void_p(grad.data_ptr()),
+                                                  C.c_void_p(totals.data_ptr()), C.byref(g), _stream(device))
+    _lib.check(rc, "das3r_raster_distortion_backward")
+    return g_means2D, g_opac, g_means3D, g_cov, g_scales, g_rot
+
+
+class _DistortionWithGeometry(torch.autograd.Function):
+    """distortion_of, differentiable with respect to the forward's geometry inputs: the forward is one das3r_raster_distortion_forward call
+    (which leaves the totals plane), the backward ONE das3r_raster_distortion_backward call; dL/dmean2D goes to the dummy means2D leaf, where
+    autograd adds it to the colour loss's."""
+    @staticmethod
+    def forward(ctx, means3D, means2D, opacities, scales, rotations, cov3Ds_precomp, sh, colors_precomp, raster_settings, state):
+        device = state.device
+        tensors = [_prep(t, device, n) for t, n in ((means3D, "means3D"), (opacities, "opacities"), (scales, "scales"), (rotations, "rotations"),
+                                                    (cov3Ds_precomp, "cov3D_precomp"), (sh, "shs"), (colors_precomp, "colors_precomp"))]
+        image, totals = _distortion_forward(state, True)
+        ctx.state, ctx.raster_settings = state, raster_settings
+        ctx.save_for_backward(*tensors, totals)
+        ctx.set_materialize_grads(False)
+        return image
+
+    @staticmethod
+    def backward(ctx, grad):
+        if grad is None:
+            return (None,) * 10
+        means3D, opacities, scales, rotations, cov3Ds_precomp, sh, colors_precomp, totals = ctx.saved_tensors
+        g_means2D, g_opac, g_means3D, g_cov, g_scales, g_rot = _distortion_backward_impl(
+            ctx.state, ctx.raster_settings, _dense(grad), totals, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
+        return (g_means3D, g_means2D, g_opac, g_scales if scales.numel() else None, g_rot if rotations.numel() else None,
+                g_cov if cov3Ds_precomp.numel() else None, None, None, None, None)
+
+
+def distortion_of(state, geometry=None):
+    """-> [1, H, W]: the ray-distortion regulariser (Mip-NeRF 360, 2DGS) of the forward that left `state`, per pixel
+        D = sum_{j<k} w_j w_k (m_j - m_k) = 1/2 sum_i sum_j w_i w_j |m_i - m_j|,    w_k = alpha_k T_k,  m_k = 1 / z_k,
+    over the splats the pixel's colour was blended from — same order (depth, index), same alpha, same stop; z the fp32 view-space depth the
+    forward saved; no background term; an empty pixel and a pixel with one contributor are exactly 0 (include/das3r_raster.h
+    das3r_raster_distortion_forward).  Nothing of the forward is repeated: one kernel over the saved lists.
+    geometry=None: a plain tensor.  geometry=AuxGeometry(settings, the forward's input tensors): differentiable with respect to means3D,
+    opacities, scales and rotations or cov3D_precomp, and dL/dmean2D arrives in geometry.means2D.grad (das3r_raster_distortion_backward: one
+    compositing kernel, a per-Gaussian fold of dL/d(1/z), the per-Gaussian backward; every discrete decision of the forward held fixed).  No
+    floating-point atomics: bit-identical from run to run.  One workgroup per tile: on few tiles with ~10 k-entry lists it is slower than it
+    could be (docs/ledger.md (cq))."""
+    if geometry is None:
+        _check_state(state)
+        return _distortion_forward(state, False)[0]
+    _check_geometry(state, geometry)
+    return _DistortionWithGeometry.apply(geometry.means3D, geometry.means2D, geometry.opacities,
+                                         *_or_empty(state.device, geometry.scales, geometry.rotations, geometry.cov3D_precomp, geometry.shs,
+                                                    geometry.colors_precomp), geometry.raster_settings, state)
+
+
 # ---- the rasterising autograd function and the module
 
 

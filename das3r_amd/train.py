@@ -44,6 +44,14 @@ def depth_term_weight(cam, opt, iteration):
     return w if (w > 0.0 and getattr(cam, "invdepthmap", None) is not None) else 0.0
 
 
+def distortion_term_weight(opt):
+    """OptimParams.distortion_weight as a host float (an `opt` without the field: 0.0): the weight of the ray-distortion term."""
+    w = float(getattr(opt, "distortion_weight", 0.0) or 0.0)
+    if not (w >= 0.0 and w < float("inf")):
+        raise ValueError(f"OptimParams.distortion_weight must be finite and >= 0 (got {w})")
+    return w
+
+
 def depth_mask_of(cam):
     m = getattr(cam, "depth_mask", None)
     return m if m is not None else torch.ones_like(cam.invdepthmap)
@@ -56,13 +64,17 @@ def train_step(model: SplatModel, cam, opt: OptimParams, iteration, pipe, backgr
     the autograd form of round 3 — same kernels, the reference's Python around them).
     fused_loss=False with fused=True: the fused pre-transform and FusedAdam behind render() / the optimizers, the loss in torch ops and the
     camera gate a host-side `if`, as the reference's loop has them; fused_loss="ssim": what das3r_amd.integrate.patch() gives an UNMODIFIED
-    train_gui.py since round 6 — the same, with the loop's `ssim` call answered by the fused SSIM map (fused.ssim_map)."""
+    train_gui.py since round 6 — the same, with the loop's `ssim` call answered by the fused SSIM map (fused.ssim_map).
+    opt.distortion_weight > 0 adds distortion_weight * mean(ray-distortion image of this render's lists) (das3r_render(return_distortion=True))
+    to the loss in both autograd forms; the direct iteration (fast_step.train_step) is taken only while the weight is 0 — its chained
+    backward carries no aux term, the direct form of this one is owed.  At 0 the step is the one it was, call for call."""
     ssim_fn = ssim
     if fused_loss == "ssim":
         from .fused import ssim_map
         ssim_fn, fused_loss = (lambda a, b, size_average=False: ssim_map(a, b)), False
     fused_loss = bool(fused) if fused_loss is None else bool(fused_loss)
-    if fused and fused_loss:
+    w_dist = distortion_term_weight(opt)   # (0.0: the step below is the one it was, call for call)
+    if fused and fused_loss and w_dist == 0.0:   # (the direct iteration's chained backward refuses aux terms: owed, docs/ledger.md (cq))
         from . import fast_step
         if fast_step.available(model, pipe):
             return fast_step.train_step(model, cam, opt, iteration, pipe, background)
@@ -71,7 +83,8 @@ def train_step(model: SplatModel, cam, opt: OptimParams, iteration, pipe, backgr
         model.oneupSHdegree()
     pose = model.get_RT(cam.uid)
     w_depth = depth_term_weight(cam, opt, iteration)   # (0.0: the step below is the photometric one, call for call)
-    pkg = das3r_render(cam, model, pipe, background, camera_pose=pose, fused=fused, **({"return_invdepth": True} if w_depth > 0.0 else {}))
+    pkg = das3r_render(cam, model, pipe, background, camera_pose=pose, fused=fused, **({"return_invdepth": True} if w_depth > 0.0 else {}),
+                       **({"return_distortion": True} if w_dist > 0.0 else {}))
     image = pkg["render"]
     gt = cam.original_image
     static = model._conf_static[cam.uid]
@@ -83,6 +96,8 @@ def train_step(model: SplatModel, cam, opt: OptimParams, iteration, pipe, backgr
         if w_depth > 0.0:
             from .fused import depth_l1_loss
             loss = loss + depth_l1_loss(pkg["invdepth"], cam.invdepthmap, depth_mask_of(cam), static, weight=w_depth)
+        if w_dist > 0.0:
+            loss = loss + w_dist * pkg["distortion"].mean()
         loss.backward(retain_graph=True)
         with torch.no_grad():
             model.optimizer.step()
@@ -103,6 +118,8 @@ def train_step(model: SplatModel, cam, opt: OptimParams, iteration, pipe, backgr
     loss = ((1.0 - opt.lambda_dssim) * Ll1 + opt.lambda_dssim * (1.0 - Lssim)).mean()
     if w_depth > 0.0:
         loss = loss + w_depth * depth_l1(pkg["invdepth"][0], cam.invdepthmap, depth_mask_of(cam), static)
+    if w_dist > 0.0:
+        loss = loss + w_dist * pkg["distortion"].mean()
     loss.backward(retain_graph=True)
     with torch.no_grad():
         model.optimizer.step()

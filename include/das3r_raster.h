@@ -519,6 +519,55 @@ int das3r_raster_aux_backward(const das3r_raster_args *args, const das3r_raster_
                               const float *dL_dalpha /* [H,W] or NULL */, float *dL_dfeatures /* [P,C] or NULL */,
                               const das3r_raster_grads *grads, das3r_stream_t stream);
 
+/* ---- ray-distortion regulariser over a forward's lists, forward and backward (opt-in) -----------------------------------------------
+ * Additive symbols under ABI 16.  The distortion loss of Mip-NeRF 360 / 2DGS: the pairwise spread of the blending weights along a ray.  It is
+ * quadratic in the weights, so no blend of per-Gaussian channels (das3r_raster_aux_forward) expresses it.
+ * Definition.  For the forward that left `saved`, and for a pixel whose colour was blended from list entries k = 0 .. n-1:
+ *   - the entries are the same ones, in the same order, with the same alpha and the same stop at n_contrib as the colour;
+ *   - w_k = alpha_k T_k;
+ *   - m_k = 1 / z_k, where z_k is the fp32 view-space depth the forward saved in the splat record (the staged 1/z of the inverse-depth image).
+ *
+ *     D[pixel] = sum_{j<k} w_j w_k (m_j - m_k)
+ *              = sum_k w_k (B_{k-1} - m_k A_{k-1}),     A_k = sum_{j<=k} w_j,  B_k = sum_{j<=k} w_j m_j
+ *
+ *   - A tile's list is ordered by (depth, index), so every term is >= 0 and D = 1/2 sum_i sum_j w_i w_j |m_i - m_j|.
+ *   - There is no background term.  An empty pixel or a pixel with one contributor is exactly 0.
+ *   - Inverse depth: 2DGS's NDC depth is affine in 1/z, and out_invdepth is in inverse depth already.
+ *   - D is invariant under m -> m + c.  Both kernels take m RELATIVE TO THE PIXEL'S WEIGHTED MEAN mu = B / A: the forward as a running mean,
+ *     B_{k-1} - m_k A_{k-1} = A_{k-1} (mu_{k-1} - m_k) with mu_k = mu_{k-1} + w_k (m_k - mu_{k-1}) / A_k, the backward relative to the final
+ *     one, where B = 0.  So B - m A does not cancel on lists whose depths nearly agree — the lists the loss exists for — and a single
+ *     outlier in front (a faint splat just past the near plane) does not cost the others their bits, as a fixed first-entry reference would.
+ * Backward.  With SA_k = sum_{j>k} w_j, SB_k = sum_{j>k} w_j m_j, A = sum w and B = sum w m:
+ *     q_k = dD/dw_k = m_k (2 SA_k - A) - (2 SB_k - B),          dD/dm_k = w_k (2 SA_k + w_k - A),
+ *     dD/dalpha_k = T_k q_k - (sum_{j>k} w_j q_j) / (1 - alpha_k)
+ * — the colour recurrence on the per-pair scalar dL_ddist[pixel] q_k; SA and SB are running sums of the back-to-front replay, A = 1 - final_T.
+ * THE TOTALS PLANE is the chosen design for B: das3r_raster_distortion_forward leaves the pixel's total in `totals` [H,W] (caller memory;
+ * NULL: not wanted) as the mean mu = B / A — the shift in which the shifted total is zero, 0 for an empty pixel — and
+ * das3r_raster_distortion_backward takes that plane back.  The backward makes no front-to-back sweep of its own.
+ * Every discrete decision of the forward is held fixed, as for das3r_raster_aux_backward: cull, radius, tile rectangle, lists and their order,
+ * the 1/255 and T < 1e-4 cut-offs, n_contrib.
+ * Launches.  Forward: ONE kernel (render_distortion_forward_kernel, front to back over the saved lists).  Backward: ONE compositing kernel
+ * (render_distortion_backward_kernel: nine-float rows with the per-instance sum of dL/dm in column 0), a fold of column 0 per Gaussian into
+ * dL/dz = -sum / z^2 (in the scratch, not in the binning buffer: a colour-only forward has no depth part there), and the per-Gaussian backward
+ * das3r_raster_backward ends with, the antialiasing factor of an antialiased forward included.
+ * Both calls read what ANY forward left in `saved`, as das3r_raster_aux_forward / _backward do: with or without out_invdepth, antialiased (hand
+ * the flags back), every binning path and forward kernel — and, for the forward call, an evaluation forward.  args for the forward call:
+ * P, image_width, image_height, debug; for the backward: args / in the forward was given.  The binning self-check is examined first.
+ * out / totals are fully written.  grads: every buffer das3r_raster_backward would ask for, fully written; the colour gradient is written as
+ * zeros.  grads->scratch: das3r_raster_distortion_backward_scratch_bytes(saved->capacity, P) bytes (the nine-float rows, then P floats),
+ * 4-byte aligned, need not be initialised.  No floating-point atomics, no unordered adds: bit-identical from run to run; nothing needs
+ * pre-zeroing.  P == 0 or nothing rendered: zeros.
+ * DAS3R_ERR_INVALID_ARG with a das3r_last_error() message, before anything is launched: NULL structs, NULL out / dL_ddist / totals (backward),
+ * NULL grads->scratch, grads->chain != NULL, and whatever das3r_raster_backward refuses.
+ * One workgroup per tile in both kernels: few tiles with very long lists leave most of the chip idle.  The bucket-parallel form is owed — a
+ * list segment combines associatively on (T, A, B, D) — see docs/ledger.md (cq). */
+int das3r_raster_distortion_forward(const das3r_raster_args *args, const das3r_raster_saved *saved, float *out /* [H,W] */,
+                                    float *totals /* [H,W] or NULL */, das3r_stream_t stream);
+size_t das3r_raster_distortion_backward_scratch_bytes(int64_t capacity, int32_t P);
+int das3r_raster_distortion_backward(const das3r_raster_args *args, const das3r_raster_in *in, const das3r_raster_saved *saved,
+                                     const float *dL_ddist /* [H,W] */, const float *totals /* [H,W]: the forward call's */,
+                                     const das3r_raster_grads *grads, das3r_stream_t stream);
+
 /* ---- introspection (used by the parity tests and the roofline accounting) ---- */
 
 /* Byte offsets of the saved intermediates inside geom / binning / img for given extents. */

@@ -84,7 +84,7 @@ class PathPolicyInputs(C.Structure):
 class PathPolicyPlan(C.Structure):
     """include/das3r_raster.h das3r_path_policy_plan."""
     _fields_ = [("local", C.c_int32), ("seg", C.c_int32), ("seg_bits", C.c_int32), ("seg_passes", C.c_int32), ("speculate", C.c_int32),
-                ("decide_fine", C.c_int32), ("gen", C.c_uint32), ("cap", C.c_int64)]
+                ("decide_fine", C.c_int32), ("gen", C.c_uint32), ("cells", C.c_int32), ("cap", C.c_int64)]
 
 
 class Switches(C.Structure):

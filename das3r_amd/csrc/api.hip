@@ -180,6 +180,8 @@ void compute_layout(int P, int64_t I, int W, int H, Layout *L, bool shjac) {
     L->b_e2 = take(4 * In);
     L->b_ghist = take(4 * 4 * RADIX_SIZE);
     L->b_ticket = take(256);
+    L->cursor_stride = I >= (int64_t)(1 << 20) ? CURSOR_STRIDE : 1;
+    L->b_cursor = take(4 * (size_t)RADIX_SIZE * (size_t)L->cursor_stride);
     L->b_status = take(onesweep_status_bytes((int64_t)In, L->tile_passes + 1));   // (+ 1: the segmented path may take one more pass)
     L->b_ctrl_bytes = o - L->b_ghist;
     L->b_ckpt = take(((size_t)In / BUCKET + (size_t)(L->ntiles > 0 ? L->ntiles : 1) + 2) * 256 * 16);
@@ -238,14 +240,14 @@ struct PolicyOnState {
     }
 };
 ForwardPlan plan_of(const das3r_path_policy_plan *p) {
-    return ForwardPlan{p->local != 0, p->seg != 0, p->seg == 2, p->seg_bits, p->seg_passes, p->speculate != 0, p->cap, p->decide_fine != 0, p->gen};
+    return ForwardPlan{p->local != 0, p->seg != 0, p->seg == 2, p->seg == 2 && p->cells != 0, p->seg_bits, p->seg_passes, p->speculate != 0, p->cap, p->decide_fine != 0, p->gen};
 }
 }  // namespace
 extern "C" void das3r_debug_path_policy_fresh(das3r_path_policy_state *state, uint32_t gen) { policy_state_to(Verdict::fresh(gen), Resume(), state); }
 extern "C" void das3r_debug_path_policy_plan(das3r_path_policy_state *state, const das3r_path_policy_inputs *in, das3r_path_policy_plan *out) {
     PolicyOnState on(state);
     const ForwardPlan p = plan_forward(on.v, on.inputs(in));
-    *out = das3r_path_policy_plan{p.local, p.bucket_local ? 2 : (p.seg ? 1 : 0), p.seg_bits, p.seg_passes, p.speculate, p.decide_fine, p.gen, p.cap};
+    *out = das3r_path_policy_plan{p.local, p.bucket_local ? 2 : (p.seg ? 1 : 0), p.seg_bits, p.seg_passes, p.speculate, p.decide_fine, p.gen, p.cells, p.cap};
 }
 extern "C" int das3r_debug_path_policy_count(das3r_path_policy_state *state, const das3r_path_policy_inputs *in, const das3r_path_policy_plan *plan, int64_t I) {
     PolicyOnState on(state);

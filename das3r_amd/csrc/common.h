@@ -158,6 +158,7 @@ static inline int tile_bits(int ntiles) {
 }
 
 // (BUCKET, the list positions between two checkpoints of a long tile list: kernel_choice.h)
+constexpr int CURSOR_STRIDE = 32;   // words between two bin cursors of cell_partition_kernel (scattered agent-scope atomics: one line per row)
 constexpr int SPLAT_REC = 4;   // float4s per Gaussian record (xyh, conic+opacity, rgb+depth, pad): 64 bytes, one cache-line gather
 
 // das3r_raster_saved.flags bit 1 (ABI 16): the forward was given out_invdepth, its binning buffer holds Layout::d_* (bits 0 and 8 - 15: forward.hip look_at_lists)
@@ -187,6 +188,8 @@ struct Layout {
     size_t g_ghist, g_ticket, g_status, g_scan_status, g_ctrl_bytes;
     int64_t capacity;  // instance capacity the binning buffer was laid out for
     size_t b_ghist, b_ticket, b_status, b_ctrl_bytes;
+    size_t b_cursor;   // u32[256 * cursor_stride] inside the control words: the bin cursors of the cells plan (cell_sort.hip)
+    int cursor_stride; // words between two cursors: CURSOR_STRIDE (a 128-byte line each) from 2^20 instances on, 1 below (few workgroups; 1 KB to zero, not 32)
     int tiles_x, tiles_y, ntiles, tbits, tile_passes;
     int chunksP, chunksI;
     // segmented binning path (segkey.h): the partition key is (tile id << dbits | depth bucket), kbits = tbits + dbits wide, in the
@@ -324,7 +327,11 @@ int launch_binning(int P, int64_t I, int W, int H, const int32_t *radii, char *g
                    bool fused_scan, uint32_t *host_late, uint32_t tag, bool debug, hipStream_t s, uint32_t **dead_keys = nullptr,
                    uint32_t *emit_slot = nullptr /*fused emission: {err, pad, ghist} ring slot, re-armed by the last kernel*/,
                    uint32_t *seg_host_flag = nullptr, uint32_t seg_flag_value = 0 /*segmented path (L.dbits > 0): mailbox word for a segment too long for LDS*/,
-                   bool local_finish = false /*L.dbits > 0: no segment sort — tile ranges from the bucketed keys, the compositing kernel finishes the lists*/);
+                   bool local_finish = false /*L.dbits > 0: no segment sort — tile ranges from the bucketed keys, the compositing kernel finishes the lists*/,
+                   bool cells = false /*with local_finish: partition by reserved ranges, finish per cell (cell_sort.hip) instead of the stable passes*/);
+// cell_sort.hip: the cells plan's partition and finish, tile ranges and self-check word included; host_flag / flag_value: the too_long mailbox word
+int launch_cell_sort(int64_t cap, char *geom, char *binning, char *img, const Layout &L, uint32_t **keys_final, uint32_t *host_late, uint32_t tag,
+                     uint32_t *host_flag, uint32_t flag_value, bool debug, hipStream_t s);
 // segsort.hip: exact (depth bits, index) order inside every (tile, depth bucket) segment of the partitioned list, in place
 int launch_segment_sort(int64_t cap, const uint32_t *n_ptr, const uint32_t *keys_final, int fbits, uint32_t *point_list, uint32_t *slot_list,
                         const uint32_t *depth_key, uint32_t last_g, uint32_t *scratch_keys, uint32_t *host_flag, uint32_t flag_value, bool debug,

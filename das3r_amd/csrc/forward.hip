@@ -468,6 +468,8 @@ int ForwardCall::bin_and_render(bool local_order, bool ctrl_zeroed, uint32_t *co
     const bool fused_scan = use_onesweep();   // scan + emission in one kernel; the classic path scans, then emits
     const bool seg = L.dbits > 0;             // segmented path: index-order emission with depth buckets, lists sorted by segment_sort_kernel
     const bool finish = seg && plan.bucket_local;   // ... or, with the same emission and passes, finished by the compositing kernel (path_policy.h bucket_local_rule)
+    // (plan.cells, with finish: launch_binning's partition step is launch_cell_sort — partition by reserved ranges + finish per cell, which
+    //  writes the tile ranges and hands over the self-check word — instead of the stable passes and tile_ranges_kernel: cells_rule)
     if (!emit_slot) {
         if (fused_scan) {
             if ((r = launch_binning_scan_emit(P, cap, out->radii, saved->geom, saved->binning, L, ctrl_zeroed, count_out, count_out_tag, a->debug != 0,
@@ -478,7 +480,7 @@ int ForwardCall::bin_and_render(bool local_order, bool ctrl_zeroed, uint32_t *co
     if (cap > 0 && (r = claim_check_slot(&host_late))) return r;
     uint32_t *dead_keys = nullptr;
     if ((r = launch_binning(P, cap, a->image_width, a->image_height, out->radii, saved->geom, saved->binning, saved->img, L, fused_scan, host_late, late_tag,
-                            a->debug != 0, s, &dead_keys, emit_slot, mb->dev + MB_TOO_LONG, plan.gen, finish))) return r;
+                            a->debug != 0, s, &dead_keys, emit_slot, mb->dev + MB_TOO_LONG, plan.gen, finish, finish && plan.cells))) return r;
     if ((r = colour_launch())) return r;   // the split preprocess: the colour kernel, beside the binning kernels enqueued above
     LocalBin lb = {(float4 *)(saved->binning + L.b_ckpt), nullptr, nullptr, nullptr, nullptr, plan.gen, (uint32_t)(P - 1), (uint32_t)cap};
     if ((r = look_at_lists(&lb))) return r;

@@ -71,8 +71,9 @@ struct Switches {
     bool sort_classic;     // DAS3R_SORT=classic: histogram + row scan + scatter per digit instead of the one-sweep passes
     bool rect_upstream;    // DAS3R_RECT=upstream: bin over upstream's 3-sigma square (bit-exact list tests)
     bool verbose;          // DAS3R_VERBOSE
-    int binning;           // DAS3R_BINNING=local | radix | seg | seg3 | bucket: 1 | -1 | 2 | 3 | 4 (0: chosen per scene; seg3 = seg with one more partition pass of
-                           // bucket bits; bucket = segmented emission, lists finished by the compositing kernel: path_policy.h bucket_local_rule)
+    int binning;           // DAS3R_BINNING=local | radix | seg | seg3 | bucket | cells: 1 | -1 | 2 | 3 | 4 | 5 (0: chosen per scene; seg3 = seg with one more partition pass of
+                           // bucket bits; bucket = segmented emission, lists finished by the compositing kernel: path_policy.h bucket_local_rule;
+                           // cells = the same, partitioned by reserved ranges and finished per cell: cells_rule)
     bool capacity_exact;   // DAS3R_CAPACITY=exact: never lay the binning buffer out speculatively
     bool fused_emit_off;   // DAS3R_FUSED_EMIT=0
     bool no_sh_stage;      // DAS3R_NO_SH_STAGE
@@ -130,7 +131,7 @@ static inline Switches parse_switches(Lookup &&lookup, bool experiments) {
     }
     w.rect_upstream = (e = env("DAS3R_RECT")) && e[0] == 'u';
     w.verbose = env("DAS3R_VERBOSE") != nullptr;
-    if ((e = env("DAS3R_BINNING"))) w.binning = e[0] == 'l' ? 1 : (e[0] == 'r' ? -1 : (e[0] == 's' ? (strchr(e, '3') ? 3 : 2) : (e[0] == 'b' ? 4 : 0)));
+    if ((e = env("DAS3R_BINNING"))) w.binning = e[0] == 'l' ? 1 : (e[0] == 'r' ? -1 : (e[0] == 's' ? (strchr(e, '3') ? 3 : 2) : (e[0] == 'b' ? 4 : (e[0] == 'c' ? 5 : 0))));
     w.capacity_exact = (e = env("DAS3R_CAPACITY")) && e[0] == 'e';
     w.fused_emit_off = (e = env("DAS3R_FUSED_EMIT")) && e[0] == '0';
     if ((e = env("DAS3R_SPLIT_COLOUR"))) w.split_colour = e[0] == '0' ? -1 : (e[0] == '1' ? 1 : 0);   // (A-B runs, tests: the split preprocess off / on)

@@ -1,5 +1,5 @@
 // path_policy.h — what a forward LEARNS about a shape (P, W, H) and what the next forward of the shape does with it: which binning path it
-// takes (local order, segmented with N partition passes, segmented emission with the local finish, global radix sort), when a shape backs off to the global sort and for how
+// takes (local order, segmented with N partition passes, segmented emission with the local finish — partitioned by the stable passes or by cells —, global radix sort), when a shape backs off to the global sort and for how
 // long, whether it speculates on its capacity, and which compositing kernels its tile lists call for.  Pure host arithmetic on a
 // caller-owned Verdict: no HIP, no switches(), no error reporting — forward.hip (das3r_raster_forward) reads the mailbox words and the
 // switches, calls in here at the places named below, and launches what the plan says.  Compiles with a plain C++17 compiler
@@ -39,8 +39,20 @@ static inline uint32_t next_gen(uint32_t gen) { return gen + 1u ? gen + 1u : 1u;
 // the key bits are there.
 static inline bool bucket_local_rule(int forced, bool onesweep, int tbits, int tile_passes, int ntiles, int64_t last_I, int radix_left) {
     if (!onesweep || seg_dbits(tbits, tile_passes) < BUCKET_LOCAL_DBITS) return false;
-    if (forced == 4) return true;
+    if (forced == 4 || forced == 5) return true;
     return forced == 0 && radix_left == 0 && ntiles > BUCKET_LOCAL_TILES && last_I > BUCKET_LOCAL_AVG * ntiles && last_I <= LOCAL_AVG * ntiles;
+}
+
+// The fifth binning plan, "cells": the fourth plan's emission, key and finish by the compositing kernel, but the instances are partitioned
+// without a chain — one pass by the top eight partition bits into ranges reserved on per-bin cursors, then every cell ordered by the low
+// eight through LDS, tile ranges included (cell_sort.hip).  Its passes are not stable; local_order_tile breaks ties by Gaussian id, so the
+// lists come out the same bits.  Holds where bucket_local_rule holds and the partition key is 8 or 16 bits wide (one or two tile passes:
+// up to 2^14 tiles; a 24-bit key would leave the finish 2^16 bins per cell); the compositing kernel and the back-off (too_long, radix_left,
+// clean) are the fourth plan's.  by_shape: CELLS_BY_SHAPE — whether the shapes bucket_local_rule picks take it unforced (ledger (cr)).
+// forced: DAS3R_BINNING=cells (5); where the rule does not hold it falls where DAS3R_BINNING=bucket falls.
+constexpr bool CELLS_BY_SHAPE = true;
+static inline bool cells_rule(int forced, bool bucket_local, int tile_passes, bool by_shape = CELLS_BY_SHAPE) {
+    return bucket_local && tile_passes <= 2 && (forced == 5 || (forced == 0 && by_shape));
 }
 
 // What the last forward of the current shape (P, W, H) taught us.
@@ -76,7 +88,7 @@ struct PolicyInputs {
     int ntiles, tbits, tile_passes;   // Layout
     uint32_t too_long;     // mailbox word: != 0: a forward of the shape with that generation number met a list too long for LDS
     uint32_t want_bits;    // mailbox word: != 0: the segmented path of that generation sorted a segment long enough to want more bucket bits
-    int forced;            // Switches::binning (DAS3R_BINNING=local | radix | seg | seg3 | bucket: 1 | -1 | 2 | 3 | 4): force one (diagnostics, tests); 0: by shape
+    int forced;            // Switches::binning (DAS3R_BINNING=local | radix | seg | seg3 | bucket | cells: 1 | -1 | 2 | 3 | 4 | 5): force one (diagnostics, tests); 0: by shape
     bool onesweep;         // use_onesweep(): false only with the classic radix passes of an experiments build, which have no fast path
     int64_t capacity_hint; // das3r_raster_args: -1 = the caller wants the exact size
     bool capacity_exact;   // Switches::capacity_exact (DAS3R_CAPACITY=exact)
@@ -86,6 +98,7 @@ struct PolicyInputs {
 struct ForwardPlan {
     bool local, seg;            // local order / segmented path; neither: the global depth sort
     bool bucket_local;          // (with seg) segmented emission and passes, no segment sort: the compositing kernel finishes the lists (bucket_local_rule)
+    bool cells;                 // (with bucket_local) partitioned by reserved ranges and finished per cell instead of by the stable passes (cells_rule)
     int seg_bits, seg_passes;   // depth-bucket bits and partition passes the segmented path would take (applied to the layout when seg)
     bool speculate;             // enqueue the whole forward for `cap` instances before its own count is known
     int64_t cap;                // (with speculate)
@@ -143,7 +156,8 @@ static inline ForwardPlan plan_forward(Verdict &v, const PolicyInputs &in) {
     const int forced = in.forced;
     p.bucket_local = bucket_local_rule(forced, in.onesweep, in.tbits, in.tile_passes, in.ntiles, v.last_I, v.radix_left);
     // (DAS3R_BINNING=bucket where the key has no room for buckets: the local order)
-    p.local = !p.bucket_local && in.onesweep && (forced == 1 || forced == 4 || (forced == 0 && v.radix_left == 0 && v.last_I <= LOCAL_AVG * in.ntiles));
+    p.cells = cells_rule(forced, p.bucket_local, in.tile_passes);
+    p.local = !p.bucket_local && in.onesweep && (forced == 1 || forced == 4 || forced == 5 || (forced == 0 && v.radix_left == 0 && v.last_I <= LOCAL_AVG * in.ntiles));
     // Long lists (round 4): the segmented path — no global depth sort; the tile partition's passes carry a depth bucket in the key bits
     // the tile ids leave free, and every (tile, bucket) segment is sorted inside LDS (segkey.h, segsort.hip).  Needs free key bits
     // and segments that stay short on average; a segment that did not fit in LDS sends the shape back to the global sort for a

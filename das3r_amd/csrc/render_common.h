@@ -433,9 +433,10 @@ __device__ __forceinline__ bool local_order_tile(const LocalBin &lb, const uint2
         // the places where the bucket changes.  The segment is read eight words at a time from its start rounded down to four (the words in
         // front of it count as they must) to past its end (behind it: words that are below nobody of the segment).  Only the entries of a TIE
         // GROUP — neighbours by rank with the same bucket and fraction, about one tile in ten has one — fetch their depth bits and are ranked
-        // again inside the group by (depth bits, position), as segsort.hip does it.
+        // again inside the group by (depth bits, Gaussian id): what (depth bits, position) gives behind stable passes (the emission is in index
+        // order), and the same whatever order the entries of a segment arrive in (cell_sort.hip).
         uint32_t *s_word = reinterpret_cast<uint32_t *>(stage), *s_byrank = s_word + 2 * TILE_PIX + 8, *s_depth = s_byrank + 2 * TILE_PIX + 8;
-        uint32_t *s_lo = s_depth + 2 * TILE_PIX, *s_hi = s_lo + 128;
+        uint32_t *s_lo = s_depth + 2 * TILE_PIX, *s_hi = s_lo + 128, *s_idr = s_hi + 128;   // (s_idr: 512 words, 9 280 of the stage's 12 288 bytes)
         const uint32_t *kk = lb.keys + range.x;
         const int wsh = lb.fbits + 9;                                  // a word's bucket sits above fraction and position
         const uint32_t kmask = (1u << (lb.dbits + lb.fbits)) - 1u;     // (dbits <= 7, fbits <= 16: the word fits 32 bits)
@@ -487,6 +488,7 @@ __device__ __forceinline__ bool local_order_tile(const LocalBin &lb, const uint2
                 }
                 rank[u] = min(r, (uint32_t)(n - 1));   // (a permutation of 0 .. n - 1 whenever the keys are what the passes leave; in bounds whatever they are)
                 s_byrank[rank[u]] = w[u];
+                s_idr[rank[u]] = g[u];
             }
         }
         __syncthreads();
@@ -500,14 +502,14 @@ __device__ __forceinline__ bool local_order_tile(const LocalBin &lb, const uint2
         __syncthreads();
 #pragma unroll
         for (int u = 0; u < 2; u++)
-            if (tied[u]) {   // the group [a, b) of ranks around mine, in (depth bits, position) order
-                const uint32_t r = rank[u], f = w[u] >> 9, mine = s_depth[r], at = w[u] & 0x1FFu;
+            if (tied[u]) {   // the group [a, b) of ranks around mine, in (depth bits, Gaussian id) order
+                const uint32_t r = rank[u], f = w[u] >> 9, mine = s_depth[r];
                 uint32_t a = r, b = r + 1u, below = 0u;
                 while (a > 0u && (s_byrank[a - 1u] >> 9) == f) a--;
                 while (b < (uint32_t)n && (s_byrank[b] >> 9) == f) b++;
                 for (uint32_t k = a; k < b; k++) {
-                    const uint32_t dk = s_depth[k], pk = s_byrank[k] & 0x1FFu;
-                    below += (dk < mine || (dk == mine && pk < at)) ? 1u : 0u;
+                    const uint32_t dk = s_depth[k];
+                    below += (dk < mine || (dk == mine && s_idr[k] < g[u])) ? 1u : 0u;
                 }
                 rank[u] = a + below;
             }
@@ -570,22 +572,36 @@ __device__ __forceinline__ bool local_order_tile(const LocalBin &lb, const uint2
         }
         __syncthreads();
         mark(7);   // the network
-        uint32_t g[LOCAL_MAX / TILE_PIX], slot[LOCAL_MAX / TILE_PIX];
+        // The network orders equal depth bits by position; entries of a tie group — neighbours with the same depth bits — are ranked again by
+        // Gaussian id, which is the position order behind stable passes and does not depend on the arrival order (as in the branch above).
+        uint32_t g[LOCAL_MAX / TILE_PIX], slot[LOCAL_MAX / TILE_PIX], to[LOCAL_MAX / TILE_PIX];
 #pragma unroll
         for (int u = 0; u < LOCAL_MAX / TILE_PIX; u++) {
             const int i = u * TILE_PIX + tid;
             const int from = i < n ? (int)((uint32_t)s_key[i] & (uint32_t)(LOCAL_MAX - 1)) : 0;
             g[u] = s_gid[from];
             slot[u] = s_slot[from];
+            to[u] = (uint32_t)i;
+            if (i < n) {
+                const uint32_t d = (uint32_t)(s_key[i] >> 32);
+                if ((i > 0 && (uint32_t)(s_key[i - 1] >> 32) == d) || (i + 1 < n && (uint32_t)(s_key[i + 1] >> 32) == d)) {
+                    int a = i, b = i + 1;
+                    while (a > 0 && (uint32_t)(s_key[a - 1] >> 32) == d) a--;
+                    while (b < n && (uint32_t)(s_key[b] >> 32) == d) b++;
+                    uint32_t below = 0u;
+                    for (int k = a; k < b; k++) below += s_gid[(uint32_t)s_key[k] & (uint32_t)(LOCAL_MAX - 1)] < g[u] ? 1u : 0u;
+                    to[u] = (uint32_t)a + below;
+                }
+            }
         }
         __syncthreads();
 #pragma unroll
         for (int u = 0; u < LOCAL_MAX / TILE_PIX; u++) {
             const int i = u * TILE_PIX + tid;
             if (i < n) {
-                s_gid[i] = g[u];
-                pl[i] = g[u];
-                sl[i] = slot[u];
+                s_gid[to[u]] = g[u];
+                pl[to[u]] = g[u];
+                sl[to[u]] = slot[u];
             }
         }
         __syncthreads();

@@ -317,7 +317,7 @@ int launch_binning_scan_emit(int P, int64_t I, const int32_t *radii, char *geom,
 // I = capacity of the binning buffer; the true instance count is read by the kernels from geom + L.g_count
 int launch_binning(int P, int64_t I, int W, int H, const int32_t *radii, char *geom, char *binning, char *img, const Layout &L,
                    bool fused_scan, uint32_t *host_late, uint32_t tag, bool debug, hipStream_t s, uint32_t **dead_keys, uint32_t *emit_slot,
-                   uint32_t *seg_host_flag, uint32_t seg_flag_value, bool local_finish) {
+                   uint32_t *seg_host_flag, uint32_t seg_flag_value, bool local_finish, bool cells) {
     const uint32_t *n_ptr = (const uint32_t *)(geom + L.g_count);
     (void)W; (void)H;
     uint2 *ranges = (uint2 *)(img + L.pub.ranges);  // zeroed by preprocess_kernel
@@ -342,6 +342,11 @@ int launch_binning(int P, int64_t I, int W, int H, const int32_t *radii, char *g
 #endif
     if (onesweep) {
         uint32_t *kfinal = nullptr;
+        if (cells && local_finish && L.dbits > 0 && !emit_slot) {   // the cells plan: no chain, ranges and self-check word from its finish (cell_sort.hip)
+            const int rc0 = launch_cell_sort(I, geom, binning, img, L, &kfinal, host_late, tag, seg_host_flag, seg_flag_value, debug, s);
+            if (!rc0 && dead_keys) *dead_keys = kfinal;
+            return rc0;
+        }
         int rc1 = launch_onesweep_partition(I, geom, binning, L, &kfinal, debug, s, emit_slot ? emit_slot + 64 : nullptr, emit_slot);
         if (rc1) return rc1;
         if (dead_keys) *dead_keys = kfinal;   // the tile keys are dead once tile_ranges_kernel has run

@@ -682,7 +682,7 @@ typedef struct {
 typedef struct {
     int32_t P, W, H, ntiles, tbits, tile_passes;   /* tbits: bits of a tile id; tile_passes = (tbits + 7) / 8 */
     uint32_t too_long, want_bits;                  /* the two mailbox words as read before the forward (0: not raised) */
-    int32_t forced;                                /* DAS3R_BINNING: 0 unset, 1 local, -1 radix, 2 seg, 3 seg3, 4 bucket */
+    int32_t forced;                                /* DAS3R_BINNING: 0 unset, 1 local, -1 radix, 2 seg, 3 seg3, 4 bucket, 5 cells */
     int32_t onesweep;                              /* 1 except with DAS3R_SORT=classic of an experiments build */
     int64_t capacity_hint;                         /* das3r_raster_args.capacity_hint */
     int32_t capacity_exact;                        /* DAS3R_CAPACITY=exact */
@@ -692,6 +692,8 @@ typedef struct {
                                                       seg == 2: segmented emission and passes, the lists finished by the compositing kernel */
     int32_t speculate, decide_fine;
     uint32_t gen;
+    int32_t cells;                                 /* with seg == 2: the instances are partitioned by reserved ranges and finished per cell
+                                                      (csrc/cell_sort.hip) instead of by the stable passes; in what used to be padding */
     int64_t cap;                                   /* with speculate */
 } das3r_path_policy_plan;
 void das3r_debug_path_policy_fresh(das3r_path_policy_state *state, uint32_t gen);   /* the state of a thread that has met no shape */

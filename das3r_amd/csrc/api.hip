@@ -398,6 +398,28 @@ static int refuse_bwd_without_invdepth(const char *who) {
     return DAS3R_ERR_INVALID_ARG;
 }
 
+// The nine-float rows of partial sums, one per instance, + 16 bytes (the per-Gaussian backward reads the rows of a workgroup as 16-byte words up
+// to the boundary above the last row); rows_aligned: the same rounded up — where whatever a call keeps behind the rows starts.
+static size_t rows_bytes(int64_t capacity) { return (capacity > 0 ? (size_t)capacity : 1) * 9 * sizeof(float) + 16; }
+static size_t rows_aligned(int64_t capacity) { return align_up(rows_bytes(capacity)); }
+static float *behind_rows(float *scratch, const Layout &L) { return (float *)((char *)scratch + rows_aligned(L.capacity)); }
+
+// What the backward entries that end in launch_preprocess_backward do first: the refusals in their order, then the saved buffers' layout.
+// P == 0: DAS3R_OK at once, *L untouched.  binning_first: a missing binning buffer is refused before the binning self-check, not after it.
+static int backward_prologue(const char *who, const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_saved *saved, const float *dL_dpix,
+                             bool depth_pass, const float *dL_dinvdepth, const das3r_raster_grads *g, bool binning_first, das3r_stream_t stream, Layout *L) {
+    int rc = validate(a, in);
+    if (rc || a->P == 0) return rc;
+    if ((rc = backward_validate(who, in, saved, dL_dpix, depth_pass, dL_dinvdepth, g))) return rc;
+    if (depth_pass && (rc = refuse_bwd_without_invdepth(who))) return rc;
+    const bool no_binning = saved->num_rendered > 0 && !saved->binning;
+    // the forward's binning self-check first: nothing is launched on the strength of an invalid image / list
+    if (!(no_binning && binning_first) && (rc = das3r_raster_check(saved, stream))) return rc;
+    if (no_binning) { set_error("%s: binning buffer missing", who); return DAS3R_ERR_INVALID_ARG; }
+    *L = saved_layout(a, saved, shjac_saved(a, in, saved));
+    return DAS3R_OK;
+}
+
 // The backward pass of das3r_raster_backward (depth_pass false), das3r_raster_backward_depth (true) and das3r_raster_backward_focal (either,
 // with `focal`): the launches of the first two are what they were, the third puts one per-Gaussian kernel and its finish between the
 // compositing passes (+ the depth fold) and the per-Gaussian backward — before grads->chain's Adam step touches the parameters it reads.
@@ -411,28 +433,22 @@ static int refuse_bwd_without_invdepth(const char *who) {
 static int backward_body(const char *who, const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_saved *saved, const float *dL_dpix,
                          bool depth_pass, const float *dL_dinvdepth, const das3r_raster_grads *g, const FocalOut *focal, das3r_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
-    int rc = validate(a, in);
+    Layout L;
+    int rc = backward_prologue(who, a, in, saved, dL_dpix, depth_pass, dL_dinvdepth, g, false, stream, &L);
     if (rc) return rc;
     const int P = a->P;
     if (P == 0) {
         if (focal) HIP_TRY(hipMemsetAsync(focal->sums, 0, 2 * sizeof(float), s));   // (per_splat has no element)
         return DAS3R_OK;
     }
-    if ((rc = backward_validate(who, in, saved, dL_dpix, depth_pass, dL_dinvdepth, g))) return rc;
-    if (depth_pass && (rc = refuse_bwd_without_invdepth(who))) return rc;
-    // the forward's binning self-check first: nothing is launched on the strength of an invalid image / list
-    if ((rc = das3r_raster_check(saved, stream))) return rc;
-    const Layout L = saved_layout(a, saved, shjac_saved(a, in, saved));
     // scratch = per-instance partial sums [num_rendered, 9]; no accumulator needs zeroing (no atomics anywhere)
     float *partial = g->scratch;
     const float *dz = nullptr;
     bool quad_rows = false;
     if (saved->num_rendered > 0) {
-        if (!saved->binning) { set_error("%s: binning buffer missing", who); return DAS3R_ERR_INVALID_ARG; }
         if ((rc = launch_render_backward(a, dL_dpix, saved->geom, saved->binning, saved->img, L, partial, s, &quad_rows, saved->num_rendered, saved->flags))) return rc;
         if (depth_pass) {
-            const size_t c = L.capacity > 0 ? (size_t)L.capacity : 1;
-            float *partial_depth = (float *)((char *)g->scratch + align_up(c * 9 * sizeof(float) + 16));
+            float *partial_depth = behind_rows(g->scratch, L);
             if ((rc = launch_depth_pass_inputs(P, a->image_width * a->image_height, saved->geom, L, saved->binning, dL_dinvdepth, s, a->debug != 0))) return rc;
             Layout Ld = L;   // the depth pass reads its splat records and checkpoints from the binning buffer's depth part
             Ld.pub.xy = L.d_recs;
@@ -488,19 +504,16 @@ extern "C" int das3r_raster_backward_focal(const das3r_raster_args *a, const das
 
 // das3r_raster_backward_scratch_bytes' rows twice: the colour pass's and the depth pass's (whose first column is the per-instance depth sum)
 extern "C" size_t das3r_raster_backward_depth_scratch_bytes(int64_t capacity) {
-    const size_t c = capacity > 0 ? (size_t)capacity : 1;
-    return align_up(c * 9 * sizeof(float) + 16) + c * 9 * sizeof(float) + 16;
+    return rows_aligned(capacity) + rows_bytes(capacity);
 }
 
-// One 36-byte row of partial sums per instance + 16 bytes (the per-Gaussian backward reads the rows of a workgroup as 16-byte
-// words up to the boundary above the last row).  (The experimental stream kernel — EXPERIMENTS=1 builds, DAS3R_RENDER_BWD=stream —
-// needs up to four 48-byte rows per instance: only then is the larger figure returned.)
+// rows_bytes.  (The experimental stream kernel — EXPERIMENTS=1 builds, DAS3R_RENDER_BWD=stream — needs up to four 48-byte rows per
+// instance: only then is the larger figure returned.)
 extern "C" size_t das3r_raster_backward_scratch_bytes(int64_t capacity) {
-    const size_t c = capacity > 0 ? (size_t)capacity : 1;
 #ifdef DAS3R_EXPERIMENTS
-    if (switches().render_bwd == BWD_STREAM) return std::max(c * 9 * sizeof(float) + 16, stream_scratch_bytes(capacity));
+    if (switches().render_bwd == BWD_STREAM) return std::max(rows_bytes(capacity), stream_scratch_bytes(capacity));
 #endif
-    return c * 9 * sizeof(float) + 16;
+    return rows_bytes(capacity);
 }
 
 // ---- extra per-Gaussian channels over a forward's saved lists (render_aux.hip) ----
@@ -560,7 +573,7 @@ extern "C" int das3r_raster_aux_adjoint(const das3r_raster_args *a, const das3r_
 // antialiasing flag).  Scratch: the nine-float rows as das3r_raster_backward_scratch_bytes rounds them, then the feature rows.
 extern "C" size_t das3r_raster_aux_backward_scratch_bytes(int64_t capacity, int32_t C) {
     const size_t c = capacity > 0 ? (size_t)capacity : 1, ch = C > 0 ? (size_t)C : 0;
-    return align_up(c * 9 * sizeof(float) + 16) + c * ch * sizeof(float) + 16;
+    return rows_aligned(capacity) + c * ch * sizeof(float) + 16;
 }
 
 extern "C" int das3r_raster_aux_backward(const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_saved *saved, int32_t C,
@@ -575,19 +588,13 @@ extern "C" int das3r_raster_aux_backward(const das3r_raster_args *a, const das3r
     if (C > 0 && (!dL_dout || (a->P > 0 && !features))) { set_error("%s: null features / dL_dout with C = %d channels", who, C); return DAS3R_ERR_INVALID_ARG; }
     if (g->chain) { set_error("%s: grads->chain is not supported here (the chained backward belongs to the colour loss)", who); return DAS3R_ERR_INVALID_ARG; }
     if (!g->scratch) { set_error("%s: null scratch (das3r_raster_aux_backward_scratch_bytes)", who); return DAS3R_ERR_INVALID_ARG; }
-    int rc = validate(a, in);
-    if (rc) return rc;
+    Layout L;
+    int rc = backward_prologue(who, a, in, saved, /*dL_dpix: not this entry's*/ g->scratch, false, nullptr, g, true, stream, &L);
     const int P = a->P, W = a->image_width, H = a->image_height;
-    if (P == 0) return DAS3R_OK;   // no gradient has a row
-    if ((rc = backward_validate(who, in, saved, /*dL_dpix: not this entry's*/ reinterpret_cast<const float *>(g->scratch), false, nullptr, g))) return rc;
-    if (saved->num_rendered > 0 && !saved->binning) { set_error("%s: binning buffer missing", who); return DAS3R_ERR_INVALID_ARG; }
-    // the forward's binning self-check first: nothing is launched on the strength of an invalid image / list
-    if ((rc = das3r_raster_check(saved, stream))) return rc;
-    const Layout L = saved_layout(a, saved, shjac_saved(a, in, saved));
+    if (rc || P == 0) return rc;   // (P == 0: no gradient has a row)
     float *partial = g->scratch;
     if (saved->num_rendered > 0) {
-        const size_t c = L.capacity > 0 ? (size_t)L.capacity : 1;
-        float *partial_f = dL_dfeatures ? (float *)((char *)g->scratch + align_up(c * 9 * sizeof(float) + 16)) : nullptr;
+        float *partial_f = dL_dfeatures ? behind_rows(g->scratch, L) : nullptr;
         if ((rc = launch_render_aux_backward(P, W, H, C, features, dL_dout, dL_dalpha, partial, partial_f, saved->geom, saved->binning, saved->img, L,
                                              a->debug != 0, s))) return rc;
         if (dL_dfeatures && (rc = launch_aux_gather(P, C, partial_f, dL_dfeatures, saved->geom, L, a->debug != 0, s))) return rc;
@@ -625,8 +632,7 @@ extern "C" int das3r_raster_distortion_forward(const das3r_raster_args *a, const
 
 // the nine-float rows as das3r_raster_backward_scratch_bytes rounds them, then dz: one float per Gaussian
 extern "C" size_t das3r_raster_distortion_backward_scratch_bytes(int64_t capacity, int32_t P) {
-    const size_t c = capacity > 0 ? (size_t)capacity : 1, p = P > 0 ? (size_t)P : 0;
-    return align_up(c * 9 * sizeof(float) + 16) + p * sizeof(float) + 16;
+    return rows_aligned(capacity) + (P > 0 ? (size_t)P : 0) * sizeof(float) + 16;
 }
 
 extern "C" int das3r_raster_distortion_backward(const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_saved *saved,
@@ -637,20 +643,14 @@ extern "C" int das3r_raster_distortion_backward(const das3r_raster_args *a, cons
     if (!dL_ddist || !totals) { set_error("%s: null dL_ddist / totals plane (das3r_raster_distortion_forward writes it)", who); return DAS3R_ERR_INVALID_ARG; }
     if (g->chain) { set_error("%s: grads->chain is not supported here (the chained backward belongs to the colour loss)", who); return DAS3R_ERR_INVALID_ARG; }
     if (!g->scratch) { set_error("%s: null scratch (das3r_raster_distortion_backward_scratch_bytes)", who); return DAS3R_ERR_INVALID_ARG; }
-    int rc = validate(a, in);
-    if (rc) return rc;
+    Layout L;
+    int rc = backward_prologue(who, a, in, saved, /*dL_dpix: not this entry's*/ dL_ddist, false, nullptr, g, true, stream, &L);
     const int P = a->P, W = a->image_width, H = a->image_height;
-    if (P == 0) return DAS3R_OK;   // no gradient has a row
-    if ((rc = backward_validate(who, in, saved, /*dL_dpix: not this entry's*/ dL_ddist, false, nullptr, g))) return rc;
-    if (saved->num_rendered > 0 && !saved->binning) { set_error("%s: binning buffer missing", who); return DAS3R_ERR_INVALID_ARG; }
-    // the forward's binning self-check first: nothing is launched on the strength of an invalid image / list
-    if ((rc = das3r_raster_check(saved, stream))) return rc;
-    const Layout L = saved_layout(a, saved, shjac_saved(a, in, saved));
+    if (rc || P == 0) return rc;   // (P == 0: no gradient has a row)
     float *partial = g->scratch;
     const float *dz = nullptr;
     if (saved->num_rendered > 0) {
-        const size_t c = L.capacity > 0 ? (size_t)L.capacity : 1;
-        float *dzw = (float *)((char *)g->scratch + align_up(c * 9 * sizeof(float) + 16));
+        float *dzw = behind_rows(g->scratch, L);
         if ((rc = launch_render_distortion_backward(P, W, H, dL_ddist, totals, partial, saved->geom, saved->binning, saved->img, L, a->debug != 0, s))) return rc;
         if ((rc = launch_distortion_fold(P, saved->geom, L, partial, dzw, a->debug != 0, s))) return rc;
         dz = dzw;

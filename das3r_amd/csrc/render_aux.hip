@@ -13,10 +13,7 @@
 // scales, rotations or opacities (that gradient is render_aux_bwd.hip's, a back-to-front replay).  That is also why the adjoint needs no
 // back-to-front replay: w = alpha T depends only on what lies in front, so both kernels take the same front-to-back walk.
 //
-// Decomposition of render_common.h: one 256-lane workgroup per 16x16 tile, one wave64 per 8x8 quadrant, the list staged through LDS
-// in batches of 256, every wave culling a batch against its quadrant with a ballot.  A pixel takes part in list position k iff
-// k < n_contrib[pixel] — the forward's own stop, not a re-derived T < 1e-4 — and alpha is pair_alpha's, the expression and the two
-// tests of every compositing kernel.
+// The walk — tile, quadrant and pixel, the staged batches, the cull, the early-outs — is render_lists.h's; a kernel here is its per-pair body.
 //
 // Few tiles with long lists (the DAS3R training shape: 416 tiles of ~11 k entries) leave one workgroup per tile at 1.6 waves per SIMD, so
 // both kernels have a second form for them (aux_long_lists: the rule of kernel_choice.h quad_lanes, on the instance count):
@@ -32,88 +29,64 @@
 // column (an entry is visited at most once per wave and batch), the four columns are added in the order 0, 1, 2, 3 and the row goes
 // to partial[emission slot][C]; aux_gather_kernel then adds a Gaussian's consecutive rows in index order.  No floating-point atomics,
 // no unordered LDS adds: bit-identical from run to run.
-#include "render_common.h"
+#include "render_lists.h"
 #include <algorithm>
 
 namespace das3r {
 
-// lanes of wave `wave`: the largest n_contrib among them (uniform)
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
-    return v;
-}
-
 template <int C, bool SPLIT>
-__global__ void __launch_bounds__(256) render_aux_forward_kernel(
-    const uint2 *__restrict__ ranges, const uint32_t *__restrict__ point_list, int W, int H, int tiles_x, int ntiles_strip /*render_common.h pack_tiles*/,
-    const float4 *__restrict__ xyh, const float4 *__restrict__ conic_opacity, const uint32_t *__restrict__ n_contrib,
-    const float *__restrict__ feat /*[P,C]*/, float *__restrict__ out /*[C,H,W]*/, uint32_t last_g, uint32_t cap, int tile_blocks /*SPLIT: xcd_grid, the blocks of one quadrant*/) {
+__global__ void __launch_bounds__(256) render_aux_forward_kernel(const ListArgs a, const float *__restrict__ feat /*[P,C]*/, float *__restrict__ out /*[C,H,W]*/,
+                                                                 int tile_blocks /*SPLIT: xcd_grid, the blocks of one quadrant*/) {
     __shared__ float4 s_xyh[TILE_PIX], s_co[TILE_PIX];
     __shared__ float s_f[TILE_PIX * C];   // row j = the feature row of staged entry j (wave-uniform reads: broadcasts)
-    __shared__ uint32_t s_max[4];
     __shared__ float s_T[SPLIT ? 4 * WAVE : 1];   // SPLIT: every wave's transmittance over its quarter of the batch, per pixel
 
-    // SPLIT: block b is quadrant b / tile_blocks of the tile of block b % tile_blocks (the four on one XCD: tile_blocks is a multiple of 8)
-    const int tile = xcd_tile(SPLIT ? (int)(blockIdx.x % (unsigned)tile_blocks) : (int)blockIdx.x, ntiles_strip, tiles_x);
-    if (tile < 0) return;
-    const int tid = threadIdx.x, lane = __lane_id(), wave = tid >> 6;
-    const int quad = SPLIT ? (int)(blockIdx.x / (unsigned)tile_blocks) : wave;   // the 8x8 quadrant this wave's lanes are the pixels of
-    const int bx = tile % tiles_x, by = tile / tiles_x;
-    int px, py;
-    quadrant_pixel(bx, by, quad, lane, px, py);
-    const bool inside = px < W && py < H;
-    const float pxf = (float)px, pyf = (float)py;
-    const float qcx = (float)(bx * TILE_X + ((quad & 1) << 3)) + 3.5f, qcy = (float)(by * TILE_Y + ((quad >> 1) << 3)) + 3.5f;
-    const uint2 range = safe_range(ranges[tile], cap);
-    const size_t pix = (size_t)py * W + px, plane = (size_t)H * W;
-    const uint32_t last_contributor = inside ? n_contrib[pix] : 0u;
-
-    // no pixel of the tile blended anything past list position max_contrib; no pixel of this wave past wmax
-    const uint32_t wmax = wave_max_u32(last_contributor);
-    if (lane == 0) s_max[wave] = wmax;
-    __syncthreads();
-    const uint32_t max_contrib = min(max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3])), range.y - range.x);   // (SPLIT: the four are equal)
-    const int rounds = ((int)max_contrib + TILE_PIX - 1) / TILE_PIX;
+    // SPLIT: block b is quadrant b / tile_blocks of the tile of block b % tile_blocks (the four on one XCD: tile_blocks is a multiple of 8);
+    // the four waves' max_contrib are then equal
+    const int lane = __lane_id(), wave = threadIdx.x >> 6;
+    const TileLane t = tile_lane(a, SPLIT ? (int)(blockIdx.x % (unsigned)tile_blocks) : (int)blockIdx.x, SPLIT ? (int)(blockIdx.x / (unsigned)tile_blocks) : wave);
+    if (t.tile < 0) return;
+    const size_t plane = (size_t)a.H * a.W;
+    const auto features = [&](const int j, const uint32_t g) {
+#pragma unroll
+        for (int c = 0; c < C; c++) s_f[j * C + c] = feat[(size_t)g * C + c];
+    };
 
     float T = 1.0f, acc[C];
 #pragma unroll
     for (int c = 0; c < C; c++) acc[c] = 0.f;
 
-    for (int i = 0; i < rounds; i++) {
-        const int done_before = i * TILE_PIX;
-        const int n = min(TILE_PIX, (int)max_contrib - done_before);
-        if (i > 0) __syncthreads();   // the previous batch (and its s_T) has been read by every wave
-        if (tid < n) {
-            const uint32_t g = min(point_list[range.x + done_before + tid], last_g);
-            s_xyh[tid] = xyh[(size_t)g * SPLAT_REC];
-            s_co[tid] = conic_opacity[(size_t)g * SPLAT_REC];
-#pragma unroll
-            for (int c = 0; c < C; c++) s_f[tid * C + c] = feat[(size_t)g * C + c];
-        }
-        __syncthreads();
-        if constexpr (SPLIT) {
+    if constexpr (SPLIT) {
+        const int rounds = ((int)t.max_contrib + TILE_PIX - 1) / TILE_PIX;
+        for (int i = 0; i < rounds; i++) {
+            const int done_before = i * TILE_PIX;
+            const int n = min(TILE_PIX, (int)t.max_contrib - done_before);
+            if (i > 0) __syncthreads();   // the previous batch (and its s_T) has been read by every wave
+            stage_batch<false>(a, t.range.x + (uint32_t)done_before, n, s_xyh, s_co, nullptr, features);
+            __syncthreads();
             // this wave's quarter of the batch, blended from T = 1: (Tseg, seg[]) — then composed with the quarters in front of it
             float Tseg = 1.0f, seg[C];
 #pragma unroll
             for (int c = 0; c < C; c++) seg[c] = 0.f;
+            // (its own loop over the one mask, on the per-lane copy of the wave's last position: on the shared walk's loop and the scalar
+            // t.wmax this kernel, alone of the five, came out 2 - 4 % slower on the training shape — docs/ledger.md (cs))
             const int s = wave * WAVE + lane;
-            uint64_t m = __ballot(s < n && quadrant_hit(s_xyh[s], qcx, qcy));
+            uint64_t m = __ballot(s < n && quadrant_hit(s_xyh[s], t.qcx, t.qcy));
             while (m != 0ull) {
                 const int j = wave * WAVE + __builtin_ctzll(m);
                 m &= m - 1ull;
                 const uint32_t position = (uint32_t)(done_before + j);
-                if (position >= wmax) break;
+                if (position >= t.wmax_lanes) break;
                 const float4 p = s_xyh[j];
                 const float4 co = s_co[j];
                 float dx, dy, G, alpha;
-                const bool active = pair_alpha(p.x, p.y, co, pxf, pyf, dx, dy, G, alpha) & (position < last_contributor);
+                const bool active = pair_alpha(p.x, p.y, co, t.pxf, t.pyf, dx, dy, G, alpha) & (position < t.last_contributor);
                 if (__ballot(active) == 0ull) continue;
-                const float a = active ? alpha : 0.f;
-                const float wT = a * Tseg;
+                const float al = active ? alpha : 0.f;
+                const float wT = al * Tseg;
 #pragma unroll
                 for (int c = 0; c < C; c++) seg[c] = __fmaf_rn(s_f[j * C + c], wT, seg[c]);
-                Tseg = Tseg * (1.0f - a);
+                Tseg = Tseg * (1.0f - al);
             }
             s_T[wave * WAVE + lane] = Tseg;
             __syncthreads();
@@ -126,50 +99,29 @@ __global__ void __launch_bounds__(256) render_aux_forward_kernel(
             }
 #pragma unroll
             for (int c = 0; c < C; c++) acc[c] = __fmaf_rn(Tstart, seg[c], acc[c]);
-        } else {
-            if ((uint32_t)done_before >= wmax) continue;   // (wave-uniform; the barriers above are still taken by every wave)
-            uint64_t masks[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const int s = k * 64 + lane;
-                masks[k] = __ballot(s < n && quadrant_hit(s_xyh[s], qcx, qcy));
-            }
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                uint64_t m = masks[k];
-                while (m != 0ull) {
-                    const int j = k * 64 + __builtin_ctzll(m);
-                    m &= m - 1ull;
-                    const uint32_t position = (uint32_t)(done_before + j);   // 0-based list position
-                    if (position >= wmax) break;                             // (uniform: the bits come in list order)
-                    const float4 p = s_xyh[j];
-                    const float4 co = s_co[j];
-                    float dx, dy, G, alpha;
-                    const bool active = pair_alpha(p.x, p.y, co, pxf, pyf, dx, dy, G, alpha) & (position < last_contributor);
-                    if (__ballot(active) == 0ull) continue;
-                    const float a = active ? alpha : 0.f;
-                    const float wT = a * T;
-#pragma unroll
-                    for (int c = 0; c < C; c++) acc[c] = __fmaf_rn(s_f[j * C + c], wT, acc[c]);
-                    T = T * (1.0f - a);
-                }
-            }
         }
-    }
-    if constexpr (SPLIT) {
         // the four waves' sums of the same 64 pixels, added in wave order (s_f is free: 4 x 64 x C floats)
         __syncthreads();
 #pragma unroll
         for (int c = 0; c < C; c++) s_f[(wave * C + c) * WAVE + lane] = acc[c];
         __syncthreads();
-        if (wave == 0 && inside) {
+        if (wave == 0 && t.inside) {
 #pragma unroll
             for (int c = 0; c < C; c++)
-                out[(size_t)c * plane + pix] = ((s_f[c * WAVE + lane] + s_f[(C + c) * WAVE + lane]) + s_f[(2 * C + c) * WAVE + lane]) + s_f[(3 * C + c) * WAVE + lane];
+                out[(size_t)c * plane + t.pix] = ((s_f[c * WAVE + lane] + s_f[(C + c) * WAVE + lane]) + s_f[(2 * C + c) * WAVE + lane]) + s_f[(3 * C + c) * WAVE + lane];
         }
-    } else if (inside) {
+    } else {
+        walk_list_front_to_back(a, t, s_xyh, s_co, features, [&](const int j, uint32_t, const bool active, const float alpha, float, float, float) {
+            const float al = active ? alpha : 0.f;
+            const float wT = al * T;
 #pragma unroll
-        for (int c = 0; c < C; c++) out[(size_t)c * plane + pix] = acc[c];
+            for (int c = 0; c < C; c++) acc[c] = __fmaf_rn(s_f[j * C + c], wT, acc[c]);
+            T = T * (1.0f - al);
+        });
+        if (t.inside) {
+#pragma unroll
+            for (int c = 0; c < C; c++) out[(size_t)c * plane + t.pix] = acc[c];
+        }
     }
 }
 
@@ -188,117 +140,66 @@ __device__ __forceinline__ float aux_reduce(const float v[C], const int lane) {
 }
 
 template <int C>
-__global__ void __launch_bounds__(256) render_aux_adjoint_kernel(
-    const uint2 *__restrict__ ranges, const uint32_t *__restrict__ point_list, int W, int H, int tiles_x, int ntiles_strip,
-    const float4 *__restrict__ xyh, const float4 *__restrict__ conic_opacity, const uint32_t *__restrict__ n_contrib,
-    const float *__restrict__ dL_dout /*[C,H,W]*/, const uint32_t *__restrict__ slot_list, float *__restrict__ partial /*[capacity,C]*/,
-    uint32_t last_g, uint32_t cap, const float4 *__restrict__ ckpt /*the forward's checkpoints of long lists; read when gridDim.y > 1*/) {
+__global__ void __launch_bounds__(256) render_aux_adjoint_kernel(const ListArgs a, const float *__restrict__ dL_dout /*[C,H,W]*/, float *__restrict__ partial /*[capacity,C]*/,
+                                                                 const float4 *__restrict__ ckpt /*the forward's checkpoints of long lists; read when gridDim.y > 1*/) {
     __shared__ float4 s_xyh[TILE_PIX], s_co[TILE_PIX];
     __shared__ uint32_t s_slot[TILE_PIX];      // emission slot of every staged entry = its row of `partial`
     __shared__ float col[4][TILE_PIX * C];     // col[wave][j * C + c]: the wave's sum for staged entry j, channel c
-    __shared__ uint32_t s_max[4];
 
-    const int tile = xcd_tile(blockIdx.x, ntiles_strip, tiles_x);
-    if (tile < 0) return;
     const int tid = threadIdx.x, lane = __lane_id(), wave = tid >> 6;
-    const int bx = tile % tiles_x, by = tile / tiles_x;
-    int px, py;
-    quadrant_pixel(bx, by, wave, lane, px, py);
-    const bool inside = px < W && py < H;
-    const float pxf = (float)px, pyf = (float)py;
-    const float qcx = (float)(bx * TILE_X + ((wave & 1) << 3)) + 3.5f, qcy = (float)(by * TILE_Y + ((wave >> 1) << 3)) + 3.5f;
-    const uint2 range = safe_range(ranges[tile], cap);
-    const size_t pix = (size_t)py * W + px, plane = (size_t)H * W;
-    const uint32_t last_contributor = inside ? n_contrib[pix] : 0u;
+    const TileLane t = tile_lane(a, blockIdx.x, wave);
+    if (t.tile < 0) return;
+    const size_t plane = (size_t)a.H * a.W;
     float g[C];
 #pragma unroll
-    for (int c = 0; c < C; c++) g[c] = inside ? dL_dout[(size_t)c * plane + pix] : 0.f;
+    for (int c = 0; c < C; c++) g[c] = t.inside ? dL_dout[(size_t)c * plane + t.pix] : 0.f;
 
-    const uint32_t wmax = wave_max_u32(last_contributor);
-    if (lane == 0) s_max[wave] = wmax;
-    __syncthreads();
-    const uint32_t len = range.y - range.x;
-    const uint32_t tile_contrib = min(max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3])), len);
     // which total this lane holds after aux_reduce
     const bool writer = C == 1 ? lane == 63 : ((lane & 7) == 0 && (lane >> 3) < C);
     const int widx = C == 1 ? 0 : (lane >> 3);
     // bucket-parallel launch (gridDim.y > 1): this workgroup takes the buckets blockIdx.y, + gridDim.y, .. of the tile's list — [lo, hi) each
     const int slices = (int)gridDim.y;
-    const int nbuckets = slices > 1 ? max(ckpt_buckets(range), 1) : 1;
-    const int cpix = (py - by * TILE_Y) * TILE_X + (px - bx * TILE_X);   // the pixel's place in a checkpoint slot
+    const int nbuckets = slices > 1 ? max(ckpt_buckets(t.range), 1) : 1;
+    const int cpix = (t.py - t.by * TILE_Y) * TILE_X + (t.px - t.bx * TILE_X);   // the pixel's place in a checkpoint slot
 
     for (int bk = (int)blockIdx.y; bk < nbuckets; bk += slices) {
-    const uint32_t lo = slices > 1 ? (uint32_t)bk * BUCKET : 0u;
-    const uint32_t hi = slices > 1 ? min(len, lo + BUCKET) : len;
-    const uint32_t max_contrib = tile_contrib > lo ? min(tile_contrib, hi) - lo : 0u;   // entries of the bucket some pixel reaches (its first ones)
-    const int rounds = ((int)max_contrib + TILE_PIX - 1) / TILE_PIX;
+        const uint32_t lo = slices > 1 ? (uint32_t)bk * BUCKET : 0u;
+        const uint32_t hi = slices > 1 ? min(t.len, lo + BUCKET) : t.len;
+        const uint32_t max_contrib = t.max_contrib > lo ? min(t.max_contrib, hi) - lo : 0u;   // entries of the bucket some pixel reaches (its first ones)
+        const int rounds = ((int)max_contrib + TILE_PIX - 1) / TILE_PIX;
 
-    // list entries beyond them are reached by no pixel of this tile: their rows are zero (cap > 0 whenever a list has entries)
-    {
-        const uint32_t ntail = (hi - lo - max_contrib) * C;
-        for (uint32_t f = tid; f < ntail; f += TILE_PIX) {
-            const uint32_t t = f / C, q = f - t * C;
-            partial[(size_t)min(slot_list[range.x + lo + max_contrib + t], cap - 1u) * C + q] = 0.f;
+        zero_unreached_rows<C>(a, partial, t.range.x + lo + max_contrib, hi - lo - max_contrib);
+        if (max_contrib == 0u) continue;   // (uniform)
+
+        // T in front of the bucket: the forward's own, from its checkpoint (a pixel outside the image has none and blends nothing)
+        float T = (bk > 0 && t.inside) ? ckpt_slot(const_cast<float4 *>(ckpt), t.range, t.tile, bk - 1)[cpix].x : 1.0f;
+        for (int i = 0; i < rounds; i++) {
+            const int done_before = i * TILE_PIX;
+            const int n = min(TILE_PIX, (int)max_contrib - done_before);
+            stage_batch<false>(a, t.range.x + lo + (uint32_t)done_before, n, s_xyh, s_co, s_slot, NoPayload());
+            // every wave zeroes its own column: an entry the wave does not visit (culled, past its pixels' stops) contributes exactly 0
+            for (int f = lane; f < TILE_PIX * C; f += WAVE) col[wave][f] = 0.f;
+            __syncthreads();
+
+            walk_front_to_back(t, s_xyh, s_co, n, lo + (uint32_t)done_before, [&](const int j, uint32_t, const bool active, const float alpha, float, float, float) {
+                const float al = active ? alpha : 0.f;
+                const float wT = al * T;
+                T = T * (1.0f - al);
+                float v[C];
+#pragma unroll
+                for (int c = 0; c < C; c++) v[c] = wT * g[c];
+                const float r = aux_reduce<C>(v, lane);
+                if (writer) col[wave][j * C + widx] = r;   // a plain store: (wave, entry) pairs are visited once
+            });
+            __syncthreads();
+            // the four waves' sums in a fixed order -> the row of the entry's emission slot
+            for (int f = tid; f < n * C; f += TILE_PIX) {
+                const int j = f / C, q = f - j * C;
+                partial[(size_t)s_slot[j] * C + q] = ((col[0][f] + col[1][f]) + col[2][f]) + col[3][f];
+            }
+            __syncthreads();
         }
     }
-    if (max_contrib == 0u) continue;   // (uniform)
-
-    // T in front of the bucket: the forward's own, from its checkpoint (a pixel outside the image has none and blends nothing)
-    float T = (bk > 0 && inside) ? ckpt_slot(const_cast<float4 *>(ckpt), range, tile, bk - 1)[cpix].x : 1.0f;
-    for (int i = 0; i < rounds; i++) {
-        const int done_before = i * TILE_PIX;
-        const int n = min(TILE_PIX, (int)max_contrib - done_before);
-        if (tid < n) {
-            const uint32_t pos = range.x + lo + done_before + tid;
-            const uint32_t gi = min(point_list[pos], last_g);
-            s_slot[tid] = min(slot_list[pos], cap - 1u);
-            s_xyh[tid] = xyh[(size_t)gi * SPLAT_REC];
-            s_co[tid] = conic_opacity[(size_t)gi * SPLAT_REC];
-        }
-        // every wave zeroes its own column: an entry the wave does not visit (culled, past its pixels' stops) contributes exactly 0
-        for (int f = lane; f < TILE_PIX * C; f += WAVE) col[wave][f] = 0.f;
-        __syncthreads();
-
-        if (lo + (uint32_t)done_before < wmax) {   // (wave-uniform)
-            uint64_t masks[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const int s = k * 64 + lane;
-                masks[k] = __ballot(s < n && quadrant_hit(s_xyh[s], qcx, qcy));
-            }
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                uint64_t m = masks[k];
-                while (m != 0ull) {
-                    const int j = k * 64 + __builtin_ctzll(m);
-                    m &= m - 1ull;
-                    const uint32_t position = lo + (uint32_t)(done_before + j);
-                    if (position >= wmax) break;
-                    const float4 p = s_xyh[j];
-                    const float4 co = s_co[j];
-                    float dx, dy, G, alpha;
-                    const bool active = pair_alpha(p.x, p.y, co, pxf, pyf, dx, dy, G, alpha) & (position < last_contributor);
-                    if (__ballot(active) == 0ull) continue;
-                    const float a = active ? alpha : 0.f;
-                    const float wT = a * T;
-                    T = T * (1.0f - a);
-                    float v[C];
-#pragma unroll
-                    for (int c = 0; c < C; c++) v[c] = wT * g[c];
-                    const float r = aux_reduce<C>(v, lane);
-                    if (writer) col[wave][j * C + widx] = r;   // a plain store: (wave, entry) pairs are visited once
-                }
-            }
-        }
-        __syncthreads();
-        // the four waves' sums in a fixed order -> the row of the entry's emission slot
-        for (int f = tid; f < n * C; f += TILE_PIX) {
-            const int j = f / C, q = f - j * C;
-            partial[(size_t)s_slot[j] * C + q] = ((col[0][f] + col[1][f]) + col[2][f]) + col[3][f];
-        }
-        __syncthreads();
-    }
-    }   // buckets
 }
 
 // dL_dfeat[i][c] (= or +=) the rows off_by_gid[i] .. + tiles_touched[i] of `partial`, added in index order; zeros for a Gaussian without
@@ -330,10 +231,6 @@ __global__ void __launch_bounds__(256) aux_gather_kernel(int P, int C, const uin
     default: { constexpr int CC = 8; WHAT; break; }     \
     }
 
-#define AUX_LISTS                                                                                                         \
-    (const uint2 *)(img + L.pub.ranges), (const uint32_t *)(binning + L.pub.point_list), W, H, L.tiles_x, pack_tiles(L),  \
-        (const float4 *)(geom + L.pub.xy), (const float4 *)(geom + L.pub.conic_opacity), (const uint32_t *)(img + L.pub.n_contrib)
-
 // few tiles, long lists (kernel_choice.h quad_lanes' shapes; from the instance COUNT: the same scene takes the same kernels however
 // its buffer was sized): the forward with four workgroups per tile, the adjoint bucket-parallel
 static bool aux_long_lists(const Layout &L, int64_t num_rendered) { return L.ntiles <= 1024 && num_rendered >= (int64_t)1024 * L.ntiles; }
@@ -341,12 +238,11 @@ static bool aux_long_lists(const Layout &L, int64_t num_rendered) { return L.nti
 int launch_render_aux_forward(int P, int W, int H, int C, const float *feat, float *out, const char *geom, const char *binning, const char *img,
                               const Layout &L, int64_t num_rendered, bool debug, hipStream_t s) {
     const int blocks = xcd_grid(L);
+    const ListArgs lists = list_args(geom, binning, img, L, W, H, P);
     if (aux_long_lists(L, num_rendered)) {
-        AUX_DISPATCH(C, DAS3R_LAUNCH((render_aux_forward_kernel<CC, true>), dim3(4 * blocks), dim3(TILE_PIX), 0, s, AUX_LISTS, feat, out, (uint32_t)(P - 1),
-                                     (uint32_t)L.capacity, blocks));
+        AUX_DISPATCH(C, DAS3R_LAUNCH((render_aux_forward_kernel<CC, true>), dim3(4 * blocks), dim3(TILE_PIX), 0, s, lists, feat, out, blocks));
     } else {
-        AUX_DISPATCH(C, DAS3R_LAUNCH((render_aux_forward_kernel<CC, false>), dim3(blocks), dim3(TILE_PIX), 0, s, AUX_LISTS, feat, out, (uint32_t)(P - 1),
-                                     (uint32_t)L.capacity, blocks));
+        AUX_DISPATCH(C, DAS3R_LAUNCH((render_aux_forward_kernel<CC, false>), dim3(blocks), dim3(TILE_PIX), 0, s, lists, feat, out, blocks));
     }
     KERNEL_CHECK(s, debug, "render_aux_forward");
     return DAS3R_OK;
@@ -356,9 +252,8 @@ int launch_render_aux_adjoint(int P, int W, int H, int C, const float *dL_dout, 
                               const char *binning, const char *img, const Layout &L, int64_t num_rendered, bool debug, hipStream_t s) {
     // slices = buckets of an average list, as the bucket-parallel backward sizes its grid (render_bwd.hip); a longer list's buckets are taken in turn
     const int slices = aux_long_lists(L, num_rendered) ? (int)std::min<int64_t>(32, std::max<int64_t>(1, num_rendered / ((int64_t)BUCKET * std::max(L.ntiles, 1)))) : 1;
-    AUX_DISPATCH(C, DAS3R_LAUNCH((render_aux_adjoint_kernel<CC>), dim3(xcd_grid(L), slices), dim3(TILE_PIX), 0, s, AUX_LISTS, dL_dout,
-                                 (const uint32_t *)(binning + L.b_slot), partial, (uint32_t)(P - 1), (uint32_t)L.capacity,
-                                 (const float4 *)(binning + L.b_ckpt)));
+    AUX_DISPATCH(C, DAS3R_LAUNCH((render_aux_adjoint_kernel<CC>), dim3(xcd_grid(L), slices), dim3(TILE_PIX), 0, s, list_args(geom, binning, img, L, W, H, P),
+                                 dL_dout, partial, (const float4 *)(binning + L.b_ckpt)));
     KERNEL_CHECK(s, debug, "render_aux_adjoint");
     DAS3R_LAUNCH(aux_gather_kernel, dim3(div_up((int64_t)P * C, 256)), dim3(256), 0, s, P, C, (const uint32_t *)(geom + L.pub.tiles_touched),
                  (const uint32_t *)(geom + L.g_off_by_gid), partial, dL_dfeat, accumulate, (uint32_t)L.capacity);

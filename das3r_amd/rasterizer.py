@@ -617,34 +617,47 @@ def _check_geometry(state, geometry):
             raise ValueError(f"geometry.{name} has {t.shape[0]} rows, the forward rasterised {state.P} Gaussians")
 
 
+def _saved_list_backward(name, scratch_bytes, call_args, state, rs, inputs, _scratch_misalign, _fill):
+    """One call of a backward over a forward's saved lists that ends in the per-Gaussian backward -> (g_means2D, g_opac, g_means3D, g_cov,
+    g_scales, g_rot).  name: the library entry (das3r_raster_aux_backward / das3r_raster_distortion_backward); scratch_bytes: what its
+    scratch takes, from its _scratch_bytes function; call_args: what it takes between the saved state and the gradient set; inputs: the
+    forward's (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)."""
+    means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp = inputs
+    device, P = state.device, state.P
+    M = sh.shape[1] if sh.numel() else 0
+    # (the colour gradient is identically zero for these losses; the per-Gaussian backward writes it all the same)
+    (g_means2D, _g_colors, g_opac, g_means3D, g_cov, _g_sh, g_scales, g_rot), g = _grad_set(device, P, M, sh.numel() > 0, cov3Ds_precomp.numel() > 0,
+                                                                                           fill=_fill)
+    if P > 0:
+        scratch, g.scratch = _scratch(scratch_bytes, device, _scratch_misalign, _fill)   # everything in it is written before it is read
+        keep = []
+        a = _fill_args(rs, P, M, device, keep)
+        i = _fill_in(means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp)
+        saved = state.saved()
+        with _on_device(device):
+            rc = getattr(_lib.load(), name)(C.byref(a), C.byref(i), C.byref(saved), *call_args, C.byref(g), _stream(device))
+        _lib.check(rc, name)
+    return g_means2D, g_opac, g_means3D, g_cov, g_scales, g_rot
+
+
 def _aux_backward_impl(state, rs, features, grad_image, grad_alpha, want_features, means3D, sh, colors_precomp, opacities, scales, rotations,
                        cov3Ds_precomp, _scratch_misalign=0, _fill=None):
     """One das3r_raster_aux_backward call: the backward of <grad_image, composite_features(features)> + <grad_alpha, alpha_of> for the forward
     that left `state` -> (g_means2D, g_opac, g_means3D, g_cov, g_scales, g_rot, g_features or None).  features [P, C <= 8] / grad_image
     [C, H, W] or both None (coverage alone); grad_alpha [1, H, W] or None.  (_fill: tests fill the scratch and every output with it first.)"""
     lib = _lib.load()
-    device, P = state.device, state.P
-    M = sh.shape[1] if sh.numel() else 0
     C_ = 0 if features is None else int(features.shape[1])
-    # (the colour gradient is identically zero for this loss; the per-Gaussian backward writes it all the same)
-    (g_means2D, _g_colors, g_opac, g_means3D, g_cov, _g_sh, g_scales, g_rot), g = _grad_set(device, P, M, sh.numel() > 0, cov3Ds_precomp.numel() > 0,
-                                                                                           fill=_fill)
-    g_feat = None
-    if want_features and C_ > 0:
-        g_feat = _new(device, _fill)(P, C_)
-    if P == 0:
-        return g_means2D, g_opac, g_means3D, g_cov, g_scales, g_rot, g_feat
-    nbytes = lib.das3r_raster_aux_backward_scratch_bytes(max(int(state.capacity), 1), C_)
-    scratch, g.scratch = _scratch(nbytes, device, _scratch_misalign, _fill)   # rows written before they are read
-    keep = []
-    a = _fill_args(rs, P, M, device, keep)
-    i = _fill_in(means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp)
-    saved = state.saved()
-    with _on_device(device):
-        rc = lib.das3r_raster_aux_backward(C.byref(a), C.byref(i), C.byref(saved), C_, _ptr(features), _ptr(grad_image), _ptr(grad_alpha),
-                                           _ptr(g_feat), C.byref(g), _stream(device))
-    _lib.check(rc, "das3r_raster_aux_backward")
-    return g_means2D, g_opac, g_means3D, g_cov, g_scales, g_rot, g_feat
+    g_feat = _new(state.device, _fill)(state.P, C_) if want_features and C_ > 0 else None
+    nbytes = lib.das3r_raster_aux_backward_scratch_bytes(max(int(state.capacity), 1), C_) if state.P else 0   # (no Gaussian: no call)
+    return _saved_list_backward("das3r_raster_aux_backward", nbytes,
+                                (C_, _ptr(features), _ptr(grad_image), _ptr(grad_alpha), _ptr(g_feat)), state, rs,
+                                (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp), _scratch_misalign, _fill) + (g_feat,)
+
+
+def _prep_geometry(device, means3D, opacities, scales, rotations, cov3Ds_precomp, sh, colors_precomp):
+    """The seven forward inputs the two autograd functions below save for their backward calls, in this order"""
+    return [_prep(t, device, n) for t, n in ((means3D, "means3D"), (opacities, "opacities"), (scales, "scales"), (rotations, "rotations"),
+                                             (cov3Ds_precomp, "cov3D_precomp"), (sh, "shs"), (colors_precomp, "colors_precomp"))]
 
 
 class _AuxWithGeometry(torch.autograd.Function):
@@ -655,8 +668,7 @@ class _AuxWithGeometry(torch.autograd.Function):
     def forward(ctx, features, means3D, means2D, opacities, scales, rotations, cov3Ds_precomp, sh, colors_precomp, raster_settings, state,
                 want_alpha):
         device = state.device
-        tensors = [_prep(t, device, n) for t, n in ((means3D, "means3D"), (opacities, "opacities"), (scales, "scales"), (rotations, "rotations"),
-                                                    (cov3Ds_precomp, "cov3D_precomp"), (sh, "shs"), (colors_precomp, "colors_precomp"))]
+        tensors = _prep_geometry(device, means3D, opacities, scales, rotations, cov3Ds_precomp, sh, colors_precomp)
         feat = None if features is None else _prep(features.detach(), device, "features")
         ctx.state, ctx.raster_settings, ctx.has_features = state, raster_settings, feat is not None
         ctx.save_for_backward(*tensors, *(() if feat is None else (feat,)))
@@ -723,24 +735,10 @@ def _distortion_backward_impl(state, rs, grad, totals, means3D, sh, colors_preco
     (g_means2D, g_opac, g_means3D, g_cov, g_scales, g_rot).  grad [1, H, W], totals [H, W]: the forward call's.  (_fill: tests fill the scratch
     and every output with it first.)"""
     lib = _lib.load()
-    device, P = state.device, state.P
-    M = sh.shape[1] if sh.numel() else 0
-    # (the colour gradient is identically zero for this loss; the per-Gaussian backward writes it all the same)
-    (g_means2D, _g_colors, g_opac, g_means3D, g_cov, _g_sh, g_scales, g_rot), g = _grad_set(device, P, M, sh.numel() > 0, cov3Ds_precomp.numel() > 0,
-                                                                                           fill=_fill)
-    if P == 0:
-        return g_means2D, g_opac, g_means3D, g_cov, g_scales, g_rot
-    nbytes = lib.das3r_raster_distortion_backward_scratch_bytes(max(int(state.capacity), 1), P)
-    scratch, g.scratch = _scratch(nbytes, device, _scratch_misalign, _fill)   # rows and dz written before they are read
-    keep = []
-    a = _fill_args(rs, P, M, device, keep)
-    i = _fill_in(means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp)
-    saved = state.saved()
-    with _on_device(device):
-        rc = lib.das3r_raster_distortion_backward(C.byref(a), C.byref(i), C.byref(saved), C.c_void_p(grad.data_ptr()),
-                                                  C.c_void_p(totals.data_ptr()), C.byref(g), _stream(device))
-    _lib.check(rc, "das3r_raster_distortion_backward")
-    return g_means2D, g_opac, g_means3D, g_cov, g_scales, g_rot
+    nbytes = lib.das3r_raster_distortion_backward_scratch_bytes(max(int(state.capacity), 1), state.P) if state.P else 0   # (no Gaussian: no call)
+    return _saved_list_backward("das3r_raster_distortion_backward", nbytes,
+                                (C.c_void_p(grad.data_ptr()), C.c_void_p(totals.data_ptr())), state, rs,
+                                (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp), _scratch_misalign, _fill)
 
 
 class _DistortionWithGeometry(torch.autograd.Function):
@@ -750,8 +748,7 @@ class _DistortionWithGeometry(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, opacities, scales, rotations, cov3Ds_precomp, sh, colors_precomp, raster_settings, state):
         device = state.device
-        tensors = [_prep(t, device, n) for t, n in ((means3D, "means3D"), (opacities, "opacities"), (scales, "scales"), (rotations, "rotations"),
-                                                    (cov3Ds_precomp, "cov3D_precomp"), (sh, "shs"), (colors_precomp, "colors_precomp"))]
+        tensors = _prep_geometry(device, means3D, opacities, scales, rotations, cov3Ds_precomp, sh, colors_precomp)
         image, totals = _distortion_forward(state, True)
         ctx.state, ctx.raster_settings = state, raster_settings
         ctx.save_for_backward(*tensors, totals)

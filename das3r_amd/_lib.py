@@ -146,6 +146,7 @@ EXPORTS = ("das3r_raster_forward", "das3r_raster_backward", "das3r_raster_backwa
            "das3r_raster_aux_forward", "das3r_raster_aux_scratch_bytes", "das3r_raster_aux_adjoint",
            "das3r_raster_aux_backward_scratch_bytes", "das3r_raster_aux_backward",
            "das3r_raster_distortion_forward", "das3r_raster_distortion_backward_scratch_bytes", "das3r_raster_distortion_backward",
+           "das3r_raster_median_forward", "das3r_raster_median_scratch_bytes", "das3r_raster_median_adjoint",
            "das3r_thin_workspace_bytes", "das3r_thin_voxels", "das3r_raster_focal_workspace_bytes", "das3r_raster_backward_focal",
            "das3r_debug_path_policy_fresh", "das3r_debug_path_policy_plan", "das3r_debug_path_policy_count", "das3r_debug_path_policy_skew",
            "das3r_debug_path_policy_hint", "das3r_debug_path_policy_forget", "das3r_debug_path_policy_resume", "das3r_debug_seg_dbits",
@@ -272,6 +273,14 @@ def load():
     L.das3r_raster_distortion_backward.restype = C.c_int
     L.das3r_raster_distortion_backward.argtypes = [C.POINTER(RasterArgs), C.POINTER(RasterIn), C.POINTER(RasterSaved), C.c_void_p, C.c_void_p,
                                                    C.POINTER(RasterGrads), C.c_void_p]
+    L.das3r_raster_median_forward.restype = C.c_int   # median depth and surface hits over a forward's lists (additive under ABI 16)
+    L.das3r_raster_median_forward.argtypes = [C.POINTER(RasterArgs), C.POINTER(RasterSaved), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]
+    L.das3r_raster_median_scratch_bytes.restype = C.c_size_t
+    L.das3r_raster_median_scratch_bytes.argtypes = [C.c_int64]
+    L.das3r_raster_median_adjoint.restype = C.c_int
+    L.das3r_raster_median_adjoint.argtypes = [C.POINTER(RasterArgs), C.POINTER(RasterSaved), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                              C.c_void_p, C.c_void_p]
     L.das3r_photometric_finish.restype = C.c_int
     L.das3r_photometric_finish.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
     L.das3r_adam_step_gated.restype = C.c_int

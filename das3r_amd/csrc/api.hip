@@ -659,6 +659,69 @@ extern "C" int das3r_raster_distortion_backward(const das3r_raster_args *a, cons
     return launch_preprocess_backward(a, in, saved->geom, saved->binning, L, g, partial, s, false, dz, (saved->flags & ANTIALIAS_FLAG) != 0);
 }
 
+// ---- median depth and surface hits over a forward's saved lists (render_median.hip) ----
+// Additive under ABI 16; include/das3r_raster.h fixes the definition.  Both calls read the saved state only, as das3r_raster_aux_forward /
+// das3r_raster_aux_adjoint do; the adjoint is the aux adjoint's sequence: one compositing kernel into per-instance rows, then the gather.
+static int median_validate(const char *who, const das3r_raster_args *a, const das3r_raster_saved *saved) {
+    if (!a || !saved) { set_error("%s: null args / saved state", who); return DAS3R_ERR_INVALID_ARG; }
+    if (a->P < 0 || a->image_width <= 0 || a->image_height <= 0) { set_error("%s: bad extents P=%d W=%d H=%d", who, a->P, a->image_width, a->image_height); return DAS3R_ERR_INVALID_ARG; }
+    return DAS3R_OK;
+}
+static int median_buffers(const char *who, const das3r_raster_args *a, const das3r_raster_saved *saved) {
+    if (a->P > 0 && saved->num_rendered > 0 && (!saved->geom || !saved->binning || !saved->img)) { set_error("%s: saved buffers missing", who); return DAS3R_ERR_INVALID_ARG; }
+    return DAS3R_OK;
+}
+
+extern "C" int das3r_raster_median_forward(const das3r_raster_args *a, const das3r_raster_saved *saved, float threshold, float *depth,
+                                           int32_t *hit_gaussian, uint32_t *hit_position, das3r_stream_t stream) {
+    static const char who[] = "das3r_raster_median_forward";
+    hipStream_t s = (hipStream_t)stream;
+    int rc = median_validate(who, a, saved);
+    if (rc) return rc;
+    if (!depth) { set_error("%s: null depth pointer", who); return DAS3R_ERR_INVALID_ARG; }
+    if (!(threshold > 0.0f && threshold < 1.0f)) { set_error("%s: threshold %g is not inside (0, 1)", who, (double)threshold); return DAS3R_ERR_INVALID_ARG; }
+    if ((rc = median_buffers(who, a, saved))) return rc;
+    const int P = a->P, W = a->image_width, H = a->image_height;
+    if (P == 0 || saved->num_rendered <= 0) {   // nothing was blended: every pixel is empty (0 / -1 / 0xFFFFFFFF)
+        const size_t npix = (size_t)W * (size_t)H;
+        HIP_TRY(hipMemsetAsync(depth, 0, sizeof(float) * npix, s));
+        if (hit_gaussian) HIP_TRY(hipMemsetAsync(hit_gaussian, 0xFF, sizeof(int32_t) * npix, s));
+        if (hit_position) HIP_TRY(hipMemsetAsync(hit_position, 0xFF, sizeof(uint32_t) * npix, s));
+        return DAS3R_OK;
+    }
+    if ((rc = das3r_raster_check(saved, stream))) return rc;   // a failed binning is an error, not a walk over bad lists
+    const Layout L = saved_layout(a, saved);
+    return launch_render_median_forward(P, W, H, threshold, depth, hit_gaussian, hit_position, saved->geom, saved->binning, saved->img, L,
+                                        a->debug != 0, s);
+}
+
+// one float per instance + 16 bytes (as das3r_raster_aux_scratch_bytes rounds its rows up)
+extern "C" size_t das3r_raster_median_scratch_bytes(int64_t capacity) {
+    return (capacity > 0 ? (size_t)capacity : 1) * sizeof(float) + 16;
+}
+
+extern "C" int das3r_raster_median_adjoint(const das3r_raster_args *a, const das3r_raster_saved *saved, const float *dL_ddepth,
+                                           const uint32_t *hit_position, float *dL_dz, int32_t accumulate, float *scratch, das3r_stream_t stream) {
+    static const char who[] = "das3r_raster_median_adjoint";
+    hipStream_t s = (hipStream_t)stream;
+    int rc = median_validate(who, a, saved);
+    if (rc) return rc;
+    if (!dL_ddepth || !hit_position) { set_error("%s: null dL_ddepth / hit_position plane (das3r_raster_median_forward writes it)", who); return DAS3R_ERR_INVALID_ARG; }
+    if (a->P > 0 && !dL_dz) { set_error("%s: null dL_dz pointer", who); return DAS3R_ERR_INVALID_ARG; }
+    if (!scratch) { set_error("%s: null scratch (das3r_raster_median_scratch_bytes)", who); return DAS3R_ERR_INVALID_ARG; }
+    if ((rc = median_buffers(who, a, saved))) return rc;
+    const int P = a->P, W = a->image_width, H = a->image_height;
+    if (P == 0) return DAS3R_OK;   // dL_dz has no rows
+    if (saved->num_rendered <= 0) {
+        if (!accumulate) HIP_TRY(hipMemsetAsync(dL_dz, 0, sizeof(float) * (size_t)P, s));
+        return DAS3R_OK;
+    }
+    if ((rc = das3r_raster_check(saved, stream))) return rc;
+    const Layout L = saved_layout(a, saved);
+    return launch_render_median_adjoint(P, W, H, dL_ddepth, hit_position, dL_dz, accumulate != 0, scratch, saved->geom, saved->binning, saved->img,
+                                        L, a->debug != 0, s);
+}
+
 extern "C" int das3r_has_experiments(void) {
 #ifdef DAS3R_EXPERIMENTS
     return 1;

@@ -375,6 +375,12 @@ int launch_render_distortion_forward(int P, int W, int H, float *out, float *tot
 int launch_render_distortion_backward(int P, int W, int H, const float *dL_ddist, const float *totals, float *partial, const char *geom,
                                       const char *binning, const char *img, const Layout &L, bool debug, hipStream_t s);
 int launch_distortion_fold(int P, const char *geom, const Layout &L, float *partial, float *dz, bool debug, hipStream_t s);
+// render_median.hip: the depth (+ Gaussian index, + list position; either null) of the entry at which T crosses tau, over the saved lists;
+// the depth's adjoint -> rows [capacity] through the emission slots, then render_aux.hip's gather into dL_dz [P] (written, or added)
+int launch_render_median_forward(int P, int W, int H, float tau, float *depth, int32_t *hit_gaussian, uint32_t *hit_position, const char *geom,
+                                 const char *binning, const char *img, const Layout &L, bool debug, hipStream_t s);
+int launch_render_median_adjoint(int P, int W, int H, const float *dL_ddepth, const uint32_t *hit_position, float *dL_dz, int accumulate,
+                                 float *rows, const char *geom, const char *binning, const char *img, const Layout &L, bool debug, hipStream_t s);
 // pair_count.hip (measurement aid): out[0] += live pairs, out[1] += (pixel, list position) pairs below the pixel's n_contrib
 int launch_count_live_pairs(const das3r_raster_args *a, char *geom, char *binning, char *img, const Layout &L, unsigned long long *out, hipStream_t s);
 int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in *in, char *geom, char *binning, const Layout &L,

@@ -126,7 +126,8 @@ class _EvalState:
 
 
 @torch.no_grad()
-def render_view_fused(model, view, pose7, background, pipe=PIPE, invdepth=False, features=None, alpha=False, return_state=False, distortion=False):
+def render_view_fused(model, view, pose7, background, pipe=PIPE, invdepth=False, features=None, alpha=False, return_state=False, distortion=False,
+                      median_depth=False):
     """render_test of one view (gaussian_renderer/__init__.py:152-277) with the pose pre-transform INSIDE the rasterizer's per-Gaussian
     kernel (include/das3r_raster.h das3r_raster_in.pre, as the direct training iteration uses it): R xyz + t, quaternion product, exp,
     sigmoid x the per-Gaussian conf_static column — the dozen PyTorch kernels of the reference's glue (a boolean-mask gather of every
@@ -135,10 +136,11 @@ def render_view_fused(model, view, pose7, background, pipe=PIPE, invdepth=False,
     invdepth (image, radii, inverse-depth image [1, H, W]: include/das3r_raster.h das3r_raster_out.out_invdepth).  features ([P, C] fp32) /
     alpha: appended after those, in this order — the [C, H, W] image of the channels blended over this forward's lists
     (rasterizer.composite_features) and the [1, H, W] coverage (rasterizer.alpha_of); distortion: then the [1, H, W] ray-distortion image
-    (rasterizer.distortion_of); return_state: last, the forward's RasterState."""
+    (rasterizer.distortion_of); median_depth: then the [1, H, W] median depth (rasterizer.median_depth_of: the view-space depth of the Gaussian
+    at which the ray's transmittance crosses one half); return_state: last, the forward's RasterState."""
     import ctypes as C
     from . import _lib
-    from .rasterizer import _forward, _on_device, _stream, alpha_of, composite_features, distortion_of
+    from .rasterizer import _forward, _on_device, _stream, alpha_of, composite_features, distortion_of, median_depth_of
     from .render import _settings
     st = model.__dict__.get("_das3r_eval")
     if st is None:
@@ -167,6 +169,8 @@ def render_view_fused(model, view, pose7, background, pipe=PIPE, invdepth=False,
         out = out + (alpha_of(state),)
     if distortion:
         out = out + (distortion_of(state),)
+    if median_depth:
+        out = out + (median_depth_of(state),)
     if return_state:
         out = out + (state,)
     return out
@@ -183,9 +187,20 @@ def invdepth_median_rel_error(invdepth, depth):
     return float(((1.0 / inv[sel] - d[sel]).abs() / d[sel]).median())
 
 
+def median_depth_median_rel_error(median_depth, depth):
+    """Diagnostic of --median-depth, the one --depth prints on the other depth image: median over the pixels with median_depth > 0 of
+    |median_depth - depth| / depth against a sequence's depth map.  NaN when no pixel is covered."""
+    z = torch.as_tensor(median_depth).detach().reshape(-1).float().cpu()
+    d = torch.as_tensor(depth).detach().reshape(-1).float().cpu()
+    sel = (z > 0) & (d > 0)
+    if not bool(sel.any()):
+        return float("nan")
+    return float(((z[sel] - d[sel]).abs() / d[sel]).median())
+
+
 @torch.no_grad()
 def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=None, poses=None, write=True, fused=False, invdepth=None,
-               exposures=None, static_map=None, alpha=None, distortion=None):
+               exposures=None, static_map=None, alpha=None, distortion=None, median_depth=None):
     """render.py:72-86.  views: cameras carrying .pose7 (qw, qx, qy, qz, tx, ty, tz world-to-camera); poses: optional [N, 4, 4]
     world-to-camera matrices that override them.  fused: render_view_fused instead of the reference's PyTorch glue in front of the
     rasterizer (opt-in, like every fused form).  invdepth: a list that receives every view's inverse-depth image [1, H, W] (written as
@@ -195,12 +210,15 @@ def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=
     (written as static/%05d.npy and alpha/%05d.npy beside invdepth/, in the same format, when `write`); None: not computed.
     distortion: a list that receives every view's ray-distortion image [1, H, W] from the render's own lists (rasterizer.distortion_of;
     written as distortion/%05d.npy, as alpha is); None: not computed.
+    median_depth: a list that receives every view's median-depth image [1, H, W] from the render's own lists (rasterizer.median_depth_of;
+    written as median_depth/%05d.npy, as alpha is); None: not computed.
     -> list of the rendered [3, H, W] tensors (on the device)."""
     dev = model.get_xyz.device
     background = background if background is not None else torch.zeros(3, device=dev)
     base = os.path.join(model_path, name, f"ours_{iteration}")
     render_path = os.path.join(base, "renders")
     want, want_static, want_alpha, want_dist = invdepth is not None, static_map is not None, alpha is not None, distortion is not None
+    want_median = median_depth is not None
     conf = None
     if want_static:
         conf = model._conf_static.detach().reshape(-1, 1).float().contiguous()
@@ -209,10 +227,10 @@ def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=
     out = []
     for idx, view in enumerate(views):
         pose = view.pose7 if poses is None else tensor_from_camera(poses[idx], dev)
-        smap = amap = dmap = None
+        smap = amap = dmap = zmap = None
         if fused:
             res = render_view_fused(model, view, pose, background, pipe, invdepth=want, features=conf, alpha=want_alpha,
-                                    **({"distortion": True} if want_dist else {}))
+                                    **({"distortion": True} if want_dist else {}), **({"median_depth": True} if want_median else {}))
             img, inv = res[0], (res[2] if want else None)
             nxt = 3 if want else 2
             if want_static:
@@ -220,14 +238,19 @@ def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=
             if want_alpha:
                 amap, nxt = res[nxt], nxt + 1
             if want_dist:
-                dmap = res[nxt]
+                dmap, nxt = res[nxt], nxt + 1
+            if want_median:
+                zmap = res[nxt]
         else:
             pkg = das3r_render(view, model, pipe, background, camera_pose=pose, variant="test", return_invdepth=want, features=conf,
-                               return_alpha=want_alpha, **({"return_state": True} if want_dist else {}))
+                               return_alpha=want_alpha, **({"return_state": True} if want_dist or want_median else {}))
             img, inv, smap, amap = pkg["render"], pkg.get("invdepth"), pkg.get("features"), pkg.get("alpha")
             if want_dist:
                 from .rasterizer import distortion_of
                 dmap = distortion_of(pkg["raster_state"])
+            if want_median:
+                from .rasterizer import median_depth_of
+                zmap = median_depth_of(pkg["raster_state"])
         if exposures is not None and exposures[idx] is not None:
             from .losses import apply_exposure
             img = apply_exposure(img, torch.as_tensor(exposures[idx], dtype=img.dtype, device=img.device))
@@ -240,9 +263,12 @@ def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=
             alpha.append(amap)
         if want_dist:
             distortion.append(dmap)
+        if want_median:
+            median_depth.append(zmap)
         if write:
             save_image(img, os.path.join(render_path, f"{idx:05d}.png"))
-            for sub, m in (("invdepth", inv if want else None), ("static", smap), ("alpha", amap), ("distortion", dmap)):
+            for sub, m in (("invdepth", inv if want else None), ("static", smap), ("alpha", amap), ("distortion", dmap),
+                           ("median_depth", zmap)):
                 if m is not None:
                     os.makedirs(os.path.join(base, sub), exist_ok=True)
                     np.save(os.path.join(base, sub, f"{idx:05d}.npy"), m[0].detach().cpu().numpy())
@@ -251,7 +277,7 @@ def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=
 
 def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=False, optimised_poses=False, device="cuda", write=True, fused=False,
                 depth=False, pipe=PIPE, prune_min_opacity=0.0, write_pruned_ply=False, exposure="none", static_map=False, alpha=False, thin_edge=None, thin_relative=None,
-                camera_fov=False, distortion=False):
+                camera_fov=False, distortion=False, median_depth=False):
     """render.py:89-123: load the trained model, write pose_interpolated.npy, render the "interp" set.  seq: the sequence the model was
     trained on (its cameras).  depth: also the inverse-depth images (invdepth/%05d.npy) and, per view, the median relative error of
     1 / invdepth against the sequence's depth map (printed: a diagnostic).  pipe: PIPE, or pipe_from_args' (pipe.antialiasing: a model
@@ -261,7 +287,9 @@ def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=Fal
     <model_path>/exposure.json (a job that trained with per-frame exposure compensation writes it) is loaded and every view whose frame
     name it holds, i.e. every training view, is written compensated; the others stay raw.  static_map / alpha: also every view's
     static-confidence map and coverage map (render_set: static/%05d.npy, alpha/%05d.npy); distortion: and its ray-distortion image
-    (distortion/%05d.npy, from the render's own lists).  thin_edge (world units) / thin_relative (multiples of
+    (distortion/%05d.npy, from the render's own lists); median_depth: and its median-depth image (median_depth/%05d.npy, from the same
+    lists) with, per view, the diagnostic `depth` prints — the median relative error against the sequence's depth map — so that the blended
+    and the median depth can be compared on one sequence.  thin_edge (world units) / thin_relative (multiples of
     the pixel footprint of `seq`'s depth maps and intrinsics: das3r_amd.thin.pixel_footprint over its confident pixels), at most one: the loaded
     model is thinned to one Gaussian per voxel first (das3r_amd.thin.thin_model, after prune_min_opacity's event when both are given);
     write_pruned_ply then saves the thinned model.  A model directory that holds fov.json (a job that trained its field of view: farm
@@ -312,6 +340,7 @@ def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=Fal
             frames = list(tr)
         poses = inter
     inv = [] if depth else None
+    med = [] if median_depth else None
     exposures = None
     if exposure == "train":
         from .io_formats import read_exposure_json, sequence_frame_names
@@ -322,10 +351,13 @@ def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=Fal
         exposures = [table.get(names[f]) for f in frames]
     imgs = render_set(model_path, "interp", iteration, views, model, pipe, bg, poses=poses, write=write, fused=fused, invdepth=inv,
                       exposures=exposures, static_map=[] if static_map else None, alpha=[] if alpha else None,
-                      **({"distortion": []} if distortion else {}))
+                      **({"distortion": []} if distortion else {}), **({"median_depth": med} if median_depth else {}))
     if depth and seq.get("depths") is not None:
         for idx, (f, d) in enumerate(zip(frames, inv)):
             print(f"view {idx:05d} (frame {f}): median |1/invdepth - depth| / depth = {invdepth_median_rel_error(d, seq['depths'][f]):.4f}")
+    if median_depth and seq.get("depths") is not None:
+        for idx, (f, z) in enumerate(zip(frames, med)):
+            print(f"view {idx:05d} (frame {f}): median |median_depth - depth| / depth = {median_depth_median_rel_error(z, seq['depths'][f]):.4f}")
     return iteration, imgs
 
 
@@ -385,6 +417,9 @@ def parser():
     ap.add_argument("--alpha", action="store_true", help="also write every view's coverage map 1 - T (alpha/%%05d.npy next to renders/)")
     ap.add_argument("--distortion", action="store_true", help="also write every view's ray-distortion image, sum_{j<k} w_j w_k (1/z_j - 1/z_k) per pixel "
                     "over the render's own lists (distortion/%%05d.npy next to renders/)")
+    ap.add_argument("--median-depth", action="store_true", help="also write every view's median depth — the view-space depth of the Gaussian at which the "
+                    "ray's transmittance crosses one half, from the render's own lists (median_depth/%%05d.npy next to renders/) — and print, per view, "
+                    "its median relative error against the sequence's depth map (what --depth prints for the blended depth)")
     return ap
 
 
@@ -396,7 +431,7 @@ def main(argv=None):
     it, imgs = render_sets(args.model_path, seq, args.iteration, args.sh_degree, args.white_background, args.optimised_poses, fused=args.fused,
                            depth=args.depth, pipe=pipe_from_args(args), prune_min_opacity=args.prune_min_opacity, write_pruned_ply=args.write_pruned_ply,
                            exposure=args.exposure, static_map=args.static_map, alpha=args.alpha, **({"camera_fov": True} if args.camera_fov else {}),
-                           **({"distortion": True} if args.distortion else {}),
+                           **({"distortion": True} if args.distortion else {}), **({"median_depth": True} if args.median_depth else {}),
                            **({"thin_edge": args.thin_edge, "thin_relative": args.thin_relative}
                               if (args.thin_edge is not None or args.thin_relative is not None) else {}))
     print(f"wrote {len(imgs)} images to {os.path.join(args.model_path, 'interp', f'ours_{it}', 'renders')}")

@@ -246,6 +246,40 @@ def contribution_scores(model, views, pipe=None, background=None):
     return scores.reshape(-1)
 
 
+@torch.no_grad()
+def surface_scores(model, views, pipe=None, background=None, threshold=0.5):
+    """-> [P] fp32: the number of pixels over `views` at which each Gaussian is the HIT — the entry at which the ray's transmittance
+    crosses `threshold` (0.5: the median; rasterizer.median_depth_of), i.e. how often the Gaussian is the visible surface.  What
+    contribution_scores does not say: a Gaussian may carry blending-weight mass on many rays and be the surface of none of them (a faint
+    floater in front, a near-copy behind the one that is hit).  Per view: one no-grad forward, one median kernel over that forward's lists
+    and the hit adjoint of a ones image (rasterizer.median_hit_adjoint), accumulated in place after the first view.  The counts are integers
+    in fp32, summing to the covered pixels of all views; no floating-point atomics: bit-identical from run to run.
+    views, the pose and the variant: contribution_scores'.  The hand-off to the pruning event:
+
+        scores = surface_scores(model, cameras, pipe, background)
+        prune_points(model, also_drop=scores == 0)         # never the surface of any pixel of any view"""
+    from types import SimpleNamespace
+    from .rasterizer import _check_threshold, median_depth_of, median_hit_adjoint
+    from .render import das3r_render
+    threshold = _check_threshold(threshold)
+    pipe = pipe or SimpleNamespace(debug=False, compute_cov3D_python=False, convert_SHs_python=False)
+    dev = model._xyz.device
+    background = background if background is not None else torch.zeros(3, device=dev)
+    variant = "render" if hasattr(model, "aggregated_mask") else "test"
+    scores = torch.zeros(int(model._xyz.shape[0]), dtype=torch.float32, device=dev)
+    ones = {}
+    for n, view in enumerate(views):
+        pose = getattr(view, "pose7", None)
+        pose = model.get_RT(view.uid) if pose is None else pose
+        state = das3r_render(view, model, pipe, background, camera_pose=pose, variant=variant, return_state=True)["raster_state"]
+        g = ones.get((state.H, state.W))
+        if g is None:
+            g = ones[(state.H, state.W)] = torch.ones(state.H, state.W, dtype=torch.float32, device=dev)
+        _, position = median_depth_of(state, threshold=threshold, return_position=True)
+        median_hit_adjoint(state, g, position, out=scores, accumulate=n > 0)
+    return scores
+
+
 def write_pruned_ply(path, model):
     """A loaded, pruned model back into the reference's PLY layout (io_formats.save_gaussians_ply)."""
     from .io_formats import save_gaussians_ply

@@ -786,6 +786,140 @@ def distortion_of(state, geometry=None):
                                                     geometry.colors_precomp), geometry.raster_settings, state)
 
 
+# ---- median depth and surface hits over a forward's lists
+
+
+def _check_threshold(threshold):
+    """-> the threshold as a float inside (0, 1); anything else (NaN included) is refused here, before the library is reached."""
+    try:
+        tau = float(threshold)
+    except (TypeError, ValueError):
+        raise TypeError(f"threshold must be a number inside (0, 1), got {type(threshold).__name__}") from None
+    if not (0.0 < tau < 1.0):
+        raise ValueError(f"threshold must be inside (0, 1) (0.5: the median), got {tau}")
+    return tau
+
+
+def _median_forward(state, tau, want_gaussian, want_position, _fill=None):
+    """One das3r_raster_median_forward call -> (depth [1, H, W], hit_gaussian [H, W] int32 or None, hit_position [H, W] int32 or None).  The
+    position plane is the library's u32 plane held in an int32 tensor: the empty marker 0xFFFFFFFF reads -1."""
+    _needs_device(state)
+    lib = _lib.load()
+    depth = _new(state.device, _fill)(1, state.H, state.W)   # all three fully written by the call
+    plane = lambda want: torch.empty(state.H, state.W, dtype=torch.int32, device=state.device) if want else None
+    hit_g, hit_p = plane(want_gaussian), plane(want_position)
+    a, saved = state._c_args()
+    with _on_device(state.device):
+        rc = lib.das3r_raster_median_forward(C.byref(a), C.byref(saved), C.c_float(tau), C.c_void_p(depth.data_ptr()),
+                                             None if hit_g is None else C.c_void_p(hit_g.data_ptr()),
+                                             None if hit_p is None else C.c_void_p(hit_p.data_ptr()), _stream(state.device))
+    _lib.check(rc, "das3r_raster_median_forward")
+    return depth, hit_g, hit_p
+
+
+def _check_hit_position(state, hit_position):
+    if not torch.is_tensor(hit_position):
+        raise TypeError("hit_position must be the int32 [H, W] plane median_depth_of(return_position=True) returned")
+    if hit_position.dtype != torch.int32:
+        raise TypeError(f"hit_position must be int32 (got {hit_position.dtype})")
+    if tuple(hit_position.shape) != (state.H, state.W):
+        raise ValueError(f"hit_position must have dimensions ({state.H}, {state.W}), got {tuple(hit_position.shape)}")
+    if hit_position.device != state.device:
+        raise RuntimeError(f"hit_position is on {hit_position.device}, the forward ran on {state.device}")
+
+
+def _median_adjoint(state, grad, hit_position, out, accumulate, _fill=None):
+    """One das3r_raster_median_adjoint call: grad [H, W], hit_position [H, W] int32 -> out [P] (written, or added to)."""
+    _needs_device(state)
+    lib = _lib.load()
+    if state.P == 0:
+        return out   # no row
+    nbytes = int(lib.das3r_raster_median_scratch_bytes(max(int(state.capacity), 1)))
+    scratch, address = _scratch(nbytes, state.device, 0, _fill)   # per-instance floats, written before they are read
+    a, saved = state._c_args()
+    with _on_device(state.device):
+        rc = lib.das3r_raster_median_adjoint(C.byref(a), C.byref(saved), C.c_void_p(grad.data_ptr()), C.c_void_p(hit_position.data_ptr()),
+                                             C.c_void_p(out.data_ptr()), int(bool(accumulate)), C.c_void_p(address), _stream(state.device))
+    _lib.check(rc, "das3r_raster_median_adjoint")
+    return out
+
+
+def median_hit_adjoint(state, grad_image, hit_position, out=None, accumulate=False, _fill=None):
+    """The adjoint of median_depth_of with respect to the Gaussians' view-space depths: grad_image [H, W] (or [1, H, W]), hit_position the
+    int32 [H, W] plane median_depth_of(return_position=True) returned -> [P], dL_dz[i] = the sum of grad_image over the pixels whose hit is
+    Gaussian i; with a ones image, the number of pixels every Gaussian is the visible surface of (das3r_amd.prune.surface_scores).  out: a
+    dense [P] fp32 tensor to write into; accumulate: add to `out` instead (needs `out`).  A Gaussian that is nobody's hit gets exactly 0;
+    a position at or past its tile's list length (the empty marker -1 among them) contributes nothing.  No floating-point atomics:
+    bit-identical from run to run."""
+    _check_state(state)
+    _check_rows(state, grad_image, "grad_image", "[H, W]")
+    if tuple(grad_image.shape) not in ((state.H, state.W), (1, state.H, state.W)):
+        raise ValueError(f"grad_image must have dimensions ({state.H}, {state.W}), got {tuple(grad_image.shape)}")
+    if grad_image.device != state.device:
+        raise RuntimeError(f"grad_image is on {grad_image.device}, the forward ran on {state.device}")
+    _check_hit_position(state, hit_position)
+    if out is None:
+        if accumulate:
+            raise ValueError("median_hit_adjoint(accumulate=True) needs the tensor to add to (out=)")
+        out = _new(state.device, _fill)(state.P)
+    else:
+        _check_rows(state, out, "out", "[P]")
+        if tuple(out.shape) != (state.P,) or not out.is_contiguous():
+            raise ValueError(f"out must be a dense tensor of {state.P} elements, got {tuple(out.shape)}")
+        if out.device != state.device:
+            raise RuntimeError(f"out is on {out.device}, the forward ran on {state.device}")
+    return _median_adjoint(state, grad_image.detach().contiguous(), hit_position.contiguous(), out, accumulate, _fill)
+
+
+class _MedianWithGeometry(torch.autograd.Function):
+    """median_depth_of, differentiable with respect to means3D: the forward is one das3r_raster_median_forward call (which leaves the hit
+    positions), the backward ONE das3r_raster_median_adjoint call -> dL_dz [P], handed on as dL_dz[:, None] * viewmatrix[:3, 2][None] — the
+    forward's own z = [x y z 1] . viewmatrix[:, 2]; a row-wise product: deterministic."""
+    @staticmethod
+    def forward(ctx, means3D, raster_settings, state, tau):
+        depth, hit_g, hit_p = _median_forward(state, tau, True, True)
+        ctx.state = state
+        ctx.z_row = raster_settings.viewmatrix.detach().to(device=state.device, dtype=torch.float32).reshape(4, 4)[:3, 2].clone()
+        ctx.save_for_backward(hit_p)
+        ctx.mark_non_differentiable(hit_g, hit_p)
+        ctx.set_materialize_grads(False)
+        return depth, hit_g, hit_p
+
+    @staticmethod
+    def backward(ctx, grad, _grad_g=None, _grad_p=None):
+        if grad is None:
+            return None, None, None, None
+        (hit_p,) = ctx.saved_tensors
+        state = ctx.state
+        dz = _median_adjoint(state, _dense(grad), hit_p, torch.empty(state.P, dtype=torch.float32, device=state.device), False)
+        return dz[:, None] * ctx.z_row[None], None, None, None
+
+
+def median_depth_of(state, geometry=None, threshold=0.5, return_hit=False, return_position=False):
+    """-> [1, H, W]: the median depth of the forward that left `state` — per pixel the fp32 view-space depth z of the HIT, the entry at
+    which the ray's transmittance crosses `threshold`:
+        hit = max { k < n : T_k > threshold },    T_0 = 1,  T_{k+1} = T_k (1 - alpha_k),
+    over the splats the pixel's colour was blended from — same order (depth, index), same alpha, same stop: the first entry behind which
+    T <= threshold, or the last contributor of a ray that never gets that opaque.  0 < threshold < 1; 0.5 is the median, a smaller value a
+    deeper quantile.  No background term; an empty pixel is exactly 0 (include/das3r_raster.h das3r_raster_median_forward).  Nothing of the
+    forward is repeated: one kernel over the saved lists, which a wave leaves as soon as its pixels are behind their hits.
+    return_hit: also the int32 [H, W] plane of the hit's Gaussian index (-1: empty pixel).  return_position: also the int32 [H, W] plane of
+    the hit's 0-based position in its tile's list (-1: empty pixel), which median_hit_adjoint takes back.  With either, a tuple in that order.
+    geometry=None: plain tensors.  geometry=AuxGeometry(settings, the forward's input tensors): the depth is differentiable with respect to
+    geometry.means3D ALONE (das3r_raster_median_adjoint: every discrete decision of the forward and the choice of the hit held fixed, so a
+    pixel's gradient moves its hit Gaussian along the view axis); no other input receives a gradient.  No floating-point atomics:
+    bit-identical from run to run."""
+    tau = _check_threshold(threshold)
+    if geometry is None:
+        _check_state(state)
+        depth, hit_g, hit_p = _median_forward(state, tau, bool(return_hit), bool(return_position))
+    else:
+        _check_geometry(state, geometry)
+        depth, hit_g, hit_p = _MedianWithGeometry.apply(geometry.means3D, geometry.raster_settings, state, tau)
+    extra = ((hit_g,) if return_hit else ()) + ((hit_p,) if return_position else ())
+    return (depth,) + extra if extra else depth
+
+
 # ---- the rasterising autograd function and the module
 
 

@@ -23,7 +23,7 @@ import math
 import torch
 
 from .camera import camera_from_tensor, projection_matrix, quat_multiply
-from .rasterizer import AuxGeometry, GaussianRasterizationSettings, GaussianRasterizer, distortion_of
+from .rasterizer import AuxGeometry, GaussianRasterizationSettings, GaussianRasterizer, distortion_of, median_depth_of
 
 _SH_C0 = 0.28209479177387814
 _SH_C1 = 0.4886025119029199
@@ -195,7 +195,7 @@ def _mode_kw(pipe, return_invdepth, features=None, return_alpha=False, aux_geome
 
 def das3r_render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, camera_pose=None,
                  filtering=None, use_conf=True, fused=False, variant="render", return_invdepth=False, features=None, return_alpha=False,
-                 return_state=False, aux_geometry_grad=False, return_distortion=False):
+                 return_state=False, aux_geometry_grad=False, return_distortion=False, return_median_depth=False):
     """viewpoint_camera: .FoVx .FoVy .image_height .image_width .projection_matrix (4x4, already transposed) [.camera_center for
     pipe.convert_SHs_python]; pc: splat model (das3r_amd.model.SplatModel or anything with the same attributes); pipe: .debug
     .compute_cov3D_python .convert_SHs_python; camera_pose: (7,) tensor (qw,qx,qy,qz,tx,ty,tz), may require grad.
@@ -212,12 +212,16 @@ def das3r_render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, ove
     sum_{j<k} w_j w_k (1/z_j - 1/z_k) per pixel, no second forward), differentiable with respect to the geometry — means, scales, rotations,
     opacities and, through them, the pose and the confidences; its dL/dmean2D joins the colour loss's in render_pkg["viewspace_points"].grad.
     False: the calls are the ones they were.
+    return_median_depth: render_pkg["median_depth"] = the [1, H, W] median depth of this render's own lists (rasterizer.median_depth_of: the
+    view-space depth of the Gaussian at which the ray's transmittance crosses one half, no second forward; 0 where nothing was blended),
+    differentiable with respect to the means and, through them, the pose; render_pkg["median_hit"] = the int32 [H, W] index of that Gaussian
+    among the rasterised ones (-1: empty pixel).  False: the calls are the ones they were.
     With OptimParams.fov_lr > 0 (pc.fov_lr) the "render" variant takes the field of view and the projection from pc.FoVx / pc.FoVy instead
     of the camera's — training, held-out passes and reports alike — and a backward pass leaves dL/dFoV on them (one host read-back of the
     two values per render: the settings are host floats)."""
     settings, kw = rasterizer_inputs(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, camera_pose, filtering,
                                      use_conf, fused, variant)
-    want_state = return_state or return_distortion
+    want_state = return_state or return_distortion or return_median_depth
     rasterizer = GaussianRasterizer(raster_settings=settings, keep_state=True) if want_state else GaussianRasterizer(raster_settings=settings)
     out = rasterizer(**kw, **_mode_kw(pipe, return_invdepth, features, return_alpha, aux_geometry_grad))   # (upstream's call when all are off)
     image, radii = out[0], out[1]
@@ -235,10 +239,13 @@ def das3r_render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, ove
         pkg["alpha"] = out[nxt]
     if return_state:
         pkg["raster_state"] = rasterizer.state
-    if return_distortion:
+    if return_distortion or return_median_depth:
         geometry = AuxGeometry(settings, kw["means3D"], kw["means2D"], kw["opacities"], kw["shs"], kw["colors_precomp"], kw["scales"],
                                kw["rotations"], kw["cov3D_precomp"])
+    if return_distortion:
         pkg["distortion"] = distortion_of(rasterizer.state, geometry=geometry)
+    if return_median_depth:
+        pkg["median_depth"], pkg["median_hit"] = median_depth_of(rasterizer.state, geometry=geometry, return_hit=True)
     return pkg
 
 

@@ -568,6 +568,50 @@ int das3r_raster_distortion_backward(const das3r_raster_args *args, const das3r_
                                      const float *dL_ddist /* [H,W] */, const float *totals /* [H,W]: the forward call's */,
                                      const das3r_raster_grads *grads, das3r_stream_t stream);
 
+/* ---- median depth and surface hits over a forward's lists, with adjoint (opt-in) ------------------------------------------------------
+ * Additive symbols under ABI 16.  The depth of the Gaussian at which a ray's transmittance crosses a threshold — the surface depth of point
+ * and mesh export, of depth evaluation, of the 2DGS / RaDe-GS depth and normal terms and of picking — and, as its by-product, which Gaussian
+ * that is.  Like the distortion it is no blend of per-Gaussian channels: das3r_raster_aux_forward cannot produce it.
+ * Definition.  Take the forward that left `saved`, a pixel whose colour was blended from list entries k = 0 .. n-1, and a threshold tau.
+ *   - The entries are the colour's own.  The order, alpha (pair_alpha) and the stop at n_contrib[pixel] are the same.
+ *   - T_k is the transmittance in front of entry k: T_0 = 1, T_{k+1} = T_k (1 - alpha_k).
+ *   - hit = max { k < n : T_k > tau }.  This is the first entry behind which T <= tau, or the last contributor when the ray never gets that
+ *     opaque.
+ *   - T_0 = 1 > tau, so every pixel with a contributor has a hit.
+ * Outputs, each a plane in caller memory and each fully written:
+ *     depth         f32 [H,W]               z_hit, the fp32 view-space depth the forward saved in the splat record (rgbd.w)
+ *                                           empty pixel: 0.0 exactly
+ *     hit_gaussian  i32 [H,W], may be NULL  Gaussian index at the hit                                             empty pixel: -1
+ *     hit_position  u32 [H,W], may be NULL  0-based position of the hit in its tile's list; the adjoint takes this back
+ *                                           empty pixel: 0xFFFFFFFF
+ * An empty pixel is one with n_contrib == 0.
+ *   - Threshold.  0 < tau < 1.  0.5 is the median.  A smaller tau gives a deeper quantile.
+ *   - No background term, no antialiasing special case.  The antialiasing factor is part of the saved opacity.
+ *   - Adjoint.  For an image g [H,W], dL_dz[i] = sum over the pixels whose hit_gaussian is i of g[pixel].  This is the whole derivative of
+ *     <g, depth> with respect to the Gaussians' view-space depths.  Every discrete decision (lists, order, stop, which entry is the hit) is
+ *     held fixed, as for the aux and distortion backwards.  With g = 1 it is the number of pixels a Gaussian is the surface of.
+ *   - Determinism.  No floating-point atomics, no unordered adds.  Both calls are bit-identical from run to run.  Nothing needs pre-zeroing.
+ * Launches.  Forward: ONE kernel (render_median_forward_kernel, front to back over the saved lists; a wave leaves the walk once all its
+ * pixels have T <= tau or are past their last contributor, the workgroup once its four waves have).  Adjoint: ONE compositing kernel
+ * (render_median_adjoint_kernel: one float per list entry into the scratch — the sum of g, in a fixed pixel order, over the pixels whose hit
+ * the entry is; 0 for every other entry), then the gather of das3r_raster_aux_adjoint at C = 1 into dL_dz [P] (=, or += with accumulate != 0;
+ * fully written, zeros for a Gaussian that is nobody's hit, unless accumulate).  A hit_position at or past its tile's list length (the
+ * empty marker, or garbage) contributes nothing and indexes nothing.
+ * Both calls read what ANY forward left in `saved`, as das3r_raster_distortion_forward / das3r_raster_aux_adjoint do: with or without
+ * das3r_raster_in.pre, with or without out_invdepth, antialiased, an evaluation forward, every binning path and forward kernel.  args supplies
+ * P, image_width, image_height and debug.  The binning self-check is examined first.  scratch: das3r_raster_median_scratch_bytes(
+ * saved->capacity) bytes (one float per list entry), 4-byte aligned, need not be initialised.  P == 0 or nothing rendered: the empty values,
+ * and zeros to dL_dz unless accumulate.
+ * DAS3R_ERR_INVALID_ARG with a das3r_last_error() message, before anything is launched: NULL structs, NULL depth, NULL dL_ddepth, NULL
+ * hit_position (adjoint), NULL dL_dz, NULL scratch, and a threshold that is not inside (0, 1), NaN included.
+ * One workgroup per tile in both kernels, as for the siblings; a long-list form is not part of these entries. */
+int das3r_raster_median_forward(const das3r_raster_args *args, const das3r_raster_saved *saved, float threshold, float *depth /* [H,W] */,
+                                int32_t *hit_gaussian /* [H,W] or NULL */, uint32_t *hit_position /* [H,W] or NULL */, das3r_stream_t stream);
+size_t das3r_raster_median_scratch_bytes(int64_t capacity);
+int das3r_raster_median_adjoint(const das3r_raster_args *args, const das3r_raster_saved *saved, const float *dL_ddepth /* [H,W] */,
+                                const uint32_t *hit_position /* [H,W]: the forward call's */, float *dL_dz /* [P] */, int32_t accumulate,
+                                float *scratch, das3r_stream_t stream);
+
 /* ---- introspection (used by the parity tests and the roofline accounting) ---- */
 
 /* Byte offsets of the saved intermediates inside geom / binning / img for given extents. */

@@ -147,6 +147,7 @@ EXPORTS = ("das3r_raster_forward", "das3r_raster_backward", "das3r_raster_backwa
            "das3r_raster_aux_backward_scratch_bytes", "das3r_raster_aux_backward",
            "das3r_raster_distortion_forward", "das3r_raster_distortion_backward_scratch_bytes", "das3r_raster_distortion_backward",
            "das3r_raster_median_forward", "das3r_raster_median_scratch_bytes", "das3r_raster_median_adjoint",
+           "das3r_gaussian_normals_forward", "das3r_gaussian_normals_backward", "das3r_normal_consistency_forward", "das3r_normal_consistency_backward",
            "das3r_thin_workspace_bytes", "das3r_thin_voxels", "das3r_raster_focal_workspace_bytes", "das3r_raster_backward_focal",
            "das3r_debug_path_policy_fresh", "das3r_debug_path_policy_plan", "das3r_debug_path_policy_count", "das3r_debug_path_policy_skew",
            "das3r_debug_path_policy_hint", "das3r_debug_path_policy_forget", "das3r_debug_path_policy_resume", "das3r_debug_seg_dbits",
@@ -281,6 +282,14 @@ def load():
     L.das3r_raster_median_adjoint.restype = C.c_int
     L.das3r_raster_median_adjoint.argtypes = [C.POINTER(RasterArgs), C.POINTER(RasterSaved), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                               C.c_void_p, C.c_void_p]
+    L.das3r_gaussian_normals_forward.restype = C.c_int   # the normal-consistency regulariser's per-Gaussian and image kernels (additive under ABI 16)
+    L.das3r_gaussian_normals_forward.argtypes = [C.POINTER(RasterArgs)] + [C.c_void_p] * 5 + [C.c_void_p]
+    L.das3r_gaussian_normals_backward.restype = C.c_int
+    L.das3r_gaussian_normals_backward.argtypes = [C.POINTER(RasterArgs)] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p]
+    L.das3r_normal_consistency_forward.restype = C.c_int
+    L.das3r_normal_consistency_forward.argtypes = [C.c_int32, C.c_int32, C.c_float, C.c_float] + [C.c_void_p] * 6 + [C.c_void_p]
+    L.das3r_normal_consistency_backward.restype = C.c_int
+    L.das3r_normal_consistency_backward.argtypes = [C.c_int32, C.c_int32, C.c_float, C.c_float] + [C.c_void_p] * 7 + [C.c_void_p]
     L.das3r_photometric_finish.restype = C.c_int
     L.das3r_photometric_finish.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
     L.das3r_adam_step_gated.restype = C.c_int

@@ -248,7 +248,7 @@ def run_sequence_job(scene_id, iterations, device, frames=6, seq_dir=None, out_d
                      prune_from=0, prune_interval=0, prune_until=0, prune_min_opacity=0.005, prune_max_world_scale=0.0,
                      exposure_lr_init=0.0, exposure_lr_final=0.0, exposure_heldout="identity",
                      thin_init_relative=None, thin_init_edge=None, thin_opacity="coverage", prune_thin_relative=None, fov_lr=0.0,
-                     distortion_weight=0.0):
+                     distortion_weight=0.0, normal_weight=0.0, normal_depth="median"):
     """One independent 'sequence': load a preprocessed DAS3R sequence directory (das3r_amd.io_formats.load_sequence) — or,
     without one, build a synthetic multi-frame scene —, optimise it with the train-step harness, report the held-out PSNR and,
     with out_dir, write what the reference writes (point_cloud/iteration_N/point_cloud.ply, pose/pose_N.npy:
@@ -274,6 +274,9 @@ def run_sequence_job(scene_id, iterations, device, frames=6, seq_dir=None, out_d
     which the checkpoints carry, and with out_dir writes fov.json (io_formats.write_fov_json), which das3r_amd.offline renders with.
     distortion_weight (default 0: off): OptimParams.distortion_weight — the ray-distortion regulariser, distortion_weight * mean over pixels of
     sum_{j<k} w_j w_k (1/z_j - 1/z_k), added to every training step's loss; with it on the steps take the autograd form (train.train_step).
+    normal_weight (default 0: off) / normal_depth ("median" or "blended"): OptimParams.normal_weight / normal_depth — the normal-consistency
+    regulariser, normal_weight * mean over pixels of static * (alpha - N_blended . N_depth), added to every training step's loss; with it on the
+    steps take the autograd form (train.train_step).
     progress: called at the job's stages and every few hundred iterations (Rendezvous.tick).  pipe: the `pipe` of training and of the held-out
     report (job_pipe; None: the default one)."""
     progress = progress or (lambda: None)
@@ -311,7 +314,8 @@ def run_sequence_job(scene_id, iterations, device, frames=6, seq_dir=None, out_d
                           exposure_lr_init=float(exposure_lr_init), exposure_lr_final=float(exposure_lr_final),
                           **({"prune_thin_edge": prune_thin_edge} if prune_thin_edge > 0.0 else {}),
                           **({"fov_lr": float(fov_lr)} if float(fov_lr) > 0.0 else {}),
-                          **({"distortion_weight": float(distortion_weight)} if float(distortion_weight) > 0.0 else {}))
+                          **({"distortion_weight": float(distortion_weight)} if float(distortion_weight) > 0.0 else {}),
+                          **({"normal_weight": float(normal_weight), "normal_depth": str(normal_depth)} if float(normal_weight) > 0.0 else {}))
         start, loop_state = 1, None
         if resume and out_dir is not None:
             from .train import latest_checkpoint, load_checkpoint
@@ -506,6 +510,10 @@ def parser():
                     "step with the poses under the PSNR gate; with --out the job writes <sequence>/fov.json, which das3r_amd.offline renders with")
     ap.add_argument("--distortion-weight", type=float, default=0.0, help="weight of the ray-distortion regulariser (off by default): the mean over pixels of "
                     "sum_{j<k} w_j w_k (1/z_j - 1/z_k) along the ray, added to every training step's loss (Mip-NeRF 360 / 2DGS)")
+    ap.add_argument("--normal-weight", type=float, default=0.0, help="weight of the normal-consistency regulariser (off by default): the mean over pixels of "
+                    "static * (alpha - blended normal . depth normal), added to every training step's loss (2DGS / GOF / PGSR / RaDe-GS)")
+    ap.add_argument("--normal-depth", default="median", choices=("median", "blended"), help="the depth image whose normal the regulariser takes: the median "
+                    "depth of the render's lists, or alpha / inverse depth")
     ap.add_argument("--exposure-heldout", default="identity", choices=("identity", "nearest"), help="the matrix a held-out view is compared under: none "
                     "(identity: the raw render) or that of the training frame with the nearest frame index")
     init = ap.add_mutually_exclusive_group()
@@ -555,14 +563,16 @@ def main(argv=None):
                                          dataset=args.dataset, progress=tick, checkpoint_every=args.checkpoint_every, resume=args.resume, pipe=pipe,
                                          depth_l1_init=args.depth_l1_init, depth_l1_final=args.depth_l1_final, **prune_kwargs(args), **exposure_kwargs(args), **thin_kw,
                                          **({"fov_lr": args.fov_lr} if args.fov_lr > 0.0 else {}),
-                                         **({"distortion_weight": args.distortion_weight} if args.distortion_weight > 0.0 else {}))
+                                         **({"distortion_weight": args.distortion_weight} if args.distortion_weight > 0.0 else {}),
+                                         **({"normal_weight": args.normal_weight, "normal_depth": args.normal_depth} if args.normal_weight > 0.0 else {}))
     else:
         mine = assign(args.sequences, rank, world)
         job = lambda s: run_sequence_job(s, args.iterations, device, fused=args.fused, progress=tick, checkpoint_every=args.checkpoint_every,
                                          resume=args.resume, out_dir=os.path.join(args.out, f"seq_{s}") if args.out else None, pipe=pipe,
                                          depth_l1_init=args.depth_l1_init, depth_l1_final=args.depth_l1_final, **prune_kwargs(args), **exposure_kwargs(args), **thin_kw,
                                          **({"fov_lr": args.fov_lr} if args.fov_lr > 0.0 else {}),
-                                         **({"distortion_weight": args.distortion_weight} if args.distortion_weight > 0.0 else {}))
+                                         **({"distortion_weight": args.distortion_weight} if args.distortion_weight > 0.0 else {}),
+                                         **({"normal_weight": args.normal_weight, "normal_depth": args.normal_depth} if args.normal_weight > 0.0 else {}))
     # (default: two in flight with the fused kernels — the measured configuration; the reference's PyTorch glue runs its backward passes in
     #  autograd's one device thread, where two jobs would queue behind each other: one at a time unless asked for)
     records = run_jobs(mine, job, args.jobs_per_gpu if args.jobs_per_gpu else (2 if (use_gpu and args.fused) else 1), device)

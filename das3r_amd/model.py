@@ -68,6 +68,13 @@ class OptimParams:   # /root/reference/arguments/__init__.py:73-90 (densificatio
     # to one depth, and needs no target.  0: off — the step is the one it was, call for call.  > 0: the autograd forms of train_step only
     # (the direct iteration of fast_step.py does not carry the term yet).
     distortion_weight: float = 0.0
+    # normal-consistency regulariser (2DGS / GOF / PGSR / RaDe-GS; not in the reference): loss += normal_weight * mean over pixels of
+    # static * (alpha - N_blended . N_depth) (rasterizer.normal_consistency over das3r_render(return_normal_consistency=True)) — it turns the
+    # Gaussians' thinnest axes to face the way the rendered depth surface does, and needs no target.  normal_depth: the depth image whose normal
+    # is taken — "median" (rasterizer.median_depth_of) or "blended" (alpha / inverse depth).  0: off — the step is the one it was, call for
+    # call.  > 0: the autograd forms of train_step only (the direct iteration of fast_step.py does not carry the term yet).
+    normal_weight: float = 0.0
+    normal_depth: str = "median"
 
 
 def log_focal_of(fovx, fovy):

@@ -127,7 +127,7 @@ class _EvalState:
 
 @torch.no_grad()
 def render_view_fused(model, view, pose7, background, pipe=PIPE, invdepth=False, features=None, alpha=False, return_state=False, distortion=False,
-                      median_depth=False):
+                      median_depth=False, normals=False):
     """render_test of one view (gaussian_renderer/__init__.py:152-277) with the pose pre-transform INSIDE the rasterizer's per-Gaussian
     kernel (include/das3r_raster.h das3r_raster_in.pre, as the direct training iteration uses it): R xyz + t, quaternion product, exp,
     sigmoid x the per-Gaussian conf_static column — the dozen PyTorch kernels of the reference's glue (a boolean-mask gather of every
@@ -137,7 +137,9 @@ def render_view_fused(model, view, pose7, background, pipe=PIPE, invdepth=False,
     alpha: appended after those, in this order — the [C, H, W] image of the channels blended over this forward's lists
     (rasterizer.composite_features) and the [1, H, W] coverage (rasterizer.alpha_of); distortion: then the [1, H, W] ray-distortion image
     (rasterizer.distortion_of); median_depth: then the [1, H, W] median depth (rasterizer.median_depth_of: the view-space depth of the Gaussian
-    at which the ray's transmittance crosses one half); return_state: last, the forward's RasterState."""
+    at which the ray's transmittance crosses one half); normals: then the [3, H, W] view-space normal image — the Gaussians' normals
+    (rasterizer.gaussian_normals of the camera-frame rotations and means, which this one option forms in torch ops) blended over the same lists —
+    and the [3, H, W] normal of the median-depth image (rasterizer.depth_normals); return_state: last, the forward's RasterState."""
     import ctypes as C
     from . import _lib
     from .rasterizer import _forward, _on_device, _stream, alpha_of, composite_features, distortion_of, median_depth_of
@@ -171,6 +173,13 @@ def render_view_fused(model, view, pose7, background, pipe=PIPE, invdepth=False,
         out = out + (distortion_of(state),)
     if median_depth:
         out = out + (median_depth_of(state),)
+    if normals:
+        from .camera import camera_from_tensor, quat_multiply
+        from .rasterizer import depth_normals, gaussian_normals
+        w2c = camera_from_tensor(pose7)
+        per_gaussian = gaussian_normals(rs, quat_multiply(pose7[:4], rot).contiguous(), model.get_scaling.detach().contiguous(),
+                                        (xyz @ w2c[:3, :3].T + w2c[:3, 3]).contiguous())
+        out = out + (composite_features(state, per_gaussian), depth_normals(median_depth_of(state), rs))
     if return_state:
         out = out + (state,)
     return out
@@ -200,7 +209,7 @@ def median_depth_median_rel_error(median_depth, depth):
 
 @torch.no_grad()
 def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=None, poses=None, write=True, fused=False, invdepth=None,
-               exposures=None, static_map=None, alpha=None, distortion=None, median_depth=None):
+               exposures=None, static_map=None, alpha=None, distortion=None, median_depth=None, normals=None):
     """render.py:72-86.  views: cameras carrying .pose7 (qw, qx, qy, qz, tx, ty, tz world-to-camera); poses: optional [N, 4, 4]
     world-to-camera matrices that override them.  fused: render_view_fused instead of the reference's PyTorch glue in front of the
     rasterizer (opt-in, like every fused form).  invdepth: a list that receives every view's inverse-depth image [1, H, W] (written as
@@ -212,13 +221,16 @@ def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=
     written as distortion/%05d.npy, as alpha is); None: not computed.
     median_depth: a list that receives every view's median-depth image [1, H, W] from the render's own lists (rasterizer.median_depth_of;
     written as median_depth/%05d.npy, as alpha is); None: not computed.
+    normals: a list that receives every view's (normal image, depth-normal image) pair, both [3, H, W] in view space — the Gaussians' normals
+    blended over the render's own lists and the normal of its median-depth image (rasterizer.gaussian_normals / depth_normals; written as
+    normals/%05d.npy and depth_normals/%05d.npy beside alpha/); None: not computed.
     -> list of the rendered [3, H, W] tensors (on the device)."""
     dev = model.get_xyz.device
     background = background if background is not None else torch.zeros(3, device=dev)
     base = os.path.join(model_path, name, f"ours_{iteration}")
     render_path = os.path.join(base, "renders")
     want, want_static, want_alpha, want_dist = invdepth is not None, static_map is not None, alpha is not None, distortion is not None
-    want_median = median_depth is not None
+    want_median, want_normals = median_depth is not None, normals is not None
     conf = None
     if want_static:
         conf = model._conf_static.detach().reshape(-1, 1).float().contiguous()
@@ -227,10 +239,11 @@ def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=
     out = []
     for idx, view in enumerate(views):
         pose = view.pose7 if poses is None else tensor_from_camera(poses[idx], dev)
-        smap = amap = dmap = zmap = None
+        smap = amap = dmap = zmap = nmap = dnmap = None
         if fused:
             res = render_view_fused(model, view, pose, background, pipe, invdepth=want, features=conf, alpha=want_alpha,
-                                    **({"distortion": True} if want_dist else {}), **({"median_depth": True} if want_median else {}))
+                                    **({"distortion": True} if want_dist else {}), **({"median_depth": True} if want_median else {}),
+                                    **({"normals": True} if want_normals else {}))
             img, inv = res[0], (res[2] if want else None)
             nxt = 3 if want else 2
             if want_static:
@@ -240,10 +253,13 @@ def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=
             if want_dist:
                 dmap, nxt = res[nxt], nxt + 1
             if want_median:
-                zmap = res[nxt]
+                zmap, nxt = res[nxt], nxt + 1
+            if want_normals:
+                nmap, dnmap = res[nxt], res[nxt + 1]
         else:
             pkg = das3r_render(view, model, pipe, background, camera_pose=pose, variant="test", return_invdepth=want, features=conf,
-                               return_alpha=want_alpha, **({"return_state": True} if want_dist or want_median else {}))
+                               return_alpha=want_alpha, **({"return_state": True} if want_dist or want_median or want_normals else {}),
+                               **({"return_normals": True} if want_normals else {}))
             img, inv, smap, amap = pkg["render"], pkg.get("invdepth"), pkg.get("features"), pkg.get("alpha")
             if want_dist:
                 from .rasterizer import distortion_of
@@ -251,6 +267,11 @@ def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=
             if want_median:
                 from .rasterizer import median_depth_of
                 zmap = median_depth_of(pkg["raster_state"])
+            if want_normals:
+                from .rasterizer import depth_normals, median_depth_of
+                from .render import _settings
+                nmap = pkg["normals"]
+                dnmap = depth_normals(median_depth_of(pkg["raster_state"]) if zmap is None else zmap, _settings(view, model, pipe, background, 1.0, dev))
         if exposures is not None and exposures[idx] is not None:
             from .losses import apply_exposure
             img = apply_exposure(img, torch.as_tensor(exposures[idx], dtype=img.dtype, device=img.device))
@@ -265,6 +286,8 @@ def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=
             distortion.append(dmap)
         if want_median:
             median_depth.append(zmap)
+        if want_normals:
+            normals.append((nmap, dnmap))
         if write:
             save_image(img, os.path.join(render_path, f"{idx:05d}.png"))
             for sub, m in (("invdepth", inv if want else None), ("static", smap), ("alpha", amap), ("distortion", dmap),
@@ -272,12 +295,16 @@ def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=
                 if m is not None:
                     os.makedirs(os.path.join(base, sub), exist_ok=True)
                     np.save(os.path.join(base, sub, f"{idx:05d}.npy"), m[0].detach().cpu().numpy())
+            for sub, m in (("normals", nmap), ("depth_normals", dnmap)):   # (three channels: the whole [3, H, W] tensor)
+                if m is not None:
+                    os.makedirs(os.path.join(base, sub), exist_ok=True)
+                    np.save(os.path.join(base, sub, f"{idx:05d}.npy"), m.detach().cpu().numpy())
     return out
 
 
 def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=False, optimised_poses=False, device="cuda", write=True, fused=False,
                 depth=False, pipe=PIPE, prune_min_opacity=0.0, write_pruned_ply=False, exposure="none", static_map=False, alpha=False, thin_edge=None, thin_relative=None,
-                camera_fov=False, distortion=False, median_depth=False):
+                camera_fov=False, distortion=False, median_depth=False, normals=False):
     """render.py:89-123: load the trained model, write pose_interpolated.npy, render the "interp" set.  seq: the sequence the model was
     trained on (its cameras).  depth: also the inverse-depth images (invdepth/%05d.npy) and, per view, the median relative error of
     1 / invdepth against the sequence's depth map (printed: a diagnostic).  pipe: PIPE, or pipe_from_args' (pipe.antialiasing: a model
@@ -289,7 +316,8 @@ def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=Fal
     static-confidence map and coverage map (render_set: static/%05d.npy, alpha/%05d.npy); distortion: and its ray-distortion image
     (distortion/%05d.npy, from the render's own lists); median_depth: and its median-depth image (median_depth/%05d.npy, from the same
     lists) with, per view, the diagnostic `depth` prints — the median relative error against the sequence's depth map — so that the blended
-    and the median depth can be compared on one sequence.  thin_edge (world units) / thin_relative (multiples of
+    and the median depth can be compared on one sequence.  normals: and its view-space normal image and the normal of its median-depth image
+    (normals/%05d.npy, depth_normals/%05d.npy, [3, H, W], beside alpha/).  thin_edge (world units) / thin_relative (multiples of
     the pixel footprint of `seq`'s depth maps and intrinsics: das3r_amd.thin.pixel_footprint over its confident pixels), at most one: the loaded
     model is thinned to one Gaussian per voxel first (das3r_amd.thin.thin_model, after prune_min_opacity's event when both are given);
     write_pruned_ply then saves the thinned model.  A model directory that holds fov.json (a job that trained its field of view: farm
@@ -351,7 +379,8 @@ def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=Fal
         exposures = [table.get(names[f]) for f in frames]
     imgs = render_set(model_path, "interp", iteration, views, model, pipe, bg, poses=poses, write=write, fused=fused, invdepth=inv,
                       exposures=exposures, static_map=[] if static_map else None, alpha=[] if alpha else None,
-                      **({"distortion": []} if distortion else {}), **({"median_depth": med} if median_depth else {}))
+                      **({"distortion": []} if distortion else {}), **({"median_depth": med} if median_depth else {}),
+                      **({"normals": []} if normals else {}))
     if depth and seq.get("depths") is not None:
         for idx, (f, d) in enumerate(zip(frames, inv)):
             print(f"view {idx:05d} (frame {f}): median |1/invdepth - depth| / depth = {invdepth_median_rel_error(d, seq['depths'][f]):.4f}")
@@ -420,6 +449,9 @@ def parser():
     ap.add_argument("--median-depth", action="store_true", help="also write every view's median depth — the view-space depth of the Gaussian at which the "
                     "ray's transmittance crosses one half, from the render's own lists (median_depth/%%05d.npy next to renders/) — and print, per view, "
                     "its median relative error against the sequence's depth map (what --depth prints for the blended depth)")
+    ap.add_argument("--normals", action="store_true", help="also write every view's normal image — the Gaussians' thinnest axes, facing the camera, blended "
+                    "over the render's own lists (normals/%%05d.npy beside alpha/) — and the normal of its median-depth image (depth_normals/%%05d.npy), "
+                    "both [3, H, W] in view space")
     return ap
 
 
@@ -432,6 +464,7 @@ def main(argv=None):
                            depth=args.depth, pipe=pipe_from_args(args), prune_min_opacity=args.prune_min_opacity, write_pruned_ply=args.write_pruned_ply,
                            exposure=args.exposure, static_map=args.static_map, alpha=args.alpha, **({"camera_fov": True} if args.camera_fov else {}),
                            **({"distortion": True} if args.distortion else {}), **({"median_depth": True} if args.median_depth else {}),
+                           **({"normals": True} if args.normals else {}),
                            **({"thin_edge": args.thin_edge, "thin_relative": args.thin_relative}
                               if (args.thin_edge is not None or args.thin_relative is not None) else {}))
     print(f"wrote {len(imgs)} images to {os.path.join(args.model_path, 'interp', f'ours_{it}', 'renders')}")

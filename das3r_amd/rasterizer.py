@@ -920,6 +920,187 @@ def median_depth_of(state, geometry=None, threshold=0.5, return_hit=False, retur
     return (depth,) + extra if extra else depth
 
 
+# ---- the normal-consistency regulariser: per-Gaussian normals, depth normals, the loss image
+
+
+def _normals_args(rs, P, device, keep):
+    """The das3r_raster_args of the per-Gaussian normal calls: P, viewmatrix and campos (and debug)."""
+    a = _lib.RasterArgs()
+    a.P, a.debug = int(P), int(bool(rs.debug))
+    vm = _small(rs.viewmatrix, device, 16, "viewmatrix")
+    cp = _small(rs.campos, device, 3, "campos")
+    keep.extend([vm, cp])
+    a.viewmatrix, a.campos = vm.data_ptr(), cp.data_ptr()
+    return a
+
+
+def _gaussian_normals_forward(rs, rotations, scales, means3D, _fill=None):
+    """One das3r_gaussian_normals_forward call -> (normals [P, 3], choice [P] uint8: k | flip << 2)."""
+    device, P = rotations.device, rotations.shape[0]
+    normals = _new(device, _fill)(P, 3)   # both fully written by the call
+    choice = torch.empty(P, dtype=torch.uint8, device=device)
+    keep = []
+    a = _normals_args(rs, P, device, keep)
+    with _on_device(device):
+        rc = _lib.load().das3r_gaussian_normals_forward(C.byref(a), _ptr(rotations), _ptr(scales), _ptr(means3D), _ptr(normals), _ptr(choice),
+                                                        _stream(device))
+    _lib.check(rc, "das3r_gaussian_normals_forward")
+    return normals, choice
+
+
+def _gaussian_normals_backward(rs, rotations, choice, grad, out=None, accumulate=False, _fill=None):
+    """One das3r_gaussian_normals_backward call: grad [P, 3] -> dL/drotations [P, 4] (written, or added to `out`)."""
+    device, P = rotations.device, rotations.shape[0]
+    if out is None:
+        out = _new(device, _fill)(P, 4)
+    keep = []
+    a = _normals_args(rs, P, device, keep)
+    with _on_device(device):
+        rc = _lib.load().das3r_gaussian_normals_backward(C.byref(a), _ptr(rotations), _ptr(choice), _ptr(grad), _ptr(out), int(bool(accumulate)),
+                                                         _stream(device))
+    _lib.check(rc, "das3r_gaussian_normals_backward")
+    return out
+
+
+class _GaussianNormals(torch.autograd.Function):
+    """gaussian_normals with its backward: the gradient goes to `rotations` alone (the thinnest axis and the flip are the forward's)."""
+    @staticmethod
+    def forward(ctx, rotations, scales, means3D, raster_settings):
+        normals, choice = _gaussian_normals_forward(raster_settings, rotations, scales, means3D)
+        ctx.raster_settings = raster_settings
+        ctx.save_for_backward(rotations, choice)
+        return normals
+
+    @staticmethod
+    def backward(ctx, grad):
+        rotations, choice = ctx.saved_tensors
+        return _gaussian_normals_backward(ctx.raster_settings, rotations, choice, _dense(grad)), None, None, None
+
+
+def gaussian_normals(raster_settings, rotations, scales, means3D):
+    """-> [P, 3]: every Gaussian's normal in view space — the axis of its smallest scale (ties: the lowest index), column k of R(q / |q|),
+    turned to face the camera (negated when axis . (mean - campos) > 0; a product of exactly 0 keeps it) and taken into view space by the
+    rotation part of raster_settings.viewmatrix (include/das3r_raster.h das3r_gaussian_normals_forward).  Differentiable with respect to
+    `rotations` ALONE, through the quaternion's normalisation; which axis and whether it is flipped are held fixed, scales and means receive
+    no gradient.  One streaming kernel each way.  The rasterizer takes a raw quaternion as given: for |q| != 1 this is the axis of the
+    NORMALISED quaternion, not an eigenvector of the sheared covariance.  A cov3D_precomp caller has no axes: both tensors are required."""
+    if not torch.is_tensor(means3D):
+        raise TypeError("means3D must be a tensor [P, 3]")
+    if means3D.shape[0] > 0 and not (_given(rotations) and _given(scales)):
+        raise ValueError("gaussian_normals needs scales and rotations: a cov3D_precomp caller has no axes")
+    for t, name, cols in ((rotations, "rotations", 4), (scales, "scales", 3)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{name} must be a tensor [P, {cols}]")
+    device = means3D.device
+    if device.type != "cuda":
+        raise RuntimeError("das3r_amd rasterizer: tensors must live on a HIP device (torch device 'cuda'); there is no CPU path")
+    P = means3D.shape[0]
+    for t, name, cols in ((rotations, "rotations", 4), (scales, "scales", 3), (means3D, "means3D", 3)):
+        if t.dim() != 2 or tuple(t.shape) != (P, cols):
+            raise ValueError(f"{name} must have dimensions ({P}, {cols}), got {tuple(t.shape)}")
+    rotations, scales, means3D = (_prep(t, device, n) for t, n in ((rotations, "rotations"), (scales, "scales"), (means3D, "means3D")))
+    if rotations.requires_grad and torch.is_grad_enabled():
+        return _GaussianNormals.apply(rotations, scales.detach(), means3D.detach(), raster_settings)
+    return _gaussian_normals_forward(raster_settings, rotations.detach(), scales.detach(), means3D.detach())[0]
+
+
+def _plane(t, H, W, name):
+    """[H, W] or [1, H, W] fp32 on a HIP device -> the dense [H, W] tensor the library reads"""
+    if not torch.is_tensor(t):
+        raise TypeError(f"{name} must be a tensor [H, W] or [1, H, W]")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32 (got {t.dtype})")
+    if tuple(t.shape) not in ((H, W), (1, H, W)):
+        raise ValueError(f"{name} must have dimensions ({H}, {W}) or (1, {H}, {W}), got {tuple(t.shape)}")
+    return t.reshape(H, W).contiguous()
+
+
+def _image_call(name, rs, *rest):
+    H, W = int(rs.image_height), int(rs.image_width)
+    device = rest[0].device
+    with _on_device(device):
+        rc = getattr(_lib.load(), name)(H, W, float(rs.tanfovx), float(rs.tanfovy), *(_ptr(t) for t in rest), _stream(device))
+    _lib.check(rc, name)
+
+
+def _check_image_inputs(depth, rs, normal=None, alpha=None, mask=None):
+    """-> (depth, normal, alpha, mask) as dense fp32 [H, W] / [3, H, W] tensors on depth's device; everything else is refused here."""
+    H, W = int(rs.image_height), int(rs.image_width)
+    if H <= 0 or W <= 0:
+        raise ValueError(f"raster_settings describes a {W} x {H} image")
+    d = _plane(depth, H, W, "depth")
+    n = a = m = None
+    if normal is not None:
+        if not torch.is_tensor(normal) or normal.dtype != torch.float32 or tuple(normal.shape) != (3, H, W):
+            raise ValueError(f"normal must be a float32 tensor of dimensions (3, {H}, {W})")
+        n = normal.contiguous()
+    if alpha is not None:
+        a = _plane(alpha, H, W, "alpha")
+    if mask is not None:
+        m = _plane(mask.detach() if torch.is_tensor(mask) else mask, H, W, "mask")
+    if d.device.type != "cuda":
+        raise RuntimeError("das3r_amd rasterizer: tensors must live on a HIP device (torch device 'cuda'); there is no CPU path")
+    for t, name in ((n, "normal"), (a, "alpha"), (m, "mask")):
+        if t is not None and t.device != d.device:
+            raise RuntimeError(f"{name} is on {t.device}, depth on {d.device}")
+    return d, n, a, m
+
+
+def depth_normals(depth, raster_settings):
+    """depth [H, W] or [1, H, W] (view-space z) -> [3, H, W]: the unit normal of the depth surface, facing the camera (a fronto-parallel plane
+    gives (0, 0, -1)), from central differences of the unprojected points p = z ray, ray through the pixel centres with raster_settings'
+    tanfovx / tanfovy (include/das3r_raster.h das3r_normal_consistency_forward).  Exactly 0 on the one-pixel border, where the pixel or one
+    of its four neighbours has no finite depth > 0, and where the surface element degenerates.  A plain tensor; normal_consistency is the
+    differentiable use of it."""
+    d, _, _, _ = _check_image_inputs(depth, raster_settings)
+    H, W = d.shape
+    out = torch.empty(3, H, W, dtype=torch.float32, device=d.device)   # fully written by the call
+    zero = torch.zeros(4, H, W, dtype=torch.float32, device=d.device)   # (the entry takes a blended normal and a coverage: none here)
+    _image_call("das3r_normal_consistency_forward", raster_settings, d.detach(), zero[:3], zero[3], None, torch.empty_like(d), out)
+    return out
+
+
+def _normal_consistency_forward(depth, normal, alpha, mask, rs):
+    """One das3r_normal_consistency_forward call on dense tensors -> the loss image [H, W]."""
+    loss = torch.empty_like(depth)   # fully written by the call
+    _image_call("das3r_normal_consistency_forward", rs, depth, normal, alpha, mask, loss, None)
+    return loss
+
+
+class _NormalConsistency(torch.autograd.Function):
+    """normal_consistency with its backward: ONE das3r_normal_consistency_backward call for the three gradients."""
+    @staticmethod
+    def forward(ctx, depth, normal, alpha, mask, raster_settings):
+        loss = _normal_consistency_forward(depth, normal, alpha, mask, raster_settings)
+        ctx.raster_settings, ctx.has_mask = raster_settings, mask is not None
+        ctx.save_for_backward(depth, normal, *(() if mask is None else (mask,)))
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad):
+        depth, normal = ctx.saved_tensors[:2]
+        mask = ctx.saved_tensors[2] if ctx.has_mask else None
+        g_depth, g_normal, g_alpha = torch.empty_like(depth), torch.empty_like(normal), torch.empty_like(depth)   # each fully written
+        _image_call("das3r_normal_consistency_backward", ctx.raster_settings, depth, normal, mask, _dense(grad), g_depth, g_normal, g_alpha)
+        return g_depth, g_normal, g_alpha, None, None
+
+
+def normal_consistency(depth, normal, alpha, raster_settings, mask=None):
+    """-> [1, H, W]: the normal-consistency loss image (2DGS's normal term) — per pixel mask * (alpha - normal . N_d), N_d = depth_normals(depth,
+    raster_settings).  With normal = sum_k w_k n_k (the Gaussians' normals blended over a forward's lists) and alpha = sum_k w_k (its coverage)
+    this is sum_k w_k (1 - n_k . N_d).  depth, alpha: [H, W] or [1, H, W]; normal: [3, H, W]; mask: [H, W] or [1, H, W], a constant, or None
+    (ones).  Exactly 0 wherever N_d is (depth_normals), and such a pixel sends exactly 0 to every gradient whatever its depth holds.
+    Differentiable with respect to depth, normal and alpha (das3r_normal_consistency_backward: dL/dalpha = g m, dL/dnormal = -g m N_d,
+    dL/ddepth gathered from the four neighbours whose stencils read the pixel).  No floating-point atomics: bit-identical from run to run."""
+    d, n, a, m = _check_image_inputs(depth, raster_settings, normal, alpha, mask)
+    if n is None or a is None:
+        raise TypeError("normal_consistency needs the blended normal [3, H, W] and the coverage [H, W]")
+    H, W = d.shape
+    if torch.is_grad_enabled() and (d.requires_grad or n.requires_grad or a.requires_grad):
+        return _NormalConsistency.apply(d, n, a, m, raster_settings).reshape(1, H, W)
+    return _normal_consistency_forward(d.detach(), n.detach(), a.detach(), m, raster_settings).reshape(1, H, W)
+
+
 # ---- the rasterising autograd function and the module
 
 

@@ -23,7 +23,8 @@ import math
 import torch
 
 from .camera import camera_from_tensor, projection_matrix, quat_multiply
-from .rasterizer import AuxGeometry, GaussianRasterizationSettings, GaussianRasterizer, distortion_of, median_depth_of
+from .rasterizer import (AuxGeometry, GaussianRasterizationSettings, GaussianRasterizer, _aux_with_geometry, distortion_of, gaussian_normals,
+                         median_depth_of, normal_consistency)
 
 _SH_C0 = 0.28209479177387814
 _SH_C1 = 0.4886025119029199
@@ -179,6 +180,9 @@ def rasterizer_inputs(cam, pc, pipe, bg_color, scaling_modifier=1.0, override_co
     return settings, kw
 
 
+NORMAL_DEPTHS = ("median", "blended")
+
+
 def _mode_kw(pipe, return_invdepth, features=None, return_alpha=False, aux_geometry_grad=False):
     """GaussianRasterizer.forward's keywords beyond upstream's eight tensors: only those that are on."""
     kw = {"return_invdepth": True} if return_invdepth else {}
@@ -195,7 +199,8 @@ def _mode_kw(pipe, return_invdepth, features=None, return_alpha=False, aux_geome
 
 def das3r_render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, camera_pose=None,
                  filtering=None, use_conf=True, fused=False, variant="render", return_invdepth=False, features=None, return_alpha=False,
-                 return_state=False, aux_geometry_grad=False, return_distortion=False, return_median_depth=False):
+                 return_state=False, aux_geometry_grad=False, return_distortion=False, return_median_depth=False, return_normals=False,
+                 return_normal_consistency=False, normal_depth="median", normal_mask=None):
     """viewpoint_camera: .FoVx .FoVy .image_height .image_width .projection_matrix (4x4, already transposed) [.camera_center for
     pipe.convert_SHs_python]; pc: splat model (das3r_amd.model.SplatModel or anything with the same attributes); pipe: .debug
     .compute_cov3D_python .convert_SHs_python; camera_pose: (7,) tensor (qw,qx,qy,qz,tx,ty,tz), may require grad.
@@ -216,21 +221,42 @@ def das3r_render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, ove
     view-space depth of the Gaussian at which the ray's transmittance crosses one half, no second forward; 0 where nothing was blended),
     differentiable with respect to the means and, through them, the pose; render_pkg["median_hit"] = the int32 [H, W] index of that Gaussian
     among the rasterised ones (-1: empty pixel).  False: the calls are the ones they were.
+    return_normals: render_pkg["normals"] = the [3, H, W] view-space normal image — the Gaussians' normals (rasterizer.gaussian_normals: the
+    thinnest axis, facing the camera) blended over this render's own lists, sum_k w_k n_k, no second forward — and render_pkg["alpha"] is
+    filled with the coverage of the same call.  Differentiable with respect to means, opacities, scales and rotations (one aux backward for both
+    images, the coverage's gradient passed directly; then the normals' own backward to the rotations); a caller's own `features=` is blended
+    by a call of its own and unchanged.  Needs scales + rotations: pipe.compute_cov3D_python has no axes and is refused.
+    return_normal_consistency (implies return_normals): render_pkg["normal_consistency"] = the [1, H, W] loss image
+    normal_mask * (alpha - normals . N_d) (rasterizer.normal_consistency), N_d the normal of the depth image z (render_pkg["normal_depth"]):
+    normal_depth="median" (the default): z = median_depth_of over the same lists, whose gradient goes to the means through the median adjoint;
+    normal_depth="blended": z = alpha / invdepth where invdepth > 0, else 0, from return_invdepth's image (the forward then renders it), in torch
+    elementwise ops.  Any other value raises ValueError.  normal_mask ([H, W] or [1, H, W], or None): a constant per-pixel factor.
+    All off: the calls are the ones they were.
     With OptimParams.fov_lr > 0 (pc.fov_lr) the "render" variant takes the field of view and the projection from pc.FoVx / pc.FoVy instead
     of the camera's — training, held-out passes and reports alike — and a backward pass leaves dL/dFoV on them (one host read-back of the
     two values per render: the settings are host floats)."""
+    if normal_depth not in NORMAL_DEPTHS:
+        raise ValueError(f"normal_depth must be one of {NORMAL_DEPTHS}, got {normal_depth!r}")
+    return_normals = bool(return_normals or return_normal_consistency)
+    blended_z = bool(return_normal_consistency) and normal_depth == "blended"
     settings, kw = rasterizer_inputs(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, camera_pose, filtering,
                                      use_conf, fused, variant)
-    want_state = return_state or return_distortion or return_median_depth
+    if return_normals and (kw["scales"] is None or kw["rotations"] is None):
+        raise ValueError("return_normals / return_normal_consistency need scales and rotations: a cov3D_precomp render (pipe.compute_cov3D_python) "
+                         "has no axes")
+    want_state = return_state or return_distortion or return_median_depth or return_normals
     rasterizer = GaussianRasterizer(raster_settings=settings, keep_state=True) if want_state else GaussianRasterizer(raster_settings=settings)
-    out = rasterizer(**kw, **_mode_kw(pipe, return_invdepth, features, return_alpha, aux_geometry_grad))   # (upstream's call when all are off)
+    out = rasterizer(**kw, **_mode_kw(pipe, return_invdepth or blended_z, features, return_alpha, aux_geometry_grad))   # (upstream's call when all are off)
     image, radii = out[0], out[1]
     if variant == "confidence":
         return image   # (render_confidence returns the image alone: gaussian_renderer/__init__.py:510)
     pkg = {"render": image, "viewspace_points": kw["means2D"], "visibility_filter": radii > 0, "radii": radii}
     nxt = 2
-    if return_invdepth:
-        pkg["invdepth"] = out[nxt]
+    invdepth = None
+    if return_invdepth or blended_z:
+        invdepth = out[nxt]
+        if return_invdepth:
+            pkg["invdepth"] = invdepth
         nxt += 1
     if features is not None:
         pkg["features"] = out[nxt]
@@ -239,13 +265,27 @@ def das3r_render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, ove
         pkg["alpha"] = out[nxt]
     if return_state:
         pkg["raster_state"] = rasterizer.state
-    if return_distortion or return_median_depth:
+    if return_distortion or return_median_depth or return_normals:
         geometry = AuxGeometry(settings, kw["means3D"], kw["means2D"], kw["opacities"], kw["shs"], kw["colors_precomp"], kw["scales"],
                                kw["rotations"], kw["cov3D_precomp"])
     if return_distortion:
         pkg["distortion"] = distortion_of(rasterizer.state, geometry=geometry)
     if return_median_depth:
         pkg["median_depth"], pkg["median_hit"] = median_depth_of(rasterizer.state, geometry=geometry, return_hit=True)
+    if return_normals:
+        # the Gaussians' normals over this render's own lists, through the aux path: the coverage comes out of the same call and its gradient
+        # goes in directly (no column of ones)
+        per_gaussian = gaussian_normals(settings, kw["rotations"], kw["scales"], kw["means3D"])
+        pkg["normals"], alpha = _aux_with_geometry(rasterizer.state, per_gaussian, geometry, True)
+        pkg.setdefault("alpha", alpha)
+    if return_normal_consistency:
+        if blended_z:
+            positive = invdepth > 0
+            z = torch.where(positive, alpha / torch.where(positive, invdepth, torch.ones_like(invdepth)), torch.zeros_like(invdepth))
+        else:
+            z = pkg["median_depth"] if return_median_depth else median_depth_of(rasterizer.state, geometry=geometry)
+        pkg["normal_depth"] = z
+        pkg["normal_consistency"] = normal_consistency(z, pkg["normals"], alpha, settings, mask=normal_mask)
     return pkg
 
 

@@ -52,6 +52,23 @@ def distortion_term_weight(opt):
     return w
 
 
+def normal_term_weight(opt):
+    """OptimParams.normal_weight as a host float (an `opt` without the field: 0.0): the weight of the normal-consistency term."""
+    w = float(getattr(opt, "normal_weight", 0.0) or 0.0)
+    if not (w >= 0.0 and w < float("inf")):
+        raise ValueError(f"OptimParams.normal_weight must be finite and >= 0 (got {w})")
+    return w
+
+
+def normal_term_depth(opt):
+    """OptimParams.normal_depth (an `opt` without the field: "median"): which depth image the normal-consistency term differentiates."""
+    from .render import NORMAL_DEPTHS
+    mode = getattr(opt, "normal_depth", "median")
+    if mode not in NORMAL_DEPTHS:
+        raise ValueError(f"OptimParams.normal_depth must be one of {NORMAL_DEPTHS}, got {mode!r}")
+    return mode
+
+
 def depth_mask_of(cam):
     m = getattr(cam, "depth_mask", None)
     return m if m is not None else torch.ones_like(cam.invdepthmap)
@@ -67,14 +84,19 @@ def train_step(model: SplatModel, cam, opt: OptimParams, iteration, pipe, backgr
     train_gui.py since round 6 — the same, with the loop's `ssim` call answered by the fused SSIM map (fused.ssim_map).
     opt.distortion_weight > 0 adds distortion_weight * mean(ray-distortion image of this render's lists) (das3r_render(return_distortion=True))
     to the loss in both autograd forms; the direct iteration (fast_step.train_step) is taken only while the weight is 0 — its chained
-    backward carries no aux term, the direct form of this one is owed.  At 0 the step is the one it was, call for call."""
+    backward carries no aux term, the direct form of this one is owed.  At 0 the step is the one it was, call for call.
+    opt.normal_weight > 0 adds normal_weight * mean(normal-consistency image of this render's lists) (das3r_render(return_normal_consistency=
+    True, normal_depth=opt.normal_depth), the frame's static map as the constant mask) in the same two forms and under the same rule: the direct
+    iteration only while the weight is 0, its direct form owed."""
     ssim_fn = ssim
     if fused_loss == "ssim":
         from .fused import ssim_map
         ssim_fn, fused_loss = (lambda a, b, size_average=False: ssim_map(a, b)), False
     fused_loss = bool(fused) if fused_loss is None else bool(fused_loss)
     w_dist = distortion_term_weight(opt)   # (0.0: the step below is the one it was, call for call)
-    if fused and fused_loss and w_dist == 0.0:   # (the direct iteration's chained backward refuses aux terms: owed, docs/ledger.md (cq))
+    w_norm = normal_term_weight(opt)
+    normal_kw = {"return_normal_consistency": True, "normal_depth": normal_term_depth(opt)} if w_norm > 0.0 else {}
+    if fused and fused_loss and w_dist == 0.0 and w_norm == 0.0:   # (the direct iteration's chained backward refuses aux terms: owed, docs/ledger.md (cq), (cu))
         from . import fast_step
         if fast_step.available(model, pipe):
             return fast_step.train_step(model, cam, opt, iteration, pipe, background)
@@ -84,7 +106,8 @@ def train_step(model: SplatModel, cam, opt: OptimParams, iteration, pipe, backgr
     pose = model.get_RT(cam.uid)
     w_depth = depth_term_weight(cam, opt, iteration)   # (0.0: the step below is the photometric one, call for call)
     pkg = das3r_render(cam, model, pipe, background, camera_pose=pose, fused=fused, **({"return_invdepth": True} if w_depth > 0.0 else {}),
-                       **({"return_distortion": True} if w_dist > 0.0 else {}))
+                       **({"return_distortion": True} if w_dist > 0.0 else {}),
+                       **(dict(normal_kw, normal_mask=model._conf_static[cam.uid].detach()) if normal_kw else {}))
     image = pkg["render"]
     gt = cam.original_image
     static = model._conf_static[cam.uid]
@@ -98,6 +121,8 @@ def train_step(model: SplatModel, cam, opt: OptimParams, iteration, pipe, backgr
             loss = loss + depth_l1_loss(pkg["invdepth"], cam.invdepthmap, depth_mask_of(cam), static, weight=w_depth)
         if w_dist > 0.0:
             loss = loss + w_dist * pkg["distortion"].mean()
+        if w_norm > 0.0:
+            loss = loss + w_norm * pkg["normal_consistency"].mean()
         loss.backward(retain_graph=True)
         with torch.no_grad():
             model.optimizer.step()
@@ -120,6 +145,8 @@ def train_step(model: SplatModel, cam, opt: OptimParams, iteration, pipe, backgr
         loss = loss + w_depth * depth_l1(pkg["invdepth"][0], cam.invdepthmap, depth_mask_of(cam), static)
     if w_dist > 0.0:
         loss = loss + w_dist * pkg["distortion"].mean()
+    if w_norm > 0.0:
+        loss = loss + w_norm * pkg["normal_consistency"].mean()
     loss.backward(retain_graph=True)
     with torch.no_grad():
         model.optimizer.step()

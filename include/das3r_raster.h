@@ -612,6 +612,68 @@ int das3r_raster_median_adjoint(const das3r_raster_args *args, const das3r_raste
                                 const uint32_t *hit_position /* [H,W]: the forward call's */, float *dL_dz /* [P] */, int32_t accumulate,
                                 float *scratch, das3r_stream_t stream);
 
+/* ---- the normal-consistency regulariser: per-Gaussian normals, the normal of a depth image, the loss image (csrc/normals.hip) ----
+ * Additive symbols under ABI 16.  The normal term of the surface-oriented splatting methods (2DGS, GOF, PGSR, RaDe-GS): the normal blended
+ * from the Gaussians must agree with the normal of the rendered depth surface.  The blend itself is das3r_raster_aux_forward over a forward's
+ * lists (three channels) and the depth is das3r_raster_median_forward's or alpha / inverse depth; what is declared here are the two ends.
+ *
+ * 1. PER-GAUSSIAN NORMALS.  Definition, for Gaussian i:
+ *   - k = argmin_j scales[i][j].  Ties take the lowest j.
+ *   - a = column k of R(q / |q|), q = rotations[i] = (r, x, y, z), R the matrix of quat_to_R in oracle/raster_oracle.c:
+ *       R = [ 1 - 2 (y y + z z)   2 (x y - r z)       2 (x z + r y)     ]
+ *           [ 2 (x y + r z)       1 - 2 (x x + z z)   2 (y z - r x)     ]
+ *           [ 2 (x z - r y)       2 (y z + r x)       1 - 2 (x x + y y) ]
+ *   - d = means3D[i] - campos.
+ *   - flip = (a . d > 0).  A dot product of exactly 0 keeps a.
+ *   - n_world = flip ? -a : a.
+ *   - normals[i] = n_world taken into view space by the rotation part of args->viewmatrix, in the row-vector convention of the preprocess
+ *     kernel: normals[i][j] = sum_c n_world[c] viewmatrix[4 c + j].
+ *   - choice[i] = k | (flip << 2).
+ * args supplies P, viewmatrix and campos only (and debug).
+ * CAVEAT.  The rasterizer uses a raw quaternion as given.  For |q| != 1 the normal is the axis of the NORMALISED quaternion, not an
+ * eigenvector of the sheared covariance the rasterizer builds from the raw one.  A quaternion whose squared norm is 0 or not finite has no
+ * axis: its normal and its gradient are exact zeros.
+ * The unit is compiled without FMA contraction: k and flip are plain IEEE fp32 decisions (the products and the two additions of a . d in
+ * the order x, y, z).
+ * Backward.  k and flip are read from choice: they are the forward's discrete decisions, held fixed.  The gradient goes to the raw
+ * quaternion, through the normalisation: with g^ = dL/d(q / |q|), dL_drotations[i] = (g^ - q^ (q^ . g^)) / |q|.  Scales and means receive
+ * none.  dL_drotations is fully written unless accumulate != 0 (then added to).
+ * Launches: ONE kernel each, one thread per Gaussian, no LDS, no atomics; bit-identical from run to run.
+ * DAS3R_ERR_INVALID_ARG with a das3r_last_error() message, before anything is launched: NULL args, P < 0, NULL viewmatrix / campos, and
+ * any NULL array (a cov3D_precomp caller has no axes and cannot call this).  P == 0 returns DAS3R_OK and launches nothing.
+ *
+ * 2. DEPTH NORMALS AND THE LOSS IMAGE.  depth [H,W] is a view-space z image.  Per pixel (x, y):
+ *   - The ray is r = (((2x+1)/W - 1) tanfovx, ((2y+1)/H - 1) tanfovy, 1): the rasterizer's pixel-centre convention.  The point is p = z r.
+ *   - Tangents by central differences, in the form that does not cancel, with z+- = z(x+-1, y), r the centre pixel's ray and
+ *     t_x = 2 tanfovx / W, t_y = 2 tanfovy / H the ray's step from one pixel to the next:
+ *       dx = ((z+ - z-) r_x + (z+ + z-) t_x,  (z+ - z-) r_y,  z+ - z-)            = p(x+1, y) - p(x-1, y) = z+ (r + t_x e_x) - z- (r - t_x e_x)
+ *       dy = ((z+ - z-) r_x,  (z+ - z-) r_y + (z+ + z-) t_y,  z+ - z-)  in y      = p(x, y+1) - p(x, y-1)
+ *   - N_d = (dy x dx) / |dy x dx|.  This orientation faces the camera: a fronto-parallel plane gives (0, 0, -1), as the per-Gaussian
+ *     normals of part 1 do.
+ *   - loss = m (alpha - normal . N_d), m = mask if given, else 1.  With normal = sum_k w_k n_k and alpha = sum_k w_k this is
+ *     sum_k w_k (1 - n_k . N_d) over the blended entries: 2DGS's term.
+ *   - A pixel is VALID iff 1 <= x <= W-2 and 1 <= y <= H-2; its own z and its four neighbours' z are finite and > 0; |dy x dx|^2 is
+ *     finite and > 0.  An invalid pixel gives exactly 0 for loss and depth_normal, and sends exactly 0 to every gradient, whatever NaN or
+ *     garbage sits in depth there.  Images with no interior pixel (H < 3 or W < 3) produce all zeros.
+ * Backward, for an upstream image g = dL_dloss: dL_dalpha = g m;  dL_dnormal = -g m N_d;  dL_ddepth in GATHER form — pixel q sums the
+ * contributions of the four neighbours whose stencil reads z_q (left, right, upper, lower, in this order), each neighbour's cross product
+ * recomputed.  A pixel's own z does not enter its own normal: it enters only its validity.  mask is a constant.
+ * Launches: ONE kernel each; a workgroup takes a 32 x 8 tile of pixels and stages the depths of the tile and its halo (1 pixel forward, 2
+ * backward: the radius-2 diamond) in LDS, every halo index clamped into the image before the load.  No floating-point atomics; nothing
+ * needs pre-zeroing; every output is fully written; bit-identical from run to run.
+ * DAS3R_ERR_INVALID_ARG with a das3r_last_error() message, before anything is launched: H, W <= 0, H * W > 2^30, a non-finite tanfov, and
+ * any NULL pointer but mask and depth_normal. */
+int das3r_gaussian_normals_forward(const das3r_raster_args *args, const float *rotations /* [P,4] */, const float *scales /* [P,3] */,
+                                   const float *means3D /* [P,3] */, float *normals /* [P,3] */, uint8_t *choice /* [P] */, das3r_stream_t stream);
+int das3r_gaussian_normals_backward(const das3r_raster_args *args, const float *rotations, const uint8_t *choice,
+                                    const float *dL_dnormals /* [P,3] */, float *dL_drotations /* [P,4] */, int32_t accumulate, das3r_stream_t stream);
+int das3r_normal_consistency_forward(int32_t H, int32_t W, float tanfovx, float tanfovy, const float *depth /* [H,W] view-space z */,
+                                     const float *normal /* [3,H,W] */, const float *alpha /* [H,W] */, const float *mask /* [H,W] or NULL */,
+                                     float *loss /* [H,W] */, float *depth_normal /* [3,H,W] or NULL */, das3r_stream_t stream);
+int das3r_normal_consistency_backward(int32_t H, int32_t W, float tanfovx, float tanfovy, const float *depth, const float *normal,
+                                      const float *mask, const float *dL_dloss /* [H,W] */, float *dL_ddepth /* [H,W] */,
+                                      float *dL_dnormal /* [3,H,W] */, float *dL_dalpha /* [H,W] */, das3r_stream_t stream);
+
 /* ---- introspection (used by the parity tests and the roofline accounting) ---- */
 
 /* Byte offsets of the saved intermediates inside geom / binning / img for given extents. */

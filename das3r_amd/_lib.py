@@ -119,6 +119,8 @@ class PreprocessForm(C.Structure):
 
 
 PRUNE_GROUP_ROWS = 1024   # DAS3R_PRUNE_GROUP_ROWS
+TSDF_MAX_VIEWS = 16       # DAS3R_TSDF_MAX_VIEWS: views per launch of das3r_tsdf_integrate (more are taken in chunks)
+TSDF_MAX_VOXELS = 1 << 28 # DAS3R_TSDF_MAX_VOXELS
 
 
 def prune_count_words(P):
@@ -149,6 +151,8 @@ EXPORTS = ("das3r_raster_forward", "das3r_raster_backward", "das3r_raster_backwa
            "das3r_raster_median_forward", "das3r_raster_median_scratch_bytes", "das3r_raster_median_adjoint",
            "das3r_gaussian_normals_forward", "das3r_gaussian_normals_backward", "das3r_normal_consistency_forward", "das3r_normal_consistency_backward",
            "das3r_thin_workspace_bytes", "das3r_thin_voxels", "das3r_raster_focal_workspace_bytes", "das3r_raster_backward_focal",
+           "das3r_tsdf_integrate", "das3r_tsdf_extract_workspace_bytes", "das3r_tsdf_extract_count", "das3r_tsdf_extract_emit",
+           "das3r_debug_tsdf_integrate_host", "das3r_debug_tsdf_extract_host", "das3r_debug_tsdf_swap_table",
            "das3r_debug_path_policy_fresh", "das3r_debug_path_policy_plan", "das3r_debug_path_policy_count", "das3r_debug_path_policy_skew",
            "das3r_debug_path_policy_hint", "das3r_debug_path_policy_forget", "das3r_debug_path_policy_resume", "das3r_debug_seg_dbits",
            "das3r_debug_parse_switches", "das3r_debug_choose_backward", "das3r_debug_choose_forward", "das3r_debug_has_invdepth_form",
@@ -250,6 +254,24 @@ def load():
     L.das3r_thin_workspace_bytes.argtypes = [C.c_int32]
     L.das3r_thin_voxels.restype = C.c_int
     L.das3r_thin_voxels.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    i3, f3 = C.POINTER(C.c_int32), C.POINTER(C.c_float)   # TSDF fusion and mesh extraction (additive under ABI 16)
+    integrate = [i3, f3, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, f3, f3, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                 C.c_void_p, C.c_float, C.c_float]
+    L.das3r_tsdf_integrate.restype = C.c_int
+    L.das3r_tsdf_integrate.argtypes = integrate + [C.c_void_p]
+    L.das3r_debug_tsdf_integrate_host.restype = C.c_int
+    L.das3r_debug_tsdf_integrate_host.argtypes = integrate
+    L.das3r_tsdf_extract_workspace_bytes.restype = C.c_size_t
+    L.das3r_tsdf_extract_workspace_bytes.argtypes = [i3]
+    L.das3r_tsdf_extract_count.restype = C.c_int
+    L.das3r_tsdf_extract_count.argtypes = [i3, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.das3r_tsdf_extract_emit.restype = C.c_int
+    L.das3r_tsdf_extract_emit.argtypes = [i3, f3, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]
+    L.das3r_debug_tsdf_extract_host.restype = C.c_int
+    L.das3r_debug_tsdf_extract_host.argtypes = [i3, f3, C.c_float] + [C.c_void_p] * 9
+    L.das3r_debug_tsdf_swap_table.restype = None
+    L.das3r_debug_tsdf_swap_table.argtypes = [C.POINTER(C.c_uint32)]
     L.das3r_raster_focal_workspace_bytes.restype = C.c_size_t   # focal gradients beside a backward pass (additive under ABI 16)
     L.das3r_raster_focal_workspace_bytes.argtypes = [C.c_int32]
     L.das3r_raster_backward_focal.restype = C.c_int

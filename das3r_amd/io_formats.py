@@ -6,7 +6,8 @@ loader reads back (/root/reference/scene/dataset_readers.py:107-227, scene/colma
     images/frame_%04d.png   sparse/0/cameras.txt   sparse/0/images.txt   pred_traj.txt (TUM)   pred_intrinsics.txt
     depth_maps/frame_%04d.npy   confidence_maps/conf_%04d.npy   dyna_avg/dyna_avg_%04d.npy   dynamic_masks/dynamic_mask_%04d.png
 Output side — the extended 3DGS PLY (/root/reference/scene/gaussian_model.py:326-364, read back at :371-418) and the optimised
-poses pose/pose_N.npy (/root/reference/train_gui.py:467-480).
+poses pose/pose_N.npy (/root/reference/train_gui.py:467-480); the triangle mesh of das3r_amd.tsdf (save_mesh_ply: a plain PLY, the
+reference has no mesh code).
 Pinned by tests/golden/ref_formats.npz (reference colmap_loader / pose_utils run on seeded inputs) and round trips."""
 import os
 
@@ -321,6 +322,89 @@ def read_ply_vertices(path):
         else:
             raise ValueError(f"unsupported PLY format {fmt}")
     return {name: np.array(data[name]) for name, _ in props}
+
+
+def save_mesh_ply(path, vertices, faces, normals=None, colours=None):
+    """A triangle mesh as a binary little-endian PLY any viewer opens: element vertex (float x y z, then float nx ny nz with `normals`, then
+    uchar red green blue with `colours` in [0, 1]: clamp(255 c + 0.5)), element face (list uchar int vertex_indices).  vertices [Nv, 3],
+    faces [Nf, 3] integers below Nv (Nf = 0: a point set), tensors or arrays."""
+    to = lambda t: np.asarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t)
+    v = np.ascontiguousarray(to(vertices), dtype="<f4").reshape(-1, 3)
+    f = np.ascontiguousarray(to(faces), dtype="<i4").reshape(-1, 3)
+    n = v.shape[0]
+    if f.size and (int(f.min()) < 0 or int(f.max()) >= n):
+        raise ValueError("save_mesh_ply: a face index is outside the vertex list")
+    fields, header = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")], "property float x\nproperty float y\nproperty float z\n"
+    if normals is not None:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header += "property float nx\nproperty float ny\nproperty float nz\n"
+    if colours is not None:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        header += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    table = np.zeros(n, dtype=np.dtype(fields))
+    table["x"], table["y"], table["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        nr = np.asarray(to(normals), dtype="<f4").reshape(n, 3)
+        table["nx"], table["ny"], table["nz"] = nr[:, 0], nr[:, 1], nr[:, 2]
+    if colours is not None:
+        c = np.clip(np.nan_to_num(np.asarray(to(colours), dtype=np.float64).reshape(n, 3)) * 255.0 + 0.5, 0, 255).astype(np.uint8)
+        table["red"], table["green"], table["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    rows = np.zeros(f.shape[0], dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+    rows["n"], rows["i"] = 3, f
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as out:
+        out.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\n%selement face %d\nproperty list uchar int vertex_indices\nend_header\n"
+                   % (n, header, f.shape[0])).encode("ascii"))
+        table.tofile(out)
+        rows.tofile(out)
+
+
+def read_mesh_ply(path):
+    """What save_mesh_ply writes (binary little-endian; scalar vertex properties; one face property, a list of exactly three indices per
+    face) -> dict(vertices [Nv, 3] float32, faces [Nf, 3] int32, normals [Nv, 3] float32 or None, colours [Nv, 3] uint8 or None)."""
+    types = {"float": "<f4", "float32": "<f4", "double": "<f8", "uchar": "u1", "uint8": "u1", "char": "i1", "short": "<i2", "ushort": "<u2",
+             "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4"}
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError("not a PLY file")
+        fmt, counts, props, lists, cur = None, {}, [], None, None
+        while True:
+            ln = f.readline()
+            if not ln:
+                raise ValueError("unterminated PLY header")
+            tok = ln.decode("ascii").split()
+            if not tok or tok[0] == "comment":
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                cur = tok[1]
+                counts[cur] = int(tok[2])
+            elif tok[0] == "property":
+                if cur == "vertex" and tok[1] != "list":
+                    props.append((tok[2], types[tok[1]]))
+                elif cur == "face" and tok[1] == "list" and lists is None:
+                    lists = (types[tok[2]], types[tok[3]])
+                else:
+                    raise ValueError("read_mesh_ply: scalar vertex properties and one face list only")
+            elif tok[0] == "end_header":
+                break
+        if fmt != "binary_little_endian" or list(counts) not in (["vertex"], ["vertex", "face"]):
+            raise ValueError("read_mesh_ply: a binary little-endian file with a vertex and a face element")
+        nv, nf = counts["vertex"], counts.get("face", 0)
+        dt = np.dtype(props)
+        v = np.frombuffer(f.read(nv * dt.itemsize), dtype=dt, count=nv)
+        faces = np.zeros((0, 3), np.int32)
+        if nf:
+            ft = np.dtype([("n", lists[0]), ("i", lists[1], (3,))])
+            rows = np.frombuffer(f.read(nf * ft.itemsize), dtype=ft, count=nf)
+            if not (rows["n"] == 3).all():
+                raise ValueError("read_mesh_ply: triangles only")
+            faces = np.array(rows["i"], dtype=np.int32)
+    names = set(v.dtype.names or ())
+    col = lambda ks, t: np.stack([v[k] for k in ks], 1).astype(t) if set(ks) <= names else None
+    return dict(vertices=col(("x", "y", "z"), np.float32), faces=faces, normals=col(("nx", "ny", "nz"), np.float32),
+                colours=col(("red", "green", "blue"), np.uint8))
 
 
 def load_gaussians_ply(path, max_sh_degree=3):

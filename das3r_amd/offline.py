@@ -304,7 +304,8 @@ def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=
 
 def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=False, optimised_poses=False, device="cuda", write=True, fused=False,
                 depth=False, pipe=PIPE, prune_min_opacity=0.0, write_pruned_ply=False, exposure="none", static_map=False, alpha=False, thin_edge=None, thin_relative=None,
-                camera_fov=False, distortion=False, median_depth=False, normals=False):
+                camera_fov=False, distortion=False, median_depth=False, normals=False, tsdf=False, tsdf_voxel=None, tsdf_relative=None, tsdf_trunc=4.0,
+                tsdf_depth="median", tsdf_min_alpha=0.5, tsdf_static_weight=False):
     """render.py:89-123: load the trained model, write pose_interpolated.npy, render the "interp" set.  seq: the sequence the model was
     trained on (its cameras).  depth: also the inverse-depth images (invdepth/%05d.npy) and, per view, the median relative error of
     1 / invdepth against the sequence's depth map (printed: a diagnostic).  pipe: PIPE, or pipe_from_args' (pipe.antialiasing: a model
@@ -322,6 +323,9 @@ def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=Fal
     model is thinned to one Gaussian per voxel first (das3r_amd.thin.thin_model, after prune_min_opacity's event when both are given);
     write_pruned_ply then saves the thinned model.  A model directory that holds fov.json (a job that trained its field of view: farm
     --fov-lr) is rendered with that field of view; camera_fov: ignore the file and keep the cameras' own.  Without the file: today's output.
+    tsdf: after the renders, the views' surface depths are fused into one TSDF grid and a mesh is taken from it (fuse_and_mesh below:
+    tsdf/mesh.ply and tsdf/tsdf.npz beside renders/); tsdf_voxel (world units) / tsdf_relative (pixel footprints, as thin_relative; default 2),
+    tsdf_trunc (voxels), tsdf_depth ("median" | "blended"), tsdf_min_alpha, tsdf_static_weight: das3r_amd.tsdf.fuse_views'.
     -> (iteration, list of rendered images)"""
     if exposure not in ("none", "train"):
         raise ValueError(f'render_sets: exposure must be "none" or "train", got {exposure!r}')
@@ -381,6 +385,10 @@ def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=Fal
                       exposures=exposures, static_map=[] if static_map else None, alpha=[] if alpha else None,
                       **({"distortion": []} if distortion else {}), **({"median_depth": med} if median_depth else {}),
                       **({"normals": []} if normals else {}))
+    if tsdf:
+        fuse_and_mesh(os.path.join(model_path, "interp", f"ours_{iteration}", "tsdf"), model, views, seq, pipe, bg, poses=poses, voxel=tsdf_voxel,
+                      relative=tsdf_relative, trunc_voxels=tsdf_trunc, depth=tsdf_depth, min_alpha=tsdf_min_alpha, static_weight=tsdf_static_weight,
+                      write=write)
     if depth and seq.get("depths") is not None:
         for idx, (f, d) in enumerate(zip(frames, inv)):
             print(f"view {idx:05d} (frame {f}): median |1/invdepth - depth| / depth = {invdepth_median_rel_error(d, seq['depths'][f]):.4f}")
@@ -388,6 +396,55 @@ def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=Fal
         for idx, (f, z) in enumerate(zip(frames, med)):
             print(f"view {idx:05d} (frame {f}): median |median_depth - depth| / depth = {median_depth_median_rel_error(z, seq['depths'][f]):.4f}")
     return iteration, imgs
+
+
+@torch.no_grad()
+def fuse_and_mesh(out_dir, model, views, seq, pipe=PIPE, background=None, poses=None, voxel=None, relative=None, trunc_voxels=4.0, depth="median",
+                  min_alpha=0.5, static_weight=False, write=True, quantile=0.01):
+    """--tsdf: fuse the loaded model's own renders of `views` into a TSDF grid over the box of its centres (das3r_amd.tsdf.bounds_from_points)
+    and take the mesh.  voxel: the edge in world units; relative: in multiples of the pixel footprint of `seq` (das3r_amd.thin.pixel_footprint,
+    as --thin-relative computes it; default 2 when neither is given), raised with a printed note while the box would exceed 2^28 voxels.
+    poses: [N, 4, 4] world-to-camera matrices that override the views' own.  Writes <out_dir>/mesh.ply (vertices, normals, colours, faces)
+    and <out_dir>/tsdf.npz (tsdf, weight, colour, origin, voxel, trunc) when `write`.  -> (grid, mesh dict)"""
+    import copy
+    from . import _lib
+    from .io_formats import save_mesh_ply
+    from .tsdf import TSDFGrid, bounds_from_points, fuse_views, grid_for_box
+    if voxel is not None and relative is not None:
+        raise ValueError("fuse_and_mesh: give voxel (world units) or relative (pixel footprints), not both")
+    dev = model.get_xyz.device
+    edge = voxel
+    if edge is None:
+        from .thin import pixel_footprint
+        if seq.get("depths") is None:
+            raise ValueError("--tsdf-relative: the sequence has no depth maps to take the pixel footprint from; give --tsdf-voxel")
+        confs = seq.get("confs")
+        edge = float(2.0 if relative is None else relative) * pixel_footprint(seq["depths"], seq["K"], None if confs is None else confs > 0.0)
+    lo, hi = bounds_from_points(model.get_xyz, quantile)
+    origin, dims = grid_for_box(lo, hi, edge)
+    while dims[0] * dims[1] * dims[2] > _lib.TSDF_MAX_VOXELS:
+        edge *= 1.25
+        origin, dims = grid_for_box(lo, hi, edge)
+        print(f"tsdf: the box would exceed 2^28 voxels; voxel edge raised to {edge:g}")
+    if poses is not None:
+        moved = []
+        for idx, v in enumerate(views):
+            v = copy.copy(v)
+            v.pose7 = tensor_from_camera(poses[idx], dev)
+            moved.append(v)
+        views = moved
+    grid = TSDFGrid(origin, edge, dims, device=dev, colour=True)
+    fuse_views(model, views, pipe, background, grid, depth=depth, min_alpha=min_alpha, static_weight=static_weight, trunc=float(trunc_voxels) * grid.voxel)
+    mesh = grid.extract()
+    print(f"tsdf: {len(views)} views fused into {dims[0]} x {dims[1]} x {dims[2]} voxels of edge {grid.voxel:g}; mesh: {mesh['vertices'].shape[0]} vertices, "
+          f"{mesh['faces'].shape[0]} triangles")
+    if write:
+        os.makedirs(out_dir, exist_ok=True)
+        save_mesh_ply(os.path.join(out_dir, "mesh.ply"), mesh["vertices"], mesh["faces"], normals=mesh["normals"], colours=mesh["colours"])
+        np.savez_compressed(os.path.join(out_dir, "tsdf.npz"), tsdf=grid.tsdf.cpu().numpy(), weight=grid.weight.cpu().numpy(),
+                            colour=grid.colour.cpu().numpy(), origin=np.asarray(grid.origin, np.float32), voxel=np.float32(grid.voxel),
+                            trunc=np.float32(grid.trunc if grid.trunc is not None else float(trunc_voxels) * grid.voxel))
+    return grid, mesh
 
 
 @torch.no_grad()
@@ -452,6 +509,17 @@ def parser():
     ap.add_argument("--normals", action="store_true", help="also write every view's normal image — the Gaussians' thinnest axes, facing the camera, blended "
                     "over the render's own lists (normals/%%05d.npy beside alpha/) — and the normal of its median-depth image (depth_normals/%%05d.npy), "
                     "both [3, H, W] in view space")
+    ap.add_argument("--tsdf", action="store_true", help="after the renders, fuse every view's surface depth into one TSDF grid and write the mesh taken "
+                    "from it — tsdf/mesh.ply (vertices, normals, colours, triangles) and tsdf/tsdf.npz (the grid) beside renders/")
+    edge = ap.add_mutually_exclusive_group()
+    edge.add_argument("--tsdf-voxel", type=float, default=None, help="with --tsdf: the voxel edge in world units")
+    edge.add_argument("--tsdf-relative", type=float, default=None, help="with --tsdf: the voxel edge in multiples of the pixel footprint of the sequence "
+                      "given with -s, as --thin-relative (default 2; raised with a note if the model's box would exceed 2^28 voxels)")
+    ap.add_argument("--tsdf-trunc", type=float, default=4.0, help="with --tsdf: the truncation distance in voxels")
+    ap.add_argument("--tsdf-depth", default="median", choices=("median", "blended"), help="with --tsdf: the depth that is fused — the median depth of "
+                    "the render's lists, or 1 / its blended inverse depth")
+    ap.add_argument("--tsdf-min-alpha", type=float, default=0.5, help="with --tsdf: pixels whose coverage is below this are not fused")
+    ap.add_argument("--tsdf-static-weight", action="store_true", help="with --tsdf: weigh every pixel by the static-confidence map of its view")
     return ap
 
 
@@ -465,6 +533,9 @@ def main(argv=None):
                            exposure=args.exposure, static_map=args.static_map, alpha=args.alpha, **({"camera_fov": True} if args.camera_fov else {}),
                            **({"distortion": True} if args.distortion else {}), **({"median_depth": True} if args.median_depth else {}),
                            **({"normals": True} if args.normals else {}),
+                           **({"tsdf": True, "tsdf_voxel": args.tsdf_voxel, "tsdf_relative": args.tsdf_relative, "tsdf_trunc": args.tsdf_trunc,
+                               "tsdf_depth": args.tsdf_depth, "tsdf_min_alpha": args.tsdf_min_alpha, "tsdf_static_weight": args.tsdf_static_weight}
+                              if args.tsdf else {}),
                            **({"thin_edge": args.thin_edge, "thin_relative": args.thin_relative}
                               if (args.thin_edge is not None or args.thin_relative is not None) else {}))
     print(f"wrote {len(imgs)} images to {os.path.join(args.model_path, 'interp', f'ours_{it}', 'renders')}")

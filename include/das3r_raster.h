@@ -867,6 +867,68 @@ int das3r_debug_choose_preprocess_backward(const das3r_preprocess_backward_input
 /* the raw name das3r_profile_report lists a launch of the form under (reads the nine flags); null: not instantiated */
 const char *das3r_debug_preprocess_backward_name(const das3r_preprocess_form *form);
 
+/* ---- TSDF fusion of depth images into a voxel grid, and a mesh out of it (csrc/tsdf.hip) ---------------------------------------------
+ * Additive symbols under ABI 16.  The last step of the 2DGS recipe: the per-view surface depths (das3r_raster_median_forward) are fused
+ * into one truncated signed distance field, and a triangle mesh with normals and colours is taken from it by marching tetrahedra.
+ *
+ * The grid: dims = (nx, ny, nz), origin = the corner of voxel (0, 0, 0) in world units, edge `voxel`; voxel (i, j, k) has its centre at
+ * origin + (i + 1/2, j + 1/2, k + 1/2) * voxel and the linear index (k * ny + j) * nx + i.  Dense fp32 tensors tsdf [nz, ny, nx],
+ * weight [nz, ny, nx] and, optionally, colour [3, nz, ny, nx]; a fresh grid holds tsdf 1, weight 0, colour 0.  At most 2^28 voxels.
+ *
+ * das3r_tsdf_integrate: V views in one call.  viewmatrix: V x 16 floats in DEVICE memory, each in the layout das3r_raster_args.viewmatrix
+ * has; tanfovx / tanfovy: V floats each in HOST memory (they are checked before anything is launched and travel as kernel arguments);
+ * depth [V, H, W]: view-space z (what das3r_raster_median_forward writes), colour_img [V, 3, H, W] (required iff the grid has colour),
+ * weight_img [V, H, W] or NULL (1 everywhere).  Per voxel, for each view in index order, in fp32 without fused multiply-adds, every sum
+ * left to right:
+ *   1. (xc, yc, zc) = centre * viewmatrix (row vector);  skip unless zc > near_z
+ *   2. u = ((xc / zc) / tanfovx + 1) * (W / 2), v likewise (pixel x covers the rays ((2 x + 1) / W - 1) * tanfovx, as in
+ *      das3r_normal_consistency_forward);  skip unless 0 <= u < W and 0 <= v < H;  px = floor(u), py = floor(v)
+ *   3. d = depth[v, py, px]: skip unless d > 0 and finite;  w = weight_img[v, py, px] or 1: skip unless w > 0 and finite
+ *   4. sdf = d - zc;  skip if sdf < -trunc (hidden behind the surface);  ts = min(1, sdf / trunc)
+ *   5. Wn = Wt + w;  T = (T * Wt + ts * w) / Wn;  each colour channel the same way;  Wt = Wn
+ * The call continues from what the grid holds: per view and per batch are the same arithmetic, bit for bit (more than
+ * DAS3R_TSDF_MAX_VIEWS views are taken in chunks of that many launches).  das3r_amd/tsdf.py integrate_torch is this rule in torch ops.
+ * One kernel per chunk, a thread per voxel; no atomics.  Refused with DAS3R_ERR_INVALID_ARG before any launch: NULL grid or depth, a
+ * non-positive or non-finite voxel, trunc or tanfov, a dim < 1, more than 2^28 voxels, a colour image without a colour grid or the reverse.
+ *
+ * das3r_tsdf_extract_count / _emit: the mesh.  A voxel is VALID iff weight > 0 and tsdf is finite, INSIDE iff it is valid and tsdf < 0.
+ * Vertices: voxel p owns the seven lattice edges p -> p + d, d = +x, +y, +z, +x+y, +x+z, +y+z, +x+y+z (types 0 - 6); an owned edge inside
+ * the grid carries a vertex iff both ends are valid and exactly one is inside: with a = tsdf(p), b = tsdf(p + d), s = a / (a - b), at
+ * origin + (p + 1/2 + s d) * voxel, with the lerp of the two colours and the normalised lerp of the two grid gradients (per axis the central
+ * difference where both neighbours are valid, one-sided where one is, 0 where neither; it points to +tsdf, free space; (0, 0, 0) where
+ * the length is zero or not finite).  Vertices are ordered by (owner's linear index, type).
+ * Triangles: cube (i, j, k), i < nx - 1, j < ny - 1, k < nz - 1, is active iff its eight corners are valid, and splits into the six Kuhn
+ * tetrahedra p0 -> p1 -> p2 -> p3 from its low to its high corner, the axes added in the orders xyz, xzy, yxz, yzx, zxy, zyx.  With I / O
+ * the inside / outside corners of a tetrahedron in path order and XY the vertex on the edge between X and Y: 1 inside: (I0O0, I0O1, I0O2);
+ * 3 inside: (O0I0, O0I1, O0I2); 2 inside: (I0O0, I0O1, I1O1), (I0O0, I1O1, I1O0); the last two indices swapped where a table of integer
+ * determinants says so, so that every normal points from the inside corners to the outside ones.  Triangles are ordered by (cube's linear
+ * index, tetrahedron, triangle); indices are int32 into the vertex list.
+ * count: the per-voxel edge masks and triangle counts, their exclusive bases, and totals[0..1] = (Nv, Nf) in device memory — the one host
+ * read between the two calls.  emit: vertices [Nv, 3], normals [Nv, 3], colours [Nv, 3] (iff the grid has colour), faces [Nf, 3]; with
+ * Nv = Nf = 0 nothing is launched.  workspace: das3r_tsdf_extract_workspace_bytes(dims) bytes, 4-byte aligned, untouched between the two
+ * calls; its first nvox uint32 words hold (edge mask | triangle count << 8) per voxel after count.  Separate launches, no atomics: two
+ * runs are bit-identical. */
+#define DAS3R_TSDF_MAX_VIEWS 16          /* views per launch of das3r_tsdf_integrate */
+#define DAS3R_TSDF_MAX_VOXELS (1 << 28)
+#define DAS3R_TSDF_GROUP_VOXELS 256
+int das3r_tsdf_integrate(const int32_t *dims, const float *origin, float voxel, float *tsdf, float *weight, float *colour, int32_t V,
+                         const float *viewmatrix, const float *tanfovx, const float *tanfovy, int32_t H, int32_t W, const float *depth,
+                         const float *colour_img, const float *weight_img, float trunc, float near_z, das3r_stream_t stream);
+size_t das3r_tsdf_extract_workspace_bytes(const int32_t *dims);   /* 0: the dims are refused */
+int das3r_tsdf_extract_count(const int32_t *dims, const float *tsdf, const float *weight, char *workspace, int32_t *totals, das3r_stream_t stream);
+int das3r_tsdf_extract_emit(const int32_t *dims, const float *origin, float voxel, const float *tsdf, const float *weight, const float *colour,
+                            const char *workspace, int32_t Nv, int32_t Nf, float *vertices, float *normals, float *colours, int32_t *faces,
+                            das3r_stream_t stream);
+/* Test aids, host-only (no device needed, no HIP call): the kernels' own per-voxel functions over HOST memory (viewmatrix included), and the
+ * winding table (word t: bit 2 c + k set where triangle k of case c of tetrahedron t has its last two indices swapped; case bit q = path
+ * corner q inside).  _extract_host: called with vertices == NULL it counts into totals[0..1], called again with the arrays it emits. */
+int das3r_debug_tsdf_integrate_host(const int32_t *dims, const float *origin, float voxel, float *tsdf, float *weight, float *colour, int32_t V,
+                                    const float *viewmatrix, const float *tanfovx, const float *tanfovy, int32_t H, int32_t W, const float *depth,
+                                    const float *colour_img, const float *weight_img, float trunc, float near_z);
+int das3r_debug_tsdf_extract_host(const int32_t *dims, const float *origin, float voxel, const float *tsdf, const float *weight, const float *colour,
+                                  char *workspace, int32_t *totals, float *vertices, float *normals, float *colours, int32_t *faces);
+void das3r_debug_tsdf_swap_table(uint32_t *out /*[6]*/);
+
 int das3r_abi_version(void);
 const char *das3r_last_error(void);
 

@@ -12,7 +12,8 @@ LIB_PATH = os.path.join(_HERE, "libdas3r_hip.so")
 ABI_VERSION = 16
 NO_BACKWARD_IN_FLAG = 8   # das3r_raster_saved.flags bit 3 on the way in to das3r_raster_forward: no backward pass will follow
 ANTIALIAS_FLAG = 16       # das3r_raster_saved.flags bit 4: an antialiased forward (asked for on the way in, set again on the way out)
-AUX_MAX_CHANNELS = 8      # DAS3R_AUX_MAX_CHANNELS: channels per das3r_raster_aux_forward / _adjoint call
+ERR_INVALID_ARG = -1      # DAS3R_ERR_INVALID_ARG
+AUX_MAX_CHANNELS = 8     # DAS3R_AUX_MAX_CHANNELS: channels per das3r_raster_aux_forward / _adjoint call
 
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
 

@@ -280,9 +280,9 @@ int ForwardCall::check_arguments() {
 }
 
 int64_t ForwardCall::run() {
-    stat_add(0);   // (kept as found: before validate — a refused call counts as a forward)
     int rc = check_arguments();
     if (rc) return rc;
+    stat_add(0);   // (a refused call is no forward: das3r_get_stats is unchanged by it, tests/test_gpu_tile_grids.py)
     const int P = a->P, W = a->image_width, H = a->image_height;
     depth = out->out_invdepth != nullptr;   // ABI 16: the binning buffer also holds Layout::d_* (d_bytes instead of binning_bytes)
     // the geometry buffer also holds Layout::g_shjac (flags bit 2) — unless the caller said that no backward will read it (flags bit 3 on the

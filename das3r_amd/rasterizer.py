@@ -20,6 +20,8 @@ import torch.nn as nn
 
 from . import _lib
 
+MAX_TILES = 1 << 22   # tiles of 16 x 16 pixels from which das3r_raster_forward refuses an image (csrc/render_common.h pack_tiles keeps 22 bits)
+
 
 class GaussianRasterizationSettings(NamedTuple):
     image_height: int
@@ -292,6 +294,9 @@ def _forward(rs, means3D, sh, colors_precomp, opacities, scales, rotations, cov3
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     P = means3D.shape[0]
     H, W = int(rs.image_height), int(rs.image_width)
+    if W > 0 and H > 0 and ((W + 15) // 16) * ((H + 15) // 16) >= MAX_TILES:
+        # the library's own refusal (csrc/forward.hip validate), raised before the image is allocated: 2^22 tiles are over a billion pixels
+        raise RuntimeError(f"das3r_raster_forward failed (status {_lib.ERR_INVALID_ARG}): image of {W} x {H} pixels has 2^22 tiles or more")
     M = 0
     if sh.numel():
         if sh.dim() != 3 or sh.shape[0] != P or sh.shape[2] != 3:

@@ -16,27 +16,9 @@ import pytest
 import torch
 
 from tests.test_gpu_bucket_local import GRADS, _dev, _view, assert_same_bits
+from tests.tile_grid_scenes import placed_scene   # (splats on the centres of chosen tiles; every image here is at least as wide as high: focal W / 1.28)
 
 pytestmark = pytest.mark.gpu
-
-
-def placed_scene(W, H, counts, seed, zlevels=None):
-    """Small splats (footprints of at most 9 pixels across) on the centres of chosen tiles: counts = {tile id: entries of its list}."""
-    from das3r_amd.synth import Scene, make_scene
-    tiles_x = (W + 15) // 16
-    tile = torch.tensor([t for t, n in counts.items() for _ in range(n)], dtype=torch.int64)
-    g = torch.Generator().manual_seed(seed)
-    tile = tile[torch.randperm(tile.numel(), generator=g)]   # (ids and tiles unrelated)
-    focal = max(100.0, W / 1.28)   # (a field of view no wider than the 128-pixel image's: footprints at the border stay inside their tile)
-    sc = make_scene(P=int(tile.numel()), W=W, H=H, focal=focal, sh_degree=1, seed=seed, s_px=(0.4, 0.6), opacity=0.05)
-    z = sc.means3D[:, 2].clone()
-    if zlevels:   # a few depth values: equal depths with different ids in every segment
-        z = 2.0 + 6.0 * torch.randint(0, zlevels, z.shape, generator=g).to(torch.float32) / zlevels
-    px = (tile % tiles_x).to(torch.float32) * 16.0 + 7.5
-    py = (tile // tiles_x).to(torch.float32) * 16.0 + 7.5
-    means = torch.stack([(px - (W - 1) / 2.0) / focal * z, (py - (H - 1) / 2.0) / focal * z, z], 1).contiguous()
-    scales = (sc.scales * (z / sc.means3D[:, 2])[:, None]).contiguous()
-    return Scene(**{**sc.__dict__, "means3D": means, "scales": scales})
 
 
 LENGTHS = (1, 256, 257, 512, 513)

@@ -154,6 +154,8 @@ EXPORTS = ("das3r_raster_forward", "das3r_raster_backward", "das3r_raster_backwa
            "das3r_thin_workspace_bytes", "das3r_thin_voxels", "das3r_raster_focal_workspace_bytes", "das3r_raster_backward_focal",
            "das3r_tsdf_integrate", "das3r_tsdf_extract_workspace_bytes", "das3r_tsdf_extract_count", "das3r_tsdf_extract_emit",
            "das3r_debug_tsdf_integrate_host", "das3r_debug_tsdf_extract_host", "das3r_debug_tsdf_swap_table",
+           "das3r_mesh_components_workspace_bytes", "das3r_mesh_components", "das3r_mesh_filter_select", "das3r_mesh_filter_faces",
+           "das3r_debug_mesh_components_host",
            "das3r_debug_path_policy_fresh", "das3r_debug_path_policy_plan", "das3r_debug_path_policy_count", "das3r_debug_path_policy_skew",
            "das3r_debug_path_policy_hint", "das3r_debug_path_policy_forget", "das3r_debug_path_policy_resume", "das3r_debug_seg_dbits",
            "das3r_debug_parse_switches", "das3r_debug_choose_backward", "das3r_debug_choose_forward", "das3r_debug_has_invdepth_form",
@@ -273,6 +275,17 @@ def load():
     L.das3r_debug_tsdf_extract_host.argtypes = [i3, f3, C.c_float] + [C.c_void_p] * 9
     L.das3r_debug_tsdf_swap_table.restype = None
     L.das3r_debug_tsdf_swap_table.argtypes = [C.POINTER(C.c_uint32)]
+    L.das3r_mesh_components_workspace_bytes.restype = C.c_size_t   # mesh clean-up: components, selection, face remap (additive under ABI 16)
+    L.das3r_mesh_components_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.das3r_mesh_components.restype = C.c_int
+    L.das3r_mesh_components.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [i3, C.c_void_p, C.c_void_p]
+    L.das3r_mesh_filter_select.restype = C.c_int
+    L.das3r_mesh_filter_select.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, i3,
+                                           C.c_void_p, C.c_void_p]
+    L.das3r_mesh_filter_faces.restype = C.c_int
+    L.das3r_mesh_filter_faces.argtypes = [C.c_int32] * 4 + [C.c_void_p] * 4 + [C.c_void_p]
+    L.das3r_debug_mesh_components_host.restype = C.c_int
+    L.das3r_debug_mesh_components_host.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 5
     L.das3r_raster_focal_workspace_bytes.restype = C.c_size_t   # focal gradients beside a backward pass (additive under ABI 16)
     L.das3r_raster_focal_workspace_bytes.argtypes = [C.c_int32]
     L.das3r_raster_backward_focal.restype = C.c_int

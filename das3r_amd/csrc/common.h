@@ -381,6 +381,8 @@ int launch_render_median_forward(int P, int W, int H, float tau, float *depth, i
                                  const char *binning, const char *img, const Layout &L, bool debug, hipStream_t s);
 int launch_render_median_adjoint(int P, int W, int H, const float *dL_ddepth, const uint32_t *hit_position, float *dL_dz, int accumulate,
                                  float *rows, const char *geom, const char *binning, const char *img, const Layout &L, bool debug, hipStream_t s);
+// prune.hip: exclusive scan of per-group kept counts (one workgroup; *total = their sum), then dst_index[i] = the new row of every row flagged 0
+int launch_prune_scan_rank(int P, int32_t *group_counts, int32_t *total, int32_t *dst_index, hipStream_t s);
 // pair_count.hip (measurement aid): out[0] += live pairs, out[1] += (pixel, list position) pairs below the pixel's n_contrib
 int launch_count_live_pairs(const das3r_raster_args *a, char *geom, char *binning, char *img, const Layout &L, unsigned long long *out, hipStream_t s);
 int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in *in, char *geom, char *binning, const Layout &L,

@@ -169,6 +169,17 @@ __global__ void __launch_bounds__(256) prune_compact_kernel(const CompactTable T
     else compact_units<uint32_t>((const uint32_t *)src, (uint32_t *)dst, upr, units, e0, dst_index, kept);
 }
 
+// the last two steps of a selection for a caller with keep flags of its own (mesh.hip): dst_index holds 0 / -1 per row, group_counts the kept
+// rows of every group of DAS3R_PRUNE_GROUP_ROWS
+int launch_prune_scan_rank(const int P, int32_t *group_counts, int32_t *total, int32_t *dst_index, hipStream_t s) {
+    const int groups = div_up(P, DAS3R_PRUNE_GROUP_ROWS);
+    DAS3R_LAUNCH(prune_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, groups, group_counts, total);
+    KERNEL_CHECK(s, false, "prune_scan");
+    DAS3R_LAUNCH(prune_rank_kernel, dim3(groups), dim3(PRUNE_THREADS), 0, s, P, (const int32_t *)group_counts, dst_index);
+    KERNEL_CHECK(s, false, "prune_rank");
+    return DAS3R_OK;
+}
+
 }  // namespace das3r
 
 using namespace das3r;

@@ -305,7 +305,7 @@ def render_set(model_path, name, iteration, views, model, pipe=PIPE, background=
 def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=False, optimised_poses=False, device="cuda", write=True, fused=False,
                 depth=False, pipe=PIPE, prune_min_opacity=0.0, write_pruned_ply=False, exposure="none", static_map=False, alpha=False, thin_edge=None, thin_relative=None,
                 camera_fov=False, distortion=False, median_depth=False, normals=False, tsdf=False, tsdf_voxel=None, tsdf_relative=None, tsdf_trunc=4.0,
-                tsdf_depth="median", tsdf_min_alpha=0.5, tsdf_static_weight=False):
+                tsdf_depth="median", tsdf_min_alpha=0.5, tsdf_static_weight=False, tsdf_min_faces=0, tsdf_keep_largest=0):
     """render.py:89-123: load the trained model, write pose_interpolated.npy, render the "interp" set.  seq: the sequence the model was
     trained on (its cameras).  depth: also the inverse-depth images (invdepth/%05d.npy) and, per view, the median relative error of
     1 / invdepth against the sequence's depth map (printed: a diagnostic).  pipe: PIPE, or pipe_from_args' (pipe.antialiasing: a model
@@ -326,6 +326,8 @@ def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=Fal
     tsdf: after the renders, the views' surface depths are fused into one TSDF grid and a mesh is taken from it (fuse_and_mesh below:
     tsdf/mesh.ply and tsdf/tsdf.npz beside renders/); tsdf_voxel (world units) / tsdf_relative (pixel footprints, as thin_relative; default 2),
     tsdf_trunc (voxels), tsdf_depth ("median" | "blended"), tsdf_min_alpha, tsdf_static_weight: das3r_amd.tsdf.fuse_views'.
+    tsdf_min_faces / tsdf_keep_largest: with either above 0 the mesh is cleaned before it is written (das3r_amd.mesh.filter_components: the
+    connected pieces with fewer faces than the keep rule's threshold go, with their vertices) and tsdf/components.json records the pieces.
     -> (iteration, list of rendered images)"""
     if exposure not in ("none", "train"):
         raise ValueError(f'render_sets: exposure must be "none" or "train", got {exposure!r}')
@@ -388,7 +390,7 @@ def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=Fal
     if tsdf:
         fuse_and_mesh(os.path.join(model_path, "interp", f"ours_{iteration}", "tsdf"), model, views, seq, pipe, bg, poses=poses, voxel=tsdf_voxel,
                       relative=tsdf_relative, trunc_voxels=tsdf_trunc, depth=tsdf_depth, min_alpha=tsdf_min_alpha, static_weight=tsdf_static_weight,
-                      write=write)
+                      write=write, **({"min_faces": tsdf_min_faces, "keep_largest": tsdf_keep_largest} if (tsdf_min_faces or tsdf_keep_largest) else {}))
     if depth and seq.get("depths") is not None:
         for idx, (f, d) in enumerate(zip(frames, inv)):
             print(f"view {idx:05d} (frame {f}): median |1/invdepth - depth| / depth = {invdepth_median_rel_error(d, seq['depths'][f]):.4f}")
@@ -400,12 +402,14 @@ def render_sets(model_path, seq, iteration=-1, sh_degree=3, white_background=Fal
 
 @torch.no_grad()
 def fuse_and_mesh(out_dir, model, views, seq, pipe=PIPE, background=None, poses=None, voxel=None, relative=None, trunc_voxels=4.0, depth="median",
-                  min_alpha=0.5, static_weight=False, write=True, quantile=0.01):
+                  min_alpha=0.5, static_weight=False, write=True, quantile=0.01, min_faces=0, keep_largest=0):
     """--tsdf: fuse the loaded model's own renders of `views` into a TSDF grid over the box of its centres (das3r_amd.tsdf.bounds_from_points)
     and take the mesh.  voxel: the edge in world units; relative: in multiples of the pixel footprint of `seq` (das3r_amd.thin.pixel_footprint,
     as --thin-relative computes it; default 2 when neither is given), raised with a printed note while the box would exceed 2^28 voxels.
     poses: [N, 4, 4] world-to-camera matrices that override the views' own.  Writes <out_dir>/mesh.ply (vertices, normals, colours, faces)
-    and <out_dir>/tsdf.npz (tsdf, weight, colour, origin, voxel, trunc) when `write`.  -> (grid, mesh dict)"""
+    and <out_dir>/tsdf.npz (tsdf, weight, colour, origin, voxel, trunc) when `write`.  min_faces / keep_largest (both 0: off, the mesh is the
+    extraction's as it is): the mesh is cleaned first (das3r_amd.mesh.filter_components) and <out_dir>/components.json holds the descending
+    face counts of its pieces, the threshold, and the kept and dropped counts.  -> (grid, mesh dict)"""
     import copy
     from . import _lib
     from .io_formats import save_mesh_ply
@@ -438,8 +442,18 @@ def fuse_and_mesh(out_dir, model, views, seq, pipe=PIPE, background=None, poses=
     mesh = grid.extract()
     print(f"tsdf: {len(views)} views fused into {dims[0]} x {dims[1]} x {dims[2]} voxels of edge {grid.voxel:g}; mesh: {mesh['vertices'].shape[0]} vertices, "
           f"{mesh['faces'].shape[0]} triangles")
+    report = None
+    if min_faces or keep_largest:
+        from .mesh import filter_components
+        mesh, report = filter_components(mesh, min_faces=min_faces, keep_largest=keep_largest)
+        print(f"tsdf: mesh clean-up (min faces {int(min_faces)}, keep largest {int(keep_largest)}: threshold {report['threshold']}): "
+              f"{report['components']} pieces -> {report['kept_components']}, {report['vertices_before']} vertices -> {report['vertices_after']}, "
+              f"{report['faces_before']} triangles -> {report['faces_after']}")
     if write:
         os.makedirs(out_dir, exist_ok=True)
+        if report is not None:
+            from .mesh import write_components_json
+            write_components_json(os.path.join(out_dir, "components.json"), report)
         save_mesh_ply(os.path.join(out_dir, "mesh.ply"), mesh["vertices"], mesh["faces"], normals=mesh["normals"], colours=mesh["colours"])
         np.savez_compressed(os.path.join(out_dir, "tsdf.npz"), tsdf=grid.tsdf.cpu().numpy(), weight=grid.weight.cpu().numpy(),
                             colour=grid.colour.cpu().numpy(), origin=np.asarray(grid.origin, np.float32), voxel=np.float32(grid.voxel),
@@ -469,6 +483,13 @@ def forward_throughput(model, views, repeats=3, background=None, fused=False):
 def pipe_from_args(args):
     """The `pipe` a command line renders with: PIPE, and pipe.antialiasing from --antialiasing."""
     return SimpleNamespace(**vars(PIPE), antialiasing=bool(getattr(args, "antialiasing", False)))
+
+
+def _count(text):
+    n = int(text)
+    if n < 0:
+        raise argparse.ArgumentTypeError(f"{text!r} is negative")
+    return n
 
 
 def parser():
@@ -520,6 +541,10 @@ def parser():
                     "the render's lists, or 1 / its blended inverse depth")
     ap.add_argument("--tsdf-min-alpha", type=float, default=0.5, help="with --tsdf: pixels whose coverage is below this are not fused")
     ap.add_argument("--tsdf-static-weight", action="store_true", help="with --tsdf: weigh every pixel by the static-confidence map of its view")
+    ap.add_argument("--tsdf-min-faces", type=_count, default=0, help="with --tsdf: before the mesh is written, drop its connected pieces with fewer "
+                    "triangles than this, and their vertices (0: off); tsdf/components.json records the pieces")
+    ap.add_argument("--tsdf-keep-largest", type=_count, default=0, help="with --tsdf: keep the K pieces with the most triangles (ties with the K-th "
+                    "stay too; 0: off); combines with --tsdf-min-faces: a piece must pass both")
     return ap
 
 
@@ -536,6 +561,8 @@ def main(argv=None):
                            **({"tsdf": True, "tsdf_voxel": args.tsdf_voxel, "tsdf_relative": args.tsdf_relative, "tsdf_trunc": args.tsdf_trunc,
                                "tsdf_depth": args.tsdf_depth, "tsdf_min_alpha": args.tsdf_min_alpha, "tsdf_static_weight": args.tsdf_static_weight}
                               if args.tsdf else {}),
+                           **({"tsdf_min_faces": args.tsdf_min_faces, "tsdf_keep_largest": args.tsdf_keep_largest}
+                              if (args.tsdf and (args.tsdf_min_faces or args.tsdf_keep_largest)) else {}),
                            **({"thin_edge": args.thin_edge, "thin_relative": args.thin_relative}
                               if (args.thin_edge is not None or args.thin_relative is not None) else {}))
     print(f"wrote {len(imgs)} images to {os.path.join(args.model_path, 'interp', f'ours_{it}', 'renders')}")

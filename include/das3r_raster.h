@@ -929,6 +929,53 @@ int das3r_debug_tsdf_extract_host(const int32_t *dims, const float *origin, floa
                                   char *workspace, int32_t *totals, float *vertices, float *normals, float *colours, int32_t *faces);
 void das3r_debug_tsdf_swap_table(uint32_t *out /*[6]*/);
 
+/* ---- Mesh clean-up: connected components, small pieces dropped (csrc/mesh.hip) --------------------------------------------------------
+ * Additive symbols under ABI 16.  Imperfectly masked movers and faint floaters leave small closed blobs in a fused TSDF, and the extraction
+ * turns each into a piece of mesh.  These calls label the connected pieces of a mesh, select the large ones and remap the faces; vertex
+ * attributes are moved by das3r_prune_compact with the vertex_dst of the selection.  Everything is integer-valued: two runs are
+ * bit-identical, and das3r_amd/mesh.py components_torch is the same definition in torch ops.
+ *
+ * Mesh and graph.  A mesh is Nv vertices and faces [Nf, 3] int32.  A face is GOOD iff its three indices lie in [0, Nv).  A good face joins
+ * its three vertices (a face with a repeated index joins the distinct ones); a bad face joins nothing.  Connectivity is by shared VERTEX,
+ * not by shared edge: union-find over vertices needs no edge map, and on the extraction's meshes the two notions agree.
+ *
+ * das3r_mesh_components.  vertex_label[v] = the smallest vertex index in v's component (canonical: independent of any order of execution);
+ * face_label[f] = vertex_label[faces[f][0]] for a good face, -1 for a bad one; face_count[r] = the good faces of the component of root r
+ * (vertex_label[r] == r), 0 at every non-root ([Nv] words); info[4]: [0] components, singletons included, [1] components with at least one
+ * face, [2] bad faces, [3] a give-up word, 0 on success.  Four launches: init; a thread per face that unions (a, b) and (b, c) in a
+ * union-find with minimum roots (parent[v] <= v always; the larger root is hooked under the smaller with an agent-scope atomic minimum; a
+ * find walks strictly decreasing indices, a union iteration that does not hook goes on with a strictly smaller pair; no thread waits for
+ * another; inside the launch the parent array is touched only with agent-scope atomic loads and minima, path halving included); a thread
+ * per vertex that flattens; a wave per 1024 faces for face_label and the counts (one integer atomic per run of equal labels).  Every loop
+ * also carries an iteration cap that sets info[3].  The call copies info to info_host (HOST memory, [4]) and waits for the stream: its one
+ * host read; a non-zero info[3] is DAS3R_ERR_OVERFLOW.  Nv == 0 or Nf == 0 launch only what they need (Nf == 0: Nv singletons).
+ * workspace: das3r_mesh_components_workspace_bytes(Nv, Nf) bytes (0: the sizes are refused), 4-byte aligned; das3r_mesh_filter_select
+ * may be given the same one.
+ *
+ * Keep rule (host arithmetic: das3r_amd/mesh.py keep_threshold).  Parameters min_faces >= 0 and keep_largest = K >= 0.  With c_1 >= c_2 >= ...
+ * the face counts of the face-bearing components, t = max(1, min_faces, c_K), the c_K term only when 1 <= K <= their number.  A component
+ * is kept iff face_count >= t: ties at c_K are all kept, so no tie-break is needed; faceless vertices always go.
+ *
+ * das3r_mesh_filter_select takes the threshold t = min_count >= 1.  A vertex is kept iff its component is kept, a face iff it is good and
+ * its component is kept; both keep their relative order (stable).  vertex_dst [Nv] / face_dst [Nf]: the new row, -1 = dropped; totals[2] =
+ * (kept vertices, kept faces) in device memory, copied to totals_host (HOST, [2]): its one host read.  Flags plus per-group counts, a
+ * one-workgroup scan, then ranks (das3r_prune_select's pattern and its scan and rank kernels).
+ * das3r_mesh_filter_faces: out_faces[face_dst[f]] = vertex_dst[faces[f]] for every kept face; kept_faces == 0 launches nothing.
+ *
+ * Refused with DAS3R_ERR_INVALID_ARG and a das3r_last_error() message before any launch: a negative size or one above 2^30, a NULL array
+ * that the sizes make necessary, a misaligned workspace, min_count < 1, kept counts outside [0, Nv] / [0, Nf]. */
+size_t das3r_mesh_components_workspace_bytes(int32_t Nv, int32_t Nf);
+int das3r_mesh_components(int32_t Nv, int32_t Nf, const int32_t *faces, int32_t *vertex_label, int32_t *face_label, int32_t *face_count,
+                          int32_t *info /* device [4] */, int32_t *info_host /* host [4] */, char *workspace, das3r_stream_t stream);
+int das3r_mesh_filter_select(int32_t Nv, int32_t Nf, const int32_t *vertex_label, const int32_t *face_label, const int32_t *face_count,
+                             int32_t min_count, int32_t *vertex_dst, int32_t *face_dst, int32_t *totals /* device [2] */,
+                             int32_t *totals_host /* host [2] */, char *workspace, das3r_stream_t stream);
+int das3r_mesh_filter_faces(int32_t Nv, int32_t Nf, int32_t kept_vertices, int32_t kept_faces, const int32_t *faces, const int32_t *face_dst,
+                            const int32_t *vertex_dst, int32_t *out_faces /* [kept_faces, 3] */, das3r_stream_t stream);
+/* Test aid, host-only (no device needed, no HIP call): the kernels' own union and find run serially over HOST memory. */
+int das3r_debug_mesh_components_host(int32_t Nv, int32_t Nf, const int32_t *faces, int32_t *vertex_label, int32_t *face_label, int32_t *face_count,
+                                     int32_t *info /* [4] */);
+
 int das3r_abi_version(void);
 const char *das3r_last_error(void);
 

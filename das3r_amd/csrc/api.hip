@@ -349,18 +349,15 @@ extern "C" int das3r_raster_learning(int32_t set, uint32_t state[2]) {
     return DAS3R_OK;
 }
 
-// The layout of a finished forward's buffers: for the capacity they were laid out for (a caller that kept only num_rendered: for that).
-// (rasterizer.py alpha_of asks das3r_raster_get_layout the same way.)
-static Layout saved_layout(const das3r_raster_args *a, const das3r_raster_saved *saved, bool shjac = false) {
-    Layout L;
-    compute_layout(a->P, saved->capacity > 0 ? saved->capacity : saved->num_rendered, a->image_width, a->image_height, &L, shjac);
-    return L;
-}
-
-// flags bit 2: the forward left the SH colour's Jacobian for the per-Gaussian backward (Layout::g_shjac), which then reads it instead of
-// the SH rows.  Without it (a caller that handed back flags = 0) the backward reads the rows as before.
-static bool shjac_saved(const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_saved *saved) {
-    return (saved->flags & SHJAC_SAVED_FLAG) != 0 && in->shs != nullptr && a->sh_degree >= 2;
+// The view of a finished forward's buffers: laid out for the capacity they were laid out for (a caller that kept only num_rendered: for that).
+// (rasterizer.py alpha_of asks das3r_raster_get_layout the same way.)  in (may be null: an entry that never reads the Jacobian planes) — flags
+// bit 2: the forward left the SH colour's Jacobian for the per-Gaussian backward (Layout::g_shjac), which then reads it instead of the SH rows.
+// Without it (a caller that handed back flags = 0) the backward reads the rows as before.
+static Buffers saved_buffers(const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_saved *saved) {
+    const bool shjac = in && (saved->flags & SHJAC_SAVED_FLAG) != 0 && in->shs != nullptr && a->sh_degree >= 2;
+    Buffers v = {saved->geom, saved->binning, saved->img, saved->geom, {}};
+    compute_layout(a->P, saved->capacity > 0 ? saved->capacity : saved->num_rendered, a->image_width, a->image_height, &v.L, shjac);
+    return v;
 }
 
 // What das3r_raster_backward (depth_pass false; dL_dinvdepth not looked at) and das3r_raster_backward_depth ask of their pointers.
@@ -402,12 +399,12 @@ static int refuse_bwd_without_invdepth(const char *who) {
 // to the boundary above the last row); rows_aligned: the same rounded up — where whatever a call keeps behind the rows starts.
 static size_t rows_bytes(int64_t capacity) { return (capacity > 0 ? (size_t)capacity : 1) * 9 * sizeof(float) + 16; }
 static size_t rows_aligned(int64_t capacity) { return align_up(rows_bytes(capacity)); }
-static float *behind_rows(float *scratch, const Layout &L) { return (float *)((char *)scratch + rows_aligned(L.capacity)); }
+static float *behind_rows(float *scratch, const Buffers &v) { return (float *)((char *)scratch + rows_aligned(v.L.capacity)); }
 
-// What the backward entries that end in launch_preprocess_backward do first: the refusals in their order, then the saved buffers' layout.
-// P == 0: DAS3R_OK at once, *L untouched.  binning_first: a missing binning buffer is refused before the binning self-check, not after it.
+// What the backward entries that end in launch_preprocess_backward do first: the refusals in their order, then the view of the saved buffers.
+// P == 0: DAS3R_OK at once, *v untouched.  binning_first: a missing binning buffer is refused before the binning self-check, not after it.
 static int backward_prologue(const char *who, const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_saved *saved, const float *dL_dpix,
-                             bool depth_pass, const float *dL_dinvdepth, const das3r_raster_grads *g, bool binning_first, das3r_stream_t stream, Layout *L) {
+                             bool depth_pass, const float *dL_dinvdepth, const das3r_raster_grads *g, bool binning_first, das3r_stream_t stream, Buffers *v) {
     int rc = validate(a, in);
     if (rc || a->P == 0) return rc;
     if ((rc = backward_validate(who, in, saved, dL_dpix, depth_pass, dL_dinvdepth, g))) return rc;
@@ -416,7 +413,7 @@ static int backward_prologue(const char *who, const das3r_raster_args *a, const 
     // the forward's binning self-check first: nothing is launched on the strength of an invalid image / list
     if (!(no_binning && binning_first) && (rc = das3r_raster_check(saved, stream))) return rc;
     if (no_binning) { set_error("%s: binning buffer missing", who); return DAS3R_ERR_INVALID_ARG; }
-    *L = saved_layout(a, saved, shjac_saved(a, in, saved));
+    *v = saved_buffers(a, in, saved);
     return DAS3R_OK;
 }
 
@@ -433,8 +430,8 @@ static int backward_prologue(const char *who, const das3r_raster_args *a, const 
 static int backward_body(const char *who, const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_saved *saved, const float *dL_dpix,
                          bool depth_pass, const float *dL_dinvdepth, const das3r_raster_grads *g, const FocalOut *focal, das3r_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
-    Layout L;
-    int rc = backward_prologue(who, a, in, saved, dL_dpix, depth_pass, dL_dinvdepth, g, false, stream, &L);
+    Buffers v;
+    int rc = backward_prologue(who, a, in, saved, dL_dpix, depth_pass, dL_dinvdepth, g, false, stream, &v);
     if (rc) return rc;
     const int P = a->P;
     if (P == 0) {
@@ -446,30 +443,24 @@ static int backward_body(const char *who, const das3r_raster_args *a, const das3
     const float *dz = nullptr;
     bool quad_rows = false;
     if (saved->num_rendered > 0) {
-        if ((rc = launch_render_backward(a, dL_dpix, saved->geom, saved->binning, saved->img, L, partial, s, &quad_rows, saved->num_rendered, saved->flags))) return rc;
+        if ((rc = launch_render_backward(a, dL_dpix, v, partial, s, &quad_rows, saved->num_rendered, saved->flags))) return rc;
         if (depth_pass) {
-            float *partial_depth = behind_rows(g->scratch, L);
-            if ((rc = launch_depth_pass_inputs(P, a->image_width * a->image_height, saved->geom, L, saved->binning, dL_dinvdepth, s, a->debug != 0))) return rc;
-            Layout Ld = L;   // the depth pass reads its splat records and checkpoints from the binning buffer's depth part
-            Ld.pub.xy = L.d_recs;
-            Ld.pub.conic_opacity = L.d_recs + 16;
-            Ld.pub.rgbd = L.d_recs + 32;
-            Ld.b_ckpt = L.d_ckpt;
+            float *partial_depth = behind_rows(g->scratch, v);
+            if ((rc = launch_depth_pass_inputs(P, a->image_width * a->image_height, v, dL_dinvdepth, s, a->debug != 0))) return rc;
             das3r_raster_args ad = *a;
-            ad.bg = (const float *)(saved->binning + L.d_bg);
+            const Buffers vd = v.depth_pass(&ad);   // its splat records, checkpoints and background (ad.bg): the binning buffer's depth part
             bool quad_rows_d = false;
-            if ((rc = launch_render_backward(&ad, (const float *)(saved->binning + L.d_dpix), saved->binning, saved->binning, saved->img, Ld, partial_depth, s,
-                                             &quad_rows_d, saved->num_rendered, saved->flags))) return rc;
-            float *dzw = (float *)(saved->binning + L.d_dz);
-            if ((rc = launch_depth_fold(P, saved->geom, L, partial, partial_depth, dzw, s, a->debug != 0))) return rc;
+            if ((rc = launch_render_backward(&ad, v.d_dpix(), vd, partial_depth, s, &quad_rows_d, saved->num_rendered, saved->flags))) return rc;
+            float *dzw = v.d_dz();
+            if ((rc = launch_depth_fold(P, v, partial, partial_depth, dzw, s, a->debug != 0))) return rc;
             dz = dzw;
         }
     }
     const bool aa = (saved->flags & ANTIALIAS_FLAG) != 0;
     // (nothing rendered: tiles_touched is all zero, the kernel reads no row and writes the zeros)
-    if (focal && (rc = launch_focal_grad(a, in, saved->geom, L, partial, quad_rows, aa, focal->sums, focal->per_splat, focal->workspace, s))) return rc;
+    if (focal && (rc = launch_focal_grad(a, in, v, partial, quad_rows, aa, focal->sums, focal->per_splat, focal->workspace, s))) return rc;
     // (the depth pass's opacity sums were folded into `partial` above: the antialiasing factor's derivative is applied once, to the total)
-    return launch_preprocess_backward(a, in, saved->geom, saved->binning, L, g, partial, s, quad_rows, dz, aa);
+    return launch_preprocess_backward(a, in, v, g, partial, s, quad_rows, dz, aa);
 }
 
 extern "C" int das3r_raster_backward(const das3r_raster_args *a, const das3r_raster_in *in, const das3r_raster_saved *saved,
@@ -539,8 +530,8 @@ extern "C" int das3r_raster_aux_forward(const das3r_raster_args *a, const das3r_
         return DAS3R_OK;
     }
     if ((rc = das3r_raster_check(saved, stream))) return rc;   // a failed binning is an error, not a walk over bad lists
-    const Layout L = saved_layout(a, saved);
-    return launch_render_aux_forward(P, W, H, C, features, out, saved->geom, saved->binning, saved->img, L, saved->num_rendered, a->debug != 0, s);
+    const Buffers v = saved_buffers(a, nullptr, saved);
+    return launch_render_aux_forward(P, W, H, C, features, out, v, saved->num_rendered, a->debug != 0, s);
 }
 
 // C floats per instance + 16 bytes (as das3r_raster_backward_scratch_bytes rounds its rows up)
@@ -562,8 +553,8 @@ extern "C" int das3r_raster_aux_adjoint(const das3r_raster_args *a, const das3r_
     }
     if (!scratch) { set_error("das3r_raster_aux_adjoint: null scratch (das3r_raster_aux_scratch_bytes)"); return DAS3R_ERR_INVALID_ARG; }
     if ((rc = das3r_raster_check(saved, stream))) return rc;
-    const Layout L = saved_layout(a, saved);
-    return launch_render_aux_adjoint(P, W, H, C, dL_dout, dL_dfeat, accumulate != 0, scratch, saved->geom, saved->binning, saved->img, L, saved->num_rendered, a->debug != 0, s);
+    const Buffers v = saved_buffers(a, nullptr, saved);
+    return launch_render_aux_adjoint(P, W, H, C, dL_dout, dL_dfeat, accumulate != 0, scratch, v, saved->num_rendered, a->debug != 0, s);
 }
 
 // ---- the aux channels' and the coverage image's gradients to the geometry (render_aux_bwd.hip) ----
@@ -588,21 +579,20 @@ extern "C" int das3r_raster_aux_backward(const das3r_raster_args *a, const das3r
     if (C > 0 && (!dL_dout || (a->P > 0 && !features))) { set_error("%s: null features / dL_dout with C = %d channels", who, C); return DAS3R_ERR_INVALID_ARG; }
     if (g->chain) { set_error("%s: grads->chain is not supported here (the chained backward belongs to the colour loss)", who); return DAS3R_ERR_INVALID_ARG; }
     if (!g->scratch) { set_error("%s: null scratch (das3r_raster_aux_backward_scratch_bytes)", who); return DAS3R_ERR_INVALID_ARG; }
-    Layout L;
-    int rc = backward_prologue(who, a, in, saved, /*dL_dpix: not this entry's*/ g->scratch, false, nullptr, g, true, stream, &L);
+    Buffers v;
+    int rc = backward_prologue(who, a, in, saved, /*dL_dpix: not this entry's*/ g->scratch, false, nullptr, g, true, stream, &v);
     const int P = a->P, W = a->image_width, H = a->image_height;
     if (rc || P == 0) return rc;   // (P == 0: no gradient has a row)
     float *partial = g->scratch;
     if (saved->num_rendered > 0) {
-        float *partial_f = dL_dfeatures ? behind_rows(g->scratch, L) : nullptr;
-        if ((rc = launch_render_aux_backward(P, W, H, C, features, dL_dout, dL_dalpha, partial, partial_f, saved->geom, saved->binning, saved->img, L,
-                                             a->debug != 0, s))) return rc;
-        if (dL_dfeatures && (rc = launch_aux_gather(P, C, partial_f, dL_dfeatures, saved->geom, L, a->debug != 0, s))) return rc;
+        float *partial_f = dL_dfeatures ? behind_rows(g->scratch, v) : nullptr;
+        if ((rc = launch_render_aux_backward(P, W, H, C, features, dL_dout, dL_dalpha, partial, partial_f, v, a->debug != 0, s))) return rc;
+        if (dL_dfeatures && (rc = launch_aux_gather(P, C, partial_f, dL_dfeatures, v, a->debug != 0, s))) return rc;
     } else if (dL_dfeatures) {
         HIP_TRY(hipMemsetAsync(dL_dfeatures, 0, sizeof(float) * (size_t)P * (size_t)C, s));
     }
     // (nothing rendered: tiles_touched is all zero, the kernel reads no row and writes the zeros; columns 0..2 are zero: so is dL/d(colour, SH))
-    return launch_preprocess_backward(a, in, saved->geom, saved->binning, L, g, partial, s, false, nullptr, (saved->flags & ANTIALIAS_FLAG) != 0);
+    return launch_preprocess_backward(a, in, v, g, partial, s, false, nullptr, (saved->flags & ANTIALIAS_FLAG) != 0);
 }
 
 // ---- the ray-distortion regulariser over a forward's saved lists (render_distort.hip) ----
@@ -626,8 +616,8 @@ extern "C" int das3r_raster_distortion_forward(const das3r_raster_args *a, const
     }
     int rc = das3r_raster_check(saved, stream);   // a failed binning is an error, not a walk over bad lists
     if (rc) return rc;
-    const Layout L = saved_layout(a, saved);
-    return launch_render_distortion_forward(P, W, H, out, totals, saved->geom, saved->binning, saved->img, L, a->debug != 0, s);
+    const Buffers v = saved_buffers(a, nullptr, saved);
+    return launch_render_distortion_forward(P, W, H, out, totals, v, a->debug != 0, s);
 }
 
 // the nine-float rows as das3r_raster_backward_scratch_bytes rounds them, then dz: one float per Gaussian
@@ -643,20 +633,20 @@ extern "C" int das3r_raster_distortion_backward(const das3r_raster_args *a, cons
     if (!dL_ddist || !totals) { set_error("%s: null dL_ddist / totals plane (das3r_raster_distortion_forward writes it)", who); return DAS3R_ERR_INVALID_ARG; }
     if (g->chain) { set_error("%s: grads->chain is not supported here (the chained backward belongs to the colour loss)", who); return DAS3R_ERR_INVALID_ARG; }
     if (!g->scratch) { set_error("%s: null scratch (das3r_raster_distortion_backward_scratch_bytes)", who); return DAS3R_ERR_INVALID_ARG; }
-    Layout L;
-    int rc = backward_prologue(who, a, in, saved, /*dL_dpix: not this entry's*/ dL_ddist, false, nullptr, g, true, stream, &L);
+    Buffers v;
+    int rc = backward_prologue(who, a, in, saved, /*dL_dpix: not this entry's*/ dL_ddist, false, nullptr, g, true, stream, &v);
     const int P = a->P, W = a->image_width, H = a->image_height;
     if (rc || P == 0) return rc;   // (P == 0: no gradient has a row)
     float *partial = g->scratch;
     const float *dz = nullptr;
     if (saved->num_rendered > 0) {
-        float *dzw = behind_rows(g->scratch, L);
-        if ((rc = launch_render_distortion_backward(P, W, H, dL_ddist, totals, partial, saved->geom, saved->binning, saved->img, L, a->debug != 0, s))) return rc;
-        if ((rc = launch_distortion_fold(P, saved->geom, L, partial, dzw, a->debug != 0, s))) return rc;
+        float *dzw = behind_rows(g->scratch, v);
+        if ((rc = launch_render_distortion_backward(P, W, H, dL_ddist, totals, partial, v, a->debug != 0, s))) return rc;
+        if ((rc = launch_distortion_fold(P, v, partial, dzw, a->debug != 0, s))) return rc;
         dz = dzw;
     }
     // (nothing rendered: tiles_touched is all zero, the kernel reads no row and writes the zeros; columns 0..2 are zero: so is dL/d(colour, SH))
-    return launch_preprocess_backward(a, in, saved->geom, saved->binning, L, g, partial, s, false, dz, (saved->flags & ANTIALIAS_FLAG) != 0);
+    return launch_preprocess_backward(a, in, v, g, partial, s, false, dz, (saved->flags & ANTIALIAS_FLAG) != 0);
 }
 
 // ---- median depth and surface hits over a forward's saved lists (render_median.hip) ----
@@ -690,9 +680,8 @@ extern "C" int das3r_raster_median_forward(const das3r_raster_args *a, const das
         return DAS3R_OK;
     }
     if ((rc = das3r_raster_check(saved, stream))) return rc;   // a failed binning is an error, not a walk over bad lists
-    const Layout L = saved_layout(a, saved);
-    return launch_render_median_forward(P, W, H, threshold, depth, hit_gaussian, hit_position, saved->geom, saved->binning, saved->img, L,
-                                        a->debug != 0, s);
+    const Buffers v = saved_buffers(a, nullptr, saved);
+    return launch_render_median_forward(P, W, H, threshold, depth, hit_gaussian, hit_position, v, a->debug != 0, s);
 }
 
 // one float per instance + 16 bytes (as das3r_raster_aux_scratch_bytes rounds its rows up)
@@ -717,9 +706,8 @@ extern "C" int das3r_raster_median_adjoint(const das3r_raster_args *a, const das
         return DAS3R_OK;
     }
     if ((rc = das3r_raster_check(saved, stream))) return rc;
-    const Layout L = saved_layout(a, saved);
-    return launch_render_median_adjoint(P, W, H, dL_ddepth, hit_position, dL_dz, accumulate != 0, scratch, saved->geom, saved->binning, saved->img,
-                                        L, a->debug != 0, s);
+    const Buffers v = saved_buffers(a, nullptr, saved);
+    return launch_render_median_adjoint(P, W, H, dL_ddepth, hit_position, dL_dz, accumulate != 0, scratch, v, a->debug != 0, s);
 }
 
 extern "C" int das3r_has_experiments(void) {
@@ -804,12 +792,12 @@ extern "C" int das3r_raster_count_live_pairs(const das3r_raster_args *a, const d
     if (a->P == 0 || saved->num_rendered <= 0) return DAS3R_OK;
     if (!saved->geom || !saved->binning || !saved->img) { set_error("das3r_raster_count_live_pairs: saved buffers missing"); return DAS3R_ERR_INVALID_ARG; }
     hipStream_t s = (hipStream_t)stream;
-    const Layout L = saved_layout(a, saved);
+    const Buffers v = saved_buffers(a, nullptr, saved);
     unsigned long long *dev = nullptr;
     HIP_TRY(hipMalloc((void **)&dev, 2 * sizeof(unsigned long long)));
     int rc = DAS3R_OK;
     if (hipMemsetAsync(dev, 0, 2 * sizeof(unsigned long long), s) != hipSuccess) rc = DAS3R_ERR_HIP;
-    if (!rc) rc = launch_count_live_pairs(a, saved->geom, saved->binning, saved->img, L, dev, s);
+    if (!rc) rc = launch_count_live_pairs(a, v, dev, s);
     if (!rc && (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(out, dev, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess)) {
         set_error("das3r_raster_count_live_pairs: device error");
         rc = DAS3R_ERR_HIP;

@@ -293,37 +293,36 @@ __global__ void __launch_bounds__(256) cell_finish_kernel(const uint32_t *__rest
 
 // The partition and the finish of the cells plan on the ping-pong buffers of the one-sweep passes (launch_onesweep_partition): the last
 // kernel writes the buffers the layout calls point_list and slot_list, *keys_final names the keys that went with them.
-int launch_cell_sort(int64_t cap, char *geom, char *binning, char *img, const Layout &L, uint32_t **keys_final, uint32_t *host_late, uint32_t tag,
+int launch_cell_sort(int64_t cap, const Buffers &v, uint32_t **keys_final, uint32_t *host_late, uint32_t tag,
                      uint32_t *host_flag, uint32_t flag_value, bool debug, hipStream_t s) {
-    if (L.part_passes > 2 || L.kbits != 8 * L.part_passes || L.dbits < 1 || L.dbits > 7) {
-        set_error("the cells plan needs a partition key of 8 or 16 bits with depth buckets (kbits %d, dbits %d, passes %d)", L.kbits, L.dbits, L.part_passes);
+    if (v.L.part_passes > 2 || v.L.kbits != 8 * v.L.part_passes || v.L.dbits < 1 || v.L.dbits > 7) {
+        set_error("the cells plan needs a partition key of 8 or 16 bits with depth buckets (kbits %d, dbits %d, passes %d)", v.L.kbits, v.L.dbits, v.L.part_passes);
         return DAS3R_ERR_INVALID_ARG;
     }
-    const uint32_t *n_ptr = (const uint32_t *)(geom + L.g_count);
-    uint32_t *err = (uint32_t *)(geom + L.g_ticket) + 8;
-    uint32_t *keyA = (uint32_t *)(binning + L.b_keyA), *keyB = (uint32_t *)(binning + L.b_keyB);
-    uint32_t *valA = (uint32_t *)(binning + L.b_valA), *valB = (uint32_t *)(binning + L.b_valB);
-    uint32_t *gid_of = (uint32_t *)(binning + L.b_gid_of), *slot_list = (uint32_t *)(binning + L.b_slot), *e_tmp = (uint32_t *)(binning + L.b_e2);
-    uint32_t *ghist = (uint32_t *)(binning + L.b_ghist), *cursor = (uint32_t *)(binning + L.b_cursor);
-    uint32_t *const pl_final = (uint32_t *)(binning + L.pub.point_list), *const pl_other = pl_final == valA ? valB : valA;
-    uint2 *ranges = (uint2 *)(img + L.pub.ranges);
-    const bool two = L.part_passes == 2;
+    const uint32_t *n_ptr = v.g_count();
+    uint32_t *err = v.err_word();
+    uint32_t *keyA = v.b_keyA(), *keyB = v.b_keyB();
+    uint32_t *gid_of = v.b_gid_of(), *slot_list = v.b_slot(), *e_tmp = v.b_e2();
+    uint32_t *ghist = v.b_ghist(), *cursor = v.b_cursor();
+    uint32_t *const pl_final = v.point_list(), *const pl_other = v.point_list_partner();
+    uint2 *ranges = v.ranges();
+    const bool two = v.L.part_passes == 2;
     if (two) {
         const int ipl = sort_items_per_lane(cap);
         const int nblocks = div_up(cap, (int64_t)256 * ipl);
 #define PART(IPL)                                                                                                                      \
     DAS3R_LAUNCH((cell_partition_kernel<IPL>), dim3(nblocks), dim3(256), 0, s, keyA, gid_of, keyB, pl_other, e_tmp, (uint32_t)cap, n_ptr, \
-                 L.kshift + 8, ghist + 256, cursor, L.cursor_stride, err)
+                 v.L.kshift + 8, ghist + 256, cursor, v.L.cursor_stride, err)
         if (ipl == 4) PART(4); else if (ipl == 8) PART(8); else PART(16);
 #undef PART
         KERNEL_CHECK(s, debug, "cell_partition");
     }
-    const uint32_t ncells = two ? (((uint32_t)L.ntiles - 1u) >> (8 - L.dbits)) + 1u : 1u;
+    const uint32_t ncells = two ? (((uint32_t)v.L.ntiles - 1u) >> (8 - v.L.dbits)) + 1u : 1u;
     const uint32_t grid = ((ncells + 7u) & ~7u) * (uint32_t)CELL_SPLIT;
     uint32_t *kout = two ? keyA : keyB;
     DAS3R_LAUNCH(cell_finish_kernel, dim3(grid), dim3(256), 0, s, two ? keyB : keyA, two ? pl_other : gid_of, two ? e_tmp : (uint32_t *)nullptr, kout,
-                 pl_final, slot_list, (uint32_t)cap, n_ptr, L.kshift, L.dbits, (uint32_t)L.ntiles, ncells, two ? ghist + 256 : (uint32_t *)nullptr,
-                 two ? cursor : (uint32_t *)nullptr, L.cursor_stride, ranges, err, host_late, tag, (uint32_t)switches().inject_fault, host_flag, flag_value);
+                 pl_final, slot_list, (uint32_t)cap, n_ptr, v.L.kshift, v.L.dbits, (uint32_t)v.L.ntiles, ncells, two ? ghist + 256 : (uint32_t *)nullptr,
+                 two ? cursor : (uint32_t *)nullptr, v.L.cursor_stride, ranges, err, host_late, tag, (uint32_t)switches().inject_fault, host_flag, flag_value);
     KERNEL_CHECK(s, debug, "cell_finish");
     *keys_final = kout;
     return DAS3R_OK;

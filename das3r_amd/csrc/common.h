@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "../../include/das3r_raster.h"
+#include "buffers.h"
 #include "kernel_choice.h"
 #include "path_policy.h"
 #include "pretransform_math.h"
@@ -172,37 +173,6 @@ constexpr uint32_t NO_BACKWARD_IN_FLAG = 8u;
 // das3r_raster_saved.flags bit 4, read on the way IN to das3r_raster_forward and set again on the way out: the antialiased forward
 // (splat_math.h aa_factor scales every splat's opacity); das3r_raster_backward / _depth differentiate the factor iff it is set
 constexpr uint32_t ANTIALIAS_FLAG = 16u;
-struct Layout {
-    das3r_raster_layout pub;
-    // private scratch offsets
-    size_t g_keyA, g_keyB, g_valA, g_valB, g_hist, g_totals, g_blocksums, g_count, g_off_by_gid, g_rect;   // g_rect: u32 per splat, binned tile rectangle x0 | x1 << 8 | y0 << 16 | y1 << 24 (0 = none)
-    size_t b_keyA, b_keyB, b_valA, b_valB, b_hist, b_totals, b_gid_of, b_slot;
-    size_t b_e2;     // u32[capacity]: ping-pong partner of b_slot for the emission slots travelling through the partition passes
-    size_t b_ckpt;   // float4[(capacity / BUCKET + ntiles + 2) * 256]: per-pixel (T, C) at the bucket boundaries of long tile lists
-    // ABI 16: what a forward with out_invdepth appends to the binning buffer (pub.binning_bytes .. d_bytes; a colour-only forward's layout is
-    // unchanged).  d_ckpt: per-pixel (T, D, 0, 0) at the same bucket boundaries as b_ckpt (D = inverse depth so far) — the depth as the first
-    // colour of a checkpoint; d_recs / d_dpix / d_bg / d_dz: written by das3r_raster_backward_depth (api.hip) for its depth pass.
-    size_t d_ckpt, d_recs, d_dpix, d_bg, d_dz, d_bytes;
-    // single-pass radix control words (sort_onesweep.hip): [global digit histograms][tickets][status granules], contiguous
-    // so that one store loop / one memset zeroes them: geom side by preprocess_kernel, binning side by a memset before emit
-    size_t g_ghist, g_ticket, g_status, g_scan_status, g_ctrl_bytes;
-    int64_t capacity;  // instance capacity the binning buffer was laid out for
-    size_t b_ghist, b_ticket, b_status, b_ctrl_bytes;
-    size_t b_cursor;   // u32[256 * cursor_stride] inside the control words: the bin cursors of the cells plan (cell_sort.hip)
-    int cursor_stride; // words between two cursors: CURSOR_STRIDE (a 128-byte line each) from 2^20 instances on, 1 below (few workgroups; 1 KB to zero, not 32)
-    int tiles_x, tiles_y, ntiles, tbits, tile_passes;
-    int chunksP, chunksI;
-    // segmented binning path (segkey.h): the partition key is (tile id << dbits | depth bucket), kbits = tbits + dbits wide, in the
-    // SAME number of passes the tile ids alone need (the backward pass lays the buffers out without knowing the path).  dbits = 0
-    // everywhere else.  g_dhist: u32[256] depth histogram of the forward
-    int dbits, kbits, kshift;   // kshift: the key's low bits hold the fraction of the depth map (segkey.h: min(16, 32 - kbits) bits), the
-                                // partition's digits start above them
-    int part_passes;            // passes of the instance partition: tile_passes, or one more when the segmented path wants more bucket bits
-    size_t g_dhist;
-    size_t g_shjac;   // f32[9][P] behind everything else of the geometry buffer: plane 3c + k = d(rgb_c)/d(dir_k) (preprocess.hip); 0 = none
-    const uint32_t *dhist_ptr;  // round 6: where this forward's depth histogram really is (a library-owned slot: forward.hip dhist_slots); null = geom + g_dhist
-    size_t i_order;   // img buffer, u32[ntiles]: the tiles longest list first (render_regions.hip tile_lpt_kernel; round 6)
-};
 // depth-bucket bits `passes` partition passes (at most three) have room for beside the tile ids (<= 0: none): path_policy.h
 static inline int seg_dbits(const Layout &L, int passes) { return seg_dbits(L.tbits, passes); }
 
@@ -244,7 +214,7 @@ constexpr int EMIT_SLOT_WORDS = 64 + 4 * 256;          // err + padding, ghist: 
 constexpr int EMIT_STATUS_GRANULES = 1024;             // >= resident grid + its groups
 
 // ---- launchers implemented in the individual .hip files ----
-// binning_ctrl (may be null): the binning buffer's control words, zeroed by the same kernel when the buffer already exists
+// binning_ctrl (may be {null, 0}): the binning buffer's control words, zeroed by the same kernel when the buffer already exists
 // arrive: a zeroed 64-bit device word (self re-arming); host_out / tag: pinned mailbox that receives num_rendered
 // The split preprocess (preprocess.hip): a library-owned non-blocking stream beside the caller's, and the two events of the fork (recorded on
 // the caller's stream behind the geometry kernel; the side stream waits for it) and of the join (recorded on the side stream behind the colour
@@ -258,27 +228,26 @@ struct SideStream {
 // side != null: the split form — the geometry kernel on s and the fork event recorded behind it; the caller then enqueues the colour kernel
 // (launch_sh_colour: side->stream waits for the fork, the join event is recorded behind the kernel) and makes s wait for side->join before
 // anything reads a colour, `clamped` or the Jacobian planes
-int launch_preprocess(const das3r_raster_args *a, const das3r_raster_in *in, int32_t *radii, char *geom, char *img, char *binning_ctrl,
-                      size_t binning_ctrl_bytes, const Layout &L, unsigned long long *arrive, uint32_t *host_out, uint32_t tag,
+int launch_preprocess(const das3r_raster_args *a, const das3r_raster_in *in, int32_t *radii, const Buffers &v, WordRange binning_ctrl, unsigned long long *arrive,
+                      uint32_t *host_out, uint32_t tag,
                       hipStream_t s, const EmitArgs *emit, uint32_t *dhist, uint32_t *dhist_next, bool aa /*ANTIALIAS_FLAG*/,
                       const SideStream *side = nullptr);
-int launch_sh_colour(const das3r_raster_args *a, const das3r_raster_in *in, char *geom, const Layout &L, const SideStream *side);
+int launch_sh_colour(const das3r_raster_args *a, const das3r_raster_in *in, const Buffers &v, const SideStream *side);
 int launch_mark_visible(int P, const float *means3D, const float *viewmatrix, uint8_t *present, hipStream_t s);
 // part 0: everything that can be enqueued before num_rendered is known; part 1: the rest, which also zeroes the binning buffer's
-// control words (binning_ctrl may be null)
-int launch_depth_sort(int P, char *geom, const Layout &L, int part, char *binning_ctrl, size_t binning_ctrl_bytes, bool debug, hipStream_t s);
+// control words (binning_ctrl may be {null, 0})
+int launch_depth_sort(int P, const Buffers &v, int part, WordRange binning_ctrl, bool debug, hipStream_t s);
 // scan of tiles_touched in depth order -> offsets / off_by_gid / count (exact path: the host then reads the count)
-int launch_scan(int P, char *geom, const Layout &L, uint32_t *host_out, uint32_t tag, bool debug, hipStream_t s, bool index_order = false);
+int launch_scan(int P, const Buffers &v, uint32_t *host_out, uint32_t tag, bool debug, hipStream_t s, bool index_order = false);
 // the same scan with the instance emission fused in (hinted path; sort_onesweep.hip)
-int launch_scan_emit(int P, int64_t cap, const int32_t *radii, char *geom, char *binning, const Layout &L, uint32_t *host_out, uint32_t tag,
+int launch_scan_emit(int P, int64_t cap, const int32_t *radii, const Buffers &v, uint32_t *host_out, uint32_t tag,
                      bool debug, hipStream_t s, bool index_order = false);
 size_t scan_status_bytes(int P);
-int launch_binning_scan_emit(int P, int64_t I, const int32_t *radii, char *geom, char *binning, const Layout &L, bool ctrl_zeroed,
+int launch_binning_scan_emit(int P, int64_t I, const int32_t *radii, const Buffers &v, bool ctrl_zeroed,
                              uint32_t *host_out, uint32_t tag, bool debug, hipStream_t s, bool index_order = false);
 size_t onesweep_status_bytes(int64_t n, int passes);
-int launch_onesweep_depth_sort(int P, char *geom, const Layout &L, int part, uint32_t *zero_ptr, uint32_t zero_words, bool debug,
-                               hipStream_t s);
-int launch_onesweep_partition(int64_t cap, char *geom, char *binning, const Layout &L, uint32_t **keys_final, bool debug, hipStream_t s,
+int launch_onesweep_depth_sort(int P, const Buffers &v, int part, WordRange zero, bool debug, hipStream_t s);
+int launch_onesweep_partition(int64_t cap, const Buffers &v, uint32_t **keys_final, bool debug, hipStream_t s,
                               uint32_t *ghist_override = nullptr, uint32_t *err_override = nullptr);
 // das3r_raster_in.pre -> the device-side view the per-Gaussian kernels take by value (pretransform_math.h); all null when the caller handed
 // over camera-frame tensors
@@ -290,31 +259,27 @@ inline PreXform pre_xform(const das3r_raster_in *in) {
     }
     return x;
 }
-int launch_render_forward_regions(const das3r_raster_args *a, float *out_color, char *geom, char *binning, char *img, const Layout &L, const LocalBin &lb,
+int launch_render_forward_regions(const das3r_raster_args *a, float *out_color, const Buffers &v, const LocalBin &lb,
                                   hipStream_t s, float *out_invdepth, float4 *dckpt);   // the same shapes: sixteen lanes per pixel, a wave per 2x2 region, four workgroups per tile (render_regions.hip)
-int launch_tile_lpt(char *img, const Layout &L, uint32_t cap, bool debug, hipStream_t s);   // render_regions.hip
-int launch_list_skew(const char *img, const char *binning, const char *geom, const Layout &L, uint32_t cap, uint32_t last_g, uint32_t *mailbox_words, uint32_t tag,
-                     bool debug, hipStream_t s);
-int launch_render_forward_slices(const das3r_raster_args *a, float *out_color, char *geom, char *binning, char *img, const Layout &L, const LocalBin &lb,
+int launch_tile_lpt(const Buffers &v, uint32_t cap, bool debug, hipStream_t s);   // render_regions.hip
+int launch_list_skew(const Buffers &v, uint32_t cap, uint32_t last_g, uint32_t *mailbox_words, uint32_t tag, bool debug, hipStream_t s);
+int launch_render_forward_slices(const das3r_raster_args *a, float *out_color, const Buffers &v, const LocalBin &lb,
                                  hipStream_t s);   // the same shapes, a block's list cut into chunks any wave takes (render_slices.hip)
-int launch_render_forward_lanes(const das3r_raster_args *a, float *out_color, char *geom, char *binning, char *img, const Layout &L,
+int launch_render_forward_lanes(const das3r_raster_args *a, float *out_color, const Buffers &v,
                                 const LocalBin &lb, hipStream_t s, float *out_invdepth, float4 *dckpt);
-int launch_render_forward_rows(const das3r_raster_args *a, float *out_color, char *geom, char *binning, char *img, const Layout &L,
+int launch_render_forward_rows(const das3r_raster_args *a, float *out_color, const Buffers &v,
                                const LocalBin &lb, hipStream_t s, float *out_invdepth, float4 *dckpt);
-int launch_render_backward_mfma(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
-                                float *partial, hipStream_t s);
+int launch_render_backward_mfma(const das3r_raster_args *a, const float *dL_dpix, const Buffers &v, float *partial, hipStream_t s);
 // independent waves (render_bwd_stream.hip): scratch = rows[capacity][4][12] + one byte per row that exists
 size_t stream_scratch_bytes(int64_t capacity);
-int launch_render_backward_stream(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
-                                  float *scratch, hipStream_t s);
+int launch_render_backward_stream(const das3r_raster_args *a, const float *dL_dpix, const Buffers &v, float *scratch, hipStream_t s);
 // slices > 1: bucket-parallel replay (grid = tiles x slices; needs the forward's checkpoints)
 // c: kernel_choice.h choose_backward (entries per round, slices, and what each kernel's forms are picked by)
-int launch_render_backward_scan(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
+int launch_render_backward_scan(const das3r_raster_args *a, const float *dL_dpix, const Buffers &v,
                                 float *partial, const BwdChoice &c, hipStream_t s);
 // 4x4 block per DPP row, pixel state in registers, fp32 accumulators (render_bwd_blk.hip)
-int launch_render_backward_blk(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
-                               float *partial, const BwdChoice &c, hipStream_t s);
-int launch_render_backward_regions(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
+int launch_render_backward_blk(const das3r_raster_args *a, const float *dL_dpix, const Buffers &v, float *partial, const BwdChoice &c, hipStream_t s);
+int launch_render_backward_regions(const das3r_raster_args *a, const float *dL_dpix, const Buffers &v,
                                float *partial, const BwdChoice &c, hipStream_t s);   // render_bwd_rgn.hip
 constexpr int LOCAL_MAX = 1024;   // longest tile list the forward kernels sort in LDS
 // chained kernels (scan, radix passes) order their workgroups by ticket unless every workgroup of the grid is resident at once
@@ -323,31 +288,31 @@ bool grid_is_resident(int nblocks);
 bool use_onesweep();  // DAS3R_SORT=classic selects the three-kernel radix passes (diagnostics / A-B)
 bool use_tight_rect();  // DAS3R_RECT=upstream bins over upstream's 3-sigma square (bit-exact list tests)
 // host_late / tag: pinned mailbox the last binning kernel copies the self-check word to (see mailbox.h)
-int launch_binning(int P, int64_t I, int W, int H, const int32_t *radii, char *geom, char *binning, char *img, const Layout &L,
+int launch_binning(int P, int64_t I, int W, int H, const int32_t *radii, const Buffers &v,
                    bool fused_scan, uint32_t *host_late, uint32_t tag, bool debug, hipStream_t s, uint32_t **dead_keys = nullptr,
                    uint32_t *emit_slot = nullptr /*fused emission: {err, pad, ghist} ring slot, re-armed by the last kernel*/,
                    uint32_t *seg_host_flag = nullptr, uint32_t seg_flag_value = 0 /*segmented path (L.dbits > 0): mailbox word for a segment too long for LDS*/,
                    bool local_finish = false /*L.dbits > 0: no segment sort — tile ranges from the bucketed keys, the compositing kernel finishes the lists*/,
                    bool cells = false /*with local_finish: partition by reserved ranges, finish per cell (cell_sort.hip) instead of the stable passes*/);
 // cell_sort.hip: the cells plan's partition and finish, tile ranges and self-check word included; host_flag / flag_value: the too_long mailbox word
-int launch_cell_sort(int64_t cap, char *geom, char *binning, char *img, const Layout &L, uint32_t **keys_final, uint32_t *host_late, uint32_t tag,
+int launch_cell_sort(int64_t cap, const Buffers &v, uint32_t **keys_final, uint32_t *host_late, uint32_t tag,
                      uint32_t *host_flag, uint32_t flag_value, bool debug, hipStream_t s);
 // segsort.hip: exact (depth bits, index) order inside every (tile, depth bucket) segment of the partitioned list, in place
 int launch_segment_sort(int64_t cap, const uint32_t *n_ptr, const uint32_t *keys_final, int fbits, uint32_t *point_list, uint32_t *slot_list,
                         const uint32_t *depth_key, uint32_t last_g, uint32_t *scratch_keys, uint32_t *host_flag, uint32_t flag_value, bool debug,
                         hipStream_t s, int dbits, uint2 *ranges, const uint32_t *err, uint32_t *host_late, uint32_t tag, uint32_t inject);
 // lb.point_list != null: the tile lists are in index order and the kernel sorts them by depth first
-int launch_render_forward(const das3r_raster_args *a, const float *colors_precomp, float *out_color, char *geom, char *binning,
-                          char *img, const Layout &L, const LocalBin &lb, hipStream_t s, float *out_invdepth /*ABI 16: NULL = colour only*/,
+int launch_render_forward(const das3r_raster_args *a, const float *colors_precomp, float *out_color, const Buffers &v,
+                          const LocalBin &lb, hipStream_t s, float *out_invdepth /*ABI 16: NULL = colour only*/,
                           float4 *dckpt /*with out_invdepth: Layout::d_ckpt*/);
 // ABI 16, das3r_raster_backward_depth (api.hip): the depth pass's splat records (xy, conic, (1/z, 0, 0, z)), upstream gradient planes
 // (dL/dinvdepth, 0, 0) and zero background; then the fold of its per-instance sums into the colour pass's and the per-Gaussian dL/dz.
-int launch_depth_pass_inputs(int P, int npix, const char *geom, const Layout &L, char *binning, const float *dL_dinvdepth, hipStream_t s, bool debug);
-int launch_depth_fold(int P, const char *geom, const Layout &L, float *partial, const float *partial_depth, float *dz, hipStream_t s, bool debug);
+int launch_depth_pass_inputs(int P, int npix, const Buffers &v, const float *dL_dinvdepth, hipStream_t s, bool debug);
+int launch_depth_fold(int P, const Buffers &v, float *partial, const float *partial_depth, float *dz, hipStream_t s, bool debug);
 // focal_grad.hip (das3r_raster_backward_focal): dL/d(log-focal offsets) from the rows the compositing backward (and the depth fold) left in
 // `partial`, before the per-Gaussian backward runs; workspace: focal_workspace_bytes(P) bytes, one row of two sums per workgroup
 size_t focal_workspace_bytes(int P);
-int launch_focal_grad(const das3r_raster_args *a, const das3r_raster_in *in, const char *geom, const Layout &L, const float *partial, bool quad_rows,
+int launch_focal_grad(const das3r_raster_args *a, const das3r_raster_in *in, const Buffers &v, const float *partial, bool quad_rows,
                       bool aa /*ANTIALIAS_FLAG*/, float *sums /*[2]*/, float *per_splat /*[P,2] or null*/, float *workspace, hipStream_t s);
 // the existence bytes [I][4] behind the quadrant rows [I][4][12] of `partial` (render_bwd_stream.hip lays them out); null: one row per instance
 static inline const uint8_t *quad_rows_exist(const float *partial, const Layout &L, bool quad_rows) {
@@ -356,36 +321,31 @@ static inline const uint8_t *quad_rows_exist(const float *partial, const Layout 
 }
 // partial: [num_rendered, 9] per-instance sums written by the render backward, gathered by the preprocess backward
 // *quad_rows (out): false = partial[I][9], one row per instance; true = the stream kernel's rows[I][4][12] + existence bytes
-int launch_render_backward(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
+int launch_render_backward(const das3r_raster_args *a, const float *dL_dpix, const Buffers &v,
                            float *partial, hipStream_t s, bool *quad_rows, int64_t num_rendered, uint32_t fwd_flags /*das3r_raster_saved.flags*/);
 // render_aux.hip: a caller's [P, C] rows composited over the saved lists of a forward (1 <= C <= DAS3R_AUX_MAX_CHANNELS), and the adjoint —
 // per-instance rows partial[capacity][C] through the emission slots, then the per-Gaussian sum (written, or added with `accumulate`)
-int launch_render_aux_forward(int P, int W, int H, int C, const float *feat, float *out, const char *geom, const char *binning, const char *img,
-                              const Layout &L, int64_t num_rendered, bool debug, hipStream_t s);
-int launch_render_aux_adjoint(int P, int W, int H, int C, const float *dL_dout, float *dL_dfeat, int accumulate, float *partial, const char *geom,
-                              const char *binning, const char *img, const Layout &L, int64_t num_rendered, bool debug, hipStream_t s);
-int launch_aux_gather(int P, int C, const float *partial, float *dL_dfeat, const char *geom, const Layout &L, bool debug, hipStream_t s);
+int launch_render_aux_forward(int P, int W, int H, int C, const float *feat, float *out, const Buffers &v, int64_t num_rendered, bool debug, hipStream_t s);
+int launch_render_aux_adjoint(int P, int W, int H, int C, const float *dL_dout, float *dL_dfeat, int accumulate, float *partial, const Buffers &v, int64_t num_rendered, bool debug, hipStream_t s);
+int launch_aux_gather(int P, int C, const float *partial, float *dL_dfeat, const Buffers &v, bool debug, hipStream_t s);
 // render_aux_bwd.hip: the compositing backward of aux channels / coverage with respect to the geometry -> partial [capacity, 9] (+ partial_f [capacity, C] or null)
 int launch_render_aux_backward(int P, int W, int H, int C, const float *feat, const float *dL_dout, const float *dL_dalpha, float *partial,
-                               float *partial_f, const char *geom, const char *binning, const char *img, const Layout &L, bool debug, hipStream_t s);
+                               float *partial_f, const Buffers &v, bool debug, hipStream_t s);
 // render_distort.hip: the ray-distortion term over the saved lists -> out [H,W] (+ totals [H,W] or null); its compositing backward ->
 // partial [capacity, 9] (column 0: the per-instance sum of dL/dm, columns 1..2 zero), then the fold of column 0 into dz [P] (column 0 zeroed)
-int launch_render_distortion_forward(int P, int W, int H, float *out, float *totals, const char *geom, const char *binning, const char *img,
-                                     const Layout &L, bool debug, hipStream_t s);
-int launch_render_distortion_backward(int P, int W, int H, const float *dL_ddist, const float *totals, float *partial, const char *geom,
-                                      const char *binning, const char *img, const Layout &L, bool debug, hipStream_t s);
-int launch_distortion_fold(int P, const char *geom, const Layout &L, float *partial, float *dz, bool debug, hipStream_t s);
+int launch_render_distortion_forward(int P, int W, int H, float *out, float *totals, const Buffers &v, bool debug, hipStream_t s);
+int launch_render_distortion_backward(int P, int W, int H, const float *dL_ddist, const float *totals, float *partial, const Buffers &v, bool debug, hipStream_t s);
+int launch_distortion_fold(int P, const Buffers &v, float *partial, float *dz, bool debug, hipStream_t s);
 // render_median.hip: the depth (+ Gaussian index, + list position; either null) of the entry at which T crosses tau, over the saved lists;
 // the depth's adjoint -> rows [capacity] through the emission slots, then render_aux.hip's gather into dL_dz [P] (written, or added)
-int launch_render_median_forward(int P, int W, int H, float tau, float *depth, int32_t *hit_gaussian, uint32_t *hit_position, const char *geom,
-                                 const char *binning, const char *img, const Layout &L, bool debug, hipStream_t s);
+int launch_render_median_forward(int P, int W, int H, float tau, float *depth, int32_t *hit_gaussian, uint32_t *hit_position, const Buffers &v, bool debug, hipStream_t s);
 int launch_render_median_adjoint(int P, int W, int H, const float *dL_ddepth, const uint32_t *hit_position, float *dL_dz, int accumulate,
-                                 float *rows, const char *geom, const char *binning, const char *img, const Layout &L, bool debug, hipStream_t s);
+                                 float *rows, const Buffers &v, bool debug, hipStream_t s);
 // prune.hip: exclusive scan of per-group kept counts (one workgroup; *total = their sum), then dst_index[i] = the new row of every row flagged 0
 int launch_prune_scan_rank(int P, int32_t *group_counts, int32_t *total, int32_t *dst_index, hipStream_t s);
 // pair_count.hip (measurement aid): out[0] += live pairs, out[1] += (pixel, list position) pairs below the pixel's n_contrib
-int launch_count_live_pairs(const das3r_raster_args *a, char *geom, char *binning, char *img, const Layout &L, unsigned long long *out, hipStream_t s);
-int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in *in, char *geom, char *binning, const Layout &L,
+int launch_count_live_pairs(const das3r_raster_args *a, const Buffers &v, unsigned long long *out, hipStream_t s);
+int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in *in, const Buffers &v,
                                const das3r_raster_grads *g, const float *partial, hipStream_t s, bool quad_rows, const float *dz /*ABI 16: [P] dL/dz of the depth pass, or null*/,
                                bool aa /*ANTIALIAS_FLAG: the forward was antialiased*/);
 

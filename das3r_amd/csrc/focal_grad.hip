@@ -111,16 +111,15 @@ __global__ void __launch_bounds__(256) focal_finish_kernel(int nrows, const floa
 
 size_t focal_workspace_bytes(int P) { return (size_t)std::max(div_up(P > 0 ? P : 0, 256), 1) * 2 * sizeof(float); }
 
-int launch_focal_grad(const das3r_raster_args *a, const das3r_raster_in *in, const char *geom, const Layout &L, const float *partial, bool quad_rows,
+int launch_focal_grad(const das3r_raster_args *a, const das3r_raster_in *in, const Buffers &v, const float *partial, bool quad_rows,
                       bool aa, float *sums, float *per_splat, float *workspace, hipStream_t s) {
     const int P = a->P;
     const int blocks = div_up(P, 256);
-    const uint8_t *exists = quad_rows_exist(partial, L, quad_rows);
+    const uint8_t *exists = quad_rows_exist(partial, v.L, quad_rows);
     const PreXform pre = pre_xform(in);
 #define ARGS                                                                                                                              \
     P, in->means3D, in->scales, a->scale_modifier, in->rotations, in->cov3D_precomp, in->opacities, pre, a->viewmatrix, a->image_width,   \
-        a->image_height, a->tanfovx, a->tanfovy, (const uint32_t *)(geom + L.pub.tiles_touched), (const uint32_t *)(geom + L.g_off_by_gid), \
-        (const float4 *)(geom + L.pub.xy), partial, exists, per_splat, workspace
+        a->image_height, a->tanfovx, a->tanfovy, v.tiles_touched(), v.g_off_by_gid(), v.xy(), partial, exists, per_splat, workspace
     if (in->cov3D_precomp) {
         if (aa) DAS3R_LAUNCH((focal_grad_kernel<true, true>), dim3(blocks), dim3(256), 0, s, ARGS);
         else DAS3R_LAUNCH((focal_grad_kernel<true, false>), dim3(blocks), dim3(256), 0, s, ARGS);

@@ -102,10 +102,10 @@ static bool dhist_slots(hipStream_t s, uint32_t **use, uint32_t **next) {
 }
 // The depth histogram of this forward (segkey.h): filled by the preprocess kernel, read by the emission.  Not segmented: none (nulls).
 // No slot: in the geometry buffer, zeroed by a memset, as before round 6 (*next stays null).
-static int seg_dhist_for(bool seg, hipStream_t s, char *geom, const Layout &L, uint32_t **use, uint32_t **next) {
+static int seg_dhist_for(bool seg, hipStream_t s, const Buffers &v, uint32_t **use, uint32_t **next) {
     *use = *next = nullptr;
     if (seg && !dhist_slots(s, use, next)) {
-        *use = (uint32_t *)(geom + L.g_dhist);
+        *use = v.g_dhist();
         HIP_TRY(hipMemsetAsync(*use, 0, 4 * 256, s));
     }
     return DAS3R_OK;
@@ -237,7 +237,7 @@ struct ForwardCall {
     Join join;                             // (s again: what the side stream owes the caller's)
     PerDevice *T = nullptr;
     Mailbox *mb = nullptr;
-    Layout L;                              // laid out for L.capacity instances; layout_and_alloc is the one place that changes it
+    Buffers v{};                           // saved's three buffers, laid out for v.L.capacity instances; layout_and_alloc is the one place that changes the layout
     PolicyInputs policy_in;
     ForwardPlan plan;
     bool local = false;                    // plan.local, until the exact flow's count says "global sort after all"
@@ -290,16 +290,16 @@ int64_t ForwardCall::run() {
     shjac = in->shs != nullptr && a->sh_degree >= 2 && !(saved->flags & NO_BACKWARD_IN_FLAG);
     no_backward = (saved->flags & NO_BACKWARD_IN_FLAG) != 0;
     aa = (saved->flags & ANTIALIAS_FLAG) != 0;   // (bit 4 on the way in: an antialiased forward; set again on the way out)
-    compute_layout(P, 0, W, H, &L, shjac);
-    saved->geom = alloc_geom(user, L.pub.geom_bytes);
-    saved->img = alloc_img(user, L.pub.img_bytes);
-    saved->binning = nullptr;
+    compute_layout(P, 0, W, H, &v.L, shjac);
+    saved->geom = v.geom = v.recs = alloc_geom(user, v.L.pub.geom_bytes);
+    saved->img = v.img = alloc_img(user, v.L.pub.img_bytes);
+    saved->binning = v.binning = nullptr;
     saved->num_rendered = 0;
     saved->capacity = 0;
     saved->check_word = nullptr;
     saved->check_tag = 0;
     saved->flags = aa ? ANTIALIAS_FLAG : 0u;
-    if (!saved->geom || !saved->img) { set_error("scratch allocation failed (geom %zu B, img %zu B)", L.pub.geom_bytes, L.pub.img_bytes); return DAS3R_ERR_ALLOC; }
+    if (!saved->geom || !saved->img) { set_error("scratch allocation failed (geom %zu B, img %zu B)", v.L.pub.geom_bytes, v.L.pub.img_bytes); return DAS3R_ERR_ALLOC; }
     if (P == 0) return empty_scene();
     if ((rc = per_device(&T))) return rc;
     mb = &T->mb;
@@ -312,7 +312,7 @@ int64_t ForwardCall::run() {
     if (too_long) mb->host[MB_TOO_LONG] = 0;
     const uint32_t want_bits = mb->host[MB_WANT_BITS];
     if (want_bits) mb->host[MB_WANT_BITS] = 0;
-    policy_in = PolicyInputs{P, W, H, L.ntiles, L.tbits, L.tile_passes, too_long, want_bits, switches().binning /* DAS3R_BINNING */, use_onesweep(),
+    policy_in = PolicyInputs{P, W, H, v.L.ntiles, v.L.tbits, v.L.tile_passes, too_long, want_bits, switches().binning /* DAS3R_BINNING */, use_onesweep(),
                              a->capacity_hint, switches().capacity_exact, &T->resume};
     plan = plan_forward(T->verdict, policy_in);
     local = plan.local;
@@ -334,7 +334,7 @@ int64_t ForwardCall::run() {
     if (rc) return rc;
     if (a->debug && late_tag && (rc = T->checks.settle(check_slot_of(late_tag), true, SlotExaminer{mb, s}))) return rc;   // debug: report this forward's self-check word right away
     saved->num_rendered = I;
-    saved->capacity = L.capacity;
+    saved->capacity = v.L.capacity;
     if (depth) saved->flags |= DEPTH_SAVED_FLAG;
     if (shjac) saved->flags |= SHJAC_SAVED_FLAG;
     return I;
@@ -345,7 +345,7 @@ int ForwardCall::empty_scene() {
     const int W = a->image_width, H = a->image_height;
     HIP_TRY(hipMemsetAsync(out->out_color, 0, sizeof(float) * 3 * (size_t)W * H, s));
     if (out->out_invdepth) HIP_TRY(hipMemsetAsync(out->out_invdepth, 0, sizeof(float) * (size_t)W * H, s));
-    HIP_TRY(hipMemsetAsync(saved->img + L.pub.ranges, 0, 8 * (size_t)L.ntiles, s));
+    HIP_TRY(hipMemsetAsync(v.ranges(), 0, 8 * (size_t)v.L.ntiles, s));
     saved->binning = alloc_binning(user, 256);   // (kept as found: 256 bytes nobody reads, and no look at what the allocator returned)
     return 0;
 }
@@ -368,17 +368,17 @@ int ForwardCall::arrival_ring() {
 // Lay L out for `cap` instances — with the plan's depth buckets when it is segmented (compute_layout starts every layout without) — and
 // have the caller allocate the binning buffer.
 int ForwardCall::layout_and_alloc(int64_t cap) {
-    compute_layout(a->P, cap, a->image_width, a->image_height, &L, shjac);
-    L.dhist_ptr = seg_dhist;
+    compute_layout(a->P, cap, a->image_width, a->image_height, &v.L, shjac);
+    v.L.dhist_ptr = seg_dhist;
     if (plan.seg) {
-        L.dbits = plan.seg_bits;
-        L.kbits = L.tbits + plan.seg_bits;
-        L.kshift = std::min(16, 32 - L.kbits);
-        L.part_passes = plan.seg_passes;
+        v.L.dbits = plan.seg_bits;
+        v.L.kbits = v.L.tbits + plan.seg_bits;
+        v.L.kshift = std::min(16, 32 - v.L.kbits);
+        v.L.part_passes = plan.seg_passes;
     }
-    saved->binning = alloc_binning(user, depth ? L.d_bytes : L.pub.binning_bytes);
+    saved->binning = v.binning = alloc_binning(user, depth ? v.L.d_bytes : v.L.pub.binning_bytes);
     if (saved->binning) return DAS3R_OK;
-    set_error("scratch allocation failed (binning %zu B)", L.pub.binning_bytes);   // (kept as found: binning_bytes even for a depth forward, which asked for d_bytes)
+    set_error("scratch allocation failed (binning %zu B)", v.L.pub.binning_bytes);   // (kept as found: binning_bytes even for a depth forward, which asked for d_bytes)
     return DAS3R_ERR_ALLOC;
 }
 
@@ -387,16 +387,15 @@ int ForwardCall::layout_and_alloc(int64_t cap) {
 int ForwardCall::preprocess(int binning_path, const EmitArgs *emit) {
     int rc;
     uint32_t *dhist = nullptr, *dhist_next = nullptr;
-    if (!emit && (rc = seg_dhist_for(plan.seg, s, saved->geom, L, &dhist, &dhist_next))) return rc;
-    L.dhist_ptr = seg_dhist = dhist;   // (the emission reads it; a layout made later takes it from seg_dhist)
+    if (!emit && (rc = seg_dhist_for(plan.seg, s, v, &dhist, &dhist_next))) return rc;
+    v.L.dhist_ptr = seg_dhist = dhist;   // (the emission reads it; a layout made later takes it from seg_dhist)
     const SideStream *side = nullptr;   // null = the fused kernel
     if (split_colour_rule(in->shs != nullptr, a->sh_degree, a->P, binning_path, no_backward, switches().split_colour)) {
         if ((rc = side_stream_for(s, &join.side))) return rc;
         side = &join.side;
     }
-    char *ctrl = plan.speculate ? saved->binning + L.b_ghist : nullptr;
-    if ((rc = launch_preprocess(a, in, out->radii, saved->geom, saved->img, ctrl, ctrl ? L.b_ctrl_bytes : 0, L, plan.speculate ? nullptr : arrive, mb->dev,
-                                count_tag, s, emit, dhist, dhist_next, aa, side))) return rc;
+    if ((rc = launch_preprocess(a, in, out->radii, v, plan.speculate ? v.b_ctrl() : WordRange{nullptr, 0}, plan.speculate ? nullptr : arrive, mb->dev, count_tag, s,
+                                emit, dhist, dhist_next, aa, side))) return rc;
     join.forked = side != nullptr;
     return DAS3R_OK;
 }
@@ -405,7 +404,7 @@ int ForwardCall::colour_launch() {
     if (!join.forked) return DAS3R_OK;
     join.forked = false;
     join.pending = true;   // (from the first call that touches the side stream on)
-    return launch_sh_colour(a, in, saved->geom, L, &join.side);
+    return launch_sh_colour(a, in, v, &join.side);
 }
 int ForwardCall::colour_join() {
     const int r = colour_launch();
@@ -436,24 +435,24 @@ int ForwardCall::claim_check_slot(uint32_t **host_late) {
 int ForwardCall::look_at_lists(LocalBin *lb) {
     int r;
     const int P = a->P;
-    const int64_t cap = L.capacity;
-    const bool by_shape = cap > 0 && quad_lanes(switches(), L.ntiles, L.capacity, /*local_lists=*/false);
+    const int64_t cap = v.L.capacity;
+    const bool by_shape = cap > 0 && quad_lanes(switches(), v.L.ntiles, v.L.capacity, /*local_lists=*/false);
     if (plan.decide_fine && by_shape) {   // (shapes the one-workgroup-per-tile kernel would take: few tiles, long lists)
         const uint32_t tag = next_tag(mb);
-        if ((r = launch_list_skew(saved->img, saved->binning, saved->geom, L, (uint32_t)cap, (uint32_t)(P - 1), mb->dev + MB_LONGEST, tag, a->debug != 0, s))) return r;
+        if ((r = launch_list_skew(v, (uint32_t)cap, (uint32_t)(P - 1), mb->dev + MB_LONGEST, tag, a->debug != 0, s))) return r;
         if ((r = mailbox_wait(mb, MB_SKEW_TAG, tag, s))) return r;
         const uint32_t longest = mb->host[MB_LONGEST], crowd16 = mb->host[MB_CROWD16];
-        const int64_t mean = skew_mean(T->verdict, cap, L.ntiles);
-        const bool now_fine = learn_skew(T->verdict, longest, crowd16, cap, L.ntiles);
+        const int64_t mean = skew_mean(T->verdict, cap, v.L.ntiles);
+        const bool now_fine = learn_skew(T->verdict, longest, crowd16, cap, v.L.ntiles);
         if (switches().verbose) fprintf(stderr, "[das3r] tile lists: longest %lld, mean %lld, %.1f of 64 consecutive entries in one quadrant -> %s kernels\n", (long long)longest,
                                         (long long)mean, crowd16 / 16.0, now_fine ? "2x2-region" : "block");
     }
     const bool fine = prefers_regions(T->verdict);
     lb->prefer_regions = fine;
     lb->tile_order = nullptr;
-    if (tile_lpt_wanted(switches(), L.ntiles, L.capacity, /*local_lists=*/false, fine)) {   // longest lists first (kernel_choice.h says why)
-        if ((r = launch_tile_lpt(saved->img, L, (uint32_t)cap, a->debug != 0, s))) return r;
-        lb->tile_order = (const uint32_t *)(saved->img + L.i_order);
+    if (tile_lpt_wanted(switches(), v.L.ntiles, v.L.capacity, /*local_lists=*/false, fine)) {   // longest lists first (kernel_choice.h says why)
+        if ((r = launch_tile_lpt(v, (uint32_t)cap, a->debug != 0, s))) return r;
+        lb->tile_order = v.i_order();
     }
     if (fine && by_shape) saved->flags |= backward_hint(T->verdict, (uint32_t)BUCKET);   // (for the backward pass of this forward: kernel_choice.h choose_backward)
     return DAS3R_OK;
@@ -464,36 +463,35 @@ int ForwardCall::look_at_lists(LocalBin *lb) {
 int ForwardCall::bin_and_render(bool local_order, bool ctrl_zeroed, uint32_t *count_out, uint32_t count_out_tag, uint32_t *emit_slot) {
     int r;
     const int P = a->P;
-    const int64_t cap = L.capacity;
+    const int64_t cap = v.L.capacity;
     const bool fused_scan = use_onesweep();   // scan + emission in one kernel; the classic path scans, then emits
-    const bool seg = L.dbits > 0;             // segmented path: index-order emission with depth buckets, lists sorted by segment_sort_kernel
+    const bool seg = v.L.dbits > 0;           // segmented path: index-order emission with depth buckets, lists sorted by segment_sort_kernel
     const bool finish = seg && plan.bucket_local;   // ... or, with the same emission and passes, finished by the compositing kernel (path_policy.h bucket_local_rule)
     // (plan.cells, with finish: launch_binning's partition step is launch_cell_sort — partition by reserved ranges + finish per cell, which
     //  writes the tile ranges and hands over the self-check word — instead of the stable passes and tile_ranges_kernel: cells_rule)
     if (!emit_slot) {
         if (fused_scan) {
-            if ((r = launch_binning_scan_emit(P, cap, out->radii, saved->geom, saved->binning, L, ctrl_zeroed, count_out, count_out_tag, a->debug != 0,
+            if ((r = launch_binning_scan_emit(P, cap, out->radii, v, ctrl_zeroed, count_out, count_out_tag, a->debug != 0,
                                               s, local_order || seg))) return r;
-        } else if ((r = launch_scan(P, saved->geom, L, nullptr, 0, a->debug != 0, s))) return r;
+        } else if ((r = launch_scan(P, v, nullptr, 0, a->debug != 0, s))) return r;
     }
     uint32_t *host_late = nullptr;
     if (cap > 0 && (r = claim_check_slot(&host_late))) return r;
     uint32_t *dead_keys = nullptr;
-    if ((r = launch_binning(P, cap, a->image_width, a->image_height, out->radii, saved->geom, saved->binning, saved->img, L, fused_scan, host_late, late_tag,
+    if ((r = launch_binning(P, cap, a->image_width, a->image_height, out->radii, v, fused_scan, host_late, late_tag,
                             a->debug != 0, s, &dead_keys, emit_slot, mb->dev + MB_TOO_LONG, plan.gen, finish, finish && plan.cells))) return r;
     if ((r = colour_launch())) return r;   // the split preprocess: the colour kernel, beside the binning kernels enqueued above
-    LocalBin lb = {(float4 *)(saved->binning + L.b_ckpt), nullptr, nullptr, nullptr, nullptr, plan.gen, (uint32_t)(P - 1), (uint32_t)cap};
+    LocalBin lb = {v.b_ckpt(), nullptr, nullptr, nullptr, nullptr, plan.gen, (uint32_t)(P - 1), (uint32_t)cap};
     if ((r = look_at_lists(&lb))) return r;
     if ((local_order || finish) && cap > 0) {
-        lb.point_list = (uint32_t *)(saved->binning + L.pub.point_list);
-        lb.slot_list = (uint32_t *)(saved->binning + L.b_slot);
+        lb.point_list = v.point_list();
+        lb.slot_list = v.b_slot();
         lb.keys = dead_keys;   // (finish: the bucketed keys of the last pass, read before a list too long for LDS takes its own stretch as scratch)
         lb.host_flag = mb->dev + MB_TOO_LONG;
-        if (finish) lb.dbits = L.dbits, lb.fbits = L.kshift;
+        if (finish) lb.dbits = v.L.dbits, lb.fbits = v.L.kshift;
     }
     if ((r = colour_join())) return r;   // (a redo finds the colours there already: nothing is pending the second time)
-    return launch_render_forward(a, in->colors_precomp, out->out_color, saved->geom, saved->binning, saved->img, L, lb, s, out->out_invdepth,
-                                 depth ? (float4 *)(saved->binning + L.d_ckpt) : nullptr);
+    return launch_render_forward(a, in->colors_precomp, out->out_color, v, lb, s, out->out_invdepth, depth ? v.d_ckpt() : nullptr);
 }
 
 // Wait for this forward's count (usually there already).  prefiltered: the caller's promise that no point fails the near-plane cull
@@ -521,8 +519,7 @@ int ForwardCall::flow_fused_emit(int64_t *I) {
     }
     uint32_t *emit_slot = (uint32_t *)(T->emit_ring + (size_t)(count_tag % ARRIVE_SLOTS) * EMIT_SLOT_BYTES);
     const EmitArgs em = {(unsigned long long *)(emit_slot + EMIT_SLOT_WORDS), count_tag, emit_slot + 64, emit_slot,
-                         (uint32_t *)(saved->binning + L.b_keyA), (uint32_t *)(saved->binning + L.b_gid_of),
-                         (uint32_t *)(saved->geom + L.g_off_by_gid), (uint32_t)L.capacity, L.tbits, (uint32_t *)(saved->geom + L.g_count), mb->dev};
+                         v.b_keyA(), v.b_gid_of(), v.g_off_by_gid(), (uint32_t)v.L.capacity, v.L.tbits, v.g_count(), mb->dev};
     T->emit.taken_by(count_tag);   // (kept as found: marked dirty before launch_preprocess, clean again only after bin_and_render returned 0)
     if ((rc = preprocess(2, &em))) return rc;
     if ((rc = bin_and_render(true, true, nullptr, 0, emit_slot))) return rc;
@@ -542,15 +539,15 @@ int ForwardCall::after_speculation(int64_t *I) {
     const int rc = read_count(I);
     if (rc) return rc;
     (void)learn_count(T->verdict, *I, policy_in, plan);   // (kept as found: the result is ignored — enqueued already, this forward keeps its path)
-    return *I > L.capacity ? redo_exact(*I) : DAS3R_OK;
+    return *I > v.L.capacity ? redo_exact(*I) : DAS3R_OK;
 }
 
 // The scene outgrew the speculative capacity: binning and compositing again, laid out for exactly I.
 int ForwardCall::redo_exact(int64_t I) {
     const int rc = layout_and_alloc(I);
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(saved->geom + L.g_ghist, 0, L.g_ctrl_bytes, s));          // tickets and look-back words of the scan
-    HIP_TRY(hipMemsetAsync(saved->img + L.pub.ranges, 0, 8 * (size_t)L.ntiles, s));
+    HIP_TRY(hipMemsetAsync(v.g_ctrl().begin, 0, v.g_ctrl().bytes, s));   // tickets and look-back words of the scan
+    HIP_TRY(hipMemsetAsync(v.ranges(), 0, 8 * (size_t)v.L.ntiles, s));
     return bin_and_render(local, false);
 }
 
@@ -561,16 +558,16 @@ int ForwardCall::flow_exact(int64_t *I) {
     const int P = a->P;
     const bool seg = plan.seg, debug = a->debug != 0;
     if ((rc = preprocess((local || seg) ? 1 : 0, nullptr))) return rc;
-    if (!local && !seg && (rc = launch_depth_sort(P, saved->geom, L, 0, nullptr, 0, debug, s))) return rc;
+    if (!local && !seg && (rc = launch_depth_sort(P, v, 0, WordRange{nullptr, 0}, debug, s))) return rc;
     if ((rc = read_count(I))) return rc;
     if (learn_count(T->verdict, *I, policy_in, plan)) {   // the scene grew: global sort after all
         local = false;
         if ((rc = colour_join())) return rc;   // (the sort scatters the depth keys the colour kernel reads)
         // (kept as found: part 0 runs here whenever the count says so, after the join — also when it ran above, also on the segmented path)
-        if ((rc = launch_depth_sort(P, saved->geom, L, 0, nullptr, 0, debug, s))) return rc;
+        if ((rc = launch_depth_sort(P, v, 0, WordRange{nullptr, 0}, debug, s))) return rc;
     }
     if ((rc = layout_and_alloc(*I))) return rc;
-    if (!local && !seg && (rc = launch_depth_sort(P, saved->geom, L, 1, saved->binning + L.b_ghist, L.b_ctrl_bytes, debug, s))) return rc;
+    if (!local && !seg && (rc = launch_depth_sort(P, v, 1, v.b_ctrl(), debug, s))) return rc;
     return bin_and_render(local, !local && !seg);
 }
 

@@ -48,10 +48,10 @@ __global__ void __launch_bounds__(256) count_live_pairs_kernel(const uint2 *__re
     }
 }
 
-int launch_count_live_pairs(const das3r_raster_args *a, char *geom, char *binning, char *img, const Layout &L, unsigned long long *out, hipStream_t s) {
-    DAS3R_LAUNCH(count_live_pairs_kernel, dim3(L.ntiles), dim3(256), 0, s, (const uint2 *)(img + L.pub.ranges),
-                 (const uint32_t *)(binning + L.pub.point_list), a->image_width, a->image_height, L.tiles_x, L.ntiles, (const float4 *)(geom + L.pub.xy),
-                 (const float4 *)(geom + L.pub.conic_opacity), (const uint32_t *)(img + L.pub.n_contrib), (uint32_t)(a->P - 1), (uint32_t)L.capacity, out);
+int launch_count_live_pairs(const das3r_raster_args *a, const Buffers &v, unsigned long long *out, hipStream_t s) {
+    DAS3R_LAUNCH(count_live_pairs_kernel, dim3(v.L.ntiles), dim3(256), 0, s, v.ranges(),
+                 v.point_list(), a->image_width, a->image_height, v.L.tiles_x, v.L.ntiles, v.xy(),
+                 v.conic_opacity(), v.n_contrib(), (uint32_t)(a->P - 1), (uint32_t)v.L.capacity, out);
     KERNEL_CHECK(s, a->debug, "count_live_pairs");
     return DAS3R_OK;
 }

@@ -491,8 +491,8 @@ __global__ void __launch_bounds__(256) mark_visible_kernel(int P, const float *_
     present[idx] = xform43(p, V).z > NEAR_PLANE ? 1 : 0;
 }
 
-int launch_preprocess(const das3r_raster_args *a, const das3r_raster_in *in, int32_t *radii, char *geom, char *img, char *binning_ctrl,
-                      size_t binning_ctrl_bytes, const Layout &L, unsigned long long *arrive, uint32_t *host_out, uint32_t tag,
+int launch_preprocess(const das3r_raster_args *a, const das3r_raster_in *in, int32_t *radii, const Buffers &v, WordRange binning_ctrl,
+                      unsigned long long *arrive, uint32_t *host_out, uint32_t tag,
                       hipStream_t s, const EmitArgs *emit, uint32_t *dhist, uint32_t *dhist_next, bool aa, const SideStream *side) {
     const int P = a->P;
     if (P == 0) return DAS3R_OK;
@@ -502,14 +502,14 @@ int launch_preprocess(const das3r_raster_args *a, const das3r_raster_in *in, int
     while ((grid.x >> __builtin_popcount(dhist_mask)) > 512u) dhist_mask = (dhist_mask << 1) | 1u;
     const bool has_sh = in->shs != nullptr, has_cov = in->cov3D_precomp != nullptr;
     const PreXform pre = pre_xform(in);
-    float *const shjac = has_sh && L.g_shjac ? (float *)(geom + L.g_shjac) : nullptr;   // (the layout has the planes when the forward wants them)
+    float *const shjac = has_sh ? v.shjac() : nullptr;   // (the layout has the planes when the forward wants them)
 #define ARGS                                                                                                              \
     P, a->sh_degree, a->M, in->means3D, in->scales, a->scale_modifier, in->rotations, in->opacities, in->shs,             \
         in->cov3D_precomp, in->colors_precomp, a->viewmatrix, a->projmatrix, a->campos, a->image_width, a->image_height,  \
-        a->tanfovx, a->tanfovy, L.tiles_x, L.tiles_y, radii, (uint32_t *)(geom + L.g_keyA), (float4 *)(geom + L.pub.xy),  \
-        (float4 *)(geom + L.pub.conic_opacity), (float4 *)(geom + L.pub.rgbd), (uint8_t *)(geom + L.pub.clamped),         \
-        (uint32_t *)(geom + L.pub.tiles_touched), (uint32_t *)(geom + L.g_rect), (use_tight_rect() ? 1 : 0) | (a->prefiltered ? 2 : 0), (uint32_t *)(geom + L.g_ghist), (uint32_t)(L.g_ctrl_bytes / 4),                 \
-        (uint32_t *)(img + L.pub.ranges), (uint32_t)(2 * L.ntiles), (uint32_t *)binning_ctrl, (uint32_t)(binning_ctrl_bytes / 4), arrive, host_out, tag, em, dhist, dhist_mask, dhist_next, pre, shjac
+        a->tanfovx, a->tanfovy, v.L.tiles_x, v.L.tiles_y, radii, v.g_keyA(), v.xy(), v.conic_opacity(), v.rgbd(),         \
+        v.clamped(), v.tiles_touched(), v.g_rect(), (use_tight_rect() ? 1 : 0) | (a->prefiltered ? 2 : 0),                \
+        v.g_ctrl().begin, v.g_ctrl().words(), (uint32_t *)v.ranges(), (uint32_t)(2 * v.L.ntiles), binning_ctrl.begin,     \
+        binning_ctrl.words(), arrive, host_out, tag, em, dhist, dhist_mask, dhist_next, pre, shjac
     const bool stage = sh_rows_staged(has_sh, a->M, a->sh_degree, ((uintptr_t)in->shs & 15) == 0, switches().no_sh_stage);
     if (side != nullptr) {   // the split form (forward.hip split_colour_rule: SH given, no fused emission, a binning path that keeps the depth keys)
         if (!has_sh || emit != nullptr) { set_error("launch_preprocess: the split form needs SH rows and a binning chain of its own"); return DAS3R_ERR_INVALID_ARG; }
@@ -548,17 +548,16 @@ int launch_preprocess(const das3r_raster_args *a, const das3r_raster_in *in, int
 
 // The colour half of the split form, on the side stream: waits for the fork event launch_preprocess recorded behind the geometry kernel,
 // leaves the join event behind the colour kernel.
-int launch_sh_colour(const das3r_raster_args *a, const das3r_raster_in *in, char *geom, const Layout &L, const SideStream *side) {
+int launch_sh_colour(const das3r_raster_args *a, const das3r_raster_in *in, const Buffers &v, const SideStream *side) {
     const int P = a->P;
     const PreXform pre = pre_xform(in);
-    float *const shjac = L.g_shjac ? (float *)(geom + L.g_shjac) : nullptr;
+    float *const shjac = v.shjac();
     const bool stage = sh_rows_staged(true, a->M, a->sh_degree, ((uintptr_t)in->shs & 15) == 0, switches().no_sh_stage);   // (the split form: SH rows given)
     HIP_TRY(hipStreamWaitEvent(side->stream, side->fork, 0));
     const int slices = div_up(P, COLOUR_T);
     const dim3 cgrid(slices < side->colour_blocks ? slices : side->colour_blocks), cblock(COLOUR_T);
 #define COLOUR_ARGS                                                                                                                 \
-    P, a->sh_degree, a->M, in->means3D, pre, in->shs, a->campos, (const uint32_t *)(geom + L.g_keyA), (float4 *)(geom + L.pub.rgbd), \
-        (uint8_t *)(geom + L.pub.clamped), shjac
+    P, a->sh_degree, a->M, in->means3D, pre, in->shs, a->campos, v.g_keyA(), v.rgbd(), v.clamped(), shjac
     if (stage) DAS3R_LAUNCH((sh_colour_kernel<true>), cgrid, cblock, 0, side->stream, COLOUR_ARGS);
     else DAS3R_LAUNCH((sh_colour_kernel<false>), cgrid, cblock, 0, side->stream, COLOUR_ARGS);
 #undef COLOUR_ARGS

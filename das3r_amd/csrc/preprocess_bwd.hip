@@ -718,12 +718,12 @@ static float *chain_scratch(hipStream_t s, size_t blocks, uint32_t **arrived) {
     return hit->buf;
 }
 
-int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in *in, char *geom, char *binning, const Layout &L,
+int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in *in, const Buffers &v,
                                const das3r_raster_grads *g, const float *partial, hipStream_t s, bool quad_rows, const float *dz, bool aa) {
     const int P = a->P;
     if (P == 0) return DAS3R_OK;
     dim3 grid(div_up(P, 256)), block(256);
-    const uint8_t *exists = quad_rows_exist(partial, L, quad_rows);
+    const uint8_t *exists = quad_rows_exist(partial, v.L, quad_rows);
     // which form: preprocess_choice.h (host arithmetic on these plain values; the CPU tests walk every row of it)
     PreprocessBackwardInputs ci;
     ci.has_sh = in->shs != nullptr;
@@ -733,7 +733,7 @@ int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in
     ci.shs_aligned16 = ((uintptr_t)in->shs & 15) == 0;
     ci.dL_dshs_aligned16 = ((uintptr_t)g->dL_dshs & 15) == 0;
     ci.no_sh_stage = switches().no_sh_stage;
-    ci.jac_saved = L.g_shjac != 0;   // (api.hip shjac_saved: flags bit 2, degree >= 2)
+    ci.jac_saved = v.shjac() != nullptr;   // (api.hip saved_buffers: flags bit 2, degree >= 2)
     ci.chained = g->chain != nullptr;
     ci.quad_rows = quad_rows;
     ci.depth = dz != nullptr;
@@ -747,10 +747,10 @@ int launch_preprocess_backward(const das3r_raster_args *a, const das3r_raster_in
     const PreXform pre = pre_xform(in);
 #define ARGS                                                                                                                 \
     P, a->sh_degree, a->M, in->means3D, in->scales, a->scale_modifier, in->rotations, in->shs, in->cov3D_precomp,            \
-        a->viewmatrix, a->projmatrix, a->campos, a->image_width, a->image_height, a->tanfovx, a->tanfovy,                    \
-        (const uint32_t *)(geom + L.pub.tiles_touched), (const uint8_t *)(geom + L.pub.clamped), partial, exists,        \
-        (const uint32_t *)(geom + L.g_off_by_gid), g->dL_dmeans2D, g->dL_dopacities, g->dL_dcolors_precomp, g->dL_dmeans3D,  \
-        g->dL_dscales, g->dL_drotations, g->dL_dshs, g->dL_dcov3D, pre, ch, dz, ci.has_sh && ci.jac_saved ? (const float *)(geom + L.g_shjac) : nullptr, in->opacities PB_TRACE_ARG
+        a->viewmatrix, a->projmatrix, a->campos, a->image_width, a->image_height, a->tanfovx, a->tanfovy, v.tiles_touched(), \
+        v.clamped(), partial, exists, v.g_off_by_gid(), g->dL_dmeans2D, g->dL_dopacities, g->dL_dcolors_precomp,             \
+        g->dL_dmeans3D, g->dL_dscales, g->dL_drotations, g->dL_dshs, g->dL_dcov3D, pre, ch, dz,                              \
+        ci.has_sh ? v.shjac() : nullptr, in->opacities PB_TRACE_ARG
     // ---- the chained form (das3r_raster_grads.chain): unstaged SH rows, raw parameters ----
     ChainArgs ch;
     memset(&ch, 0, sizeof(ch));
@@ -848,16 +848,16 @@ __global__ void __launch_bounds__(256) depth_fold_kernel(int P, const uint32_t *
     const float z = rgbd[(size_t)i * SPLAT_REC].w;
     dz[i] = n > 0u ? -s / (z * z) : 0.f;
 }
-int launch_depth_pass_inputs(int P, int npix, const char *geom, const Layout &L, char *binning, const float *dL_dinvdepth, hipStream_t s, bool debug) {
+int launch_depth_pass_inputs(int P, int npix, const Buffers &v, const float *dL_dinvdepth, hipStream_t s, bool debug) {
     const int n = std::max(std::max(P, npix), 4);
-    DAS3R_LAUNCH(depth_pass_inputs_kernel, dim3(div_up(n, 256)), dim3(256), 0, s, P, npix, (const float4 *)(geom + L.pub.xy), (float4 *)(binning + L.d_recs),
-                 dL_dinvdepth, (float *)(binning + L.d_dpix), (float *)(binning + L.d_bg));
+    DAS3R_LAUNCH(depth_pass_inputs_kernel, dim3(div_up(n, 256)), dim3(256), 0, s, P, npix, v.xy(), v.d_recs(),
+                 dL_dinvdepth, v.d_dpix(), v.d_bg());
     KERNEL_CHECK(s, debug, "depth_pass_inputs");
     return DAS3R_OK;
 }
-int launch_depth_fold(int P, const char *geom, const Layout &L, float *partial, const float *partial_depth, float *dz, hipStream_t s, bool debug) {
-    DAS3R_LAUNCH(depth_fold_kernel, dim3(div_up(P, 256)), dim3(256), 0, s, P, (const uint32_t *)(geom + L.pub.tiles_touched),
-                 (const uint32_t *)(geom + L.g_off_by_gid), (const float4 *)(geom + L.pub.rgbd), partial, partial_depth, dz);
+int launch_depth_fold(int P, const Buffers &v, float *partial, const float *partial_depth, float *dz, hipStream_t s, bool debug) {
+    DAS3R_LAUNCH(depth_fold_kernel, dim3(div_up(P, 256)), dim3(256), 0, s, P, v.tiles_touched(),
+                 v.g_off_by_gid(), v.rgbd(), partial, partial_depth, dz);
     KERNEL_CHECK(s, debug, "depth_fold");
     return DAS3R_OK;
 }

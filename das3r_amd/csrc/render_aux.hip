@@ -235,11 +235,10 @@ __global__ void __launch_bounds__(256) aux_gather_kernel(int P, int C, const uin
 // its buffer was sized): the forward with four workgroups per tile, the adjoint bucket-parallel
 static bool aux_long_lists(const Layout &L, int64_t num_rendered) { return L.ntiles <= 1024 && num_rendered >= (int64_t)1024 * L.ntiles; }
 
-int launch_render_aux_forward(int P, int W, int H, int C, const float *feat, float *out, const char *geom, const char *binning, const char *img,
-                              const Layout &L, int64_t num_rendered, bool debug, hipStream_t s) {
-    const int blocks = xcd_grid(L);
-    const ListArgs lists = list_args(geom, binning, img, L, W, H, P);
-    if (aux_long_lists(L, num_rendered)) {
+int launch_render_aux_forward(int P, int W, int H, int C, const float *feat, float *out, const Buffers &v, int64_t num_rendered, bool debug, hipStream_t s) {
+    const int blocks = xcd_grid(v.L);
+    const ListArgs lists = list_args(v, W, H, P);
+    if (aux_long_lists(v.L, num_rendered)) {
         AUX_DISPATCH(C, DAS3R_LAUNCH((render_aux_forward_kernel<CC, true>), dim3(4 * blocks), dim3(TILE_PIX), 0, s, lists, feat, out, blocks));
     } else {
         AUX_DISPATCH(C, DAS3R_LAUNCH((render_aux_forward_kernel<CC, false>), dim3(blocks), dim3(TILE_PIX), 0, s, lists, feat, out, blocks));
@@ -248,23 +247,22 @@ int launch_render_aux_forward(int P, int W, int H, int C, const float *feat, flo
     return DAS3R_OK;
 }
 
-int launch_render_aux_adjoint(int P, int W, int H, int C, const float *dL_dout, float *dL_dfeat, int accumulate, float *partial, const char *geom,
-                              const char *binning, const char *img, const Layout &L, int64_t num_rendered, bool debug, hipStream_t s) {
+int launch_render_aux_adjoint(int P, int W, int H, int C, const float *dL_dout, float *dL_dfeat, int accumulate, float *partial, const Buffers &v, int64_t num_rendered, bool debug, hipStream_t s) {
     // slices = buckets of an average list, as the bucket-parallel backward sizes its grid (render_bwd.hip); a longer list's buckets are taken in turn
-    const int slices = aux_long_lists(L, num_rendered) ? (int)std::min<int64_t>(32, std::max<int64_t>(1, num_rendered / ((int64_t)BUCKET * std::max(L.ntiles, 1)))) : 1;
-    AUX_DISPATCH(C, DAS3R_LAUNCH((render_aux_adjoint_kernel<CC>), dim3(xcd_grid(L), slices), dim3(TILE_PIX), 0, s, list_args(geom, binning, img, L, W, H, P),
-                                 dL_dout, partial, (const float4 *)(binning + L.b_ckpt)));
+    const int slices = aux_long_lists(v.L, num_rendered) ? (int)std::min<int64_t>(32, std::max<int64_t>(1, num_rendered / ((int64_t)BUCKET * std::max(v.L.ntiles, 1)))) : 1;
+    AUX_DISPATCH(C, DAS3R_LAUNCH((render_aux_adjoint_kernel<CC>), dim3(xcd_grid(v.L), slices), dim3(TILE_PIX), 0, s, list_args(v, W, H, P),
+                                 dL_dout, partial, v.b_ckpt()));
     KERNEL_CHECK(s, debug, "render_aux_adjoint");
-    DAS3R_LAUNCH(aux_gather_kernel, dim3(div_up((int64_t)P * C, 256)), dim3(256), 0, s, P, C, (const uint32_t *)(geom + L.pub.tiles_touched),
-                 (const uint32_t *)(geom + L.g_off_by_gid), partial, dL_dfeat, accumulate, (uint32_t)L.capacity);
+    DAS3R_LAUNCH(aux_gather_kernel, dim3(div_up((int64_t)P * C, 256)), dim3(256), 0, s, P, C, v.tiles_touched(),
+                 v.g_off_by_gid(), partial, dL_dfeat, accumulate, (uint32_t)v.L.capacity);
     KERNEL_CHECK(s, debug, "aux_gather");
     return DAS3R_OK;
 }
 
 // the gather alone, for rows another kernel left (render_aux_bwd.hip: the geometry backward writes them on its own walk)
-int launch_aux_gather(int P, int C, const float *partial, float *dL_dfeat, const char *geom, const Layout &L, bool debug, hipStream_t s) {
-    DAS3R_LAUNCH(aux_gather_kernel, dim3(div_up((int64_t)P * C, 256)), dim3(256), 0, s, P, C, (const uint32_t *)(geom + L.pub.tiles_touched),
-                 (const uint32_t *)(geom + L.g_off_by_gid), partial, dL_dfeat, 0, (uint32_t)L.capacity);
+int launch_aux_gather(int P, int C, const float *partial, float *dL_dfeat, const Buffers &v, bool debug, hipStream_t s) {
+    DAS3R_LAUNCH(aux_gather_kernel, dim3(div_up((int64_t)P * C, 256)), dim3(256), 0, s, P, C, v.tiles_touched(),
+                 v.g_off_by_gid(), partial, dL_dfeat, 0, (uint32_t)v.L.capacity);
     KERNEL_CHECK(s, debug, "aux_gather");
     return DAS3R_OK;
 }

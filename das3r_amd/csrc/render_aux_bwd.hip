@@ -86,7 +86,7 @@ __global__ void __launch_bounds__(256) render_aux_backward_kernel(const ListArgs
 
 // (FEAT instantiations only where there are feature rows to write: C > 0 and partial_f given)
 #define AUXB_LAUNCH(N, FEAT) \
-    DAS3R_LAUNCH((render_aux_backward_kernel<N, FEAT>), dim3(xcd_grid(L)), dim3(TILE_PIX), 0, s, lists, feat, dL_dout, dL_dalpha, partial, partial_f)
+    DAS3R_LAUNCH((render_aux_backward_kernel<N, FEAT>), dim3(xcd_grid(v.L)), dim3(TILE_PIX), 0, s, lists, feat, dL_dout, dL_dalpha, partial, partial_f)
 #define AUXB_CASE(N)                                  \
     case N:                                           \
         if (N > 0 && partial_f) AUXB_LAUNCH(N, (N > 0)); \
@@ -95,8 +95,8 @@ __global__ void __launch_bounds__(256) render_aux_backward_kernel(const ListArgs
 
 // partial: [capacity, 9] rows for launch_preprocess_backward; partial_f: [capacity, C] rows for aux_gather_kernel, or null (no dL_dfeatures)
 int launch_render_aux_backward(int P, int W, int H, int C, const float *feat, const float *dL_dout, const float *dL_dalpha, float *partial,
-                               float *partial_f, const char *geom, const char *binning, const char *img, const Layout &L, bool debug, hipStream_t s) {
-    const ListArgs lists = list_args(geom, binning, img, L, W, H, P);
+                               float *partial_f, const Buffers &v, bool debug, hipStream_t s) {
+    const ListArgs lists = list_args(v, W, H, P);
     switch (C) {
         AUXB_CASE(0)
         AUXB_CASE(1)

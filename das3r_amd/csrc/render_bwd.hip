@@ -162,40 +162,38 @@ __global__ void __launch_bounds__(256) render_backward_kernel(
     }
 }
 
-int launch_render_backward(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
+int launch_render_backward(const das3r_raster_args *a, const float *dL_dpix, const Buffers &v,
                            float *partial, hipStream_t s, bool *quad_rows, int64_t num_rendered, uint32_t fwd_flags) {
     *quad_rows = false;
     // which decomposition, how many entries per round and how many workgroups per tile: kernel_choice.h
     const Switches &sw = switches();
-    const BwdChoice c = choose_backward(sw, num_rendered, L.ntiles, fwd_flags);
+    const BwdChoice c = choose_backward(sw, num_rendered, v.L.ntiles, fwd_flags);
     switch (c.kernel) {
 #ifdef DAS3R_EXPERIMENTS
         case BWD_STREAM:
             *quad_rows = true;
-            return launch_render_backward_stream(a, dL_dpix, geom, binning, img, L, partial, s);
-        case BWD_MFMA: return launch_render_backward_mfma(a, dL_dpix, geom, binning, img, L, partial, s);
+            return launch_render_backward_stream(a, dL_dpix, v, partial, s);
+        case BWD_MFMA: return launch_render_backward_mfma(a, dL_dpix, v, partial, s);
 #else
         case BWD_STREAM:
         case BWD_MFMA:
             set_error("DAS3R_RENDER_BWD=%s: this library was built without the superseded kernels (make EXPERIMENTS=1)", bwd_kernel_name(c.kernel));
             return DAS3R_ERR_INVALID_ARG;
 #endif
-        case BWD_BLK: return launch_render_backward_blk(a, dL_dpix, geom, binning, img, L, partial, c, s);
-        case BWD_REGIONS: return launch_render_backward_regions(a, dL_dpix, geom, binning, img, L, partial, c, s);
-        case BWD_SCAN: return launch_render_backward_scan(a, dL_dpix, geom, binning, img, L, partial, c, s);
+        case BWD_BLK: return launch_render_backward_blk(a, dL_dpix, v, partial, c, s);
+        case BWD_REGIONS: return launch_render_backward_regions(a, dL_dpix, v, partial, c, s);
+        case BWD_SCAN: return launch_render_backward_scan(a, dL_dpix, v, partial, c, s);
         default: break;   // BWD_DPP: below
     }
     const bool use_dpp = !sw.bwd_reduce_shfl;   // "shfl" selects the ds_bpermute reference reduction (diagnostics)
     const int ablate = sw.ablate;               // perf experiments only: bit0 = no partial stores, bit2 = no cross-lane reduction
 #define ARGS                                                                                                                 \
-    (const uint2 *)(img + L.pub.ranges), (const uint32_t *)(binning + L.pub.point_list), a->image_width, a->image_height,    \
-        L.tiles_x, pack_tiles(L), (const float4 *)(geom + L.pub.xy), (const float4 *)(geom + L.pub.conic_opacity),                \
-        (const float4 *)(geom + L.pub.rgbd), a->bg, (const float *)(img + L.pub.final_T),                                    \
-        (const uint32_t *)(img + L.pub.n_contrib), dL_dpix, (const uint32_t *)(binning + L.b_slot), partial, ablate, \
-        (uint32_t)(a->P - 1), (uint32_t)L.capacity, pair_counters()
+    v.ranges(), v.point_list(), a->image_width, a->image_height, v.L.tiles_x, pack_tiles(v.L), v.xy(), v.conic_opacity(),    \
+        v.rgbd(), a->bg, v.final_T(), v.n_contrib(), dL_dpix, v.b_slot(), partial, ablate, (uint32_t)(a->P - 1),             \
+        (uint32_t)v.L.capacity, pair_counters()
     const int pad_lds = sw.bwd_pad_lds;   // occupancy experiments
-    if (use_dpp) DAS3R_LAUNCH((render_backward_kernel<true>), dim3(xcd_grid(L)), dim3(TILE_PIX), pad_lds, s, ARGS);
-    else DAS3R_LAUNCH((render_backward_kernel<false>), dim3(xcd_grid(L)), dim3(TILE_PIX), 0, s, ARGS);
+    if (use_dpp) DAS3R_LAUNCH((render_backward_kernel<true>), dim3(xcd_grid(v.L)), dim3(TILE_PIX), pad_lds, s, ARGS);
+    else DAS3R_LAUNCH((render_backward_kernel<false>), dim3(xcd_grid(v.L)), dim3(TILE_PIX), 0, s, ARGS);
 #undef ARGS
     KERNEL_CHECK(s, a->debug, "render_backward");
     return DAS3R_OK;

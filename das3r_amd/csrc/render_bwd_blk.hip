@@ -346,32 +346,30 @@ __global__ void __launch_bounds__(256, OCC) render_backward_blk_kernel(
     }
 }
 
-int launch_render_backward_blk(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
+int launch_render_backward_blk(const das3r_raster_args *a, const float *dL_dpix, const Buffers &v,
                                float *partial, const BwdChoice &c, hipStream_t s) {
     const int mb = c.mb, slices = c.slices;
 #define ARGS                                                                                                              \
-    (const uint2 *)(img + L.pub.ranges), (const uint32_t *)(binning + L.pub.point_list), a->image_width, a->image_height, \
-        L.tiles_x, pack_tiles(L), (const float4 *)(geom + L.pub.xy), (const float4 *)(geom + L.pub.conic_opacity),             \
-        (const float4 *)(geom + L.pub.rgbd), a->bg, (const float *)(img + L.pub.final_T),                                 \
-        (const uint32_t *)(img + L.pub.n_contrib), dL_dpix, (const uint32_t *)(binning + L.b_slot), partial,              \
-        (uint32_t)(a->P - 1), (uint32_t)L.capacity, (const float4 *)(binning + L.b_ckpt), PAIRS_ARG
+    v.ranges(), v.point_list(), a->image_width, a->image_height, v.L.tiles_x, pack_tiles(v.L), v.xy(), v.conic_opacity(), \
+        v.rgbd(), a->bg, v.final_T(), v.n_contrib(), dL_dpix, v.b_slot(), partial, (uint32_t)(a->P - 1),                  \
+        (uint32_t)v.L.capacity, v.b_ckpt(), PAIRS_ARG
 #define GO(MBV, PIX, OCC)                                                                                                                             \
     do {                                                                                                                                              \
-        if (slices > 1) DAS3R_LAUNCH((render_backward_blk_kernel<MBV, PIX, 0, OCC, true>), dim3(xcd_grid(L), slices), dim3(TILE_PIX), 0, s, ARGS);   \
-        else DAS3R_LAUNCH((render_backward_blk_kernel<MBV, PIX, 0, OCC, false>), dim3(xcd_grid(L), 1), dim3(TILE_PIX), 0, s, ARGS);                   \
+        if (slices > 1) DAS3R_LAUNCH((render_backward_blk_kernel<MBV, PIX, 0, OCC, true>), dim3(xcd_grid(v.L), slices), dim3(TILE_PIX), 0, s, ARGS);  \
+        else DAS3R_LAUNCH((render_backward_blk_kernel<MBV, PIX, 0, OCC, false>), dim3(xcd_grid(v.L), 1), dim3(TILE_PIX), 0, s, ARGS);                 \
     } while (0)
     // DAS3R_RENDER_BWD=blk<entries per round>[p<PIX>][o<workgroups per CU>]: blk128 (registers), blk128p1 (constants in LDS), blk160p1o4 ...
     // (what an unforced launch gets: kernel_choice.h choose_backward)
     const int pix = c.pix, occ = c.occ;
 #define BY_PIX(MBV, OCC) do { if (pix == 2) GO(MBV, 2, OCC); else if (pix == 1) GO(MBV, 1, OCC); else GO(MBV, 0, OCC); } while (0)
     if (switches().mutate == 1) {   // the mutated kernel (a test aid: include/das3r_raster.h das3r_debug_mutate), in the two shipped default forms
-        if (slices > 1) DAS3R_LAUNCH((render_backward_blk_kernel<192, 0, 32, 4, true>), dim3(xcd_grid(L), slices), dim3(TILE_PIX), 0, s, ARGS);
-        else DAS3R_LAUNCH((render_backward_blk_kernel<128, 1, 32, 5, false>), dim3(xcd_grid(L), 1), dim3(TILE_PIX), 0, s, ARGS);
+        if (slices > 1) DAS3R_LAUNCH((render_backward_blk_kernel<192, 0, 32, 4, true>), dim3(xcd_grid(v.L), slices), dim3(TILE_PIX), 0, s, ARGS);
+        else DAS3R_LAUNCH((render_backward_blk_kernel<128, 1, 32, 5, false>), dim3(xcd_grid(v.L), 1), dim3(TILE_PIX), 0, s, ARGS);
     } else
 #ifdef DAS3R_EXPERIMENTS
     if (mb == 128 && pix == 1 && switches().ablate_set) {
         const int abl = switches().ablate;
-#define GA(A) DAS3R_LAUNCH((render_backward_blk_kernel<128, 1, A>), dim3(xcd_grid(L), slices > 1 ? slices : 1), dim3(TILE_PIX), 0, s, ARGS)
+#define GA(A) DAS3R_LAUNCH((render_backward_blk_kernel<128, 1, A>), dim3(xcd_grid(v.L), slices > 1 ? slices : 1), dim3(TILE_PIX), 0, s, ARGS)
         if (abl == 1) GA(1); else if (abl == 2) GA(2); else if (abl == 4) GA(4); else if (abl == 8) GA(8); else if (abl == 16) GA(16); else if (abl == 3) GA(3); else if (abl == 7) GA(7); else GA(0);
 #undef GA
     } else

@@ -250,14 +250,13 @@ __global__ void __launch_bounds__(256) render_backward_mfma_kernel(
     }
 }
 
-int launch_render_backward_mfma(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
-                                float *partial, hipStream_t s) {
-    DAS3R_LAUNCH(render_backward_mfma_kernel, dim3(xcd_grid(L)), dim3(TILE_PIX), 0, s, (const uint2 *)(img + L.pub.ranges),
-                 (const uint32_t *)(binning + L.pub.point_list), a->image_width, a->image_height, L.tiles_x, pack_tiles(L),
-                 (const float4 *)(geom + L.pub.xy), (const float4 *)(geom + L.pub.conic_opacity),
-                 (const float4 *)(geom + L.pub.rgbd), a->bg, (const float *)(img + L.pub.final_T),
-                 (const uint32_t *)(img + L.pub.n_contrib), dL_dpix, (const uint32_t *)(binning + L.b_slot), partial,
-                 (uint32_t)(a->P - 1), (uint32_t)L.capacity);
+int launch_render_backward_mfma(const das3r_raster_args *a, const float *dL_dpix, const Buffers &v, float *partial, hipStream_t s) {
+    DAS3R_LAUNCH(render_backward_mfma_kernel, dim3(xcd_grid(v.L)), dim3(TILE_PIX), 0, s, v.ranges(),
+                 v.point_list(), a->image_width, a->image_height, v.L.tiles_x, pack_tiles(v.L),
+                 v.xy(), v.conic_opacity(),
+                 v.rgbd(), a->bg, v.final_T(),
+                 v.n_contrib(), dL_dpix, v.b_slot(), partial,
+                 (uint32_t)(a->P - 1), (uint32_t)v.L.capacity);
     KERNEL_CHECK(s, a->debug, "render_backward_mfma");
     return DAS3R_OK;
 }

@@ -383,28 +383,26 @@ __global__ void __launch_bounds__(256, OCC) render_backward_regions_kernel(
     }
 }
 
-int launch_render_backward_regions(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
+int launch_render_backward_regions(const das3r_raster_args *a, const float *dL_dpix, const Buffers &v,
                                    float *partial, const BwdChoice &c, hipStream_t s) {
     const int mb = c.mb, slices = c.slices;
 #define ARGS                                                                                                              \
-    (const uint2 *)(img + L.pub.ranges), (const uint32_t *)(binning + L.pub.point_list), a->image_width, a->image_height, \
-        L.tiles_x, pack_tiles(L), (const float4 *)(geom + L.pub.xy), (const float4 *)(geom + L.pub.conic_opacity),             \
-        (const float4 *)(geom + L.pub.rgbd), a->bg, (const float *)(img + L.pub.final_T),                                 \
-        (const uint32_t *)(img + L.pub.n_contrib), dL_dpix, (const uint32_t *)(binning + L.b_slot), partial,              \
-        (uint32_t)(a->P - 1), (uint32_t)L.capacity, (const float4 *)(binning + L.b_ckpt), pair_counters()
-#define GO(MBV, OCC) DAS3R_LAUNCH((render_backward_regions_kernel<MBV, OCC>), dim3(xcd_grid(L), std::max(slices, 1)), dim3(TILE_PIX), 0, s, ARGS)
-#define GQ(MBV, OCC, G) DAS3R_LAUNCH((render_backward_regions_kernel<MBV, OCC, false, 0, G>), dim3(xcd_grid(L), std::max(slices, 1)), dim3(TILE_PIX), 0, s, ARGS)
+    v.ranges(), v.point_list(), a->image_width, a->image_height, v.L.tiles_x, pack_tiles(v.L), v.xy(), v.conic_opacity(), \
+        v.rgbd(), a->bg, v.final_T(), v.n_contrib(), dL_dpix, v.b_slot(), partial, (uint32_t)(a->P - 1),                  \
+        (uint32_t)v.L.capacity, v.b_ckpt(), pair_counters()
+#define GO(MBV, OCC) DAS3R_LAUNCH((render_backward_regions_kernel<MBV, OCC>), dim3(xcd_grid(v.L), std::max(slices, 1)), dim3(TILE_PIX), 0, s, ARGS)
+#define GQ(MBV, OCC, G) DAS3R_LAUNCH((render_backward_regions_kernel<MBV, OCC, false, 0, G>), dim3(xcd_grid(v.L), std::max(slices, 1)), dim3(TILE_PIX), 0, s, ARGS)
     // DAS3R_RENDER_BWD=fine<entries per round>: LDS per workgroup = 212 MB + 4.2 KB -> 96: 24.5 KB, 128: 31.3 KB (5 per CU), 160: 38.1 (4), 192: 44.9 (3),
     // 256: 58.4 (2)
 #ifdef DAS3R_EXPERIMENTS
     if (mb == 128 && switches().ablate_set) {
         const int abl = switches().ablate;
-#define GA(A) DAS3R_LAUNCH((render_backward_regions_kernel<128, 5, false, A>), dim3(xcd_grid(L), std::max(slices, 1)), dim3(TILE_PIX), 0, s, ARGS)
+#define GA(A) DAS3R_LAUNCH((render_backward_regions_kernel<128, 5, false, A>), dim3(xcd_grid(v.L), std::max(slices, 1)), dim3(TILE_PIX), 0, s, ARGS)
         if (abl == 1) GA(1); else if (abl == 2) GA(2); else if (abl == 5) GA(5); else if (abl == 8) GA(8); else if (abl == 13) GA(13); else GA(0);
 #undef GA
     } else
 #endif
-    if (switches().mutate == 1) DAS3R_LAUNCH((render_backward_regions_kernel<128, 5, true>), dim3(xcd_grid(L), std::max(slices, 1)), dim3(TILE_PIX), 0, s, ARGS);
+    if (switches().mutate == 1) DAS3R_LAUNCH((render_backward_regions_kernel<128, 5, true>), dim3(xcd_grid(v.L), std::max(slices, 1)), dim3(TILE_PIX), 0, s, ARGS);
     else if (c.strips == STRIPS_QUADRANT) GQ(128, 5, 0);      // fine128q: strips, a wave per quadrant (A-B runs)
     else if (c.strips == STRIPS_INTERLEAVED) GQ(128, 5, 1);   // fine128s: strips, interleaved
     else if (mb == 64) GO(64, 5);

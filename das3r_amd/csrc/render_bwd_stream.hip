@@ -322,26 +322,23 @@ size_t stream_scratch_bytes(int64_t capacity) {
     return align_up(c * 4 * 12 * sizeof(float)) + align_up(c * 4);
 }
 
-int launch_render_backward_stream(const das3r_raster_args *a, const float *dL_dpix, char *geom, char *binning, char *img, const Layout &L,
-                                  float *scratch, hipStream_t s) {
-    const size_t c = L.capacity > 0 ? (size_t)L.capacity : 1;
+int launch_render_backward_stream(const das3r_raster_args *a, const float *dL_dpix, const Buffers &v, float *scratch, hipStream_t s) {
+    const size_t c = v.L.capacity > 0 ? (size_t)v.L.capacity : 1;
     uint8_t *exists = reinterpret_cast<uint8_t *>(scratch) + align_up(c * 4 * 12 * sizeof(float));
     HIP_TRY(hipMemsetAsync(exists, 0, c * 4, s));
 #define ARGS                                                                                                              \
-    (const uint2 *)(img + L.pub.ranges), (const uint32_t *)(binning + L.pub.point_list), a->image_width, a->image_height, \
-        L.tiles_x, pack_tiles(L), (const float4 *)(geom + L.pub.xy), (const float4 *)(geom + L.pub.conic_opacity),             \
-        (const float4 *)(geom + L.pub.rgbd), a->bg, (const float *)(img + L.pub.final_T),                                 \
-        (const uint32_t *)(img + L.pub.n_contrib), dL_dpix, (const uint32_t *)(binning + L.b_slot), scratch, exists,     \
-        (uint32_t)(a->P - 1), (uint32_t)L.capacity
-#define GO(AB) DAS3R_LAUNCH((render_backward_stream_kernel<AB>), dim3(xcd_grid(L)), dim3(TILE_PIX), 0, s, ARGS)
+    v.ranges(), v.point_list(), a->image_width, a->image_height, v.L.tiles_x, pack_tiles(v.L), v.xy(), v.conic_opacity(), \
+        v.rgbd(), a->bg, v.final_T(), v.n_contrib(), dL_dpix, v.b_slot(), scratch, exists, (uint32_t)(a->P - 1),          \
+        (uint32_t)v.L.capacity
+#define GO(AB) DAS3R_LAUNCH((render_backward_stream_kernel<AB>), dim3(xcd_grid(v.L)), dim3(TILE_PIX), 0, s, ARGS)
     const int abl = switches().ablate_set ? switches().ablate : 0;
     if (abl == 1) GO(1);
     else if (abl == 2) GO(2);
     else if (abl == 3) GO(3);
     else if (abl == 4) GO(4);
     else if (abl == 8) GO(8);
-    else if (abl == 103) DAS3R_LAUNCH((render_backward_stream_kernel<0, 3>), dim3(xcd_grid(L)), dim3(TILE_PIX), 0, s, ARGS);
-    else if (abl == 105) DAS3R_LAUNCH((render_backward_stream_kernel<0, 5>), dim3(xcd_grid(L)), dim3(TILE_PIX), 0, s, ARGS);
+    else if (abl == 103) DAS3R_LAUNCH((render_backward_stream_kernel<0, 3>), dim3(xcd_grid(v.L)), dim3(TILE_PIX), 0, s, ARGS);
+    else if (abl == 105) DAS3R_LAUNCH((render_backward_stream_kernel<0, 5>), dim3(xcd_grid(v.L)), dim3(TILE_PIX), 0, s, ARGS);
     else GO(0);
 #undef GO
 #undef ARGS

@@ -141,25 +141,23 @@ __global__ void __launch_bounds__(256) distortion_fold_kernel(int P, const uint3
     dz[i] = n > 0u ? -s / (z * z) : 0.f;
 }
 
-int launch_render_distortion_forward(int P, int W, int H, float *out, float *totals, const char *geom, const char *binning, const char *img,
-                                     const Layout &L, bool debug, hipStream_t s) {
-    DAS3R_LAUNCH(render_distortion_forward_kernel, dim3(xcd_grid(L)), dim3(TILE_PIX), 0, s, list_args(geom, binning, img, L, W, H, P), out,
+int launch_render_distortion_forward(int P, int W, int H, float *out, float *totals, const Buffers &v, bool debug, hipStream_t s) {
+    DAS3R_LAUNCH(render_distortion_forward_kernel, dim3(xcd_grid(v.L)), dim3(TILE_PIX), 0, s, list_args(v, W, H, P), out,
                  totals);
     KERNEL_CHECK(s, debug, "render_distortion_forward");
     return DAS3R_OK;
 }
 
-int launch_render_distortion_backward(int P, int W, int H, const float *dL_ddist, const float *totals, float *partial, const char *geom,
-                                      const char *binning, const char *img, const Layout &L, bool debug, hipStream_t s) {
-    DAS3R_LAUNCH(render_distortion_backward_kernel, dim3(xcd_grid(L)), dim3(TILE_PIX), 0, s, list_args(geom, binning, img, L, W, H, P),
+int launch_render_distortion_backward(int P, int W, int H, const float *dL_ddist, const float *totals, float *partial, const Buffers &v, bool debug, hipStream_t s) {
+    DAS3R_LAUNCH(render_distortion_backward_kernel, dim3(xcd_grid(v.L)), dim3(TILE_PIX), 0, s, list_args(v, W, H, P),
                  dL_ddist, totals, partial);
     KERNEL_CHECK(s, debug, "render_distortion_backward");
     return DAS3R_OK;
 }
 
-int launch_distortion_fold(int P, const char *geom, const Layout &L, float *partial, float *dz, bool debug, hipStream_t s) {
-    DAS3R_LAUNCH(distortion_fold_kernel, dim3(div_up(P, 256)), dim3(256), 0, s, P, (const uint32_t *)(geom + L.pub.tiles_touched),
-                 (const uint32_t *)(geom + L.g_off_by_gid), (const float4 *)(geom + L.pub.rgbd), partial, dz, (uint32_t)L.capacity);
+int launch_distortion_fold(int P, const Buffers &v, float *partial, float *dz, bool debug, hipStream_t s) {
+    DAS3R_LAUNCH(distortion_fold_kernel, dim3(div_up(P, 256)), dim3(256), 0, s, P, v.tiles_touched(),
+                 v.g_off_by_gid(), v.rgbd(), partial, dz, (uint32_t)v.L.capacity);
     KERNEL_CHECK(s, debug, "distortion_fold");
     return DAS3R_OK;
 }

@@ -111,31 +111,29 @@ __global__ void __launch_bounds__(256) render_forward_kernel(const uint2 *__rest
     }
 }
 
-int launch_render_forward(const das3r_raster_args *a, const float *colors_precomp, float *out_color, char *geom, char *binning,
-                          char *img, const Layout &L, const LocalBin &lb, hipStream_t s, float *out_invdepth, float4 *dckpt) {
+int launch_render_forward(const das3r_raster_args *a, const float *colors_precomp, float *out_color, const Buffers &v,
+                          const LocalBin &lb, hipStream_t s, float *out_invdepth, float4 *dckpt) {
     (void)colors_precomp;  // precomputed colours were copied into rgbd by the preprocess kernel
     // which kernel: kernel_choice.h (lb.point_list != null: lists in local depth order, which only this kernel and the rows kernel sort)
-    const FwdKernel k = choose_forward(switches(), L.ntiles, L.capacity, lb.point_list != nullptr, lb.prefer_regions);
+    const FwdKernel k = choose_forward(switches(), v.L.ntiles, v.L.capacity, lb.point_list != nullptr, lb.prefer_regions);
     if (out_invdepth && !fwd_has_invdepth_form(k)) {   // (das3r_raster_forward refuses this combination before it launches anything; kept as a guard)
         set_error("DAS3R_RENDER=%s has no inverse-depth form (das3r_raster_out.out_invdepth)", fwd_kernel_name(k));
         return DAS3R_ERR_INVALID_ARG;
     }
     switch (k) {
-        case FWD_SLICES: return launch_render_forward_slices(a, out_color, geom, binning, img, L, lb, s);
+        case FWD_SLICES: return launch_render_forward_slices(a, out_color, v, lb, s);
         // one workgroup per tile (lanes), or four (regions) where the tile lists are skewed: the host has been told by the forwards before this one
-        case FWD_REGIONS: return launch_render_forward_regions(a, out_color, geom, binning, img, L, lb, s, out_invdepth, dckpt);
-        case FWD_LANES: return launch_render_forward_lanes(a, out_color, geom, binning, img, L, lb, s, out_invdepth, dckpt);
-        case FWD_ROWS: return launch_render_forward_rows(a, out_color, geom, binning, img, L, lb, s, out_invdepth, dckpt);
+        case FWD_REGIONS: return launch_render_forward_regions(a, out_color, v, lb, s, out_invdepth, dckpt);
+        case FWD_LANES: return launch_render_forward_lanes(a, out_color, v, lb, s, out_invdepth, dckpt);
+        case FWD_ROWS: return launch_render_forward_rows(a, out_color, v, lb, s, out_invdepth, dckpt);
         default: break;   // FWD_QUAD: below
     }
     const int pad_lds = switches().fwd_pad_lds;   // occupancy experiments
 #define ARGS                                                                                                                    \
-    (const uint2 *)(img + L.pub.ranges), (const uint32_t *)(binning + L.pub.point_list), a->image_width, a->image_height, L.tiles_x, \
-        pack_tiles(L), (const float4 *)(geom + L.pub.xy), (const float4 *)(geom + L.pub.conic_opacity),                              \
-        (const float4 *)(geom + L.pub.rgbd), a->bg, (float *)(img + L.pub.final_T), (uint32_t *)(img + L.pub.n_contrib), out_color, \
-        lb, pair_counters(), out_invdepth, dckpt
-    if (out_invdepth) DAS3R_LAUNCH((render_forward_kernel<true>), dim3(xcd_grid(L)), dim3(TILE_PIX), pad_lds, s, ARGS);
-    else DAS3R_LAUNCH((render_forward_kernel<false>), dim3(xcd_grid(L)), dim3(TILE_PIX), pad_lds, s, ARGS);
+    v.ranges(), v.point_list(), a->image_width, a->image_height, v.L.tiles_x, pack_tiles(v.L), v.xy(), v.conic_opacity(),       \
+        v.rgbd(), a->bg, v.final_T(), v.n_contrib(), out_color, lb, pair_counters(), out_invdepth, dckpt
+    if (out_invdepth) DAS3R_LAUNCH((render_forward_kernel<true>), dim3(xcd_grid(v.L)), dim3(TILE_PIX), pad_lds, s, ARGS);
+    else DAS3R_LAUNCH((render_forward_kernel<false>), dim3(xcd_grid(v.L)), dim3(TILE_PIX), pad_lds, s, ARGS);
 #undef ARGS
     KERNEL_CHECK(s, a->debug, "render_forward");
     return DAS3R_OK;

@@ -32,11 +32,11 @@ struct ListArgs {
     uint32_t last_g, cap;
 };
 
-static inline ListArgs list_args(const char *geom, const char *binning, const char *img, const Layout &L, int W, int H, int P) {
-    return {(const uint2 *)(img + L.pub.ranges), (const uint32_t *)(binning + L.pub.point_list), W, H, L.tiles_x, pack_tiles(L),
-            (const float4 *)(geom + L.pub.xy), (const float4 *)(geom + L.pub.conic_opacity), (const float4 *)(geom + L.pub.rgbd),
-            (const uint32_t *)(img + L.pub.n_contrib), (const float *)(img + L.pub.final_T), (const uint32_t *)(binning + L.b_slot),
-            (uint32_t)(P - 1), (uint32_t)L.capacity};
+static inline ListArgs list_args(const Buffers &v, int W, int H, int P) {
+    return {v.ranges(), v.point_list(), W, H, v.L.tiles_x, pack_tiles(v.L),
+            v.xy(), v.conic_opacity(), v.rgbd(),
+            v.n_contrib(), v.final_T(), v.b_slot(),
+            (uint32_t)(P - 1), (uint32_t)v.L.capacity};
 }
 
 // lanes of a wave: the largest value among them (uniform)

@@ -126,21 +126,20 @@ __global__ void __launch_bounds__(256) render_median_adjoint_kernel(const ListAr
 __global__ void aux_gather_kernel(int P, int C, const uint32_t *__restrict__ tiles_touched, const uint32_t *__restrict__ off_by_gid,
                                   const float *__restrict__ partial, float *__restrict__ dL_dfeat, int accumulate, uint32_t cap);
 
-int launch_render_median_forward(int P, int W, int H, float tau, float *depth, int32_t *hit_gaussian, uint32_t *hit_position, const char *geom,
-                                 const char *binning, const char *img, const Layout &L, bool debug, hipStream_t s) {
-    DAS3R_LAUNCH(render_median_forward_kernel, dim3(xcd_grid(L)), dim3(TILE_PIX), 0, s, list_args(geom, binning, img, L, W, H, P), tau, depth,
+int launch_render_median_forward(int P, int W, int H, float tau, float *depth, int32_t *hit_gaussian, uint32_t *hit_position, const Buffers &v, bool debug, hipStream_t s) {
+    DAS3R_LAUNCH(render_median_forward_kernel, dim3(xcd_grid(v.L)), dim3(TILE_PIX), 0, s, list_args(v, W, H, P), tau, depth,
                  hit_gaussian, hit_position);
     KERNEL_CHECK(s, debug, "render_median_forward");
     return DAS3R_OK;
 }
 
 int launch_render_median_adjoint(int P, int W, int H, const float *dL_ddepth, const uint32_t *hit_position, float *dL_dz, int accumulate,
-                                 float *rows, const char *geom, const char *binning, const char *img, const Layout &L, bool debug, hipStream_t s) {
-    DAS3R_LAUNCH(render_median_adjoint_kernel, dim3(xcd_grid(L)), dim3(TILE_PIX), 0, s, list_args(geom, binning, img, L, W, H, P), dL_ddepth,
+                                 float *rows, const Buffers &v, bool debug, hipStream_t s) {
+    DAS3R_LAUNCH(render_median_adjoint_kernel, dim3(xcd_grid(v.L)), dim3(TILE_PIX), 0, s, list_args(v, W, H, P), dL_ddepth,
                  hit_position, rows);
     KERNEL_CHECK(s, debug, "render_median_adjoint");
-    DAS3R_LAUNCH(aux_gather_kernel, dim3(div_up((int64_t)P, 256)), dim3(256), 0, s, P, 1, (const uint32_t *)(geom + L.pub.tiles_touched),
-                 (const uint32_t *)(geom + L.g_off_by_gid), rows, dL_dz, accumulate, (uint32_t)L.capacity);
+    DAS3R_LAUNCH(aux_gather_kernel, dim3(div_up((int64_t)P, 256)), dim3(256), 0, s, P, 1, v.tiles_touched(),
+                 v.g_off_by_gid(), rows, dL_dz, accumulate, (uint32_t)v.L.capacity);
     KERNEL_CHECK(s, debug, "aux_gather");
     return DAS3R_OK;
 }

@@ -370,27 +370,25 @@ __global__ void __launch_bounds__(1024) tile_lpt_kernel(const uint2 *__restrict_
     order[rank] = (uint32_t)t;
 }
 
-int launch_tile_lpt(char *img, const Layout &L, uint32_t cap, bool debug, hipStream_t s) {
-    DAS3R_LAUNCH(tile_lpt_kernel, dim3(1), dim3(1024), 0, s, (const uint2 *)(img + L.pub.ranges), L.ntiles, cap, (uint32_t *)(img + L.i_order));
+int launch_tile_lpt(const Buffers &v, uint32_t cap, bool debug, hipStream_t s) {
+    DAS3R_LAUNCH(tile_lpt_kernel, dim3(1), dim3(1024), 0, s, v.ranges(), v.L.ntiles, cap, v.i_order());
     KERNEL_CHECK(s, debug, "tile_lpt");
     return DAS3R_OK;
 }
 
-int launch_list_skew(const char *img, const char *binning, const char *geom, const Layout &L, uint32_t cap, uint32_t last_g, uint32_t *mailbox_words, uint32_t tag,
-                     bool debug, hipStream_t s) {
-    DAS3R_LAUNCH(list_skew_kernel, dim3(1), dim3(256), 0, s, (const uint2 *)(img + L.pub.ranges), L.ntiles, L.tiles_x, cap, (const uint32_t *)(binning + L.pub.point_list),
-                 (const float4 *)(geom + L.pub.xy), last_g, mailbox_words, tag);
+int launch_list_skew(const Buffers &v, uint32_t cap, uint32_t last_g, uint32_t *mailbox_words, uint32_t tag, bool debug, hipStream_t s) {
+    DAS3R_LAUNCH(list_skew_kernel, dim3(1), dim3(256), 0, s, v.ranges(), v.L.ntiles, v.L.tiles_x, cap, v.point_list(),
+                 v.xy(), last_g, mailbox_words, tag);
     KERNEL_CHECK(s, debug, "list_skew");
     return DAS3R_OK;
 }
 
-int launch_render_forward_regions(const das3r_raster_args *a, float *out_color, char *geom, char *binning, char *img, const Layout &L, const LocalBin &lb,
+int launch_render_forward_regions(const das3r_raster_args *a, float *out_color, const Buffers &v, const LocalBin &lb,
                                   hipStream_t s, float *out_invdepth, float4 *dckpt) {
 #define ARGS                                                                                                                                   \
-    (const uint2 *)(img + L.pub.ranges), (const uint32_t *)(binning + L.pub.point_list), a->image_width, a->image_height, L.tiles_x, pack_tiles(L), \
-        (const float4 *)(geom + L.pub.xy), (const float4 *)(geom + L.pub.conic_opacity), (const float4 *)(geom + L.pub.rgbd), a->bg,                \
-        (float *)(img + L.pub.final_T), (uint32_t *)(img + L.pub.n_contrib), out_color, lb, pair_counters(), out_invdepth, dckpt
-    const dim3 grid(lb.tile_order ? 32 * div_up(L.ntiles, 8) : 4 * xcd_grid(L));
+    v.ranges(), v.point_list(), a->image_width, a->image_height, v.L.tiles_x, pack_tiles(v.L), v.xy(), v.conic_opacity(), v.rgbd(), a->bg,     \
+        v.final_T(), v.n_contrib(), out_color, lb, pair_counters(), out_invdepth, dckpt
+    const dim3 grid(lb.tile_order ? 32 * div_up(v.L.ntiles, 8) : 4 * xcd_grid(v.L));
     if (out_invdepth) DAS3R_LAUNCH((render_forward_regions_kernel<true>), grid, dim3(RG_THREADS), 0, s, ARGS);
     else DAS3R_LAUNCH((render_forward_regions_kernel<false>), grid, dim3(RG_THREADS), 0, s, ARGS);
 #undef ARGS

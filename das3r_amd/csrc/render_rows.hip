@@ -286,20 +286,18 @@ __global__ void __launch_bounds__(256) FWD_WAVES(PREFETCH || DEPTH) render_forwa
 }
 
 // (taken once a tile's list is long: kernel_choice.h row_private)
-int launch_render_forward_rows(const das3r_raster_args *a, float *out_color, char *geom, char *binning, char *img, const Layout &L,
+int launch_render_forward_rows(const das3r_raster_args *a, float *out_color, const Buffers &v,
                                const LocalBin &lb, hipStream_t s, float *out_invdepth, float4 *dckpt) {
 #define ARGS                                                                                                              \
-    (const uint2 *)(img + L.pub.ranges), (const uint32_t *)(binning + L.pub.point_list), a->image_width, a->image_height,  \
-        L.tiles_x, pack_tiles(L), (const float4 *)(geom + L.pub.xy), (const float4 *)(geom + L.pub.conic_opacity),         \
-        (const float4 *)(geom + L.pub.rgbd), a->bg, (float *)(img + L.pub.final_T), (uint32_t *)(img + L.pub.n_contrib),   \
-        out_color, lb, PAIRS_ARG, out_invdepth, dckpt
+    v.ranges(), v.point_list(), a->image_width, a->image_height, v.L.tiles_x, pack_tiles(v.L), v.xy(), v.conic_opacity(), \
+        v.rgbd(), a->bg, v.final_T(), v.n_contrib(), out_color, lb, PAIRS_ARG, out_invdepth, dckpt
     // globally sorted lists and fewer tiles than the chip has workgroup slots (4 per CU and more): see PREFETCH
-    const bool prefetch = lb.point_list == nullptr && L.ntiles <= 1024 && !switches().fwd_no_prefetch;
+    const bool prefetch = lb.point_list == nullptr && v.L.ntiles <= 1024 && !switches().fwd_no_prefetch;
     if (out_invdepth) {
-        if (prefetch) DAS3R_LAUNCH((render_forward_rows_kernel<true, true>), dim3(xcd_grid(L)), dim3(TILE_PIX), 0, s, ARGS);
-        else DAS3R_LAUNCH((render_forward_rows_kernel<false, true>), dim3(xcd_grid(L)), dim3(TILE_PIX), 0, s, ARGS);
-    } else if (prefetch) DAS3R_LAUNCH((render_forward_rows_kernel<true>), dim3(xcd_grid(L)), dim3(TILE_PIX), 0, s, ARGS);
-    else DAS3R_LAUNCH((render_forward_rows_kernel<false>), dim3(xcd_grid(L)), dim3(TILE_PIX), 0, s, ARGS);
+        if (prefetch) DAS3R_LAUNCH((render_forward_rows_kernel<true, true>), dim3(xcd_grid(v.L)), dim3(TILE_PIX), 0, s, ARGS);
+        else DAS3R_LAUNCH((render_forward_rows_kernel<false, true>), dim3(xcd_grid(v.L)), dim3(TILE_PIX), 0, s, ARGS);
+    } else if (prefetch) DAS3R_LAUNCH((render_forward_rows_kernel<true>), dim3(xcd_grid(v.L)), dim3(TILE_PIX), 0, s, ARGS);
+    else DAS3R_LAUNCH((render_forward_rows_kernel<false>), dim3(xcd_grid(v.L)), dim3(TILE_PIX), 0, s, ARGS);
 #undef ARGS
     KERNEL_CHECK(s, a->debug, "render_forward_rows");
     return DAS3R_OK;

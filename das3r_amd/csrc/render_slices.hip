@@ -278,13 +278,11 @@ __global__ void __launch_bounds__(LN_THREADS) __attribute__((amdgpu_waves_per_eu
     }
 }
 
-int launch_render_forward_slices(const das3r_raster_args *a, float *out_color, char *geom, char *binning, char *img, const Layout &L, const LocalBin &lb,
-                                 hipStream_t s) {
+int launch_render_forward_slices(const das3r_raster_args *a, float *out_color, const Buffers &v, const LocalBin &lb, hipStream_t s) {
 #define ARGS                                                                                                                                   \
-    (const uint2 *)(img + L.pub.ranges), (const uint32_t *)(binning + L.pub.point_list), a->image_width, a->image_height, L.tiles_x, pack_tiles(L), \
-        (const float4 *)(geom + L.pub.xy), (const float4 *)(geom + L.pub.conic_opacity), (const float4 *)(geom + L.pub.rgbd), a->bg,                \
-        (float *)(img + L.pub.final_T), (uint32_t *)(img + L.pub.n_contrib), out_color, lb, pair_counters()
-    DAS3R_LAUNCH(render_forward_slices_kernel, dim3(xcd_grid(L)), dim3(LN_THREADS), 0, s, ARGS);
+    v.ranges(), v.point_list(), a->image_width, a->image_height, v.L.tiles_x, pack_tiles(v.L), v.xy(), v.conic_opacity(), v.rgbd(), a->bg,     \
+        v.final_T(), v.n_contrib(), out_color, lb, pair_counters()
+    DAS3R_LAUNCH(render_forward_slices_kernel, dim3(xcd_grid(v.L)), dim3(LN_THREADS), 0, s, ARGS);
 #undef ARGS
     KERNEL_CHECK(s, a->debug, "render_forward_slices");
     return DAS3R_OK;

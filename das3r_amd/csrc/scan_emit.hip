@@ -250,21 +250,17 @@ size_t scan_status_bytes(int P) {
 #else
 #define SCAN_TRACE_ARG
 #endif
-#define RECT32 ((L.tiles_x <= 255 && L.tiles_y <= 255) ? (const uint32_t *)(geom + L.g_rect) : (const uint32_t *)nullptr)
 #define SCAN_COMMON                                                                                                           \
-    P, order, (const uint32_t *)(geom + L.pub.tiles_touched),                          \
-        (uint32_t *)(geom + L.pub.offsets), (uint32_t *)(geom + L.g_off_by_gid), (uint32_t *)(geom + L.g_count),             \
-        (u64 *)(geom + L.g_scan_status), (u64 *)(geom + L.g_scan_status) + nblocks,                                    \
-        grid_is_resident(nblocks) ? (uint32_t *)nullptr : (uint32_t *)(geom + L.g_ticket) + 16,   \
-        (uint32_t *)(geom + L.g_ticket) + 8, host_out, tag
+    P, order, v.tiles_touched(), v.offsets(), v.g_off_by_gid(), v.g_count(), v.g_scan_status(), v.g_scan_status() + nblocks,  \
+        grid_is_resident(nblocks) ? (uint32_t *)nullptr : v.scan_ticket(), v.err_word(), host_out, tag
 
-int launch_scan(int P, char *geom, const Layout &L, uint32_t *host_out, uint32_t tag, bool debug, hipStream_t s, bool index_order) {
+int launch_scan(int P, const Buffers &v, uint32_t *host_out, uint32_t tag, bool debug, hipStream_t s, bool index_order) {
     const int nblocks = scan_blocks(P);
-    const uint32_t *order = index_order ? nullptr : (const uint32_t *)(geom + L.pub.sorted_idx);
+    const uint32_t *order = index_order ? nullptr : v.sorted_idx();
 #define GO(IT)                                                                                                               \
-    DAS3R_LAUNCH((scan_emit_kernel<false, IT>), dim3(nblocks), dim3(256), 0, s, SCAN_COMMON, 0, 0,                            \
-                 (const float4 *)(geom + L.pub.xy),                                                                           \
-                 (const int32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, (uint32_t *)nullptr, 0, 0, RECT32, 0, 0,           \
+    DAS3R_LAUNCH((scan_emit_kernel<false, IT>), dim3(nblocks), dim3(256), 0, s, SCAN_COMMON, 0, 0,                           \
+                 v.xy(),                                                                                                     \
+                 (const int32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, (uint32_t *)nullptr, 0, 0, v.rect32(), 0, 0, \
                  (const uint32_t *)nullptr, (const uint32_t *)nullptr SCAN_TRACE_ARG)
     switch (scan_items(P)) { case 1: GO(1); break; case 2: GO(2); break; case 4: GO(4); break; case 8: GO(8); break; default: GO(16); }
 #undef GO
@@ -272,15 +268,15 @@ int launch_scan(int P, char *geom, const Layout &L, uint32_t *host_out, uint32_t
     return DAS3R_OK;
 }
 
-int launch_scan_emit(int P, int64_t cap, const int32_t *radii, char *geom, char *binning, const Layout &L, uint32_t *host_out, uint32_t tag,
+int launch_scan_emit(int P, int64_t cap, const int32_t *radii, const Buffers &v, uint32_t *host_out, uint32_t tag,
                      bool debug, hipStream_t s, bool index_order) {
     const int nblocks = scan_blocks(P);
-    const uint32_t *order = index_order ? nullptr : (const uint32_t *)(geom + L.pub.sorted_idx);
+    const uint32_t *order = index_order ? nullptr : v.sorted_idx();
 #define GO(IT)                                                                                                               \
-    DAS3R_LAUNCH((scan_emit_kernel<true, IT>), dim3(nblocks), dim3(256), 0, s, SCAN_COMMON, L.tiles_x, L.tiles_y,              \
-                 (const float4 *)(geom + L.pub.xy), radii, (uint32_t *)(binning + L.b_keyA), (uint32_t *)(binning + L.b_gid_of), \
-                 (uint32_t)cap, (uint32_t *)(binning + L.b_ghist), L.kbits, use_tight_rect() ? 1 : 0, RECT32, index_order ? L.dbits : 0, L.kshift, \
-                 (const uint32_t *)(geom + L.pub.depth_key), L.dhist_ptr ? L.dhist_ptr : (const uint32_t *)(geom + L.g_dhist) SCAN_TRACE_ARG)
+    DAS3R_LAUNCH((scan_emit_kernel<true, IT>), dim3(nblocks), dim3(256), 0, s, SCAN_COMMON, v.L.tiles_x, v.L.tiles_y,        \
+                 v.xy(), radii, v.b_keyA(), v.b_gid_of(),                                                                    \
+                 (uint32_t)cap, v.b_ghist(), v.L.kbits, use_tight_rect() ? 1 : 0, v.rect32(), index_order ? v.L.dbits : 0, v.L.kshift, \
+                 v.depth_key(), v.dhist() SCAN_TRACE_ARG)
     switch (scan_items(P)) { case 1: GO(1); break; case 2: GO(2); break; case 4: GO(4); break; case 8: GO(8); break; default: GO(16); }
 #undef GO
     KERNEL_CHECK(s, debug, "scan_emit");

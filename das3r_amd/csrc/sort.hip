@@ -285,14 +285,14 @@ __global__ void __launch_bounds__(256) tile_ranges_kernel(uint32_t cap, const ui
 }
 
 // ---------------------------------------------------------------- host side
-int launch_depth_sort(int P, char *geom, const Layout &L, int part, char *binning_ctrl, size_t binning_ctrl_bytes, bool debug, hipStream_t s) {
-    uint32_t *keyA = (uint32_t *)(geom + L.g_keyA), *keyB = (uint32_t *)(geom + L.g_keyB);
-    uint32_t *valA = (uint32_t *)(geom + L.g_valA), *valB = (uint32_t *)(geom + L.g_valB);
-    uint32_t *hist = (uint32_t *)(geom + L.g_hist), *totals = (uint32_t *)(geom + L.g_totals);
+int launch_depth_sort(int P, const Buffers &v, int part, WordRange binning_ctrl, bool debug, hipStream_t s) {
+    uint32_t *keyA = v.g_keyA(), *keyB = v.g_keyB();
+    uint32_t *valA = v.g_valA(), *valB = v.g_valB();
+    uint32_t *hist = v.g_hist(), *totals = v.g_totals();
     if (P == 0) return DAS3R_OK;
     // 4 passes: A -> B -> A -> B -> A ; final ranks land in valA (== pub.sorted_idx)
     int rc;
-    if (use_onesweep()) return launch_onesweep_depth_sort(P, geom, L, part, (uint32_t *)binning_ctrl, (uint32_t)(binning_ctrl_bytes / 4), debug, s);
+    if (use_onesweep()) return launch_onesweep_depth_sort(P, v, part, binning_ctrl, debug, s);
 #ifdef DAS3R_EXPERIMENTS
     if (part == 1) return DAS3R_OK;   // classic path: everything ran in part 0 (its binning does not use control words)
     if ((rc = radix_pass(keyA, nullptr, keyB, valB, P, 0, 8, hist, totals, debug, s))) return rc;
@@ -307,34 +307,34 @@ int launch_depth_sort(int P, char *geom, const Layout &L, int part, char *binnin
 
 // Hinted path, first half of the binning: zero the control words, then scan + emit in one kernel.  The caller copies the
 // count back right behind it and then calls launch_binning(..., fused_scan = true) for the partition.
-int launch_binning_scan_emit(int P, int64_t I, const int32_t *radii, char *geom, char *binning, const Layout &L, bool ctrl_zeroed,
+int launch_binning_scan_emit(int P, int64_t I, const int32_t *radii, const Buffers &v, bool ctrl_zeroed,
                              uint32_t *host_out, uint32_t tag, bool debug, hipStream_t s, bool index_order) {
     if (I == 0 || P == 0) return DAS3R_OK;
-    if (!ctrl_zeroed) HIP_TRY(hipMemsetAsync(binning + L.b_ghist, 0, L.b_ctrl_bytes, s));
-    return launch_scan_emit(P, I, radii, geom, binning, L, host_out, tag, debug, s, index_order);
+    if (!ctrl_zeroed) HIP_TRY(hipMemsetAsync(v.b_ctrl().begin, 0, v.b_ctrl().bytes, s));
+    return launch_scan_emit(P, I, radii, v, host_out, tag, debug, s, index_order);
 }
 
-// I = capacity of the binning buffer; the true instance count is read by the kernels from geom + L.g_count
-int launch_binning(int P, int64_t I, int W, int H, const int32_t *radii, char *geom, char *binning, char *img, const Layout &L,
+// I = capacity of the binning buffer; the true instance count is read by the kernels from g_count
+int launch_binning(int P, int64_t I, int W, int H, const int32_t *radii, const Buffers &v,
                    bool fused_scan, uint32_t *host_late, uint32_t tag, bool debug, hipStream_t s, uint32_t **dead_keys, uint32_t *emit_slot,
                    uint32_t *seg_host_flag, uint32_t seg_flag_value, bool local_finish, bool cells) {
-    const uint32_t *n_ptr = (const uint32_t *)(geom + L.g_count);
+    const uint32_t *n_ptr = v.g_count();
     (void)W; (void)H;
-    uint2 *ranges = (uint2 *)(img + L.pub.ranges);  // zeroed by preprocess_kernel
+    uint2 *ranges = v.ranges();  // zeroed by preprocess_kernel
     if (I == 0 || P == 0) return DAS3R_OK;
-    uint32_t *keyA = (uint32_t *)(binning + L.b_keyA), *keyB = (uint32_t *)(binning + L.b_keyB);
-    uint32_t *valA = (uint32_t *)(binning + L.b_valA), *valB = (uint32_t *)(binning + L.b_valB);
-    uint32_t *hist = (uint32_t *)(binning + L.b_hist), *totals = (uint32_t *)(binning + L.b_totals);
-    uint32_t *gid_of = (uint32_t *)(binning + L.b_gid_of), *inv = (uint32_t *)(binning + L.b_slot);
+    uint32_t *keyA = v.b_keyA(), *keyB = v.b_keyB();
+    uint32_t *valA = v.b_valA(), *valB = v.b_valB();
+    uint32_t *hist = v.b_hist(), *totals = v.b_totals();
+    uint32_t *gid_of = v.b_gid_of(), *inv = v.b_slot();
     const bool onesweep = use_onesweep();
     (void)onesweep;   // the binning control words were zeroed by the last depth pass (launch_depth_sort part 1)
 #ifdef DAS3R_EXPERIMENTS
     if (!fused_scan) {   // (hinted path: launch_binning_scan_emit has already emitted the instances)
     const int emit_blocks = div_up(P, 256) < 1024 ? div_up(P, 256) : 1024;
-    DAS3R_LAUNCH(emit_kernel, dim3(emit_blocks), dim3(256), 0, s, P, L.tiles_x, L.tiles_y,
-                 (const uint32_t *)(geom + L.pub.sorted_idx), (const uint32_t *)(geom + L.pub.tiles_touched),
-                 (const uint32_t *)(geom + L.pub.offsets), (const float4 *)(geom + L.pub.xy), radii, keyA, gid_of, (uint32_t)I,
-                 onesweep ? (uint32_t *)(binning + L.b_ghist) : (uint32_t *)nullptr, L.tbits, use_tight_rect() ? 1 : 0);
+    DAS3R_LAUNCH(emit_kernel, dim3(emit_blocks), dim3(256), 0, s, P, v.L.tiles_x, v.L.tiles_y,
+                 v.sorted_idx(), v.tiles_touched(),
+                 v.offsets(), v.xy(), radii, keyA, gid_of, (uint32_t)I,
+                 onesweep ? v.b_ghist() : (uint32_t *)nullptr, v.L.tbits, use_tight_rect() ? 1 : 0);
     KERNEL_CHECK(s, debug, "emit");
     }
 #else
@@ -342,26 +342,26 @@ int launch_binning(int P, int64_t I, int W, int H, const int32_t *radii, char *g
 #endif
     if (onesweep) {
         uint32_t *kfinal = nullptr;
-        if (cells && local_finish && L.dbits > 0 && !emit_slot) {   // the cells plan: no chain, ranges and self-check word from its finish (cell_sort.hip)
-            const int rc0 = launch_cell_sort(I, geom, binning, img, L, &kfinal, host_late, tag, seg_host_flag, seg_flag_value, debug, s);
+        if (cells && local_finish && v.L.dbits > 0 && !emit_slot) {   // the cells plan: no chain, ranges and self-check word from its finish (cell_sort.hip)
+            const int rc0 = launch_cell_sort(I, v, &kfinal, host_late, tag, seg_host_flag, seg_flag_value, debug, s);
             if (!rc0 && dead_keys) *dead_keys = kfinal;
             return rc0;
         }
-        int rc1 = launch_onesweep_partition(I, geom, binning, L, &kfinal, debug, s, emit_slot ? emit_slot + 64 : nullptr, emit_slot);
+        int rc1 = launch_onesweep_partition(I, v, &kfinal, debug, s, emit_slot ? emit_slot + 64 : nullptr, emit_slot);
         if (rc1) return rc1;
         if (dead_keys) *dead_keys = kfinal;   // the tile keys are dead once tile_ranges_kernel has run
         // (local_finish: no segment sort — the tile ranges below come from the bucketed keys, which stay in kfinal for the compositing kernel)
-        if (L.dbits > 0 && !local_finish) {   // segmented path: exact depth order inside every (tile, bucket) segment, in place (segsort.hip)
+        if (v.L.dbits > 0 && !local_finish) {   // segmented path: exact depth order inside every (tile, bucket) segment, in place (segsort.hip)
             uint32_t *other = kfinal == keyA ? keyB : keyA;   // the previous pass's keys: dead, scratch for a segment too long for LDS
             // (round 6: it also writes the tile ranges and hands over the self-check word — no tile_ranges launch behind it; the segmented path
             //  never runs with the fused emission, whose ring slot that kernel re-arms)
-            return launch_segment_sort(I, n_ptr, kfinal, L.kshift, (uint32_t *)(binning + L.pub.point_list), (uint32_t *)(binning + L.b_slot),
-                                       (const uint32_t *)(geom + L.pub.depth_key), (uint32_t)(P - 1), other, seg_host_flag, seg_flag_value, debug, s,
-                                       L.dbits, ranges, (const uint32_t *)(geom + L.g_ticket) + 8, host_late, tag, (uint32_t)switches().inject_fault);
+            return launch_segment_sort(I, n_ptr, kfinal, v.L.kshift, v.point_list(), v.b_slot(),
+                                       v.depth_key(), (uint32_t)(P - 1), other, seg_host_flag, seg_flag_value, debug, s,
+                                       v.L.dbits, ranges, v.err_word(), host_late, tag, (uint32_t)switches().inject_fault);
         }
         const int rearm = emit_slot ? EMIT_SLOT_WORDS : 0;
         DAS3R_LAUNCH(tile_ranges_kernel, dim3(div_up(std::max<int64_t>(div_up(I, 4), rearm), 256)), dim3(256), 0, s, (uint32_t)I, n_ptr, kfinal, ranges,
-                     emit_slot ? emit_slot : (uint32_t *)(geom + L.g_ticket) + 8, host_late, tag, (uint32_t)rearm, (uint32_t)switches().inject_fault, L.dbits + L.kshift);
+                     emit_slot ? emit_slot : v.err_word(), host_late, tag, (uint32_t)rearm, (uint32_t)switches().inject_fault, v.L.dbits + v.L.kshift);
         KERNEL_CHECK(s, debug, "tile_ranges");
         return DAS3R_OK;
     }
@@ -370,9 +370,9 @@ int launch_binning(int P, int64_t I, int W, int H, const int32_t *radii, char *g
     // payload = emission slot e (identity on the first pass); the last pass turns it into the splat id and records inv[e]
     uint32_t *kin = keyA, *vin = nullptr, *kout = keyB, *vout = valB;
     int shift = 0, rc;
-    for (int p = 0; p < L.tile_passes; p++) {
-        const int dw = tile_digit_width(L.tbits), bits = (L.tbits - shift) < dw ? (L.tbits - shift) : dw;
-        const bool last = p == L.tile_passes - 1;
+    for (int p = 0; p < v.L.tile_passes; p++) {
+        const int dw = tile_digit_width(v.L.tbits), bits = (v.L.tbits - shift) < dw ? (v.L.tbits - shift) : dw;
+        const bool last = p == v.L.tile_passes - 1;
         if ((rc = radix_pass(kin, vin, kout, vout, I, shift, bits, hist, totals, debug, s, last ? gid_of : nullptr, last ? inv : nullptr, n_ptr)))
             return rc;
         shift += bits;
@@ -383,7 +383,7 @@ int launch_binning(int P, int64_t I, int W, int H, const int32_t *radii, char *g
     // kin/vin now hold the partitioned (tile id, gaussian id) lists; vin == binning + pub.point_list by construction
     if (dead_keys) *dead_keys = kin;
     DAS3R_LAUNCH(tile_ranges_kernel, dim3(div_up(div_up(I, 4), 256)), dim3(256), 0, s, (uint32_t)I, n_ptr, kin, ranges,
-                 (uint32_t *)(geom + L.g_ticket) + 8, host_late, tag, 0u, (uint32_t)switches().inject_fault, 0);
+                 v.err_word(), host_late, tag, 0u, (uint32_t)switches().inject_fault, 0);
     KERNEL_CHECK(s, debug, "tile_ranges");
 #else
     (void)keyA; (void)keyB; (void)valA; (void)valB; (void)hist; (void)totals; (void)inv;

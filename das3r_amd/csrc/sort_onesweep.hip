@@ -396,19 +396,18 @@ size_t onesweep_status_bytes(int64_t n, int passes) {
 
 // Depth sort of the P splats: ctrl = [ghist 4x256 u32][tickets 4 u32 (+pad)][status 4 passes], zeroed by preprocess_kernel.
 // part: 0 = histogram + passes 0..2 (enqueued before the host knows num_rendered), 1 = pass 3, which also zeroes
-// zero_ptr[0..zero_words) — the binning buffer's control words
-int launch_onesweep_depth_sort(int P, char *geom, const Layout &L, int part, uint32_t *zero_ptr, uint32_t zero_words, bool debug,
-                               hipStream_t s) {
-    uint32_t *keyA = (uint32_t *)(geom + L.g_keyA), *keyB = (uint32_t *)(geom + L.g_keyB);
-    uint32_t *valA = (uint32_t *)(geom + L.g_valA), *valB = (uint32_t *)(geom + L.g_valB);
-    uint32_t *ghist = (uint32_t *)(geom + L.g_ghist), *ticket = (uint32_t *)(geom + L.g_ticket);
-    uint32_t *err = (uint32_t *)(geom + L.g_ticket) + 8;  // inside the zeroed control region
-    u64 *status = (u64 *)(geom + L.g_status);
+// zero — the binning buffer's control words
+int launch_onesweep_depth_sort(int P, const Buffers &v, int part, WordRange zero, bool debug, hipStream_t s) {
+    uint32_t *keyA = v.g_keyA(), *keyB = v.g_keyB();
+    uint32_t *valA = v.g_valA(), *valB = v.g_valB();
+    uint32_t *ghist = v.g_ghist(), *ticket = v.g_ticket();
+    uint32_t *err = v.err_word();
+    u64 *status = v.g_status();
     const size_t per_pass = onesweep_status_bytes(P, 1) / sizeof(u64);
     int rc;
     if (part == 1)
         return onesweep_pass(keyB, valB, nullptr, valA, P, nullptr, 24, 8, ghist + 768, status + 3 * per_pass, ticket + 3, nullptr, nullptr, err,
-                             debug, s, zero_ptr, zero_words);
+                             debug, s, zero.begin, zero.words());
     const int hist_blocks = div_up(P, 256) < 512 ? div_up(P, 256) : 512;
     DAS3R_LAUNCH(depth_hist_kernel, dim3(hist_blocks), dim3(256), 0, s, keyA, (uint32_t)P, ghist);
     KERNEL_CHECK(s, debug, "depth_hist");
@@ -421,27 +420,26 @@ int launch_onesweep_depth_sort(int P, char *geom, const Layout &L, int part, uin
 
 // Stable partition of the emitted instances by tile id.  ctrl (binning buffer) = [ghist 2x256][tickets][status], zeroed by
 // a memset before emit; emit_kernel accumulated the two digit histograms.
-int launch_onesweep_partition(int64_t cap, char *geom, char *binning, const Layout &L, uint32_t **keys_final, bool debug, hipStream_t s,
+int launch_onesweep_partition(int64_t cap, const Buffers &v, uint32_t **keys_final, bool debug, hipStream_t s,
                               uint32_t *ghist_override, uint32_t *err_override) {
-    const uint32_t *n_ptr = (const uint32_t *)(geom + L.g_count);
-    uint32_t *err = err_override ? err_override : (uint32_t *)(geom + L.g_ticket) + 8;  // inside the zeroed control region
-    uint32_t *keyA = (uint32_t *)(binning + L.b_keyA), *keyB = (uint32_t *)(binning + L.b_keyB);
-    uint32_t *valA = (uint32_t *)(binning + L.b_valA), *valB = (uint32_t *)(binning + L.b_valB);
-    uint32_t *gid_of = (uint32_t *)(binning + L.b_gid_of), *slot_list = (uint32_t *)(binning + L.b_slot), *e_tmp = (uint32_t *)(binning + L.b_e2);
-    uint32_t *ghist = ghist_override ? ghist_override : (uint32_t *)(binning + L.b_ghist), *ticket = (uint32_t *)(binning + L.b_ticket);
-    u64 *status = (u64 *)(binning + L.b_status);
+    const uint32_t *n_ptr = v.g_count();
+    uint32_t *err = err_override ? err_override : v.err_word();
+    uint32_t *keyA = v.b_keyA(), *keyB = v.b_keyB();
+    uint32_t *gid_of = v.b_gid_of(), *slot_list = v.b_slot(), *e_tmp = v.b_e2();
+    uint32_t *ghist = ghist_override ? ghist_override : v.b_ghist(), *ticket = v.b_ticket();
+    u64 *status = v.b_status();
     const size_t per_pass = onesweep_status_bytes(cap, 1) / sizeof(u64);
     // payloads: the splat id (read from gid_of by the first pass, then ping-pong so that the LAST pass writes the buffer the layout calls
     // point_list, whatever the number of passes: the backward pass lays the buffers out from tile_passes alone) and the emission slot e
     // (the input index in the first pass, then ping-pong so that the last pass writes slot_list)
-    uint32_t *const pl_final = (uint32_t *)(binning + L.pub.point_list), *const pl_other = pl_final == valA ? valB : valA;
-    const int passes = L.part_passes;
+    uint32_t *const pl_final = v.point_list(), *const pl_other = v.point_list_partner();
+    const int passes = v.L.part_passes;
     uint32_t *kin = keyA, *kout = keyB;
     const uint32_t *vin = gid_of, *v2in = nullptr;
     int shift = 0, rc;
     for (int p = 0; p < passes; p++) {
-        const int dw = tile_digit_width(L.kbits), bits = (L.kbits - shift) < dw ? (L.kbits - shift) : dw;   // (kbits = tbits unless segmented: common.h)
-        const int at = shift + L.kshift;   // (segmented: the digits sit above the fraction bits of the key)
+        const int dw = tile_digit_width(v.L.kbits), bits = (v.L.kbits - shift) < dw ? (v.L.kbits - shift) : dw;   // (kbits = tbits unless segmented: buffers.h)
+        const int at = shift + v.L.kshift;   // (segmented: the digits sit above the fraction bits of the key)
         uint32_t *vout = ((passes - 1 - p) & 1) ? pl_other : pl_final;
         uint32_t *v2out = ((passes - 1 - p) & 1) ? e_tmp : slot_list;
         if ((rc = onesweep_pass(kin, vin, kout, vout, cap, n_ptr, at, bits, ghist + p * 256, status + p * per_pass, ticket + p,

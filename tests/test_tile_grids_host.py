@@ -141,7 +141,7 @@ def test_scene_reaches_what_it_is_there_for(name):
         assert ((x0 <= 255) & (x1 >= 257) & (x1 - x0 <= 6)).sum() >= 3, "small squares across column 255 | 256"
     if ty > 256:
         assert ((y0 <= 255) & (y1 >= 257) & (y1 - y0 <= 6)).sum() >= 3
-    # the packed word (preprocess.hip: x0 | x1 << 8 | y0 << 16 | y1 << 24) holds these rectangles where RECT32 lets the emission read it, and
+    # the packed word (preprocess.hip: x0 | x1 << 8 | y0 << 16 | y1 << 24) holds these rectangles where rect32() (buffers.h) lets the emission read it, and
     # nowhere else: an emission that read it on the larger grids would bin other rectangles than these
     word = (x0 | (x1 << 8) | (y0 << 16) | (y1 << 24)) & 0xFFFFFFFF
     unpacked = (word & 255, (word >> 16) & 255, (word >> 8) & 255, word >> 24)

@@ -2,7 +2,7 @@
 
 What the forward's binning does depends on the tile grid: the bits of a tile id (common.h tile_bits), the partition passes and their digit
 widths (tile_digit_width), the key bits the passes leave free for depth buckets (path_policy.h seg_dbits) — which decide what every forced
-DAS3R_BINNING resolves to —, and whether the emission may read the packed rectangles (scan_emit.hip RECT32: at most 255 tiles per axis).
+DAS3R_BINNING resolves to —, and whether the emission may read the packed rectangles (buffers.h rect32(): at most 255 tiles per axis).
 SHAPES holds the smallest image of each regime; the functions below RESTATE the formulas of common.h and path_policy.h in Python (they
 are not read from the library: tests/test_tile_grids_host.py holds them against it and against REGIMES, the table worked out by hand),
 and the GPU tests take their expected plan from here, never from what a run happened to do.
@@ -112,7 +112,7 @@ def regime(name):
 
 
 def packed_rectangles(name):
-    """scan_emit.hip RECT32: the emission reads the packed 8-bit rectangles only while neither axis has more than 255 tiles."""
+    """buffers.h rect32(): the emission reads the packed 8-bit rectangles only while neither axis has more than 255 tiles."""
     tx, ty = grid(*SHAPES[name])
     return tx <= 255 and ty <= 255
 
